@@ -17,7 +17,12 @@ after every step instead).  Inputs are resident in HBM before the timed region. 
 performed compare = one unit of the reference report's `Wells` column
 (count_well_duplicates.py:93), read back from the device's own counters.
 
-Extra objects on the JSON line:
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the
+headline line: `value` compares/s, `ms_per_step` (wall time of one timed step, slowest rank).
+`--dump-outputs DIR` writes the last timed step's merged counter block (DIR/counter_block.npy,
+float64); the inputs are seeded, so two builds can be compared output for output.
+
+Extra objects on the JSON line, measured only with `--full`:
   roofline      HBM roofline of the dominant kernel (k_scan_q): algorithmic bytes
                 B = C*(L+4) + Tv*(L+5) + 8*(1+5*levels)*tiles per launch over the
                 kernel's mean duration, measured with HIP events on the launch stream around every
@@ -105,6 +110,14 @@ def parse(argv=None):
                          "merged block, against the C oracle (the planes are regenerated on the host from the spec)")
     ap.add_argument("--dump-block", default=None,
                     help="rank 0 saves the last step's merged [ranks*tiles, 1+5*levels] counter block here (.npy)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/<name>.npy (float64): "
+                         "counter_block = the merged [ranks*tiles, 1+5*levels] counter block")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the roofline of the scan kernel (HIP events "
+                         "in the timed region, the two-lane control, the full gather, the read-only stream rate), the "
+                         "CPU baselines (checked against the device counters), the other compare modes, layouts and "
+                         "configs (other_modes) and the end-to-end run on real files (e2e)")
     ap.add_argument("--dry-run", action="store_true",
                     help="print the launcher's command line (JSON) instead of running it; touches no GPU")
     return ap.parse_args(argv)
@@ -767,21 +780,26 @@ def main(argv=None):
     # records around EVERY launch costs the step 6 % - measured: 0.1355 against 0.1278 ms at 20 steps - so
     # at the driver's 20 steps every fourth launch is timed, at 200 every eighth: 5 and 25 launches), and
     # one more pair around the whole region on the same stream: the GPU-side time of all K launches
-    # with their counter memsets, the cross-check of the per-launch figure
-    sc.set_option("profile", int(os.environ.get("WD_BENCH_PROFILE_EVERY", 0)) or max(1, min(8, args.steps // 5)))
-    sc.profile_reset()
-    region = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    # with their counter memsets, the cross-check of the per-launch figure.  --full only: a plain run
+    # times the launches and nothing else
+    if args.full:
+        sc.set_option("profile", int(os.environ.get("WD_BENCH_PROFILE_EVERY", 0)) or max(1, min(8, args.steps // 5)))
+        sc.profile_reset()
+        region = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
     fence()
     t_start = time.perf_counter()
-    region[0].record(stream)
+    if args.full:
+        region[0].record(stream)
     block = run(args.steps)
-    region[1].record(stream)
+    if args.full:
+        region[1].record(stream)
     fence()
     elapsed = time.perf_counter() - t_start
-    region_ms = region[0].elapsed_time(region[1]) / max(1, args.steps)
-    kern_ms_total, launches = sc.profile_get()
+    if args.full:
+        region_ms = region[0].elapsed_time(region[1]) / max(1, args.steps)
+        kern_ms_total, launches = sc.profile_get()
+        sc.set_option("profile", 0)
     headline_kernel = sc.last_kernel()
-    sc.set_option("profile", 0)
     sc.scan_status()
     elapsed = wdist.max_over_ranks(elapsed, world, device="cpu" if rehearsal else "cuda")   # slowest rank
 
@@ -792,6 +810,11 @@ def main(argv=None):
     counts = block.cpu().numpy()
     if rank == 0 and args.dump_block:
         np.save(args.dump_block, counts)
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the scan path receives from the last timed step: the merged int64 counter block,
+        # written as float64 (every count is far below 2**53, so the values are exact)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "counter_block.npy"), counts.astype(np.float64))
     compares_all = int(counts[:, 1:1 + levels].sum())          # sum of Wells over every rank
     mine = counts[rank * args.tiles:(rank + 1) * args.tiles]
     compares_rank = int(mine[:, 1:1 + levels].sum())
@@ -799,7 +822,69 @@ def main(argv=None):
     ms_per_step = elapsed / max(1, args.steps) * 1e3
     value = compares_all / (elapsed / max(1, args.steps))
 
-    # ---- roofline of the dominant kernel: HIP events on the launch stream ----------------
+    # ---- --check-tiles: sampled rows of the MERGED block (every rank's) against the oracle ----
+    checked = None
+    if rank == 0 and args.check_tiles > 0:
+        from oracle import oracle
+        rng = np.random.default_rng(5)
+        total_rows = world * args.tiles
+        pick = sorted(rng.choice(total_rows, size=min(args.check_tiles, total_rows), replace=False).tolist())
+        wells_u = np.unique(np.concatenate([centre, nbr]).astype(np.int64))
+        c2 = np.searchsorted(wells_u, centre).astype(np.int32)
+        n2 = np.searchsorted(wells_u, nbr).astype(np.int32)
+        planes_h, filters_h = [], []
+        for row in pick:                     # (only the wells the targets touch: the oracle reads no others)
+            ln, t = lane_tiles_of(row // args.tiles)[row % args.tiles]
+            planes_h.append([synth.plane_bytes(spec, ln, t, c, wells_u) for c in range(L)])
+            filters_h.append(synth.filter_bytes(spec, ln, t, wells_u))
+        out = oracle.count_tiles_mt(planes_h, filters_h, c2, lvl_off, n2, mode, k, min(16, len(pick)))
+        dev = counts[pick].copy()
+        dev[:, 1 + 3 * levels:1 + 4 * levels] = np.cumsum(dev[:, 1 + 3 * levels:1 + 4 * levels], axis=1)
+        dev[:, 1 + 4 * levels:] = np.cumsum(dev[:, 1 + 4 * levels:][:, ::-1], axis=1)[:, ::-1]
+        if not (dev == out).all():
+            raise SystemExit("bench: merged block differs from the CPU oracle on sampled tiles %s" % pick)
+        checked = {"rows": pick, "ranks_covered": sorted({r // args.tiles for r in pick}), "oracle": "count_tiles_mt"}
+
+    def finish(extra):
+        """Rank 0 prints the result line (the headline, then `extra`); every rank releases its GPU state."""
+        if rank == 0:
+            per_lane = len(workload.tiles_for_stype(args.stype))
+            named = {("hiseq_x", 96, 1): "BASELINE configs[1]", ("hiseq_4000", 112, 1): "BASELINE configs[2] layout"}.get(
+                (args.stype, args.tiles, lpr), "custom layout")
+            if args.stype == "hiseq_4000" and world * lpr == 8 and args.tiles == 112 * lpr:
+                named = "BASELINE configs[2]: 8 lanes x 112 tiles" + ("" if lpr == 1 else ", %d lanes per rank" % lpr)
+            line = {
+                "metric": "target x neighbour seq-compares/sec (whole node)",
+                "value": round(value, 1), "unit": "compares/s",
+                "n_gpus": world, "rccl_world": None if ranks_seen is None else ranks_seen["rccl_world"],
+                "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(ms_per_step, 5), "higher_is_better": True, "scaling": "weak",
+                "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+                "config": {"workload": "%d lane(s) x %d tiles (%s) x %d targets x %d levels, %d bp; %s per GPU (%s)"
+                                       % (world * lpr, args.tiles // lpr, args.stype, T, levels, L,
+                                          "one lane" if lpr == 1 else "%d lanes" % lpr, named),
+                           "lanes_per_rank": lpr, "resident_bytes_per_rank": args.tiles * (L + 1) * n_clusters,
+                           "checked_against_oracle": checked,
+                           "mode": args.mode, "k": k, "early_exit": not args.no_early_exit,
+                           "clusters_per_tile": n_clusters, "compares_per_step": compares_all,
+                           "valid_targets_per_rank": valid_rank, "parallelism": "tiles sharded, %d rank(s)" % world,
+                           "merge": None if not use_dist else "one int64 all-reduce per %d step(s)" % chunk,
+                           "process_group": ranks_seen,
+                           "setup_s": round(setup_s, 1)},
+            }
+            line.update(extra)
+            print(json.dumps(line))
+        if tb is not None:
+            tb.free()
+        sc.close()
+        if use_dist:
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish({})
+        return
+
+    # ---- --full from here on: roofline of the dominant kernel: HIP events on the launch stream ----
     sc.set_option("profile", 1)
     if launches == 0:                                           # --steps 0
         sc.profile_reset()
@@ -1056,70 +1141,13 @@ def main(argv=None):
                   "sample": "first %d targets of 1 tile (%d compares) in %.2f s, pure-Python restatement of "
                             "get_seqs + the compare loop, planes already gunzipped" % (n_py, py_compares, t_py)}
 
-    # ---- --check-tiles: sampled rows of the MERGED block (every rank's) against the oracle ----
-    checked = None
-    if rank == 0 and args.check_tiles > 0:
-        from oracle import oracle
-        rng = np.random.default_rng(5)
-        total_rows = world * args.tiles
-        pick = sorted(rng.choice(total_rows, size=min(args.check_tiles, total_rows), replace=False).tolist())
-        wells_u = np.unique(np.concatenate([centre, nbr]).astype(np.int64))
-        c2 = np.searchsorted(wells_u, centre).astype(np.int32)
-        n2 = np.searchsorted(wells_u, nbr).astype(np.int32)
-        planes_h, filters_h = [], []
-        for row in pick:                     # (only the wells the targets touch: the oracle reads no others)
-            ln, t = lane_tiles_of(row // args.tiles)[row % args.tiles]
-            planes_h.append([synth.plane_bytes(spec, ln, t, c, wells_u) for c in range(L)])
-            filters_h.append(synth.filter_bytes(spec, ln, t, wells_u))
-        out = oracle.count_tiles_mt(planes_h, filters_h, c2, lvl_off, n2, mode, k, min(16, len(pick)))
-        dev = counts[pick].copy()
-        dev[:, 1 + 3 * levels:1 + 4 * levels] = np.cumsum(dev[:, 1 + 3 * levels:1 + 4 * levels], axis=1)
-        dev[:, 1 + 4 * levels:] = np.cumsum(dev[:, 1 + 4 * levels:][:, ::-1], axis=1)[:, ::-1]
-        if not (dev == out).all():
-            raise SystemExit("bench: merged block differs from the CPU oracle on sampled tiles %s" % pick)
-        checked = {"rows": pick, "ranks_covered": sorted({r // args.tiles for r in pick}), "oracle": "count_tiles_mt"}
-
     e2e = None
     if rank == 0 and world == 1 and args.e2e_tiles > 0 and args.profile_steps > 0 and args.mode == "eq":
         tb.free()                                             # (the e2e run brings its own tiles)
         tb = None
         e2e = e2e_probe(local_rank, args.e2e_tiles, rows, cols, centre, lvl_off, nbr)
-    if rank == 0:
-        per_lane = len(workload.tiles_for_stype(args.stype))
-        named = {("hiseq_x", 96, 1): "BASELINE configs[1]", ("hiseq_4000", 112, 1): "BASELINE configs[2] layout"}.get(
-            (args.stype, args.tiles, lpr), "custom layout")
-        if args.stype == "hiseq_4000" and world * lpr == 8 and args.tiles == 112 * lpr:
-            named = "BASELINE configs[2]: 8 lanes x 112 tiles" + ("" if lpr == 1 else ", %d lanes per rank" % lpr)
-        line = {
-            "metric": "target x neighbour seq-compares/sec (whole node)",
-            "value": round(value, 1), "unit": "compares/s",
-            "n_gpus": world, "rccl_world": None if ranks_seen is None else ranks_seen["rccl_world"],
-            "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 5), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "config": {"workload": "%d lane(s) x %d tiles (%s) x %d targets x %d levels, %d bp; %s per GPU (%s)"
-                                   % (world * lpr, args.tiles // lpr, args.stype, T, levels, L,
-                                      "one lane" if lpr == 1 else "%d lanes" % lpr, named),
-                       "lanes_per_rank": lpr, "resident_bytes_per_rank": args.tiles * (L + 1) * n_clusters,
-                       "checked_against_oracle": checked,
-                       "mode": args.mode, "k": k, "early_exit": not args.no_early_exit,
-                       "clusters_per_tile": n_clusters, "compares_per_step": compares_all,
-                       "valid_targets_per_rank": valid_rank, "parallelism": "tiles sharded, %d rank(s)" % world,
-                       "merge": None if not use_dist else "one int64 all-reduce per %d step(s)" % chunk,
-                       "process_group": ranks_seen,
-                       "setup_s": round(setup_s, 1)},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "cpu_baseline_python": cpu_py,
-            "e2e": e2e,
-            "other_modes": other,
-        }
-        print(json.dumps(line))
-    if tb is not None:
-        tb.free()
-    sc.close()
-    if use_dist:
-        dist.destroy_process_group()
+    finish({"roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_python": cpu_py, "e2e": e2e,
+            "other_modes": other})
 
 
 if __name__ == "__main__":

@@ -54,11 +54,53 @@ def test_no_launcher_for_one_gpu_or_under_torchrun():
     assert p.returncode == 0 and _last_json(p.stdout)["launcher"] is None
 
 
+def test_full_and_dump_outputs_are_opt_in():
+    """Everything beside the headline is measured behind --full, off by default; --dump-outputs names a directory."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "outs"])
+    assert a.full is True and a.dump_outputs == "outs"
+
+
 def test_launcher_passes_the_childs_exit_code(tmp_path):
     """The launcher leaves with its child's exit code: a bad flag in the ranks' argv fails the
     torchrun child (argparse, before any GPU call), and `bench.py --gpus 2` reports that."""
     p = _run(["--gpus", "2", "--mode", "eq", "--steps", "1", "--option", "malformed"], timeout=300)
     assert p.returncode != 0
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_step_and_full_adds_the_rest(tmp_path):
+    """A plain run prints the headline alone; --dump-outputs writes the last timed step's counter block
+    (float64, exact): the block --dump-block saves, the same from run to run and for any number of steps.
+    --full adds the roofline - its HIP events, one per launch here, count exactly --steps launches - and
+    the CPU baseline, which checks the device counters against the oracle."""
+    common = ["--gpus", "1", "--tiles", "4", "--warmup", "1"]
+    outs = []
+    for steps in (3, 5):
+        d = tmp_path / ("out%d" % steps)
+        blk = str(tmp_path / ("blk%d.npy" % steps))
+        p = _run(common + ["--steps", str(steps), "--dump-outputs", str(d), "--dump-block", blk])
+        assert p.returncode == 0, p.stderr[-4000:]
+        line = _last_json(p.stdout)
+        assert line["steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "compares/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+        for key in ("roofline", "cpu_baseline", "cpu_baseline_python", "e2e", "other_modes"):
+            assert key not in line, key
+        got = np.load(d / "counter_block.npy")
+        assert got.dtype == np.float64 and got.shape == (4, 26)
+        assert (got == np.load(blk)).all()
+        assert line["config"]["compares_per_step"] == int(got[:, 1:6].sum()) > 0
+        outs.append(got)
+    assert (outs[0] == outs[1]).all()
+    p = _run(common + ["--steps", "3", "--full", "--cpu-tiles", "2", "--profile-steps", "0"],
+             env={"WD_BENCH_PROFILE_EVERY": "1"})
+    assert p.returncode == 0, p.stderr[-4000:]
+    full = _last_json(p.stdout)
+    assert full["roofline"]["launches_timed"] == 3 and full["roofline"]["kernel_ms"] > 0
+    assert full["cpu_baseline"]["parity_checked_tiles"] == 2
+    assert full["config"]["compares_per_step"] == int(outs[0][:, 1:6].sum())
 
 
 @pytest.mark.gpu
