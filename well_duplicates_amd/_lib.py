@@ -99,10 +99,17 @@ PROTOTYPES = {
     "wd_synth_filter": (_i, [_vp, _vp, ctypes.POINTER(SynthSpecC), _i, _i]),
 }
 
+# name -> (restype, argtypes); every symbol include/welldup_sets.h declares beyond welldup.h
+SETS_PROTOTYPES = {
+    "wd_dup_sets_workspace": (_i, [_i64, _i, ctypes.POINTER(_sz)]),
+    "wd_dup_sets": (_i, [_vp, _i, _i, _i, _i, _pp, _pp, _i64, _vp, _sz, _i64, _vp, _vp, _pp, ctypes.POINTER(_i64)]),
+}
+DUPSET_SIZE_BINS = 8
+
 _lib = None
 
 
-UNITS = ("core", "scan", "queue", "lines", "dense", "ingest")      # csrc/welldup_<unit>.hip -> one object each
+UNITS = ("core", "scan", "queue", "lines", "dense", "ingest", "sets")      # csrc/welldup_<unit>.hip -> one object each
 OBJ_DIR = os.path.join(HERE, "build_obj")
 
 
@@ -123,7 +130,7 @@ def _deps(path: str, seen=None) -> set:
 
 
 def source_build_id() -> str:
-    """sha256 over the library's sources (csrc/*, include/welldup.h): what `wd_build_id()` of a library
+    """sha256 over the library's sources (csrc/*, include/welldup.h, include/welldup_sets.h): what `wd_build_id()` of a library
     built from this tree returns.  Counter profiles and resource tables carry it (tools/pmc_collect.py),
     so that evidence is tied to the code that produced it, not to a kernel's name."""
     import hashlib
@@ -131,6 +138,7 @@ def source_build_id() -> str:
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)
                    if f.endswith((".hip", ".inc", ".h")))
     files.append(os.path.join(INCLUDE, "welldup.h"))
+    files.append(os.path.join(INCLUDE, "welldup_sets.h"))
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         with open(f, "rb") as fh:
@@ -178,6 +186,8 @@ def unit_of_kernel(kernel: str) -> str:
         return "dense"
     if kernel.startswith(("k_inflate", "k_cbcl", "k_gather", "k_interleave", "k_scatter")):
         return "ingest"
+    if kernel.startswith("k_sets"):
+        return "sets"
     return "scan"
 
 
@@ -235,7 +245,7 @@ def load():
             "%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the scan path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in list(PROTOTYPES.items()) + list(SETS_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

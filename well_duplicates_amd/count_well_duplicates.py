@@ -21,7 +21,9 @@ Differences from the reference, all deliberate:
   * `-t` with a pattern that matches nothing raises the AssertionError the reference
     intends (its own message formatting raises NameError first);
   * extra flags: --device, --dist-backend, --tile-batch, --threads, --strict, -o/--output,
-    --all-wells, --slocs, --layout, --serial-ingest;
+    --all-wells, --slocs, --layout, --serial-ingest, --dup-sets, --dup-sets-out;
+  * --all-wells --dup-sets groups every tile's wells into duplicate sets and follows each lane's report
+    with their counts and the exact duplication (report.write_dup_sets);
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
@@ -119,11 +121,24 @@ def parse_args(argv=None):
                         "what the double-buffered ingest gains)")
     p.add_argument("--strict", action="store_true",
                    help="reproduce the reference's ZeroDivisionError on a lane without duplicates")
+    p.add_argument("--dup-sets", action="store_true",
+                   help="with --all-wells: group every tile's PF wells into duplicate sets (single linkage over "
+                        "the duplicate pairs of levels <= l) and print, after each lane's report, the sets, the "
+                        "wells in them, the redundant wells and the exact duplication (redundant / PF wells)")
+    p.add_argument("--dup-sets-out", default=None, metavar="PATH",
+                   help="with --dup-sets: write lane, tile, well and set (the smallest well index of its set) of "
+                        "every well in a set of two or more to this TSV file (single process only)")
     args = p.parse_args(argv)
     if not args.coord_file and not args.all_wells:
         p.error("the following arguments are required: -f/--coord_file (or --all-wells)")
     if args.layout == "interleaved" and (args.all_wells or (args.edit_distance > 3 and not args.hamming)):
         p.error("--layout interleaved needs sampled targets (-f) and, for the edit distance, -e <= 3")
+    if args.dup_sets and not args.all_wells:
+        p.error("--dup-sets needs --all-wells (with sampled targets the pairs only leave the centres)")
+    if args.dup_sets_out and not args.dup_sets:
+        p.error("--dup-sets-out needs --dup-sets")
+    if args.dup_sets_out and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        p.error("--dup-sets-out is written by a single process only")
     return args
 
 
@@ -198,10 +213,23 @@ class _Loading:
             f.result()                      # re-raises the loader's exception (FileNotFoundError, ...)
 
 
+def set_members(labels: np.ndarray):
+    """One tile's labels (wd_dup_sets) -> (wells, set labels) of the wells in sets of two or more, by well."""
+    valid = labels != INVALID_TARGET
+    size = np.bincount(labels[valid].astype(np.int64), minlength=labels.shape[0])
+    member = np.zeros(labels.shape[0], dtype=bool)
+    member[valid] = size[labels[valid].astype(np.int64)] >= 2
+    wells = np.flatnonzero(member)
+    return wells, labels[wells]
+
+
 def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells, tile_batch,
-               threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None):
+               threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
+               dup_sets=0):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
+    dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
+    2 = and their members (into["members"][(lane, tile)] = (wells, labels), set_members).
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -343,7 +371,14 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
             n_clusters = tb.N
             if want_log:
                 sc.hitlog_enable(max(1024, int(nbr.size) * len(chunk)))
-            blocks, _ = tb.count(mode, k)
+            if dup_sets:
+                blocks, set_rows, labels = tb.dup_sets(mode, k, labels=dup_sets > 1)
+                for i, t in enumerate(chunk):
+                    into["sets"][(lane, t)] = report.DupSetCounts.from_block(set_rows[i], levels)
+                    if labels is not None:
+                        into["members"][(lane, t)] = set_members(labels[i])
+            else:
+                blocks, _ = tb.count(mode, k)
             _lap("batch %d: scanned" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
             if want_log:
@@ -392,6 +427,15 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
         for tb in spare:
             tb.free()
     return counts, logs
+
+
+def write_set_members(path, members):
+    """--dup-sets-out: lane, tile, well, set of every well in a set of two or more, by lane, tile, well."""
+    with open(path, "w") as fh:
+        fh.write("lane\ttile\twell\tset\n")
+        for lane, tile in sorted(members, key=lambda lt: (str(lt[0]), str(lt[1]))):
+            wells, labels = members[(lane, tile)]
+            fh.writelines("%s\t%s\t%d\t%d\n" % (lane, tile, w, s) for w, s in zip(wells.tolist(), labels.tolist()))
 
 
 def main(argv=None, exiting=False):
@@ -520,27 +564,35 @@ def _main(args, log, wdist, rank, world, device, opener, early):
             pos = {item: i for i, item in enumerate(items)}
             mine = wdist.shard(items, rank, world)
             ncnt = 1 + 5 * levels
-            rows = np.zeros((len(mine), ncnt), dtype=np.int64)
+            # --dup-sets: the duplicate sets' counters ride in the same row (one all-reduce either way)
+            nsets = 1 + 3 * levels + len(report.SIZE_BIN_NAMES) if args.dup_sets else 0
+            rows = np.zeros((len(mine), ncnt + nsets), dtype=np.int64)
             logs = {}
 
             def emit(lane, block):          # a finished lane: its log lines, then its report (:269)
-                counts = {t: report.TileCounts.from_block(block[pos[(lane, t)]], levels) for t in tiles}
+                counts = {t: report.TileCounts.from_block(block[pos[(lane, t)]][:ncnt], levels) for t in tiles}
                 for t in tiles:
                     lines = logs.get((lane, t))
                     if lines:
                         log("\n".join(lines))
                 report.write_report(lane, n_targets, counts, verbose=not args.summary_only,
                                     strict=args.strict, out=out_fh)
+                if args.dup_sets:
+                    sets = {t: report.DupSetCounts.from_block(block[pos[(lane, t)]][ncnt:], levels) for t in tiles}
+                    report.write_dup_sets(lane, sets, verbose=not args.summary_only, out=out_fh, levels=levels)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
                 where = {item: i for i, item in enumerate(mine)}
-                results = {"counts": {}, "logs": {}}      # scan_lanes fills these, lane_done reads them
+                results = {"counts": {}, "logs": {}, "sets": {}, "members": {}}   # scan_lanes fills these, lane_done reads them
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
                         c = results["counts"][(lane, t)]
-                        rows[where[(lane, t)]] = [c.targets] + c.wells + c.dups + c.hit + c.first + c.last
+                        rows[where[(lane, t)]][:ncnt] = [c.targets] + c.wells + c.dups + c.hit + c.first + c.last
+                        if args.dup_sets:
+                            d = results["sets"][(lane, t)]
+                            rows[where[(lane, t)]][ncnt:] = [d.pf] + d.sets + d.in_sets + d.redundant + d.sizes
                         if (lane, t) in results["logs"]:
                             logs[(lane, t)] = results["logs"][(lane, t)]
                     if world == 1:          # as the reference: a lane is reported when it is done
@@ -552,7 +604,10 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                0 if (args.quiet or args.all_wells) else len(cycles),
                                overlap=not args.serial_ingest,
                                interleave=resident_layout(args, mode, k, csr, reader, lanes, tiles, cycle_list),
-                               gpu_inflate=not args.host_inflate, lane_done=lane_done, into=results)
+                               gpu_inflate=not args.host_inflate, lane_done=lane_done, into=results,
+                               dup_sets=(2 if args.dup_sets_out else 1) if args.dup_sets else 0)
+                    if args.dup_sets_out:
+                        write_set_members(args.dup_sets_out, results["members"])
             except Exception as e:          # noqa: BLE001 - re-raised below, on every rank
                 err = e
             if world > 1:

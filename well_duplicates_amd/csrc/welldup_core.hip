@@ -1,12 +1,13 @@
 // welldup_core.hip - context, options, device memory helpers, hit log, profile, RCCL binding, synthetic
 // data: the part of the C ABI (include/welldup.h) that launches no compare kernel.
 //
-// libwelldup.so is built from four translation units (one code object each, linked into one library):
+// libwelldup.so is built from these translation units (one code object each, linked into one library):
 //   welldup_core.hip    this file
 //   welldup_scan.hip    targets, the sampled scans (k_scan, k_scan_q, k_scan_lines, k_scan_lev_generic),
 //                       wd_scan_async / wd_count_tiles, the neighbour-index generator
 //   welldup_dense.hip   the dense path (every well a centre): tables and the k_dense_* chain
 //   welldup_ingest.hip  files -> HBM: DEFLATE on the GPU, the host loaders, CBCL, wd_gather_wells
+//   welldup_sets.hip    duplicate sets of every tile from the hit log (include/welldup_sets.h)
 // wd_ctx.h holds the context they share; the .inc files hold the kernels, each included by one unit.
 #include "wd_ctx.h"
 
@@ -92,6 +93,9 @@ void drain_events(wd_ctx *ctx)
 
 }  // namespace wd
 
+// welldup_sets.hip (declared here, not in wd_ctx.h: every other unit's sources stay as they are)
+namespace wd { const char *unit_id_sets(); }
+
 using namespace wd;
 
 extern "C" {
@@ -106,12 +110,12 @@ int wd_version(void) { return 100; }
 #endif
 const char *wd_build_id(void)
 {
-    // "<all sources> core=<..> scan=<..> queue=<..> lines=<..> dense=<..> ingest=<..>": the whole tree's hash,
+    // "<all sources> core=<..> scan=<..> queue=<..> lines=<..> dense=<..> ingest=<..> sets=<..>": the whole tree's hash,
     // then one per translation unit (its .hip and everything it includes), so that evidence about a kernel
     // goes stale when ITS code changes and not when a comment in the ingest does
     static const std::string id = std::string(WD_BUILD_ID) + " core=" + WD_UNIT_ID + " scan=" + unit_id_scan() +
                                   " queue=" + unit_id_queue() + " lines=" + unit_id_lines() +
-                                  " dense=" + unit_id_dense() + " ingest=" + unit_id_ingest();
+                                  " dense=" + unit_id_dense() + " ingest=" + unit_id_ingest() + " sets=" + unit_id_sets();
     return id.c_str();
 }
 

@@ -188,3 +188,72 @@ def output_writer(lane, sample_size, lane_dupl, levels=0, verbose=False, out=Non
     tiles = {tile: TileCounts.from_target_stats(tc, levels) for tile, tc in lane_dupl.items()}
     write_report(lane, sample_size, tiles, levels=levels, verbose=verbose, out=out,
                  strict=strict)
+
+
+SIZE_BIN_NAMES = ("2", "3", "4", "5", "6", "7", "8", "9+")
+
+
+@dataclass
+class DupSetCounts:
+    """Duplicate sets of one tile, or of several added up (include/welldup_sets.h, wd_dup_sets):
+    PF wells, and per level (cumulative: the graph of the edges of level <= l) the sets of >= 2 wells,
+    the wells in them and the redundant wells (InSets - Sets); size bins of the outermost level's sets."""
+    pf: int = 0
+    sets: List[int] = field(default_factory=list)
+    in_sets: List[int] = field(default_factory=list)
+    redundant: List[int] = field(default_factory=list)
+    sizes: List[int] = field(default_factory=lambda: [0] * len(SIZE_BIN_NAMES))
+
+    @property
+    def levels(self) -> int:
+        return len(self.sets)
+
+    @classmethod
+    def zeros(cls, levels: int) -> "DupSetCounts":
+        return cls(0, [0] * levels, [0] * levels, [0] * levels, [0] * len(SIZE_BIN_NAMES))
+
+    @classmethod
+    def from_block(cls, block: Sequence[int], levels: int) -> "DupSetCounts":
+        """Decode one out_sets row: [PF, Sets[levels], InSets[levels], Redundant[levels], size bins]."""
+        b = [int(v) for v in block]
+        assert len(b) == 1 + 3 * levels + len(SIZE_BIN_NAMES)
+        cut = lambda k: b[1 + k * levels: 1 + (k + 1) * levels]
+        return cls(b[0], cut(0), cut(1), cut(2), b[1 + 3 * levels:])
+
+    def __add__(self, other: "DupSetCounts") -> "DupSetCounts":
+        if self.levels != other.levels:
+            raise ValueError("duplicate sets of %d and %d levels" % (self.levels, other.levels))
+        add = lambda a, b: [x + y for x, y in zip(a, b)]
+        return DupSetCounts(self.pf + other.pf, add(self.sets, other.sets), add(self.in_sets, other.in_sets),
+                            add(self.redundant, other.redundant), add(self.sizes, other.sizes))
+
+    def exact_duplication(self) -> float:
+        """Redundant wells of the outermost level / PF wells (0 without PF wells)."""
+        return self.redundant[-1] / self.pf if self.pf and self.levels else 0.0
+
+
+def write_dup_sets(lane, counts: Dict[str, DupSetCounts], verbose: bool = False, out=None, levels: int = 0) -> None:
+    """The duplicate-set block that follows a lane's report under --dup-sets: per-tile lines (verbose, in
+    sorted tile order as write_report), the lane's sums, the set sizes and the exact duplication."""
+    out = out or sys.stdout
+    if not levels:
+        levels = next((c.levels for c in counts.values()), 0)
+    tot = DupSetCounts.zeros(levels)
+    print(file=out)
+    for tile in sorted(counts.keys()):
+        dc = counts[tile]
+        tot = tot + dc
+        if verbose:
+            print("DupSets: %s\tTile: %s\tPF wells: %i" % (lane, tile, dc.pf), file=out)
+            for lev in range(levels):
+                print("Level: %i\tSets: %i\tInSets: %i\tRedundant: %i" % (
+                    lev + 1, dc.sets[lev], dc.in_sets[lev], dc.redundant[lev]), file=out)
+    print("DupSetsSummary: %s\tTiles: %i\tPF wells: %i" % (lane, len(counts), tot.pf), file=out)
+    for lev in range(levels):
+        r_in = tot.in_sets[lev] / tot.pf if tot.pf else 0.0
+        r_red = tot.redundant[lev] / tot.pf if tot.pf else 0.0
+        print("Level: %i\tSets: %i\tInSets: %i (%.5f)\tRedundant: %i (%.5f)" % (
+            lev + 1, tot.sets[lev], tot.in_sets[lev], r_in, tot.redundant[lev], r_red), file=out)
+    print("SetSizes (level %i): %s" % (levels, "\t".join(
+        "%s: %i" % (name, n) for name, n in zip(SIZE_BIN_NAMES, tot.sizes))), file=out)
+    print("Exact duplication (Redundant/PF wells): {:.2%}".format(tot.exact_duplication()), file=out)

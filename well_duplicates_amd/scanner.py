@@ -229,6 +229,33 @@ class Scanner:
             pto.ctypes.data_as(ctypes.c_void_p) if per_target else None))
         return blocks, pto
 
+    def dup_sets_workspace_bytes(self, n_clusters: int, n_tiles: int) -> int:
+        """Device bytes wd_dup_sets needs as its workspace for n_tiles tiles of n_clusters wells."""
+        b = ctypes.c_size_t()
+        self._ck(self._lib.wd_dup_sets_workspace(int(n_clusters), int(n_tiles), ctypes.byref(b)))
+        return b.value
+
+    def dup_sets(self, planes: Sequence[Sequence[int]], filters: Sequence[int], n_clusters: int, mode: int, k: int,
+                 workspace: int, workspace_bytes: int, labels: Optional[Sequence[int]] = None, edge_cap: int = 0,
+                 tables=None, L=None):
+        """The scan of count_tiles plus the duplicate sets of every tile (wd_dup_sets, include/welldup_sets.h);
+        needs every well as a target.  labels: n_tiles device addresses of N uint32 each, or None.
+        Returns (blocks [n_tiles, 1 + 5*levels], sets [n_tiles, 1 + 3*levels + 8], edges processed):
+        a sets row is [PF wells, Sets[levels], InSets[levels], Redundant[levels], size bins 2..8, 9+]."""
+        n_tiles = len(filters)
+        if L is None:
+            L = len(planes[0]) if n_tiles else 0
+        pt, ft = tables if tables is not None else self._tables(planes, filters, L)
+        blocks = np.zeros((n_tiles, 1 + 5 * self.levels), dtype=np.int64)
+        sets = np.zeros((n_tiles, 1 + 3 * self.levels + _lib.DUPSET_SIZE_BINS), dtype=np.int64)
+        lt = (ctypes.c_void_p * max(1, n_tiles))(*[int(p) for p in labels]) if labels is not None else None
+        edges = ctypes.c_int64()
+        self._ck(self._lib.wd_dup_sets(
+            self._ctx, n_tiles, L, mode, k, pt, ft, int(n_clusters), ctypes.c_void_p(workspace), int(workspace_bytes),
+            int(edge_cap), blocks.ctypes.data_as(ctypes.c_void_p), sets.ctypes.data_as(ctypes.c_void_p), lt,
+            ctypes.byref(edges)))
+        return blocks, sets, edges.value
+
     def scan_async(self, tables, n_tiles: int, L: int, n_clusters: int, mode: int, k: int,
                    out_tile_dev: int, out_per_target_dev: Optional[int] = None):
         pt, ft = tables
@@ -448,6 +475,11 @@ class TileBatch:
             self.d_tmp = scanner.malloc(tmp_bytes) if tmp_bytes else 0
             self._cap = (self.plane_bytes, self.filter_bytes, tmp_bytes)
         self.tables = Scanner._tables(self.plane_ptrs(), self.filter_ptrs(), L)
+        # duplicate sets (dup_sets): workspace and labels, allocated on first use, kept with the buffers
+        self.d_sets, self.sets_bytes, self.edges = 0, 0, 0
+        if reuse is not None and reuse.sc is scanner and reuse.d_sets:
+            self.d_sets, self.sets_bytes, self._sets_cap = reuse.d_sets, reuse.sets_bytes, reuse._sets_cap
+            reuse.d_sets = 0
 
     def plane_ptr(self, tile: int, cycle: int) -> int:
         """Address of well 0 of the cycle (wells are `interleave` bytes apart)."""
@@ -511,8 +543,33 @@ class TileBatch:
         finally:
             self.sc.set_option("well_stride", 1)
 
+    def dup_sets(self, mode: int, k: int, labels: bool = False, edge_cap: int = 0):
+        """count() plus the duplicate sets of every tile (Scanner.dup_sets; every well must be a target).
+        -> (blocks, sets rows, labels uint32 [n_tiles, N] or None).  edges_processed is left in self.edges."""
+        ws = self.sc.dup_sets_workspace_bytes(self.N, self.n_tiles)
+        lbl_bytes = 4 * self.N * self.n_tiles if labels else 0
+        if not self.d_sets or self._sets_cap < ws + lbl_bytes:
+            if self.d_sets:
+                self.sc.free(self.d_sets)
+                self.d_sets = 0
+            self._sets_cap = ws + lbl_bytes
+            self.d_sets = self.sc.malloc(max(1, self._sets_cap))
+        self.sets_bytes = ws
+        d_lbl = self.d_sets + ws if labels else 0
+        lbl_ptrs = [d_lbl + 4 * self.N * i for i in range(self.n_tiles)] if labels else None
+        self.sc.set_option("well_stride", self.interleave)
+        try:
+            blocks, sets, self.edges = self.sc.dup_sets(None, self.filter_ptrs(), self.N, mode, k, self.d_sets, ws,
+                                                        labels=lbl_ptrs, edge_cap=edge_cap, tables=self.tables, L=self.L)
+        finally:
+            self.sc.set_option("well_stride", 1)
+        lab = None
+        if labels:
+            lab = self.sc.d2h(d_lbl, lbl_bytes, np.uint32).reshape(self.n_tiles, self.N)
+        return blocks, sets, lab
+
     def free(self):
-        for ptr in (self.d_planes, self.d_filters, self.d_tmp):
+        for ptr in (self.d_planes, self.d_filters, self.d_tmp, self.d_sets):
             if ptr:
                 self.sc.free(ptr)
-        self.d_planes = self.d_filters = self.d_tmp = 0
+        self.d_planes = self.d_filters = self.d_tmp = self.d_sets = 0
