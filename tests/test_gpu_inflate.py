@@ -581,3 +581,92 @@ def test_failed_cycles_are_decoded_beside_the_batch_not_after_it(sc, tmp_path):
     for q in range(4):
         assert (got[:, q] == want[q]).all(), q
     sc.free(group)
+
+
+def _cbcl_blocks(path):
+    """The tile table of a .cbcl file: [(tile, clusters, uncompressed size, compressed size)] (:263-292)."""
+    import struct
+    with open(path, "rb") as fh:
+        head = fh.read(48)
+        count = struct.unpack_from("<I", head, 44)[0]
+        return [struct.unpack("<IIII", fh.read(16)) for _ in range(count)]
+
+
+def test_cbcl_batch_across_ring_chunks_beside_a_bcl_batch(sc, tmp_path):
+    """A .cbcl batch whose blocks fill several chunks of a small pinned ring (so chunks are refilled
+    while the batch is read), in both layouts, while a second thread loads a .bcl.gz batch with its
+    filters through the same ring: every plane as the single-entry loaders make it, every entry
+    decoded on the GPU."""
+    from concurrent.futures import ThreadPoolExecutor
+    from well_duplicates_amd import bcl
+    from well_duplicates_amd.scanner import TileBatch
+    chunk_mb = sc.get_option("inflate_chunk_mb")
+    sc.set_option("inflate_chunk_mb", 1)
+    try:
+        n, tiles, cycles = 1000003, ["1101", "1102", "1103"], list(range(6))
+        spec = synth.SynthSpec(seed=21, n_clusters=n, row=1000, nocall_per_64k=3000, qual_levels=7)
+        synth.write_run_dir_cbcl(spec, str(tmp_path), [1], tiles, cycles)
+        rd = bcl.BCLReader(str(tmp_path))
+        handles = [rd.get_tile(1, t) for t in tiles]
+        jobs = [(i, c) for i in range(len(tiles)) for c in cycles]
+        # the blocks as the batch groups them into chunks of 1 MiB: each fits one, together they fill five
+        sizes = []
+        for i, c in jobs:
+            blk = {b[0]: b for b in _cbcl_blocks(handles[i].cbcl_path(c))}[int(tiles[i])]
+            assert blk[2] == (blk[1] + 1) // 2 and 18 <= blk[3] and blk[3] + 32 <= 1 << 20, blk
+            sizes.append((blk[3] + 15) // 16 * 16)
+        chunks, used = 1, 0
+        for s in sizes:
+            chunks, used = (chunks + 1, s) if used + s > 1 << 20 else (chunks, used + s)
+        assert chunks >= 5, chunks
+        one = TileBatch(sc, len(tiles), len(cycles), n)
+        flat = TileBatch(sc, len(tiles), len(cycles), n)
+        lanes = TileBatch(sc, len(tiles), len(cycles), n, interleave=4)
+        for tb in (one, flat, lanes):
+            for i, h in enumerate(handles):
+                sc.load_filter(h.filter_file, tb.filter_ptr(i), n)
+        for i, c in jobs:
+            sc.load_cbcl_tile(handles[i].cbcl_path(c), int(tiles[i]), one.filter_ptr(i), n, one.plane_ptr(i, c))
+        # the .bcl.gz batch: two tiles of another size, their planes and filters
+        n2 = 300007
+        spec2 = synth.SynthSpec(seed=22, n_clusters=n2, row=400, qual_levels=7)
+        gz_ref = TileBatch(sc, 2, len(cycles), n2)
+        gz = TileBatch(sc, 2, len(cycles), n2)
+        paths, dsts, filters = [], [], []
+        for i, t in enumerate((1101, 1102)):
+            for c in cycles:
+                p = tmp_path / ("t%d_c%d.bcl.gz" % (t, c))
+                p.write_bytes(_bcl(synth.plane_bytes(spec2, 2, t, c)))
+                paths.append(str(p))
+                dsts.append(gz.plane_ptr(i, c))
+                sc.load_bcl_gz(str(p), gz_ref.plane_ptr(i, c), n2)
+            f = tmp_path / ("s_2_%d.filter" % t)
+            f.write_bytes(synth.filter_file_bytes(synth.filter_bytes(spec2, 2, t)))
+            filters.append((str(f), gz.filter_ptr(i)))
+            sc.load_filter(str(f), gz_ref.filter_ptr(i), n2)
+        g0, h0 = sc.get_option("inflate_files_gpu"), sc.get_option("inflate_files_host")
+
+        def cbcl_batches():
+            for tb, stride in ((flat, 1), (lanes, 4)):
+                sc.load_cbcl_batch([(handles[i].cbcl_path(c), int(tiles[i]), tb.filter_ptr(i), tb.plane_ptr(i, c))
+                                    for i, c in jobs], n, threads=4, well_stride=stride)
+
+        with ThreadPoolExecutor(max_workers=2) as pool:
+            a = pool.submit(cbcl_batches)
+            b = pool.submit(sc.load_bcl_gz_batch, paths, dsts, n2, threads=4, filters=filters)
+            a.result()
+            b.result()
+        assert sc.get_option("inflate_files_gpu") - g0 == 2 * len(jobs) + len(paths)
+        assert sc.get_option("inflate_files_host") == h0
+        for i, c in jobs:
+            want = one.download_plane(i, c)
+            assert (flat.download_plane(i, c) == want).all(), (i, c)
+            assert (lanes.download_plane(i, c) == want).all(), (i, c)
+        for i in range(2):
+            assert (gz.download_filter(i) == gz_ref.download_filter(i)).all(), i
+            for c in cycles:
+                assert (gz.download_plane(i, c) == gz_ref.download_plane(i, c)).all(), (i, c)
+        for tb in (one, flat, lanes, gz_ref, gz):
+            tb.free()
+    finally:
+        sc.set_option("inflate_chunk_mb", chunk_mb)

@@ -138,9 +138,9 @@ struct wd_ctx {
     static constexpr int kSlotStreams = 4;
     hipStream_t slot_streams[kSlotStreams] = {};
 
-    // ingest through the GPU decoder (wd_load_bcl_gz_batch): the reader threads fill a ring of
-    // pinned chunks; each chunk's files are copied into the batch's arena in device memory and
-    // decoded by a launch of their own, on one of a pool of streams, while the next chunk is read
+    // ingest through the GPU decoder (wd_load_tile_files_batch, wd_load_cbcl_batch): the reader threads
+    // fill a ring of pinned chunks; each chunk's files are copied into the batch's arena in device memory
+    // and decoded on one of the decode streams while the next chunk is read
     struct InflateChunk {
         uint8_t *pinned = nullptr;
         hipEvent_t copied = nullptr;                   // the chunk's H2D copy is done: it may be refilled
@@ -154,9 +154,8 @@ struct wd_ctx {
     // times), and with a stream of their own for the chunk copies the next launch's files arrive while
     // this one decodes.  Consecutive batches take turns on two decode streams, so that the next batch's
     // workgroups move in as this batch's retire (400-file batches: 36 -> 33 ms per batch).
-    static constexpr int kInflateStreams = 4;          // decode streams that exist; `inflate_decode_streams` of them are used
-    int inflate_decode_streams = 2;                    // option / WD_DECODE_STREAMS
-    int inflate_launch_files = 1024;                   // option / WD_LAUNCH_FILES: files per decoder launch within a batch
+    static constexpr int kInflateLaunchFiles = 1024;   // files per decoder launch within a .bcl.gz batch
+    static constexpr int kInflateStreams = 2;          // decode streams; inflate_streams[kInflateStreams] is the copy stream
     unsigned inflate_launch_seq = 0;                   // launches so far: they take the decode streams in turn
     hipEvent_t inflate_joined[kInflateStreams] = {};   // a batch's launches on a stream are done
     size_t inflate_chunk_bytes = 16u << 20;            // option "inflate_chunk_mb" (pinning memory costs time: keep the ring small)

@@ -445,21 +445,12 @@ inline void nt_copy(uint8_t *dst, const uint8_t *src, size_t n)
         memcpy(dst + i, src + i, n - i);
 }
 
-// -> bytes read (== n on success).  `direct`: the old way (WD_RING_DIRECT=1, for comparisons).
-inline size_t read_into_ring(int fd, uint8_t *dst, size_t n, off_t at, std::vector<uint8_t> &bounce, bool direct)
+// -> bytes read (== n on success)
+inline size_t read_into_ring(int fd, uint8_t *dst, size_t n, off_t at, std::vector<uint8_t> &bounce)
 {
-    size_t got = 0;
-    if (direct) {
-        while (got < n) {
-            const ssize_t k = pread(fd, dst + got, n - got, at + (off_t)got);
-            if (k <= 0)
-                break;
-            got += (size_t)k;
-        }
-        return got;
-    }
     if (bounce.size() < kBounceBytes)
         bounce.resize(kBounceBytes);
+    size_t got = 0;
     while (got < n) {
         const ssize_t k = pread(fd, bounce.data(), std::min(kBounceBytes, n - got), at + (off_t)got);
         if (k <= 0)
@@ -469,36 +460,6 @@ inline size_t read_into_ring(int fd, uint8_t *dst, size_t n, off_t at, std::vect
     }
     _mm_sfence();                                           // the stores are on their way before the chunk is reported read
     return got;
-}
-
-// Wait for a chunk's copy.  The events are blocking ones (a thread woken by an interrupt); WD_CHUNK_SPIN=1
-// polls instead, for experiments with what the wake-up costs.
-hipError_t wait_copied(hipEvent_t ev)
-{
-    static const bool spin = getenv("WD_CHUNK_SPIN") && atoi(getenv("WD_CHUNK_SPIN")) != 0;
-    if (!spin)
-        return hipEventSynchronize(ev);
-    for (;;) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e != hipErrorNotReady)
-            return e;
-        for (int i = 0; i < 64; i++)
-            __builtin_ia32_pause();
-    }
-}
-
-// how the ring's chunks are pinned (WD_RING_FLAGS: experiments with what the readers' writes cost the DMA)
-unsigned ring_flags()
-{
-    const char *e = getenv("WD_RING_FLAGS");
-    if (!e)
-        return hipHostMallocDefault;
-    unsigned f = 0;
-    if (strstr(e, "wc")) f |= hipHostMallocWriteCombined;
-    if (strstr(e, "noncoherent")) f |= hipHostMallocNonCoherent;
-    if (strstr(e, "coherent") && !strstr(e, "noncoherent")) f |= hipHostMallocCoherent;
-    if (strstr(e, "portable")) f |= hipHostMallocPortable;
-    return f;
 }
 
 // buffers of a batch: pinned ring, streams, arena for `arena_bytes` of compressed files, n job slots
@@ -524,17 +485,13 @@ extern "C++" int wd::inflate_prepare_shared(wd_ctx *ctx, int n_chunks)
         wd_ctx::InflateChunk &ch = ctx->inflate_chunks[c];
         if (!ch.copied && hipEventCreateWithFlags(&ch.copied, hipEventDisableTiming | hipEventBlockingSync) != hipSuccess)
             return WD_ERR_HIP;
-        if (!ch.pinned && hipHostMalloc((void **)&ch.pinned, ctx->inflate_chunk_cap + 64, ring_flags()) != hipSuccess)
+        if (!ch.pinned && hipHostMalloc((void **)&ch.pinned, ctx->inflate_chunk_cap + 64, hipHostMallocDefault) != hipSuccess)
             return WD_ERR_NOMEM;
     }
-    // the copy stream and as many decode streams as are used (creating and destroying a stream costs 1 - 3 ms)
-    const int n_dec = std::max(1, std::min(wd_ctx::kInflateStreams, getenv("WD_DECODE_STREAMS") ? atoi(getenv("WD_DECODE_STREAMS"))
-                                                                                                 : ctx->inflate_decode_streams));
-    for (int u = 0; u <= wd_ctx::kInflateStreams; u++) {
-        hipStream_t &st = ctx->inflate_streams[u];
-        if ((u < n_dec || u == wd_ctx::kInflateStreams) && !st && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess)
+    // the decode streams and the copy stream (creating and destroying a stream costs 1 - 3 ms)
+    for (hipStream_t &st : ctx->inflate_streams)
+        if (!st && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess)
             return WD_ERR_HIP;
-    }
     for (auto &ev : ctx->inflate_ready)
         if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
             return WD_ERR_HIP;
@@ -579,90 +536,73 @@ int inflate_prepare(wd_ctx *ctx, wd_ctx::InflateSlot &sl, int n_chunks, size_t a
     return WD_OK;
 }
 
-}  // namespace
+// ---- a batch through the GPU decoder ------------------------------------------------------------
+// Entry i of a batch is a gzip stream at some place of the file paths[i].  Reader threads bring the
+// streams into the pinned ring, the chunks go to the batch's arena one by one on the copy stream, and
+// launches on the decode streams inflate them.  A result is checked against its stream's trailer and
+// the format's own rule; whatever the GPU decoder did not take or did not like goes to the format's host
+// loader, whose verdict counts.  The format (BclFiles, CbclBlocks) says what differs:
+//   paths, plan(rc, pos, size, chunk_bytes)   where every entry's stream is (PENDING), or HOST, or its error
+//   out_room(i)                    arena bytes behind the compressed streams for entry i's output
+//   place(i, room, job)            where the decoder writes entry i's output (obase, out_cap)
+//   plain(i), copy_plain(i, bytes, dev, stream)   entries checked and copied as they are, not decoded
+//   decode_now(trailer, size)      decoded on the host by its reader thread at once
+//   kLaunchFiles, waves(nj, n_jobs), small_window(trailer, size)   how the entries are launched
+//   after_decode(stream, h_jobs, d_jobs, d_res, files, nj)   kernels queued behind a launch
+//   accept(i, result), host_load(i)
+enum : int { PENDING = 1, HOST = 2, EARLY = 3 };                         // beside the WD_* codes (<= 0)
 
-int wd_load_bcl_gz_batch(wd_ctx *ctx, int n_files, const char *const *paths, uint8_t *const *dst_dev,
-                         int64_t n_clusters, int threads, int *rc_out)
+extern "C++" {
+template <class Fmt>
+int inflate_batch(wd_ctx *ctx, Fmt &fmt, int n, int threads, int *rc_out)
 {
-    return wd_load_tile_files_batch(ctx, n_files, paths, dst_dev, nullptr, n_clusters, 1, threads, rc_out);
-}
-
-static int load_tile_files_batch_impl(wd_ctx *ctx, int n_files, const char *const *paths, uint8_t *const *dst_dev,
-                                      const uint8_t *is_filter, int64_t n_clusters, int well_stride, int threads, int *rc_out);
-
-int wd_load_tile_files_batch(wd_ctx *ctx, int n_files, const char *const *paths, uint8_t *const *dst_dev,
-                             const uint8_t *is_filter, int64_t n_clusters, int well_stride, int threads, int *rc_out)
-{
-    return guarded(ctx, [&] {
-        return load_tile_files_batch_impl(ctx, n_files, paths, dst_dev, is_filter, n_clusters, well_stride, threads, rc_out);
-    });
-}
-
-static int load_tile_files_batch_impl(wd_ctx *ctx, int n_files, const char *const *paths, uint8_t *const *dst_dev,
-                                      const uint8_t *is_filter, int64_t n_clusters, int well_stride, int threads, int *rc_out)
-{
-    if (well_stride != 1 && well_stride != 4)
-        return WD_ERR_ARG;
-    if (!ctx || n_files < 0 || (n_files && (!paths || !dst_dev)) || n_clusters < 0 || n_clusters > 0x7FFFFFF0ll)
-        return WD_ERR_ARG;
-    if (hipSetDevice(ctx->device) != hipSuccess)
-        return WD_ERR_HIP;
-    const auto call_t0 = std::chrono::steady_clock::now();               // (WD_INFLATE_STATS)
+    using clock = std::chrono::steady_clock;
+    auto ms = [](clock::time_point a, clock::time_point b) { return 1e3 * std::chrono::duration<double>(b - a).count(); };
+    const bool want_stats = getenv("WD_INFLATE_STATS") != nullptr;
+    const bool dma_probe = want_stats && atoi(getenv("WD_INFLATE_STATS")) >= 2;
+    const auto call_t0 = clock::now();
     // a slot for the whole call, the shared ring / streams only while this batch is read and launched
     InflateTurn batch_lock(ctx);
     wd_ctx::InflateSlot &slot = ctx->inflate_slots[batch_lock.ticket % wd_ctx::kInflateSlots];
     std::lock_guard<std::mutex> slot_lock(slot.mu);
     threads = reader_threads(threads);
-    const bool ring_direct = getenv("WD_RING_DIRECT") && atoi(getenv("WD_RING_DIRECT")) != 0;
     constexpr int kChunks = wd_ctx::kInflateChunks, kStreams = wd_ctx::kInflateStreams;
     const size_t chunk_bytes = ctx->inflate_chunk_bytes;
+    const auto turn_t0 = clock::now();                                   // (this call's turn has come)
 
-    enum : int { PENDING = 1, HOST = 2, EARLY = 3 };                     // beside the WD_* codes (<= 0)
-    std::vector<int> rc((size_t)n_files, PENDING), early_rc((size_t)n_files, WD_OK);
-    std::atomic<long long> n_early{0};
-    std::vector<size_t> size((size_t)n_files, 0), offset((size_t)n_files, 0);   // offset: in the group's chunk
-    std::vector<uint32_t> stream_off((size_t)n_files, 0);
-    std::vector<uint64_t> trailer((size_t)n_files, 0);                   // CRC-32 | length << 32, as the file ends
-    std::vector<int> group_of((size_t)n_files, -1);
+    std::vector<int> rc((size_t)n, PENDING), early_rc((size_t)n, WD_OK);
+    std::vector<uint64_t> pos((size_t)n, 0), trailer((size_t)n, 0);     // trailer: CRC-32 | length << 32, as the stream ends
+    std::vector<size_t> size((size_t)n, 0);
+    fmt.plan(rc, pos, size, chunk_bytes);
+    // groups of consecutive entries that fit a chunk; the arena holds the groups, then the entries' output rooms
+    std::vector<size_t> offset((size_t)n, 0), out_at((size_t)n, 0);    // offset: in the group's chunk
+    std::vector<uint32_t> stream_off((size_t)n, 0);
+    std::vector<int> group_of((size_t)n, -1);
     struct Group { int first, last; size_t bytes, arena_at; std::atomic<int> remaining{0}; };
     std::vector<std::unique_ptr<Group>> groups;
-    size_t arena_bytes = 0, n_jobs = 0;
-    const auto turn_t0 = std::chrono::steady_clock::now();               // (this call's turn has come)
-    // sizes, then groups of consecutive files that fit a chunk
-    for (int i = 0; i < n_files; i++) {
-        struct stat st;
-        if (!paths[i] || !dst_dev[i] || (((uintptr_t)dst_dev[i] & 3) && (well_stride == 1 || (is_filter && is_filter[i])))) {
-            rc[(size_t)i] = WD_ERR_ARG;
-        } else if (stat(paths[i], &st) != 0 || !S_ISREG(st.st_mode)) {
-            rc[(size_t)i] = WD_ERR_IO;                                   // FileNotFoundError in the reference
-        } else if (is_filter && is_filter[i] && (st.st_size < 12 || (int64_t)st.st_size != 12 + n_clusters)) {
-            rc[(size_t)i] = WD_ERR_FORMAT;                               // bcl_direct_reader.py:240
-        } else if ((size_t)st.st_size + 16 > chunk_bytes || st.st_size < 12 || (uint64_t)st.st_size > 0x1FFFFFF0ull ||
-                   (st.st_size < 18 && !(is_filter && is_filter[i]))) {
-            rc[(size_t)i] = HOST;
-        } else {
-            size[(size_t)i] = (size_t)st.st_size;
-            const size_t padded = (size[(size_t)i] + 15) & ~(size_t)15;
-            if (groups.empty() || groups.back()->bytes + padded > chunk_bytes)
-                groups.emplace_back(new Group{i, i, 0, arena_bytes});
-            Group &g = *groups.back();
-            offset[(size_t)i] = g.bytes;
-            g.bytes += padded;
-            arena_bytes += padded;
-            g.last = i;
-            g.remaining.fetch_add(1);
-            group_of[(size_t)i] = (int)groups.size() - 1;
-            n_jobs++;
-        }
+    size_t comp_bytes = 0, out_bytes = 0, n_jobs = 0;
+    for (int i = 0; i < n; i++) {
+        if (rc[(size_t)i] != PENDING)
+            continue;
+        const size_t padded = (size[(size_t)i] + 15) & ~(size_t)15;
+        if (groups.empty() || groups.back()->bytes + padded > chunk_bytes)
+            groups.emplace_back(new Group{i, i, 0, comp_bytes});
+        Group &g = *groups.back();
+        offset[(size_t)i] = g.bytes;
+        g.bytes += padded;
+        comp_bytes += padded;
+        g.last = i;
+        g.remaining.fetch_add(1);
+        group_of[(size_t)i] = (int)groups.size() - 1;
+        out_at[(size_t)i] = out_bytes;
+        out_bytes += fmt.out_room(i);
+        n_jobs++;
     }
     const int n_groups = (int)groups.size();
-    const auto stat_t1 = std::chrono::steady_clock::now();
+    const size_t out_base = (comp_bytes + 255) & ~(size_t)255;
+    const auto stat_t1 = clock::now();
     if (n_groups) {
-        // (interleaved layout: the planes are decoded into the arena and scattered into their byte lanes)
-        const size_t plane_room = well_stride == 4 ? (((size_t)n_clusters + 8 + 255) & ~(size_t)255) : 0;
-        const int prc = inflate_prepare(ctx, slot, std::min(n_groups, kChunks),
-                                        ((arena_bytes + 255) & ~(size_t)255) + plane_room * n_jobs, n_jobs);
-        if (prc)
+        if (const int prc = inflate_prepare(ctx, slot, std::min(n_groups, kChunks), out_base + out_bytes, n_jobs))
             return prc;
         // (the batch before may still be decoding; its chunk copies are behind us after this)
         if (hipStreamSynchronize(ctx->inflate_streams[kStreams]) != hipSuccess)
@@ -673,12 +613,12 @@ static int load_tile_files_batch_impl(wd_ctx *ctx, int n_files, const char *cons
     std::condition_variable cv;
     int free_upto = kChunks;                 // groups < free_upto may be filled
     bool abort_all = false;
-    std::atomic<int> next_file{0};
-
+    std::atomic<int> next_entry{0};
+    std::atomic<long long> n_early{0};
     auto reader = [&]() {
         for (;;) {
-            const int i = next_file.fetch_add(1);
-            if (i >= n_files)
+            const int i = next_entry.fetch_add(1);
+            if (i >= n)
                 return;
             const int g = group_of[(size_t)i];
             if (g < 0)
@@ -692,26 +632,18 @@ static int load_tile_files_batch_impl(wd_ctx *ctx, int n_files, const char *cons
             uint8_t *dst = ctx->inflate_chunks[g % kChunks].pinned + offset[(size_t)i];
             const size_t sz = size[(size_t)i];
             bool ok = false, early = false;
-            const int fd = open(paths[i], O_RDONLY);
+            const int fd = open(fmt.paths[i], O_RDONLY);
             if (fd >= 0) {
                 thread_local std::vector<uint8_t> bounce;
-                ok = read_into_ring(fd, dst, sz, 0, bounce, ring_direct) == sz;
+                ok = read_into_ring(fd, dst, sz, (off_t)pos[(size_t)i], bounce) == sz;
                 close(fd);
             }
-            if (ok && is_filter && is_filter[i]) {                       // .filter: header 0, 3, n (:148-152, :236), then the bytes
-                uint32_t head[3];
-                memcpy(head, dst, 12);
-                if (head[0] != 0 || head[1] != 3 || (int64_t)head[2] != n_clusters)
-                    rc[(size_t)i] = WD_ERR_FORMAT;
-            } else if (!ok || !inf_gzip_header(dst, sz, &stream_off[(size_t)i])) {
+            // (a plain entry is checked and copied by the chunk loop)
+            if (!ok || (!fmt.plain(i) && !inf_gzip_header(dst, sz, &stream_off[(size_t)i]))) {
                 rc[(size_t)i] = HOST;                                    // let the host path say what is wrong with it
-            } else {
+            } else if (!fmt.plain(i)) {
                 memcpy(&trailer[(size_t)i], dst + sz - 8, 8);
-                // A file that expands four hundredfold and more (a failed cycle: a plane of no-calls) holds
-                // stretches the GPU decoder declines (one piece of the stream, 256-fold).  Sending it
-                // through the launch only to decode it on the host afterwards would hold this batch back
-                // by a serial tail: this thread decodes it NOW, beside the reads, the copies and the launch.
-                if ((trailer[(size_t)i] >> 32) >= (uint64_t)sz * 400) {
+                if (fmt.decode_now(trailer[(size_t)i], sz)) {
                     early = true;
                     rc[(size_t)i] = EARLY;                               // (before the group is reported read: the chunk loop must not queue it)
                 }
@@ -721,8 +653,7 @@ static int load_tile_files_batch_impl(wd_ctx *ctx, int n_files, const char *cons
                 cv.notify_all();
             }
             if (early) {
-                const int hrc = wd_load_bcl_gz_strided(ctx, paths[i], dst_dev[i], n_clusters, well_stride);
-                early_rc[(size_t)i] = hrc;
+                early_rc[(size_t)i] = fmt.host_load(i);
                 n_early.fetch_add(1);
             }
         }
@@ -733,53 +664,46 @@ static int load_tile_files_batch_impl(wd_ctx *ctx, int n_files, const char *cons
         abort_all = true;
         cv.notify_all();
     };
-    if (pool.start(std::min(threads, std::max(1, n_files)), reader, ctx->test_thread_limit) == 0)
+    if (pool.start(std::min(threads, std::max(1, n)), reader, ctx->test_thread_limit) == 0)
         return WD_ERR_NOMEM;                     // not one reader thread could be started
 
-    // The chunks go to the arena one by one on the copy stream; a launch on the decode stream waits
+    // The chunks go to the arena one by one on the copy stream; a launch on a decode stream waits
     // for the copy of its last chunk (see kInflateLaunchFiles).
-    std::vector<int> job_file;                                           // file index of every job, in launch order
+    std::vector<int> job_file;                                           // entry of every job, in launch order
     job_file.reserve(n_jobs);
     int hip_rc = WD_OK;
     hipStream_t copy_stream = ctx->inflate_streams[kStreams];
-    const int copy_depth = std::max(1, std::min(kChunks - 1, getenv("WD_COPY_DEPTH") ? atoi(getenv("WD_COPY_DEPTH")) : 1));
-    const int n_dec = std::max(1, std::min(kStreams, getenv("WD_DECODE_STREAMS") ? atoi(getenv("WD_DECODE_STREAMS")) : ctx->inflate_decode_streams));
-    const size_t launch_files = (size_t)std::max(64, getenv("WD_LAUNCH_FILES") ? atoi(getenv("WD_LAUNCH_FILES")) : ctx->inflate_launch_files);
-    int si = (int)(ctx->inflate_launch_seq % (unsigned)n_dec);           // consecutive launches decode on the streams in turn
+    int si = (int)(ctx->inflate_launch_seq % (unsigned)kStreams);        // consecutive launches decode on the streams in turn
     unsigned used_streams = 0;                                           // bit u: this batch launched on stream u
     size_t j0 = 0;                                                       // first job of the launch being gathered
-    double wait_read_s = 0, wait_copy_s = 0;                             // (WD_INFLATE_STATS) what the chunk loop waits for
-    const bool dma_probe = getenv("WD_INFLATE_STATS") && atoi(getenv("WD_INFLATE_STATS")) >= 2;
+    double wait_read_ms = 0, wait_copy_ms = 0;                             // (WD_INFLATE_STATS) what the chunk loop waits for
     std::vector<hipEvent_t> dma_ev;
     size_t dma_bytes = 0;
-    const auto loop_t0 = std::chrono::steady_clock::now();
+    const auto loop_t0 = clock::now();
     for (int g = 0; g < n_groups && hip_rc == WD_OK; g++) {
         Group &grp = *groups[(size_t)g];
         {
-            const auto w0 = std::chrono::steady_clock::now();
+            const auto w0 = clock::now();
             std::unique_lock<std::mutex> lk(mu);
             cv.wait(lk, [&] { return grp.remaining.load() == 0; });
-            wait_read_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
+            wait_read_ms += ms(w0, clock::now());
         }
         wd_ctx::InflateChunk &ch = ctx->inflate_chunks[g % kChunks];
         uint8_t *dev = slot.arena + grp.arena_at;
-        std::vector<int> plain;                                          // .filter files of the chunk: copied, not decoded
+        std::vector<int> plain;                                          // entries of the chunk copied, not decoded
         for (int i = grp.first; i <= grp.last; i++) {
             if (group_of[(size_t)i] != g || rc[(size_t)i] != PENDING)
                 continue;
-            if (is_filter && is_filter[i]) {
+            if (fmt.plain(i)) {
                 plain.push_back(i);
                 continue;
             }
             InfJob &j = slot.h_jobs[job_file.size()];
             j.file = reinterpret_cast<const uint32_t *>(dev + offset[(size_t)i]);
-            j.obase = well_stride == 4 ? slot.arena + ((arena_bytes + 255) & ~(size_t)255) +
-                                             ((((size_t)n_clusters + 8 + 255) & ~(size_t)255) * job_file.size())
-                                       : dst_dev[i] - 4;
             j.file_bytes = (uint32_t)size[(size_t)i];
             j.stream_off = stream_off[(size_t)i];
-            j.out_cap = (uint32_t)(n_clusters + 4);
             j.pad_ = 0;
+            fmt.place(i, slot.arena + out_base + out_at[(size_t)i], j);
             job_file.push_back(i);
         }
         if (dma_probe && (int)dma_ev.size() < 2 * n_groups) {           // (WD_INFLATE_STATS=2: how long the engine itself takes)
@@ -798,19 +722,19 @@ static int load_tile_files_batch_impl(wd_ctx *ctx, int n_files, const char *cons
         }
         dma_bytes += grp.bytes;
         for (int i : plain) {
-            if (n_clusters > 0 && hipMemcpyAsync(dst_dev[i], dev + offset[(size_t)i] + 12, (size_t)n_clusters,
-                                                  hipMemcpyDeviceToDevice, copy_stream) != hipSuccess) {
+            // (WD_OK once the copy is queued: the call returns after the copy stream has drained)
+            rc[(size_t)i] = fmt.copy_plain(i, ch.pinned + offset[(size_t)i], dev + offset[(size_t)i], copy_stream);
+            if (rc[(size_t)i] == WD_ERR_HIP) {
                 hip_rc = WD_ERR_HIP;
                 break;
             }
-            rc[(size_t)i] = WD_OK;                                       // (the call returns after the copy stream has drained)
         }
         if (hip_rc != WD_OK)
             break;
-        // enough files for a launch, or the last chunk: decode them
-        if (g + 1 == n_groups || job_file.size() - j0 >= launch_files) {
+        // enough entries for a launch, or the last chunk: decode them
+        if (g + 1 == n_groups || job_file.size() - j0 >= Fmt::kLaunchFiles) {
             const unsigned nj = (unsigned)(job_file.size() - j0);
-            si = (int)(ctx->inflate_launch_seq % (unsigned)n_dec);
+            si = (int)(ctx->inflate_launch_seq % (unsigned)kStreams);
             hipStream_t stream = ctx->inflate_streams[si];
             if (nj) {
                 ctx->inflate_launch_seq++;
@@ -822,16 +746,12 @@ static int load_tile_files_batch_impl(wd_ctx *ctx, int n_files, const char *cons
                     hip_rc = WD_ERR_HIP;
                     break;
                 }
-                // waves per file: eight while every file of the launch gets a CU of its own (24 ms per
-                // file), else four (34 ms, two files per CU - three, 36 ms, when no file of the launch
-                // expands much: the small-window form); one wave per file (89 ms, three per CU) on request
-                // (a launch that is one of several of its batch shares the chip with the others: four waves)
-                const int waves = ctx->inflate_waves ? ctx->inflate_waves : (nj <= 256 && n_jobs <= 256) ? 8 : 4;
+                // waves per entry: the format's rule, or 1, 4 or 8 on request; the small-window form of four
+                // waves when the format allows it for every entry of the launch
+                const int waves = ctx->inflate_waves ? ctx->inflate_waves : fmt.waves(nj, n_jobs);
                 bool slim = true;
-                for (size_t q = j0; q < job_file.size() && slim; q++) {
-                    const int i = job_file[q];
-                    slim = (trailer[(size_t)i] >> 32) * 4 <= (uint64_t)size[(size_t)i] * 7;
-                }
+                for (size_t q = j0; q < job_file.size() && slim; q++)
+                    slim = fmt.small_window(trailer[(size_t)job_file[q]], size[(size_t)job_file[q]]);
                 InfJob *dj = slot.d_jobs + j0;
                 InfResult *dr = slot.d_res + j0;
                 if (waves == 8)
@@ -843,34 +763,28 @@ static int load_tile_files_batch_impl(wd_ctx *ctx, int n_files, const char *cons
                 else
                     hipLaunchKernelGGL((k_inflate<1, 512>), dim3(nj), dim3(64), 0, stream, dj, dr);
                 hipLaunchKernelGGL(k_inflate_crc, dim3(nj), dim3(256), 0, stream, dj, dr);
-                if (well_stride == 4 && n_clusters > 0)
-                    for (unsigned q = 0; q < nj; q++)
-                        hipLaunchKernelGGL(k_scatter_plane4,
-                                           dim3((unsigned)((n_clusters + 4ll * kBlock - 1) / (4ll * kBlock))), dim3(kBlock), 0,
-                                           stream, slot.h_jobs[j0 + q].obase + 4, (long long)n_clusters,
-                                           dst_dev[job_file[j0 + q]]);
+                fmt.after_decode(stream, slot.h_jobs + j0, dj, dr, job_file.data() + j0, nj);
                 if (hipGetLastError() != hipSuccess ||
-                    hipMemcpyAsync(slot.h_res + j0, slot.d_res + j0, sizeof(InfResult) * nj,
-                                   hipMemcpyDeviceToHost, stream) != hipSuccess) {
+                    hipMemcpyAsync(slot.h_res + j0, dr, sizeof(InfResult) * nj, hipMemcpyDeviceToHost, stream) != hipSuccess) {
                     hip_rc = WD_ERR_HIP;
                     break;
                 }
             }
             j0 = job_file.size();
         }
-        if (g >= copy_depth) {
-            // group g - copy_depth + kChunks wants the chunk of group g - copy_depth: once that copy is
-            // done the readers may fill it again.  copy_depth copies are queued at any time, so that the
-            // engine has the next one at hand when this thread is late in noticing that one has ended
-            // (it shares its CPUs with the readers)
-            const auto w0 = std::chrono::steady_clock::now();
-            if (wait_copied(ctx->inflate_chunks[(g - copy_depth) % kChunks].copied) != hipSuccess) {
+        if (g >= 1) {
+            // group g - 1 + kChunks wants the chunk of group g - 1: once that copy is done the readers may
+            // fill it again.  One copy stays queued behind the one in flight, so that the engine has the next
+            // one at hand when this thread is late in noticing that one has ended (it shares its CPUs with
+            // the readers)
+            const auto w0 = clock::now();
+            if (hipEventSynchronize(ctx->inflate_chunks[(g - 1) % kChunks].copied) != hipSuccess) {
                 hip_rc = WD_ERR_HIP;
                 break;
             }
-            wait_copy_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
+            wait_copy_ms += ms(w0, clock::now());
             std::lock_guard<std::mutex> lk(mu);
-            free_upto = g - copy_depth + 1 + kChunks;
+            free_upto = g + kChunks;
             cv.notify_all();
         }
     }
@@ -880,35 +794,31 @@ static int load_tile_files_batch_impl(wd_ctx *ctx, int n_files, const char *cons
         cv.notify_all();
     }
     pool.join();
-    std::vector<uint8_t> was_early((size_t)n_files, 0);
-    for (int i = 0; i < n_files; i++)
+    std::vector<uint8_t> was_early((size_t)n, 0);
+    for (int i = 0; i < n; i++)
         if (rc[(size_t)i] == EARLY) {
-            rc[(size_t)i] = early_rc[(size_t)i];                         // the host loader's verdict, as for every file it takes
+            rc[(size_t)i] = early_rc[(size_t)i];                         // the host loader's verdict, as for every entry it takes
             was_early[(size_t)i] = 1;
         }
     ctx->inflate_files_host += n_early.load();
     ctx->inflate_files_early += n_early.load();
-    if (getenv("WD_INFLATE_STATS")) {
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-            return 1e3 * std::chrono::duration<double>(b - a).count();
-        };
+    if (want_stats)
         fprintf(stderr, "[wd inflate] waited %.1f ms for its turn, %.1f ms of stat, %.1f ms of buffers and the copy stream; "
                         "chunk loop %.1f ms for %d chunks: waited %.1f ms for the readers, %.1f ms for chunk copies\n",
-                ms(call_t0, turn_t0), ms(turn_t0, stat_t1), ms(stat_t1, loop_t0),
-                ms(loop_t0, std::chrono::steady_clock::now()), n_groups, 1e3 * wait_read_s, 1e3 * wait_copy_s);
-    }
+                ms(call_t0, turn_t0), ms(turn_t0, stat_t1), ms(stat_t1, loop_t0), ms(loop_t0, clock::now()), n_groups,
+                wait_read_ms, wait_copy_ms);
     if (dma_probe && !dma_ev.empty()) {
         (void)hipStreamSynchronize(copy_stream);
         double busy = 0, span = 0, longest = 0;
         for (size_t q = 0; q + 1 < dma_ev.size(); q += 2) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, dma_ev[q], dma_ev[q + 1]);
-            busy += ms;
-            longest = std::max<double>(longest, ms);
+            float t = 0;
+            (void)hipEventElapsedTime(&t, dma_ev[q], dma_ev[q + 1]);
+            busy += t;
+            longest = std::max<double>(longest, t);
         }
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, dma_ev.front(), dma_ev.back());
-        span = ms;
+        float t = 0;
+        (void)hipEventElapsedTime(&t, dma_ev.front(), dma_ev.back());
+        span = t;
         fprintf(stderr, "[wd inflate] the copies themselves: %.1f MB in %zu copies, engine busy %.1f ms (%.1f GB/s while copying, "
                         "longest copy %.2f ms), first start to last end %.1f ms\n",
                 dma_bytes / 1e6, dma_ev.size() / 2, busy, dma_bytes / 1e6 / std::max(busy, 1e-9), longest, span);
@@ -916,7 +826,7 @@ static int load_tile_files_batch_impl(wd_ctx *ctx, int n_files, const char *cons
             (void)hipEventDestroy(e);
     }
     // the next batch may start reading; this one waits for its last results
-    // (.filter copies ride on the copy stream: the decode stream's event must come after them)
+    // (plain copies ride on the copy stream: the decode stream's event must come after them)
     // (the last launch's stream gathers the others the batch used, then signals the batch done)
     for (int u = 0; u < kStreams && hip_rc == WD_OK && n_groups; u++)
         if (u != si && (used_streams >> u & 1u) &&
@@ -931,27 +841,28 @@ static int load_tile_files_batch_impl(wd_ctx *ctx, int n_files, const char *cons
     if (hip_rc != WD_OK)
         (void)hipDeviceSynchronize();                                    // nothing of a failed call stays in flight
     batch_lock.unlock();
-    const auto launched_t = std::chrono::steady_clock::now();
+    const auto launched_t = clock::now();
     if (hip_rc == WD_OK && n_groups && hipEventSynchronize(slot.done) != hipSuccess)
         hip_rc = WD_ERR_HIP;
     if (hip_rc != WD_OK)
         return hip_rc;
 
-    const bool want_stats = getenv("WD_INFLATE_STATS") != nullptr;
     if (want_stats)
         fprintf(stderr, "[wd inflate] decoded %.1f ms after the last launch was queued, %.1f ms after the call began\n",
-                1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - launched_t).count(),
-                1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - call_t0).count());
+                ms(launched_t, clock::now()), ms(call_t0, clock::now()));
     unsigned long long st[14] = {0}, real_sum = 0;
     for (size_t j = 0; j < job_file.size(); j++) {
         const int i = job_file[j];
         const InfResult &r = slot.h_res[j];
         const uint32_t crc = (uint32_t)trailer[(size_t)i], isize = (uint32_t)(trailer[(size_t)i] >> 32);
         const bool good = r.status == INF_OK && (size_t)r.end_byte + 8 == size[(size_t)i] && crc == r.crc &&
-                          isize == r.produced && (int64_t)r.produced == n_clusters + 4 && (int64_t)r.head == n_clusters;
+                          isize == r.produced && fmt.accept(i, r);
         rc[(size_t)i] = good ? WD_OK : HOST;
         real_sum += r.t_real;
         if (want_stats) {
+            if (!good)
+                fprintf(stderr, "[wd inflate] entry %d declined: status %u produced %u (room %u) end %u of %zu crc %08x/%08x isize %u\n",
+                        i, r.status, r.produced, slot.h_jobs[j].out_cap, r.end_byte, size[(size_t)i], r.crc, crc, isize);
             const unsigned long long v[12] = {r.t_header, r.t_build, r.t_stage, r.t_pass, r.t_emit, r.t_resolve,
                                               r.t_flush, r.t_total, r.windows, r.passes, r.rounds, r.blocks};
             for (int q = 0; q < 12; q++)
@@ -981,13 +892,13 @@ static int load_tile_files_batch_impl(wd_ctx *ctx, int n_files, const char *cons
 
     // whatever the GPU decoder did not take or did not like: the host loader, whose verdict counts
     std::vector<int> todo;
-    for (int i = 0; i < n_files; i++)
+    long long by_gpu = 0;
+    for (int i = 0; i < n; i++) {
         if (rc[(size_t)i] == HOST || rc[(size_t)i] == PENDING)
             todo.push_back(i);
+        by_gpu += rc[(size_t)i] == WD_OK && !fmt.plain(i) && !was_early[(size_t)i];
+    }
     ctx->inflate_files_host += (long long)todo.size();
-    long long by_gpu = 0;
-    for (int i = 0; i < n_files; i++)
-        by_gpu += rc[(size_t)i] == WD_OK && !(is_filter && is_filter[i]) && !was_early[(size_t)i];
     ctx->inflate_files_gpu += by_gpu;
     if (!todo.empty()) {
         std::atomic<size_t> next{0};
@@ -996,9 +907,7 @@ static int load_tile_files_batch_impl(wd_ctx *ctx, int n_files, const char *cons
                 const size_t k = next.fetch_add(1);
                 if (k >= todo.size())
                     return;
-                const int i = todo[k];
-                rc[(size_t)i] = is_filter && is_filter[i] ? wd_load_filter(ctx, paths[i], dst_dev[i], n_clusters)
-                                                          : wd_load_bcl_gz_strided(ctx, paths[i], dst_dev[i], n_clusters, well_stride);
+                rc[(size_t)todo[k]] = fmt.host_load(todo[k]);
             }
         };
         Crew hp;
@@ -1007,13 +916,108 @@ static int load_tile_files_batch_impl(wd_ctx *ctx, int n_files, const char *cons
         hp.join();
     }
     int first = WD_OK;
-    for (int i = 0; i < n_files; i++) {
+    for (int i = 0; i < n; i++) {
         if (rc_out)
             rc_out[i] = rc[(size_t)i];
         if (first == WD_OK && rc[(size_t)i] != WD_OK)
             first = rc[(size_t)i];
     }
     return first;
+}
+}  // extern "C++"
+
+// .bcl.gz planes and .filter files (wd_load_tile_files_batch): an entry is a whole file
+struct BclFiles {
+    wd_ctx *ctx;
+    const char *const *paths;
+    uint8_t *const *dst_dev;
+    const uint8_t *is_filter;
+    int64_t n_clusters;
+    int well_stride;
+    static constexpr size_t kLaunchFiles = wd_ctx::kInflateLaunchFiles;
+
+    void plan(std::vector<int> &rc, std::vector<uint64_t> &, std::vector<size_t> &size, size_t chunk_bytes) const
+    {
+        for (int i = 0; i < (int)rc.size(); i++) {
+            struct stat st;
+            if (!paths[i] || !dst_dev[i] || (((uintptr_t)dst_dev[i] & 3) && (well_stride == 1 || plain(i))))
+                rc[(size_t)i] = WD_ERR_ARG;
+            else if (stat(paths[i], &st) != 0 || !S_ISREG(st.st_mode))
+                rc[(size_t)i] = WD_ERR_IO;                               // FileNotFoundError in the reference
+            else if (plain(i) && (st.st_size < 12 || (int64_t)st.st_size != 12 + n_clusters))
+                rc[(size_t)i] = WD_ERR_FORMAT;                           // bcl_direct_reader.py:240
+            else if ((size_t)st.st_size + 16 > chunk_bytes || st.st_size < 12 || (uint64_t)st.st_size > 0x1FFFFFF0ull ||
+                     (st.st_size < 18 && !plain(i)))
+                rc[(size_t)i] = HOST;
+            else
+                size[(size_t)i] = (size_t)st.st_size;
+        }
+    }
+    // (interleaved layout: the planes are decoded into the arena and scattered into their byte lanes)
+    size_t out_room(int i) const { return well_stride == 4 && !plain(i) ? ((size_t)n_clusters + 8 + 255) & ~(size_t)255 : 0; }
+    void place(int i, uint8_t *room, InfJob &j) const
+    {
+        j.obase = well_stride == 4 ? room : dst_dev[i] - 4;
+        j.out_cap = (uint32_t)(n_clusters + 4);
+    }
+    bool plain(int i) const { return is_filter && is_filter[i]; }
+    int copy_plain(int i, const uint8_t *file, const uint8_t *file_dev, hipStream_t st) const
+    {
+        uint32_t head[3];                                                // .filter: header 0, 3, n (:148-152, :236), then the bytes
+        memcpy(head, file, 12);
+        if (head[0] != 0 || head[1] != 3 || (int64_t)head[2] != n_clusters)
+            return WD_ERR_FORMAT;
+        return n_clusters > 0 && hipMemcpyAsync(dst_dev[i], file_dev + 12, (size_t)n_clusters, hipMemcpyDeviceToDevice, st) != hipSuccess
+                   ? WD_ERR_HIP
+                   : WD_OK;
+    }
+    // A file that expands four hundredfold and more (a failed cycle: a plane of no-calls) holds stretches
+    // the GPU decoder declines (one piece of the stream, 256-fold).  Sending it through the launch only to
+    // decode it on the host afterwards would hold this batch back by a serial tail: its reader thread
+    // decodes it NOW, beside the reads, the copies and the launch.
+    static bool decode_now(uint64_t trailer, size_t size) { return (trailer >> 32) >= (uint64_t)size * 400; }
+    // waves per file: eight while every file of the launch gets a CU of its own (24 ms per file), else
+    // four (34 ms, two files per CU - three, 36 ms, when no file of the launch expands much: the
+    // small-window form); one wave per file (89 ms, three per CU) on request
+    // (a launch that is one of several of its batch shares the chip with the others: four waves)
+    static int waves(unsigned nj, size_t n_jobs) { return nj <= 256 && n_jobs <= 256 ? 8 : 4; }
+    static bool small_window(uint64_t trailer, size_t size) { return (trailer >> 32) * 4 <= (uint64_t)size * 7; }
+    void after_decode(hipStream_t st, const InfJob *h_jobs, const InfJob *, const InfResult *, const int *files, unsigned nj) const
+    {
+        if (well_stride == 4 && n_clusters > 0)
+            for (unsigned q = 0; q < nj; q++)
+                hipLaunchKernelGGL(k_scatter_plane4, dim3((unsigned)((n_clusters + 4ll * kBlock - 1) / (4ll * kBlock))), dim3(kBlock),
+                                   0, st, h_jobs[q].obase + 4, (long long)n_clusters, dst_dev[files[q]]);
+    }
+    bool accept(int, const InfResult &r) const { return (int64_t)r.produced == n_clusters + 4 && (int64_t)r.head == n_clusters; }
+    int host_load(int i) const
+    {
+        return plain(i) ? wd_load_filter(ctx, paths[i], dst_dev[i], n_clusters)
+                        : wd_load_bcl_gz_strided(ctx, paths[i], dst_dev[i], n_clusters, well_stride);
+    }
+};
+
+}  // namespace
+
+int wd_load_bcl_gz_batch(wd_ctx *ctx, int n_files, const char *const *paths, uint8_t *const *dst_dev,
+                         int64_t n_clusters, int threads, int *rc_out)
+{
+    return wd_load_tile_files_batch(ctx, n_files, paths, dst_dev, nullptr, n_clusters, 1, threads, rc_out);
+}
+
+int wd_load_tile_files_batch(wd_ctx *ctx, int n_files, const char *const *paths, uint8_t *const *dst_dev,
+                             const uint8_t *is_filter, int64_t n_clusters, int well_stride, int threads, int *rc_out)
+{
+    return guarded(ctx, [&] {
+        if (well_stride != 1 && well_stride != 4)
+            return WD_ERR_ARG;
+        if (!ctx || n_files < 0 || (n_files && (!paths || !dst_dev)) || n_clusters < 0 || n_clusters > 0x7FFFFFF0ll)
+            return WD_ERR_ARG;
+        if (hipSetDevice(ctx->device) != hipSuccess)
+            return WD_ERR_HIP;
+        BclFiles fmt{ctx, paths, dst_dev, is_filter, n_clusters, well_stride};
+        return inflate_batch(ctx, fmt, n_files, threads, rc_out);
+    });
 }
 
 int wd_load_filter(wd_ctx *ctx, const char *path, uint8_t *dst_dev, int64_t n_clusters)
@@ -1047,6 +1051,79 @@ try {
     return WD_OK;
 } WD_CATCH
 
+namespace {
+
+// A .cbcl file's header '<HIBBI' + bins and its tile table (bcl_direct_reader.py:263-295)
+struct CbclBlock {
+    uint64_t pos;                                            // where the tile's gzip block starts in the file
+    uint32_t usize, csize;
+    int excluded;                                            // only the wells that pass the filter are in the block
+};
+struct CbclTable {
+    uint32_t hsize = 0;
+    std::vector<uint8_t> offs;                               // (tile, clusters, usize, csize) per tile, then the excluded flag
+    // -> WD_OK, or WD_ERR_FORMAT for a tile that is not in the table (assert t_number == tile_as_int, :295)
+    int find(int tile_number, CbclBlock &b) const
+    {
+        uint64_t pos = hsize;
+        for (size_t t = 0; t + 16 < offs.size(); t += 16) {
+            uint32_t rec[4];
+            memcpy(rec, offs.data() + t, 16);
+            if ((int)rec[0] == tile_number) {
+                b = CbclBlock{pos, rec[2], rec[3], offs.back() ? 1 : 0};
+                return WD_OK;
+            }
+            pos += rec[3];
+        }
+        return WD_ERR_FORMAT;
+    }
+};
+
+// -> WD_OK, WD_ERR_IO (the file cannot be opened) or WD_ERR_FORMAT
+int read_cbcl_table(const char *path, CbclTable &t)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f)
+        return WD_ERR_IO;
+    const int rc = [&] {
+        uint8_t head[12 + 4 * 8 + 4];                        // header, the four bins, the tile count
+        uint16_t version;
+        uint32_t bins, tile_count;
+        if (fread(head, 1, 12, f) != 12)
+            return WD_ERR_FORMAT;
+        memcpy(&version, head, 2);
+        memcpy(&t.hsize, head + 2, 4);
+        memcpy(&bins, head + 8, 4);
+        if (version != 1 || t.hsize <= 32 || head[6] != 2 || head[7] != 2 || bins != 4)   // :266-270
+            return WD_ERR_FORMAT;
+        if (fread(head + 12, 1, sizeof(head) - 12, f) != sizeof(head) - 12)
+            return WD_ERR_FORMAT;
+        memcpy(&tile_count, head + sizeof(head) - 4, 4);
+        if (tile_count > (1u << 20))                         // (before any allocation sized by it)
+            return WD_ERR_FORMAT;
+        t.offs.resize((size_t)tile_count * 16 + 1);
+        return fread(t.offs.data(), 1, t.offs.size(), f) == t.offs.size() ? WD_OK : WD_ERR_FORMAT;
+    }();
+    fclose(f);
+    return rc;
+}
+
+// A packed block (two wells per byte) -> its plane: nibble -> byte, and the excluded-wells indirection
+// through the tile's filter (the chunk sums of the passing wells go to `sums`, one word per kCbclChunk wells)
+void queue_cbcl_expand(hipStream_t st, const uint8_t *packed, long long n_records, const uint8_t *filter_dev, uint32_t *sums,
+                       int64_t n_clusters, int excluded, uint8_t *dst_dev, int well_stride)
+{
+    const int chunks = (int)((n_clusters + kCbclChunk - 1) / kCbclChunk);
+    if (excluded) {
+        hipLaunchKernelGGL(k_cbcl_count, dim3(chunks), dim3(kBlock), 0, st, filter_dev, (long long)n_clusters, sums);
+        hipLaunchKernelGGL(k_cbcl_scan, dim3(1), dim3(kBlock), 0, st, sums, chunks);
+    }
+    hipLaunchKernelGGL(k_cbcl_expand, dim3(chunks), dim3(kBlock), 0, st, packed, n_records, filter_dev, sums,
+                       (long long)n_clusters, excluded, dst_dev, well_stride);
+}
+
+}  // namespace
+
 int wd_load_cbcl_tile(wd_ctx *ctx, const char *path, int tile_number, const uint8_t *filter_dev,
                       int64_t n_clusters, uint8_t *dst_dev)
 {
@@ -1060,53 +1137,25 @@ try {
         return WD_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess)
         return WD_ERR_HIP;
-    FILE *f = fopen(path, "rb");
-    if (!f)
-        return WD_ERR_IO;
-    // header '<HIBBI' + bins + tile table (bcl_direct_reader.py:263-292)
-    uint8_t head[12];
-    auto bail = [&](int code) { fclose(f); return code; };
-    if (fread(head, 1, 12, f) != 12)
-        return bail(WD_ERR_FORMAT);
-    uint16_t version; uint32_t hsize, bins;
-    memcpy(&version, head, 2); memcpy(&hsize, head + 2, 4); memcpy(&bins, head + 8, 4);
-    if (version != 1 || hsize <= 32 || head[6] != 2 || head[7] != 2 || bins != 4)   // :266-270
-        return bail(WD_ERR_FORMAT);
-    std::vector<uint8_t> tab((size_t)bins * 8 + 4);
-    if (fread(tab.data(), 1, tab.size(), f) != tab.size())
-        return bail(WD_ERR_FORMAT);
-    uint32_t tile_count;
-    memcpy(&tile_count, tab.data() + tab.size() - 4, 4);
-    if (tile_count > (1u << 20))
-        return bail(WD_ERR_FORMAT);
-    std::vector<uint8_t> offs((size_t)tile_count * 16 + 1);
-    if (fread(offs.data(), 1, offs.size(), f) != offs.size())
-        return bail(WD_ERR_FORMAT);
-    const int excluded = offs.back() ? 1 : 0;
-    uint64_t pos = hsize;
-    uint32_t usize = 0, csize = 0;
-    bool found = false;
-    for (uint32_t t = 0; t < tile_count; t++) {
-        uint32_t rec[4];
-        memcpy(rec, offs.data() + (size_t)t * 16, 16);
-        if ((int)rec[0] == tile_number) {
-            usize = rec[2];
-            csize = rec[3];
-            found = true;
-            break;
-        }
-        pos += rec[3];
-    }
-    if (!found)
-        return bail(WD_ERR_FORMAT);                          // assert t_number == tile_as_int (:295)
+    CbclTable tab;
+    CbclBlock blk;
+    int rc = read_cbcl_table(path, tab);
+    if (rc == WD_OK)
+        rc = tab.find(tile_number, blk);
+    if (rc != WD_OK)
+        return rc;
+    const uint32_t usize = blk.usize, csize = blk.csize;
     std::vector<uint8_t> raw((size_t)csize + 16, 0);         // fast_gunzip reads in 8-byte words
-    if (fseek(f, (long)pos, SEEK_SET) != 0 || (csize && fread(raw.data(), 1, csize, f) != csize))
-        return bail(WD_ERR_IO);
-    fclose(f);
+    FILE *f = fopen(path, "rb");
+    const bool read = f && fseek(f, (long)blk.pos, SEEK_SET) == 0 && (!csize || fread(raw.data(), 1, csize, f) == csize);
+    if (f)
+        fclose(f);
+    if (!read)
+        return WD_ERR_IO;
 
     SlotLease lease(ctx);
     wd_ctx::IngestSlot *sl = lease.slot;
-    int rc = slot_reserve(ctx, sl, (size_t)usize + 64 + kInflateSlack);
+    rc = slot_reserve(ctx, sl, (size_t)usize + 64 + kInflateSlack);
     if (rc)
         return rc;
     size_t produced = 0;
@@ -1142,34 +1191,110 @@ try {
         return WD_OK;
     if (produced && hipMemcpyAsync(sl->dev, sl->pinned, produced, hipMemcpyHostToDevice, sl->stream) != hipSuccess)
         return WD_ERR_HIP;
-    if (excluded) {
-        hipLaunchKernelGGL(k_cbcl_count, dim3(chunks), dim3(kBlock), 0, sl->stream, filter_dev,
-                           (long long)n_clusters, sums);
-        hipLaunchKernelGGL(k_cbcl_scan, dim3(1), dim3(kBlock), 0, sl->stream, sums, chunks);
-    }
-    hipLaunchKernelGGL(k_cbcl_expand, dim3(chunks), dim3(kBlock), 0, sl->stream, sl->dev, n_records,
-                       filter_dev, sums, (long long)n_clusters, excluded, dst_dev, well_stride);
+    queue_cbcl_expand(sl->stream, sl->dev, n_records, filter_dev, sums, n_clusters, blk.excluded, dst_dev, well_stride);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(sl->stream) != hipSuccess)
         return WD_ERR_HIP;
     // the reference dies with IndexError only if a *requested* well lies beyond the block; a
     // block shorter than the tile is reported the same way here when no filter can excuse it
-    if (!excluded && n_records < n_clusters)
+    if (!blk.excluded && n_records < n_clusters)
         return WD_ERR_INDEX;
     return WD_OK;
 } WD_CATCH
 
 // ---- a batch of NovaSeq tile blocks through the GPU decoder -----------------------------------
+namespace {
+
 // Entry i: the block of tile tile_number[i] in the .cbcl file paths[i] (all tiles of a surface share
 // one file per cycle) -> an n_clusters-byte plane at dst_dev[i], exactly what wd_load_cbcl_tile does
-// (bcl_direct_reader.py:255-325).  The files' headers and tile tables are parsed on the host (once
-// per file), reader threads bring the tiles' gzip blocks into the pinned ring, the GPU inflates them
-// (one launch for the batch) into packed planes in the arena and expands those (nibble -> byte, the
-// excluded-wells indirection through the tile's filter, which must already be in filter_dev[i]).
+// (bcl_direct_reader.py:255-325).  The files' tile tables are read on the host (once per file), the GPU
+// inflates the blocks (one launch for the batch) into packed planes in the arena and expands those
+// (the excluded-wells indirection goes through the tile's filter, which must already be in filter_dev[i]).
 // An entry the GPU decoder declines or whose checks fail (CRC-32, length) goes through
 // wd_load_cbcl_tile, whose return code is reported; so do the table checks' failures.
-static int load_cbcl_batch_impl(wd_ctx *ctx, int n, const char *const *paths, const int *tile_number,
-                                const uint8_t *const *filter_dev, uint8_t *const *dst_dev, int64_t n_clusters, int well_stride,
-                                int threads, int *rc_out);
+struct CbclBlocks {
+    wd_ctx *ctx;
+    const char *const *paths;
+    const int *tile_number;
+    const uint8_t *const *filter_dev;
+    uint8_t *const *dst_dev;
+    int64_t n_clusters;
+    int well_stride;
+    std::vector<CbclBlock> blk;
+    static constexpr size_t kLaunchFiles = SIZE_MAX;
+
+    void plan(std::vector<int> &rc, std::vector<uint64_t> &pos, std::vector<size_t> &size, size_t chunk_bytes)
+    {
+        // the tile tables, once per file (:263-295)
+        std::vector<int> order(rc.size());
+        for (size_t i = 0; i < order.size(); i++)
+            order[i] = (int)i;
+        std::sort(order.begin(), order.end(), [&](int a, int b) {
+            const int c = paths[a] && paths[b] ? strcmp(paths[a], paths[b]) : (paths[a] ? 1 : 0) - (paths[b] ? 1 : 0);
+            return c < 0 || (c == 0 && a < b);
+        });
+        blk.resize(rc.size());
+        for (size_t k = 0; k < order.size();) {
+            const char *path = paths[order[k]];
+            size_t k1 = k + 1;
+            while (path && k1 < order.size() && paths[order[k1]] && strcmp(paths[order[k1]], path) == 0)
+                k1++;
+            CbclTable tab;
+            const int file_rc = path ? read_cbcl_table(path, tab) : WD_ERR_ARG;
+            for (; k < k1; k++) {
+                const size_t i = (size_t)order[k];
+                CbclBlock &b = blk[i];
+                int r = file_rc != WD_OK ? file_rc : !dst_dev[i] || !filter_dev[i] ? WD_ERR_ARG : tab.find(tile_number[i], b);
+                if (r == WD_OK && ((size_t)b.csize + 32 > chunk_bytes || b.csize < 18 || b.usize == 0 || b.usize > 0x3FFFFFF0u))
+                    r = HOST;
+                if (r != WD_OK)
+                    rc[i] = r;
+                pos[i] = b.pos;
+                size[i] = b.csize;
+            }
+        }
+    }
+    // the packed plane, then its chunk sums
+    size_t out_room(int i) const
+    {
+        return (((size_t)blk[(size_t)i].usize + 255) & ~(size_t)255) +
+               (size_t)std::max((n_clusters + kCbclChunk - 1) / kCbclChunk, (int64_t)1) * 4 + 252;
+    }
+    void place(int i, uint8_t *room, InfJob &j) const
+    {
+        j.obase = room;
+        j.out_cap = blk[(size_t)i].usize;
+    }
+    static bool plain(int) { return false; }
+    static int copy_plain(int, const uint8_t *, const uint8_t *, hipStream_t) { return WD_OK; }
+    static bool decode_now(uint64_t, size_t) { return false; }
+    static int waves(unsigned nj, size_t) { return nj <= 256 ? 8 : 4; }
+    static bool small_window(uint64_t, size_t) { return false; }
+    void after_decode(hipStream_t st, const InfJob *h_jobs, const InfJob *d_jobs, const InfResult *d_res, const int *files,
+                      unsigned nj) const
+    {
+        hipLaunchKernelGGL(k_inflate_heads, dim3((nj + 255) / 256), dim3(256), 0, st, d_jobs, d_res, (int)nj);
+        // (the expansions take the table's block length on trust; the results say whether it held)
+        for (unsigned q = 0; q < nj && n_clusters > 0; q++) {
+            const CbclBlock &b = blk[(size_t)files[q]];
+            uint8_t *packed = h_jobs[q].obase;
+            queue_cbcl_expand(st, packed, (long long)b.usize * 2, filter_dev[files[q]],
+                              (uint32_t *)(packed + (((size_t)b.usize + 255) & ~(size_t)255)), n_clusters, b.excluded,
+                              dst_dev[files[q]], well_stride);
+        }
+    }
+    // (a block shorter than the tile without excluded wells: the host path's IndexError)
+    bool accept(int i, const InfResult &r) const
+    {
+        const CbclBlock &b = blk[(size_t)i];
+        return r.produced == b.usize && (b.excluded || (long long)b.usize * 2 >= n_clusters);
+    }
+    int host_load(int i) const
+    {
+        return wd_load_cbcl_tile_strided(ctx, paths[i], tile_number[i], filter_dev[i], n_clusters, dst_dev[i], well_stride);
+    }
+};
+
+}  // namespace
 
 int wd_load_cbcl_batch(wd_ctx *ctx, int n, const char *const *paths, const int *tile_number,
                        const uint8_t *const *filter_dev, uint8_t *const *dst_dev, int64_t n_clusters, int threads,
@@ -1183,338 +1308,14 @@ int wd_load_cbcl_batch_strided(wd_ctx *ctx, int n, const char *const *paths, con
                                int well_stride, int threads, int *rc_out)
 {
     return guarded(ctx, [&] {
-        return load_cbcl_batch_impl(ctx, n, paths, tile_number, filter_dev, dst_dev, n_clusters, well_stride, threads, rc_out);
-    });
-}
-
-static int load_cbcl_batch_impl(wd_ctx *ctx, int n, const char *const *paths, const int *tile_number,
-                                const uint8_t *const *filter_dev, uint8_t *const *dst_dev, int64_t n_clusters, int well_stride,
-                                int threads, int *rc_out)
-{
-    if (!ctx || n < 0 || (n && (!paths || !tile_number || !filter_dev || !dst_dev)) || n_clusters < 0 ||
-        n_clusters > 0x7FFFFFF0ll || (well_stride != 1 && well_stride != 4))
-        return WD_ERR_ARG;
-    if (hipSetDevice(ctx->device) != hipSuccess)
-        return WD_ERR_HIP;
-    InflateTurn batch_lock(ctx);
-    wd_ctx::InflateSlot &slot = ctx->inflate_slots[batch_lock.ticket % wd_ctx::kInflateSlots];
-    std::lock_guard<std::mutex> slot_lock(slot.mu);
-    threads = reader_threads(threads);
-    const bool ring_direct = getenv("WD_RING_DIRECT") && atoi(getenv("WD_RING_DIRECT")) != 0;
-    constexpr int kChunks = wd_ctx::kInflateChunks, kStreams = wd_ctx::kInflateStreams;
-    const size_t chunk_bytes = ctx->inflate_chunk_bytes;
-    enum : int { PENDING = 1, HOST = 2 };
-    struct Entry { uint64_t pos = 0; uint32_t usize = 0, csize = 0, stream_off = 0; int excluded = 0; };
-    std::vector<Entry> ent((size_t)n);
-    std::vector<int> rc((size_t)n, PENDING);
-    // the tile tables, once per file (:263-295)
-    {
-        std::vector<int> order((size_t)n);
-        for (int i = 0; i < n; i++)
-            order[(size_t)i] = i;
-        std::sort(order.begin(), order.end(), [&](int a, int b) {
-            const int c = paths[a] && paths[b] ? strcmp(paths[a], paths[b]) : (paths[a] ? 1 : 0) - (paths[b] ? 1 : 0);
-            return c < 0 || (c == 0 && a < b);
-        });
-        for (size_t k = 0; k < order.size();) {
-            size_t k1 = k;
-            const char *path = paths[order[k]];
-            while (k1 < order.size() && paths[order[k1]] && path && strcmp(paths[order[k1]], path) == 0)
-                k1++;
-            if (k1 == k)
-                k1 = k + 1;
-            int file_rc = WD_OK;
-            std::vector<uint8_t> offs;
-            uint32_t hsize = 0, tile_count = 0;
-            FILE *f = path ? fopen(path, "rb") : nullptr;
-            if (!path) {
-                file_rc = WD_ERR_ARG;
-            } else if (!f) {
-                file_rc = WD_ERR_IO;
-            } else {
-                uint8_t head[12];
-                uint16_t version = 0;
-                uint32_t bins = 0;
-                if (fread(head, 1, 12, f) != 12) {
-                    file_rc = WD_ERR_FORMAT;
-                } else {
-                    memcpy(&version, head, 2);
-                    memcpy(&hsize, head + 2, 4);
-                    memcpy(&bins, head + 8, 4);
-                    if (version != 1 || hsize <= 32 || head[6] != 2 || head[7] != 2 || bins != 4)   // :266-270
-                        file_rc = WD_ERR_FORMAT;
-                }
-                if (file_rc == WD_OK) {
-                    std::vector<uint8_t> tab((size_t)bins * 8 + 4);
-                    if (fread(tab.data(), 1, tab.size(), f) != tab.size()) {
-                        file_rc = WD_ERR_FORMAT;
-                    } else {
-                        memcpy(&tile_count, tab.data() + tab.size() - 4, 4);
-                        if (tile_count > (1u << 20)) {                   // (before any allocation sized by it)
-                            file_rc = WD_ERR_FORMAT;
-                            tile_count = 0;
-                        } else {
-                            offs.resize((size_t)tile_count * 16 + 1);
-                            if (fread(offs.data(), 1, offs.size(), f) != offs.size())
-                                file_rc = WD_ERR_FORMAT;
-                        }
-                    }
-                }
-                fclose(f);
-            }
-            for (size_t q = k; q < k1; q++) {
-                const int i = order[q];
-                if (file_rc != WD_OK || !dst_dev[i] || !filter_dev[i]) {
-                    rc[(size_t)i] = file_rc != WD_OK ? file_rc : WD_ERR_ARG;
-                    continue;
-                }
-                uint64_t pos = hsize;
-                bool found = false;
-                for (uint32_t t = 0; t < tile_count; t++) {
-                    uint32_t rec[4];
-                    memcpy(rec, offs.data() + (size_t)t * 16, 16);
-                    if ((int)rec[0] == tile_number[i]) {
-                        ent[(size_t)i].pos = pos;
-                        ent[(size_t)i].usize = rec[2];
-                        ent[(size_t)i].csize = rec[3];
-                        ent[(size_t)i].excluded = offs.back() ? 1 : 0;
-                        found = true;
-                        break;
-                    }
-                    pos += rec[3];
-                }
-                if (!found)
-                    rc[(size_t)i] = WD_ERR_FORMAT;                       // assert t_number == tile_as_int (:295)
-            }
-            k = k1;
-        }
-    }
-    // chunks of the ring, room in the arena: [compressed blocks][packed planes + chunk sums]
-    const int exp_chunks = (int)((n_clusters + kCbclChunk - 1) / kCbclChunk);
-    std::vector<size_t> offset((size_t)n, 0), out_at((size_t)n, 0);
-    std::vector<int> group_of((size_t)n, -1);
-    struct Group { int first, last; size_t bytes, arena_at; std::atomic<int> remaining{0}; };
-    std::vector<std::unique_ptr<Group>> groups;
-    size_t comp_bytes = 0, out_bytes = 0, n_jobs = 0;
-    for (int i = 0; i < n; i++) {
-        if (rc[(size_t)i] != PENDING)
-            continue;
-        const Entry &e = ent[(size_t)i];
-        if ((size_t)e.csize + 32 > chunk_bytes || e.csize < 18 || e.usize == 0 || e.usize > 0x3FFFFFF0u) {
-            rc[(size_t)i] = HOST;
-            continue;
-        }
-        const size_t padded = ((size_t)e.csize + 15) & ~(size_t)15;
-        if (groups.empty() || groups.back()->bytes + padded > chunk_bytes)
-            groups.emplace_back(new Group{i, i, 0, comp_bytes});
-        Group &g = *groups.back();
-        offset[(size_t)i] = g.bytes;
-        g.bytes += padded;
-        comp_bytes += padded;
-        g.last = i;
-        g.remaining.fetch_add(1);
-        group_of[(size_t)i] = (int)groups.size() - 1;
-        out_at[(size_t)i] = out_bytes;
-        out_bytes += (((size_t)e.usize + 255) & ~(size_t)255) + (size_t)std::max(exp_chunks, 1) * 4 + 252;
-        n_jobs++;
-    }
-    const int n_groups = (int)groups.size();
-    if (n_groups) {
-        const int prc = inflate_prepare(ctx, slot, std::min(n_groups, kChunks), comp_bytes + out_bytes + 256, n_jobs);
-        if (prc)
-            return prc;
-        if (hipStreamSynchronize(ctx->inflate_streams[kStreams]) != hipSuccess)
+        if (!ctx || n < 0 || (n && (!paths || !tile_number || !filter_dev || !dst_dev)) || n_clusters < 0 ||
+            n_clusters > 0x7FFFFFF0ll || (well_stride != 1 && well_stride != 4))
+            return WD_ERR_ARG;
+        if (hipSetDevice(ctx->device) != hipSuccess)
             return WD_ERR_HIP;
-    }
-    uint8_t *out_base = slot.arena ? slot.arena + ((comp_bytes + 255) & ~(size_t)255) : nullptr;
-    std::vector<uint64_t> trailer((size_t)n, 0);
-    std::mutex mu;
-    std::condition_variable cv;
-    int free_upto = kChunks;
-    bool abort_all = false;
-    std::atomic<int> next_file{0};
-    auto reader = [&]() {
-        for (;;) {
-            const int i = next_file.fetch_add(1);
-            if (i >= n)
-                return;
-            const int g = group_of[(size_t)i];
-            if (g < 0)
-                continue;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return abort_all || g < free_upto; });
-                if (abort_all)
-                    return;
-            }
-            Entry &e = ent[(size_t)i];
-            uint8_t *dst = ctx->inflate_chunks[g % kChunks].pinned + offset[(size_t)i];
-            bool ok = false;
-            const int fd = open(paths[i], O_RDONLY);
-            if (fd >= 0) {
-                thread_local std::vector<uint8_t> bounce;
-                ok = read_into_ring(fd, dst, e.csize, (off_t)e.pos, bounce, ring_direct) == e.csize;
-                close(fd);
-            }
-            if (!ok || !inf_gzip_header(dst, e.csize, &e.stream_off))
-                rc[(size_t)i] = HOST;
-            else
-                memcpy(&trailer[(size_t)i], dst + e.csize - 8, 8);
-            if (groups[(size_t)g]->remaining.fetch_sub(1) == 1) {
-                std::lock_guard<std::mutex> lk(mu);
-                cv.notify_all();
-            }
-        }
-    };
-    Crew pool;
-    pool.wake = [&] {
-        std::lock_guard<std::mutex> lk(mu);
-        abort_all = true;
-        cv.notify_all();
-    };
-    if (pool.start(std::min(threads, std::max(1, n)), reader, ctx->test_thread_limit) == 0)
-        return WD_ERR_NOMEM;
-    std::vector<int> job_file;
-    job_file.reserve(n_jobs);
-    int hip_rc = WD_OK;
-    const int si = (int)(ctx->inflate_launch_seq++ % (unsigned)std::max(1, std::min(kStreams, ctx->inflate_decode_streams)));
-    hipStream_t copy_stream = ctx->inflate_streams[kStreams], stream = ctx->inflate_streams[si];
-    for (int g = 0; g < n_groups && hip_rc == WD_OK; g++) {
-        Group &grp = *groups[(size_t)g];
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return grp.remaining.load() == 0; });
-        }
-        wd_ctx::InflateChunk &ch = ctx->inflate_chunks[g % kChunks];
-        uint8_t *dev = slot.arena + grp.arena_at;
-        for (int i = grp.first; i <= grp.last; i++) {
-            if (group_of[(size_t)i] != g || rc[(size_t)i] != PENDING)
-                continue;
-            InfJob &j = slot.h_jobs[job_file.size()];
-            j.file = reinterpret_cast<const uint32_t *>(dev + offset[(size_t)i]);
-            j.obase = out_base + out_at[(size_t)i];
-            j.file_bytes = ent[(size_t)i].csize;
-            j.stream_off = ent[(size_t)i].stream_off;
-            j.out_cap = ent[(size_t)i].usize;
-            j.pad_ = 0;
-            job_file.push_back(i);
-        }
-        if (hipMemcpyAsync(dev, ch.pinned, grp.bytes, hipMemcpyHostToDevice, copy_stream) != hipSuccess ||
-            hipEventRecord(ch.copied, copy_stream) != hipSuccess) {
-            hip_rc = WD_ERR_HIP;
-            break;
-        }
-        if (g >= 1) {                                            // (as in wd_load_tile_files_batch)
-            if (hipEventSynchronize(ctx->inflate_chunks[(g - 1) % kChunks].copied) != hipSuccess) {
-                hip_rc = WD_ERR_HIP;
-                break;
-            }
-            std::lock_guard<std::mutex> lk(mu);
-            free_upto = g + kChunks;
-            cv.notify_all();
-        }
-    }
-    const unsigned nj = (unsigned)job_file.size();
-    if (hip_rc == WD_OK && nj) {                             // one launch for the batch, then the expansions
-        if (hipEventRecord(ctx->inflate_ready[si], copy_stream) != hipSuccess ||
-            hipStreamWaitEvent(stream, ctx->inflate_ready[si], 0) != hipSuccess ||
-            hipMemcpyAsync(slot.d_jobs, slot.h_jobs, sizeof(InfJob) * nj, hipMemcpyHostToDevice, stream) != hipSuccess)
-            hip_rc = WD_ERR_HIP;
-    }
-    if (hip_rc == WD_OK && nj) {
-        const int waves = ctx->inflate_waves ? ctx->inflate_waves : nj <= 256 ? 8 : 4;
-        if (waves == 8)
-            hipLaunchKernelGGL((k_inflate<8, 256>), dim3(nj), dim3(512), 0, stream, slot.d_jobs, slot.d_res);
-        else if (waves == 4)
-            hipLaunchKernelGGL((k_inflate<4, 256>), dim3(nj), dim3(256), 0, stream, slot.d_jobs, slot.d_res);
-        else
-            hipLaunchKernelGGL((k_inflate<1, 512>), dim3(nj), dim3(64), 0, stream, slot.d_jobs, slot.d_res);
-        hipLaunchKernelGGL(k_inflate_crc, dim3(nj), dim3(256), 0, stream, slot.d_jobs, slot.d_res);
-        hipLaunchKernelGGL(k_inflate_heads, dim3((nj + 255) / 256), dim3(256), 0, stream, slot.d_jobs, slot.d_res, (int)nj);
-        // (the expansions take the table's block length on trust; the results below say whether it held)
-        for (unsigned q = 0; q < nj && n_clusters > 0; q++) {
-            const int i = job_file[q];
-            const Entry &e = ent[(size_t)i];
-            uint8_t *packed = out_base + out_at[(size_t)i];
-            uint32_t *sums = (uint32_t *)(packed + (((size_t)e.usize + 255) & ~(size_t)255));
-            if (e.excluded) {
-                hipLaunchKernelGGL(k_cbcl_count, dim3(exp_chunks), dim3(kBlock), 0, stream, filter_dev[i], (long long)n_clusters,
-                                   sums);
-                hipLaunchKernelGGL(k_cbcl_scan, dim3(1), dim3(kBlock), 0, stream, sums, exp_chunks);
-            }
-            hipLaunchKernelGGL(k_cbcl_expand, dim3(exp_chunks), dim3(kBlock), 0, stream, packed, (long long)e.usize * 2,
-                               filter_dev[i], sums, (long long)n_clusters, e.excluded, dst_dev[i], well_stride);
-        }
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(slot.h_res, slot.d_res, sizeof(InfResult) * nj, hipMemcpyDeviceToHost, stream) != hipSuccess)
-            hip_rc = WD_ERR_HIP;
-    }
-    if (hip_rc != WD_OK) {
-        std::lock_guard<std::mutex> lk(mu);
-        abort_all = true;
-        cv.notify_all();
-    }
-    pool.join();
-    if (hip_rc == WD_OK && n_groups && hipEventRecord(slot.done, stream) != hipSuccess)
-        hip_rc = WD_ERR_HIP;
-    if (hip_rc != WD_OK)
-        (void)hipDeviceSynchronize();
-    batch_lock.unlock();
-    if (hip_rc == WD_OK && n_groups && hipEventSynchronize(slot.done) != hipSuccess)
-        hip_rc = WD_ERR_HIP;
-    if (hip_rc != WD_OK)
-        return hip_rc;
-    unsigned long long real_sum = 0;
-    for (size_t j = 0; j < job_file.size(); j++) {
-        const int i = job_file[j];
-        const InfResult &r = slot.h_res[j];
-        const Entry &e = ent[(size_t)i];
-        const uint32_t crc = (uint32_t)trailer[(size_t)i], isize = (uint32_t)(trailer[(size_t)i] >> 32);
-        const bool good = r.status == INF_OK && (size_t)r.end_byte + 8 == e.csize && crc == r.crc && isize == r.produced &&
-                          r.produced == e.usize;
-        // (a block shorter than the tile without excluded wells: the host path's IndexError)
-        rc[(size_t)i] = good && (e.excluded || (long long)e.usize * 2 >= n_clusters) ? WD_OK : HOST;
-        real_sum += r.t_real;
-        if (!good && getenv("WD_INFLATE_STATS"))
-            fprintf(stderr, "[wd inflate] block %d declined: status %u produced %u (table %u) end %u of %u crc %08x/%08x isize %u\n",
-                    i, r.status, r.produced, e.usize, r.end_byte, e.csize, r.crc, crc, isize);
-    }
-    if (!job_file.empty())
-        ctx->inflate_us_per_file = (long long)(real_sum / 100 / job_file.size());
-    std::vector<int> todo;
-    long long by_gpu = 0;
-    for (int i = 0; i < n; i++) {
-        if (rc[(size_t)i] == HOST || rc[(size_t)i] == PENDING)
-            todo.push_back(i);
-        by_gpu += rc[(size_t)i] == WD_OK;
-    }
-    ctx->inflate_files_gpu += by_gpu;
-    ctx->inflate_files_host += (long long)todo.size();
-    if (!todo.empty()) {
-        std::atomic<size_t> next{0};
-        auto host = [&]() {
-            for (;;) {
-                const size_t k = next.fetch_add(1);
-                if (k >= todo.size())
-                    return;
-                const int i = todo[k];
-                rc[(size_t)i] = wd_load_cbcl_tile_strided(ctx, paths[i], tile_number[i], filter_dev[i], n_clusters, dst_dev[i],
-                                                          well_stride);
-            }
-        };
-        Crew hp;
-        if (hp.start((int)std::min((size_t)threads, todo.size()) - 1, host, ctx->test_thread_limit) >= 0)
-            host();
-        hp.join();
-    }
-    int first = WD_OK;
-    for (int i = 0; i < n; i++) {
-        if (rc_out)
-            rc_out[i] = rc[(size_t)i];
-        if (first == WD_OK && rc[(size_t)i] != WD_OK)
-            first = rc[(size_t)i];
-    }
-    return first;
+        CbclBlocks fmt{ctx, paths, tile_number, filter_dev, dst_dev, n_clusters, well_stride, {}};
+        return inflate_batch(ctx, fmt, n, threads, rc_out);
+    });
 }
 
 int wd_gather_wells(wd_ctx *ctx, const uint8_t *const *planes, int L, const int32_t *idx, int64_t n,
