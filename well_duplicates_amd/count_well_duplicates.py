@@ -21,9 +21,12 @@ Differences from the reference, all deliberate:
   * `-t` with a pattern that matches nothing raises the AssertionError the reference
     intends (its own message formatting raises NameError first);
   * extra flags: --device, --dist-backend, --tile-batch, --threads, --strict, -o/--output,
-    --all-wells, --slocs, --layout, --serial-ingest, --dup-sets, --dup-sets-out;
+    --all-wells, --slocs, --layout, --serial-ingest, --dup-sets, --dup-sets-out, --tile-dups, --tile-dups-out;
   * --all-wells --dup-sets groups every tile's wells into duplicate sets and follows each lane's report
     with their counts and the exact duplication (report.write_dup_sets);
+  * --all-wells --tile-dups groups every tile's PF wells into classes of equal reads, wherever on the tile they
+    lie, and follows each lane's report with the duplication of the tiles as a whole and the share of it
+    that lies inside the rings (report.write_tile_dups);
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
@@ -128,6 +131,16 @@ def parse_args(argv=None):
     p.add_argument("--dup-sets-out", default=None, metavar="PATH",
                    help="with --dup-sets: write lane, tile, well and set (the smallest well index of its set) of "
                         "every well in a set of two or more to this TSV file (single process only)")
+    p.add_argument("--tile-dups", action="store_true",
+                   help="with --all-wells: group every tile's PF wells into classes of equal reads over the scanned "
+                        "cycles, wherever on the tile they lie, and print, after each lane's report, the classes, the "
+                        "wells in them, how many of those have a classmate within each level of rings, and the "
+                        "duplication of the tile as a whole (redundant / PF wells).  The classes are always by "
+                        "equality, whatever -e / --hamming the scan runs with: near-duplicate classes over a whole "
+                        "tile are a different algorithm and are not offered")
+    p.add_argument("--tile-dups-out", default=None, metavar="PATH",
+                   help="with --tile-dups: write lane, tile, well and class (the smallest well index of its class) of "
+                        "every well in a class of two or more to this TSV file (single process only)")
     args = p.parse_args(argv)
     if not args.coord_file and not args.all_wells:
         p.error("the following arguments are required: -f/--coord_file (or --all-wells)")
@@ -139,6 +152,12 @@ def parse_args(argv=None):
         p.error("--dup-sets-out needs --dup-sets")
     if args.dup_sets_out and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         p.error("--dup-sets-out is written by a single process only")
+    if args.tile_dups and not args.all_wells:
+        p.error("--tile-dups needs --all-wells (the rings of every well say which classmates are local)")
+    if args.tile_dups_out and not args.tile_dups:
+        p.error("--tile-dups-out needs --tile-dups")
+    if args.tile_dups_out and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        p.error("--tile-dups-out is written by a single process only")
     return args
 
 
@@ -225,11 +244,13 @@ def set_members(labels: np.ndarray):
 
 def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells, tile_batch,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
-               dup_sets=0):
+               dup_sets=0, tile_dups=0):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
     2 = and their members (into["members"][(lane, tile)] = (wells, labels), set_members).
+    tile_dups (needs `into`): the same for the read classes of every tile (TileBatch.tile_dups), run on the resident
+    batch after the scan: into["tdups"][(lane, tile)] = TileDupCounts, into["tmembers"][(lane, tile)].
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -380,6 +401,13 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
             else:
                 blocks, _ = tb.count(mode, k)
             _lap("batch %d: scanned" % bi)
+            if tile_dups:
+                td_rows, td_labels = tb.tile_dups(labels=tile_dups > 1)
+                for i, t in enumerate(chunk):
+                    into["tdups"][(lane, t)] = report.TileDupCounts.from_block(td_rows[i], levels, wells=n_clusters)
+                    if td_labels is not None:
+                        into["tmembers"][(lane, t)] = set_members(td_labels[i])
+                _lap("batch %d: read classes" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
             if want_log:
                 hits, total = sc.hitlog_fetch(max(1024, int(nbr.size) * len(chunk)))
@@ -429,10 +457,11 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     return counts, logs
 
 
-def write_set_members(path, members):
-    """--dup-sets-out: lane, tile, well, set of every well in a set of two or more, by lane, tile, well."""
+def write_set_members(path, members, column="set"):
+    """--dup-sets-out (--tile-dups-out: column "class"): lane, tile, well, set of every well in a set of two or
+    more, by lane, tile, well."""
     with open(path, "w") as fh:
-        fh.write("lane\ttile\twell\tset\n")
+        fh.write("lane\ttile\twell\t%s\n" % column)
         for lane, tile in sorted(members, key=lambda lt: (str(lt[0]), str(lt[1]))):
             wells, labels = members[(lane, tile)]
             fh.writelines("%s\t%s\t%d\t%d\n" % (lane, tile, w, s) for w, s in zip(wells.tolist(), labels.tolist()))
@@ -566,7 +595,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
             ncnt = 1 + 5 * levels
             # --dup-sets: the duplicate sets' counters ride in the same row (one all-reduce either way)
             nsets = 1 + 3 * levels + len(report.SIZE_BIN_NAMES) if args.dup_sets else 0
-            rows = np.zeros((len(mine), ncnt + nsets), dtype=np.int64)
+            # --tile-dups: and the read classes' columns behind them
+            ntd = 4 + 2 * levels + len(report.CLASS_BIN_NAMES) if args.tile_dups else 0
+            rows = np.zeros((len(mine), ncnt + nsets + ntd), dtype=np.int64)
             logs = {}
 
             def emit(lane, block):          # a finished lane: its log lines, then its report (:269)
@@ -578,13 +609,19 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 report.write_report(lane, n_targets, counts, verbose=not args.summary_only,
                                     strict=args.strict, out=out_fh)
                 if args.dup_sets:
-                    sets = {t: report.DupSetCounts.from_block(block[pos[(lane, t)]][ncnt:], levels) for t in tiles}
+                    sets = {t: report.DupSetCounts.from_block(block[pos[(lane, t)]][ncnt:ncnt + nsets], levels)
+                            for t in tiles}
                     report.write_dup_sets(lane, sets, verbose=not args.summary_only, out=out_fh, levels=levels)
+                if args.tile_dups:          # (every well is a target: n_targets is the tile's size)
+                    tds = {t: report.TileDupCounts.from_block(block[pos[(lane, t)]][ncnt + nsets:], levels,
+                                                              wells=n_targets) for t in tiles}
+                    report.write_tile_dups(lane, tds, verbose=not args.summary_only, out=out_fh, levels=levels)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
                 where = {item: i for i, item in enumerate(mine)}
-                results = {"counts": {}, "logs": {}, "sets": {}, "members": {}}   # scan_lanes fills these, lane_done reads them
+                # scan_lanes fills these, lane_done reads them
+                results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {}}
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
@@ -592,7 +629,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                         rows[where[(lane, t)]][:ncnt] = [c.targets] + c.wells + c.dups + c.hit + c.first + c.last
                         if args.dup_sets:
                             d = results["sets"][(lane, t)]
-                            rows[where[(lane, t)]][ncnt:] = [d.pf] + d.sets + d.in_sets + d.redundant + d.sizes
+                            rows[where[(lane, t)]][ncnt:ncnt + nsets] = [d.pf] + d.sets + d.in_sets + d.redundant + d.sizes
+                        if args.tile_dups:
+                            rows[where[(lane, t)]][ncnt + nsets:] = results["tdups"][(lane, t)].to_block()
                         if (lane, t) in results["logs"]:
                             logs[(lane, t)] = results["logs"][(lane, t)]
                     if world == 1:          # as the reference: a lane is reported when it is done
@@ -605,9 +644,12 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                overlap=not args.serial_ingest,
                                interleave=resident_layout(args, mode, k, csr, reader, lanes, tiles, cycle_list),
                                gpu_inflate=not args.host_inflate, lane_done=lane_done, into=results,
-                               dup_sets=(2 if args.dup_sets_out else 1) if args.dup_sets else 0)
+                               dup_sets=(2 if args.dup_sets_out else 1) if args.dup_sets else 0,
+                               tile_dups=(2 if args.tile_dups_out else 1) if args.tile_dups else 0)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
+                    if args.tile_dups_out:
+                        write_set_members(args.tile_dups_out, results["tmembers"], column="class")
             except Exception as e:          # noqa: BLE001 - re-raised below, on every rank
                 err = e
             if world > 1:

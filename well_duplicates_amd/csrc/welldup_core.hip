@@ -95,6 +95,7 @@ void drain_events(wd_ctx *ctx)
 
 // welldup_sets.hip (declared here, not in wd_ctx.h: every other unit's sources stay as they are)
 namespace wd { const char *unit_id_sets(); }
+#include "wd_tiledups.h"        // unit_id_tiledups()
 
 using namespace wd;
 
@@ -110,12 +111,13 @@ int wd_version(void) { return 100; }
 #endif
 const char *wd_build_id(void)
 {
-    // "<all sources> core=<..> scan=<..> queue=<..> lines=<..> dense=<..> ingest=<..> sets=<..>": the whole tree's hash,
+    // "<all sources> core=<..> scan=<..> queue=<..> lines=<..> dense=<..> ingest=<..> sets=<..> tiledups=<..>": the whole tree's hash,
     // then one per translation unit (its .hip and everything it includes), so that evidence about a kernel
     // goes stale when ITS code changes and not when a comment in the ingest does
     static const std::string id = std::string(WD_BUILD_ID) + " core=" + WD_UNIT_ID + " scan=" + unit_id_scan() +
                                   " queue=" + unit_id_queue() + " lines=" + unit_id_lines() +
-                                  " dense=" + unit_id_dense() + " ingest=" + unit_id_ingest() + " sets=" + unit_id_sets();
+                                  " dense=" + unit_id_dense() + " ingest=" + unit_id_ingest() + " sets=" + unit_id_sets() +
+                                  " tiledups=" + unit_id_tiledups();
     return id.c_str();
 }
 

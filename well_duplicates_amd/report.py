@@ -257,3 +257,89 @@ def write_dup_sets(lane, counts: Dict[str, DupSetCounts], verbose: bool = False,
     print("SetSizes (level %i): %s" % (levels, "\t".join(
         "%s: %i" % (name, n) for name, n in zip(SIZE_BIN_NAMES, tot.sizes))), file=out)
     print("Exact duplication (Redundant/PF wells): {:.2%}".format(tot.exact_duplication()), file=out)
+
+
+CLASS_BIN_NAMES = ("2", "3", "4", "5", "6", "7", "8", ">=9")
+
+
+@dataclass
+class TileDupCounts:
+    """Read classes of one tile, or of several added up (include/welldup_tiledups.h, wd_tile_dups): PF wells,
+    the classes of >= 2 PF wells with equal reads, the wells in them, the redundant wells (InClasses - Classes);
+    per level (cumulative) the wells in classes with a classmate in their rings and the sizes of those wells'
+    rings; size bins of the classes.  even_den = InClasses * (wells of the tile - 1): what RingWells is divided
+    by for the share a classmate placed anywhere on the tile would have in the rings (0 = tile size not given)."""
+    pf: int = 0
+    classes: int = 0
+    in_classes: int = 0
+    redundant: int = 0
+    local: List[int] = field(default_factory=list)
+    ring_wells: List[int] = field(default_factory=list)
+    sizes: List[int] = field(default_factory=lambda: [0] * len(CLASS_BIN_NAMES))
+    even_den: int = 0
+
+    @property
+    def levels(self) -> int:
+        return len(self.local)
+
+    @classmethod
+    def zeros(cls, levels: int) -> "TileDupCounts":
+        return cls(0, 0, 0, 0, [0] * levels, [0] * levels, [0] * len(CLASS_BIN_NAMES), 0)
+
+    @classmethod
+    def from_block(cls, block: Sequence[int], levels: int, wells: int = 0) -> "TileDupCounts":
+        """Decode one out_rows row: [PF, Classes, InClasses, Redundant, Local[levels], RingWells[levels], size
+        bins]; wells: the wells of the tile (PF or not), for the evenly-spread figure."""
+        b = [int(v) for v in block]
+        assert len(b) == 4 + 2 * levels + len(CLASS_BIN_NAMES)
+        return cls(b[0], b[1], b[2], b[3], b[4:4 + levels], b[4 + levels:4 + 2 * levels], b[4 + 2 * levels:],
+                   b[2] * (int(wells) - 1) if wells > 1 else 0)
+
+    def to_block(self) -> List[int]:
+        return [self.pf, self.classes, self.in_classes, self.redundant] + self.local + self.ring_wells + self.sizes
+
+    def __add__(self, other: "TileDupCounts") -> "TileDupCounts":
+        if self.levels != other.levels:
+            raise ValueError("tile duplicates of %d and %d levels" % (self.levels, other.levels))
+        add = lambda a, b: [x + y for x, y in zip(a, b)]
+        return TileDupCounts(self.pf + other.pf, self.classes + other.classes, self.in_classes + other.in_classes,
+                             self.redundant + other.redundant, add(self.local, other.local),
+                             add(self.ring_wells, other.ring_wells), add(self.sizes, other.sizes),
+                             self.even_den + other.even_den)
+
+    def tile_duplication(self) -> float:
+        """Redundant wells / PF wells (0 without PF wells)."""
+        return self.redundant / self.pf if self.pf else 0.0
+
+    def local_share(self) -> float:
+        """Wells in classes with a classmate in their rings (outermost level) / wells in classes."""
+        return self.local[-1] / self.in_classes if self.in_classes and self.levels else 0.0
+
+
+def write_tile_dups(lane, counts: Dict[str, TileDupCounts], verbose: bool = False, out=None, levels: int = 0) -> None:
+    """The block that follows a lane's report (and its duplicate-set block) under --tile-dups: per-tile lines
+    (verbose, in sorted tile order as write_report), the lane's sums, the class sizes, the duplication of the
+    tiles as a whole and the share of it that is local."""
+    out = out or sys.stdout
+    if not levels:
+        levels = next((c.levels for c in counts.values()), 0)
+    tot = TileDupCounts.zeros(levels)
+    print(file=out)
+    for tile in sorted(counts.keys()):
+        tc = counts[tile]
+        tot = tot + tc
+        if verbose:
+            print("TileDups: %s\tTile: %s\tPF wells: %i\tClasses: %i\tInClasses: %i\tRedundant: %i" % (
+                lane, tile, tc.pf, tc.classes, tc.in_classes, tc.redundant), file=out)
+            for lev in range(levels):
+                print("Level: %i\tLocal: %i\tRingWells: %i" % (lev + 1, tc.local[lev], tc.ring_wells[lev]), file=out)
+    print("TileDupsSummary: %s\tTiles: %i\tPF wells: %i\tClasses: %i\tInClasses: %i (%.5f)\tRedundant: %i (%.5f)" % (
+        lane, len(counts), tot.pf, tot.classes, tot.in_classes, tot.in_classes / tot.pf if tot.pf else 0.0,
+        tot.redundant, tot.redundant / tot.pf if tot.pf else 0.0), file=out)
+    for lev in range(levels):
+        print("Level: %i\tLocal: %i (%.5f of InClasses)\tEvenly spread: %.5f" % (
+            lev + 1, tot.local[lev], tot.local[lev] / tot.in_classes if tot.in_classes else 0.0,
+            tot.ring_wells[lev] / tot.even_den if tot.even_den else 0.0), file=out)
+    print("ClassSizes: %s" % "\t".join("%s: %i" % (name, n) for name, n in zip(CLASS_BIN_NAMES, tot.sizes)), file=out)
+    print("Tile duplication (Redundant/PF wells): {:.2%}".format(tot.tile_duplication()), file=out)
+    print("Local share at level {} (Local/InClasses): {:.2%}".format(levels, tot.local_share()), file=out)

@@ -256,6 +256,29 @@ class Scanner:
             ctypes.byref(edges)))
         return blocks, sets, edges.value
 
+    def tile_dups_workspace_bytes(self, n_clusters: int, n_tiles: int) -> int:
+        """Device bytes wd_tile_dups needs as its workspace for n_tiles tiles of n_clusters wells."""
+        b = ctypes.c_size_t()
+        self._ck(self._lib.wd_tile_dups_workspace(int(n_clusters), int(n_tiles), ctypes.byref(b)))
+        return b.value
+
+    def tile_dups(self, planes: Sequence[Sequence[int]], filters: Sequence[int], n_clusters: int, workspace: int,
+                  workspace_bytes: int, labels: Optional[Sequence[int]] = None, hash_bits: int = 0, tables=None, L=None):
+        """The read classes of every tile (wd_tile_dups, include/welldup_tiledups.h): PF wells with equal reads
+        wherever on the tile they lie; needs every well as a target.  labels: n_tiles device addresses of N
+        uint32 each, or None.  Returns rows [n_tiles, 4 + 2*levels + 8]: [PF wells, Classes, InClasses,
+        Redundant, Local[levels], RingWells[levels], size bins 2..8, 9+]."""
+        n_tiles = len(filters)
+        if L is None:
+            L = len(planes[0]) if n_tiles else 0
+        pt, ft = tables if tables is not None else self._tables(planes, filters, L)
+        rows = np.zeros((n_tiles, 4 + 2 * self.levels + _lib.DUPSET_SIZE_BINS), dtype=np.int64)
+        lt = (ctypes.c_void_p * max(1, n_tiles))(*[int(p) for p in labels]) if labels is not None else None
+        self._ck(self._lib.wd_tile_dups(
+            self._ctx, n_tiles, L, pt, ft, int(n_clusters), ctypes.c_void_p(workspace), int(workspace_bytes),
+            int(hash_bits), rows.ctypes.data_as(ctypes.c_void_p), lt))
+        return rows
+
     def scan_async(self, tables, n_tiles: int, L: int, n_clusters: int, mode: int, k: int,
                    out_tile_dev: int, out_per_target_dev: Optional[int] = None):
         pt, ft = tables
@@ -480,6 +503,11 @@ class TileBatch:
         if reuse is not None and reuse.sc is scanner and reuse.d_sets:
             self.d_sets, self.sets_bytes, self._sets_cap = reuse.d_sets, reuse.sets_bytes, reuse._sets_cap
             reuse.d_sets = 0
+        # read classes (tile_dups): the same, with a buffer of its own
+        self.d_tdups, self._tdups_cap = 0, 0
+        if reuse is not None and reuse.sc is scanner and reuse.d_tdups:
+            self.d_tdups, self._tdups_cap = reuse.d_tdups, reuse._tdups_cap
+            reuse.d_tdups = 0
 
     def plane_ptr(self, tile: int, cycle: int) -> int:
         """Address of well 0 of the cycle (wells are `interleave` bytes apart)."""
@@ -568,8 +596,32 @@ class TileBatch:
             lab = self.sc.d2h(d_lbl, lbl_bytes, np.uint32).reshape(self.n_tiles, self.N)
         return blocks, sets, lab
 
+    def tile_dups(self, labels: bool = False, hash_bits: int = 0):
+        """The read classes of every tile of the batch (Scanner.tile_dups; every well must be a target, the
+        batch a plane per cycle).  -> (rows, labels uint32 [n_tiles, N] or None)."""
+        ws = self.sc.tile_dups_workspace_bytes(self.N, self.n_tiles)
+        lbl_bytes = 4 * self.N * self.n_tiles if labels else 0
+        if not self.d_tdups or self._tdups_cap < ws + lbl_bytes:
+            if self.d_tdups:
+                self.sc.free(self.d_tdups)
+                self.d_tdups = 0
+            self._tdups_cap = ws + lbl_bytes
+            self.d_tdups = self.sc.malloc(max(1, self._tdups_cap))
+        d_lbl = self.d_tdups + ws if labels else 0
+        lbl_ptrs = [d_lbl + 4 * self.N * i for i in range(self.n_tiles)] if labels else None
+        self.sc.set_option("well_stride", self.interleave)
+        try:
+            rows = self.sc.tile_dups(None, self.filter_ptrs(), self.N, self.d_tdups, ws, labels=lbl_ptrs,
+                                     hash_bits=hash_bits, tables=self.tables, L=self.L)
+        finally:
+            self.sc.set_option("well_stride", 1)
+        lab = None
+        if labels:
+            lab = self.sc.d2h(d_lbl, lbl_bytes, np.uint32).reshape(self.n_tiles, self.N)
+        return rows, lab
+
     def free(self):
-        for ptr in (self.d_planes, self.d_filters, self.d_tmp, self.d_sets):
+        for ptr in (self.d_planes, self.d_filters, self.d_tmp, self.d_sets, self.d_tdups):
             if ptr:
                 self.sc.free(ptr)
-        self.d_planes = self.d_filters = self.d_tmp = self.d_sets = 0
+        self.d_planes = self.d_filters = self.d_tmp = self.d_sets = self.d_tdups = 0
