@@ -15,7 +15,8 @@
  *                of the well or the well in a ring <= l of m (the rule welldup_sets.h uses for an edge);
  *   RingWells[l] over the wells in classes, the sum of the sizes of their rings <= l: what Local[l] would
  *                be for classmates spread evenly is RingWells[l] / (InClasses * (N - 1)) per classmate.
- * Classes are by equality only; near-duplicate classes over a whole tile are a different algorithm.
+ * Classes are by equality only; the near-duplicate clusters of a whole tile (Hamming distance <= K) are
+ * wd_tile_near_dups in welldup_tilenear.h.
  */
 #ifndef WELLDUP_TILEDUPS_H
 #define WELLDUP_TILEDUPS_H

@@ -112,6 +112,13 @@ TILEDUPS_PROTOTYPES = {
     "wd_tile_dups": (_i, [_vp, _i, _i, _pp, _pp, _i64, _vp, _sz, _i, _vp, _pp]),
 }
 
+# name -> (restype, argtypes); every symbol include/welldup_tilenear.h declares beyond the three above
+TILENEAR_PROTOTYPES = {
+    "wd_tile_near_dups_workspace": (_i, [_i64, _i, _i, ctypes.POINTER(_sz)]),
+    "wd_tile_near_dups": (_i, [_vp, _i, _i, _pp, _pp, _i64, _i, _vp, _sz, _i, _i64, _vp, _pp]),
+}
+TILENEAR_MAX_K = 3
+
 _lib = None
 
 
@@ -137,7 +144,7 @@ def _deps(path: str, seen=None) -> set:
 
 def source_build_id() -> str:
     """sha256 over the library's sources (csrc/*, include/welldup.h, include/welldup_sets.h,
-    include/welldup_tiledups.h): what `wd_build_id()` of a library
+    include/welldup_tiledups.h, include/welldup_tilenear.h): what `wd_build_id()` of a library
     built from this tree returns.  Counter profiles and resource tables carry it (tools/pmc_collect.py),
     so that evidence is tied to the code that produced it, not to a kernel's name."""
     import hashlib
@@ -147,6 +154,7 @@ def source_build_id() -> str:
     files.append(os.path.join(INCLUDE, "welldup.h"))
     files.append(os.path.join(INCLUDE, "welldup_sets.h"))
     files.append(os.path.join(INCLUDE, "welldup_tiledups.h"))
+    files.append(os.path.join(INCLUDE, "welldup_tilenear.h"))
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         with open(f, "rb") as fh:
@@ -196,7 +204,7 @@ def unit_of_kernel(kernel: str) -> str:
         return "ingest"
     if kernel.startswith("k_sets"):
         return "sets"
-    if kernel.startswith("k_td_"):
+    if kernel.startswith(("k_td_", "k_tn_")):
         return "tiledups"
     return "scan"
 
@@ -255,7 +263,8 @@ def load():
             "%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the scan path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in list(PROTOTYPES.items()) + list(SETS_PROTOTYPES.items()) + list(TILEDUPS_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(SETS_PROTOTYPES.items()) + list(TILEDUPS_PROTOTYPES.items()) + \
+            list(TILENEAR_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

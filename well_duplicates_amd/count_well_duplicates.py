@@ -21,12 +21,14 @@ Differences from the reference, all deliberate:
   * `-t` with a pattern that matches nothing raises the AssertionError the reference
     intends (its own message formatting raises NameError first);
   * extra flags: --device, --dist-backend, --tile-batch, --threads, --strict, -o/--output,
-    --all-wells, --slocs, --layout, --serial-ingest, --dup-sets, --dup-sets-out, --tile-dups, --tile-dups-out;
+    --all-wells, --slocs, --layout, --serial-ingest, --dup-sets, --dup-sets-out, --tile-dups, --tile-dups-out,
+    --tile-dups-hamming, --tile-dups-pair-budget;
   * --all-wells --dup-sets groups every tile's wells into duplicate sets and follows each lane's report
     with their counts and the exact duplication (report.write_dup_sets);
   * --all-wells --tile-dups groups every tile's PF wells into classes of equal reads, wherever on the tile they
     lie, and follows each lane's report with the duplication of the tiles as a whole and the share of it
-    that lies inside the rings (report.write_tile_dups);
+    that lies inside the rings (report.write_tile_dups); --tile-dups-hamming K adds the same for the clusters of
+    reads within Hamming distance K of each other (report.write_tile_near_dups);
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
@@ -40,7 +42,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import bcl as bcl_direct_reader
-from . import report, workload
+from . import _lib, report, workload
 from .report import LENGTH, TALLY, output_writer  # noqa: F401  (reference module surface)
 from .scanner import INVALID_TARGET, Scanner, TileBatch, compare_mode
 from .targets import load_targets, load_targets_csr
@@ -137,10 +139,21 @@ def parse_args(argv=None):
                         "wells in them, how many of those have a classmate within each level of rings, and the "
                         "duplication of the tile as a whole (redundant / PF wells).  The classes are always by "
                         "equality, whatever -e / --hamming the scan runs with: near-duplicate classes over a whole "
-                        "tile are a different algorithm and are not offered")
+                        "tile are what --tile-dups-hamming adds")
     p.add_argument("--tile-dups-out", default=None, metavar="PATH",
                    help="with --tile-dups: write lane, tile, well and class (the smallest well index of its class) of "
                         "every well in a class of two or more to this TSV file (single process only)")
+    p.add_argument("--tile-dups-hamming", type=int, default=None, metavar="K",
+                   help="with --tile-dups: also group every tile's PF wells into clusters of reads linked by Hamming "
+                        "distance <= K (1..%d; single linkage, exact, wherever on the tile the wells lie) and print a "
+                        "second block of the same shape for them, with the pairs of distinct reads within K and the "
+                        "tile-wide duplication at Hamming <= K beside the one by equality.  Hamming only: clusters "
+                        "by edit distance over a whole tile are not offered (an insertion or deletion shifts "
+                        "every later segment of the read)" % _lib.TILENEAR_MAX_K)
+    p.add_argument("--tile-dups-pair-budget", type=int, default=0, metavar="N",
+                   help="with --tile-dups-hamming: the most candidate pairs one segment of one tile may have before "
+                        "the run is refused (reads of low diversity: amplicons, a shared adaptor); 0 = the "
+                        "library's default, max(16 x wells, 2^24)")
     args = p.parse_args(argv)
     if not args.coord_file and not args.all_wells:
         p.error("the following arguments are required: -f/--coord_file (or --all-wells)")
@@ -158,6 +171,14 @@ def parse_args(argv=None):
         p.error("--tile-dups-out needs --tile-dups")
     if args.tile_dups_out and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         p.error("--tile-dups-out is written by a single process only")
+    if args.tile_dups_hamming is not None and not args.tile_dups:
+        p.error("--tile-dups-hamming needs --tile-dups")
+    if args.tile_dups_hamming is not None and not 1 <= args.tile_dups_hamming <= _lib.TILENEAR_MAX_K:
+        p.error("--tile-dups-hamming takes 1..%d" % _lib.TILENEAR_MAX_K)
+    if args.tile_dups_pair_budget < 0:
+        p.error("--tile-dups-pair-budget must not be negative")
+    if args.tile_dups_pair_budget and args.tile_dups_hamming is None:
+        p.error("--tile-dups-pair-budget needs --tile-dups-hamming")
     return args
 
 
@@ -244,13 +265,15 @@ def set_members(labels: np.ndarray):
 
 def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells, tile_batch,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
-               dup_sets=0, tile_dups=0):
+               dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
     2 = and their members (into["members"][(lane, tile)] = (wells, labels), set_members).
     tile_dups (needs `into`): the same for the read classes of every tile (TileBatch.tile_dups), run on the resident
     batch after the scan: into["tdups"][(lane, tile)] = TileDupCounts, into["tmembers"][(lane, tile)].
+    tile_near = K > 0 (with tile_dups): and the clusters at Hamming distance <= K (TileBatch.tile_near_dups):
+    into["tnear"][(lane, tile)] = TileNearCounts, into["tnmembers"][(lane, tile)] = (wells, classes, clusters).
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -408,6 +431,14 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                     if td_labels is not None:
                         into["tmembers"][(lane, t)] = set_members(td_labels[i])
                 _lap("batch %d: read classes" % bi)
+                if tile_near:
+                    tn_rows, tn_labels = tb.tile_near_dups(tile_near, labels=tile_dups > 1, pair_budget=pair_budget)
+                    for i, t in enumerate(chunk):
+                        into["tnear"][(lane, t)] = report.TileNearCounts.from_block(tn_rows[i], levels, wells=n_clusters)
+                        if tn_labels is not None:
+                            ws, clusters = set_members(tn_labels[i])
+                            into["tnmembers"][(lane, t)] = (ws, td_labels[i][ws], clusters)
+                    _lap("batch %d: read clusters" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
             if want_log:
                 hits, total = sc.hitlog_fetch(max(1024, int(nbr.size) * len(chunk)))
@@ -465,6 +496,17 @@ def write_set_members(path, members, column="set"):
         for lane, tile in sorted(members, key=lambda lt: (str(lt[0]), str(lt[1]))):
             wells, labels = members[(lane, tile)]
             fh.writelines("%s\t%s\t%d\t%d\n" % (lane, tile, w, s) for w, s in zip(wells.tolist(), labels.tolist()))
+
+
+def write_cluster_members(path, members):
+    """--tile-dups-out under --tile-dups-hamming: lane, tile, well, class, cluster of every well in a cluster of
+    two or more, by lane, tile, well (class: the well's own index when it is in no class)."""
+    with open(path, "w") as fh:
+        fh.write("lane\ttile\twell\tclass\tcluster\n")
+        for lane, tile in sorted(members, key=lambda lt: (str(lt[0]), str(lt[1]))):
+            wells, classes, clusters = members[(lane, tile)]
+            fh.writelines("%s\t%s\t%d\t%d\t%d\n" % (lane, tile, w, c, s)
+                          for w, c, s in zip(wells.tolist(), classes.tolist(), clusters.tolist()))
 
 
 def main(argv=None, exiting=False):
@@ -597,7 +639,10 @@ def _main(args, log, wdist, rank, world, device, opener, early):
             nsets = 1 + 3 * levels + len(report.SIZE_BIN_NAMES) if args.dup_sets else 0
             # --tile-dups: and the read classes' columns behind them
             ntd = 4 + 2 * levels + len(report.CLASS_BIN_NAMES) if args.tile_dups else 0
-            rows = np.zeros((len(mine), ncnt + nsets + ntd), dtype=np.int64)
+            # --tile-dups-hamming: and the clusters' behind those
+            near_k = args.tile_dups_hamming or 0
+            ntn = 5 + 2 * levels + len(report.CLASS_BIN_NAMES) if near_k else 0
+            rows = np.zeros((len(mine), ncnt + nsets + ntd + ntn), dtype=np.int64)
             logs = {}
 
             def emit(lane, block):          # a finished lane: its log lines, then its report (:269)
@@ -613,15 +658,24 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                             for t in tiles}
                     report.write_dup_sets(lane, sets, verbose=not args.summary_only, out=out_fh, levels=levels)
                 if args.tile_dups:          # (every well is a target: n_targets is the tile's size)
-                    tds = {t: report.TileDupCounts.from_block(block[pos[(lane, t)]][ncnt + nsets:], levels,
-                                                              wells=n_targets) for t in tiles}
+                    tds = {t: report.TileDupCounts.from_block(block[pos[(lane, t)]][ncnt + nsets:ncnt + nsets + ntd],
+                                                              levels, wells=n_targets) for t in tiles}
                     report.write_tile_dups(lane, tds, verbose=not args.summary_only, out=out_fh, levels=levels)
+                if near_k:
+                    tns = {t: report.TileNearCounts.from_block(block[pos[(lane, t)]][ncnt + nsets + ntd:], levels,
+                                                               wells=n_targets) for t in tiles}
+                    equal = report.TileDupCounts.zeros(levels)
+                    for t in tiles:
+                        equal = equal + tds[t]
+                    report.write_tile_near_dups(lane, near_k, tns, verbose=not args.summary_only, out=out_fh,
+                                                levels=levels, equal=equal)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
                 where = {item: i for i, item in enumerate(mine)}
                 # scan_lanes fills these, lane_done reads them
-                results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {}}
+                results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
+                           "tnear": {}, "tnmembers": {}}
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
@@ -631,7 +685,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                             d = results["sets"][(lane, t)]
                             rows[where[(lane, t)]][ncnt:ncnt + nsets] = [d.pf] + d.sets + d.in_sets + d.redundant + d.sizes
                         if args.tile_dups:
-                            rows[where[(lane, t)]][ncnt + nsets:] = results["tdups"][(lane, t)].to_block()
+                            rows[where[(lane, t)]][ncnt + nsets:ncnt + nsets + ntd] = results["tdups"][(lane, t)].to_block()
+                        if near_k:
+                            rows[where[(lane, t)]][ncnt + nsets + ntd:] = results["tnear"][(lane, t)].to_block()
                         if (lane, t) in results["logs"]:
                             logs[(lane, t)] = results["logs"][(lane, t)]
                     if world == 1:          # as the reference: a lane is reported when it is done
@@ -645,10 +701,13 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                interleave=resident_layout(args, mode, k, csr, reader, lanes, tiles, cycle_list),
                                gpu_inflate=not args.host_inflate, lane_done=lane_done, into=results,
                                dup_sets=(2 if args.dup_sets_out else 1) if args.dup_sets else 0,
-                               tile_dups=(2 if args.tile_dups_out else 1) if args.tile_dups else 0)
+                               tile_dups=(2 if args.tile_dups_out else 1) if args.tile_dups else 0,
+                               tile_near=near_k, pair_budget=args.tile_dups_pair_budget)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
-                    if args.tile_dups_out:
+                    if args.tile_dups_out and near_k:
+                        write_cluster_members(args.tile_dups_out, results["tnmembers"])
+                    elif args.tile_dups_out:
                         write_set_members(args.tile_dups_out, results["tmembers"], column="class")
             except Exception as e:          # noqa: BLE001 - re-raised below, on every rank
                 err = e

@@ -10,6 +10,7 @@
 //                     and the level of every classmate met there is taken for both ends
 //   k_td_levels       histogram of the first levels (the host accumulates it into Local)
 // This unit reads the context (targets, stream) and keeps no state in it.
+// tile_near.inc (included at the end) builds the near-duplicate clusters of welldup_tilenear.h on these parts.
 #include "wd_ctx.h"
 #include "wd_tiledups.h"
 #include "welldup_tiledups.h"
@@ -550,3 +551,5 @@ try {
 } WD_CATCH
 
 }  // extern "C"
+
+#include "tile_near.inc"      // near-duplicate clusters (include/welldup_tilenear.h) on the parts above

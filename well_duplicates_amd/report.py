@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import sys
 from dataclasses import dataclass, field
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence
 
 TALLY = 0    # count_well_duplicates.py:17
 LENGTH = 1   # count_well_duplicates.py:18
@@ -343,3 +343,94 @@ def write_tile_dups(lane, counts: Dict[str, TileDupCounts], verbose: bool = Fals
     print("ClassSizes: %s" % "\t".join("%s: %i" % (name, n) for name, n in zip(CLASS_BIN_NAMES, tot.sizes)), file=out)
     print("Tile duplication (Redundant/PF wells): {:.2%}".format(tot.tile_duplication()), file=out)
     print("Local share at level {} (Local/InClasses): {:.2%}".format(levels, tot.local_share()), file=out)
+
+
+@dataclass
+class TileNearCounts:
+    """Near-duplicate read clusters of one tile, or of several added up (include/welldup_tilenear.h,
+    wd_tile_near_dups): PF wells, the clusters of >= 2 PF wells linked by Hamming distance <= K, the wells in
+    them, the redundant wells (InClusters - Clusters), the pairs of distinct reads within K; per level
+    (cumulative) the wells in clusters with a well of their cluster in their rings and the sizes of those wells'
+    rings; size bins of the clusters.  even_den as TileDupCounts, over the wells in clusters."""
+    pf: int = 0
+    clusters: int = 0
+    in_clusters: int = 0
+    redundant: int = 0
+    near_pairs: int = 0
+    local: List[int] = field(default_factory=list)
+    ring_wells: List[int] = field(default_factory=list)
+    sizes: List[int] = field(default_factory=lambda: [0] * len(CLASS_BIN_NAMES))
+    even_den: int = 0
+
+    @property
+    def levels(self) -> int:
+        return len(self.local)
+
+    @classmethod
+    def zeros(cls, levels: int) -> "TileNearCounts":
+        return cls(0, 0, 0, 0, 0, [0] * levels, [0] * levels, [0] * len(CLASS_BIN_NAMES), 0)
+
+    @classmethod
+    def from_block(cls, block: Sequence[int], levels: int, wells: int = 0) -> "TileNearCounts":
+        """Decode one out_rows row: [PF, Clusters, InClusters, Redundant, NearPairs, Local[levels],
+        RingWells[levels], size bins]; wells: the wells of the tile (PF or not)."""
+        b = [int(v) for v in block]
+        assert len(b) == 5 + 2 * levels + len(CLASS_BIN_NAMES)
+        return cls(b[0], b[1], b[2], b[3], b[4], b[5:5 + levels], b[5 + levels:5 + 2 * levels], b[5 + 2 * levels:],
+                   b[2] * (int(wells) - 1) if wells > 1 else 0)
+
+    def to_block(self) -> List[int]:
+        return ([self.pf, self.clusters, self.in_clusters, self.redundant, self.near_pairs] + self.local +
+                self.ring_wells + self.sizes)
+
+    def __add__(self, other: "TileNearCounts") -> "TileNearCounts":
+        if self.levels != other.levels:
+            raise ValueError("tile near-duplicates of %d and %d levels" % (self.levels, other.levels))
+        add = lambda a, b: [x + y for x, y in zip(a, b)]
+        return TileNearCounts(self.pf + other.pf, self.clusters + other.clusters, self.in_clusters + other.in_clusters,
+                              self.redundant + other.redundant, self.near_pairs + other.near_pairs,
+                              add(self.local, other.local), add(self.ring_wells, other.ring_wells),
+                              add(self.sizes, other.sizes), self.even_den + other.even_den)
+
+    def tile_duplication(self) -> float:
+        """Redundant wells / PF wells (0 without PF wells)."""
+        return self.redundant / self.pf if self.pf else 0.0
+
+    def local_share(self) -> float:
+        """Wells in clusters with a well of their cluster in their rings (outermost level) / wells in clusters."""
+        return self.local[-1] / self.in_clusters if self.in_clusters and self.levels else 0.0
+
+
+def write_tile_near_dups(lane, k: int, counts: Dict[str, TileNearCounts], verbose: bool = False, out=None,
+                         levels: int = 0, equal: Optional[TileDupCounts] = None) -> None:
+    """The block that follows a lane's --tile-dups block under --tile-dups-hamming K, of the same shape, for the
+    clusters at Hamming distance <= K.  equal: the lane's sums of the --tile-dups block, whose tile duplication
+    is printed beside that of the clusters."""
+    out = out or sys.stdout
+    if not levels:
+        levels = next((c.levels for c in counts.values()), 0)
+    tot = TileNearCounts.zeros(levels)
+    print(file=out)
+    for tile in sorted(counts.keys()):
+        tc = counts[tile]
+        tot = tot + tc
+        if verbose:
+            print("TileNearDups: %s\tTile: %s\tHamming: %i\tPF wells: %i\tClusters: %i\tInClusters: %i\tRedundant: %i\t"
+                  "NearPairs: %i" % (lane, tile, k, tc.pf, tc.clusters, tc.in_clusters, tc.redundant, tc.near_pairs),
+                  file=out)
+            for lev in range(levels):
+                print("Level: %i\tLocal: %i\tRingWells: %i" % (lev + 1, tc.local[lev], tc.ring_wells[lev]), file=out)
+    print("TileNearDupsSummary: %s\tTiles: %i\tHamming: %i\tPF wells: %i\tClusters: %i\tInClusters: %i (%.5f)\t"
+          "Redundant: %i (%.5f)\tNearPairs: %i" % (
+              lane, len(counts), k, tot.pf, tot.clusters, tot.in_clusters, tot.in_clusters / tot.pf if tot.pf else 0.0,
+              tot.redundant, tot.redundant / tot.pf if tot.pf else 0.0, tot.near_pairs), file=out)
+    for lev in range(levels):
+        print("Level: %i\tLocal: %i (%.5f of InClusters)\tEvenly spread: %.5f" % (
+            lev + 1, tot.local[lev], tot.local[lev] / tot.in_clusters if tot.in_clusters else 0.0,
+            tot.ring_wells[lev] / tot.even_den if tot.even_den else 0.0), file=out)
+    print("ClusterSizes: %s" % "\t".join("%s: %i" % (name, n) for name, n in zip(CLASS_BIN_NAMES, tot.sizes)), file=out)
+    line = "Tile duplication at Hamming <= {} (Redundant/PF wells): {:.2%}".format(k, tot.tile_duplication())
+    if equal is not None:
+        line += "\tby equality: {:.2%}".format(equal.tile_duplication())
+    print(line, file=out)
+    print("Local share at level {} (Local/InClusters): {:.2%}".format(levels, tot.local_share()), file=out)

@@ -279,6 +279,31 @@ class Scanner:
             int(hash_bits), rows.ctypes.data_as(ctypes.c_void_p), lt))
         return rows
 
+    def tile_near_dups_workspace_bytes(self, n_clusters: int, n_tiles: int, k: int) -> int:
+        """Device bytes wd_tile_near_dups needs as its workspace for n_tiles tiles of n_clusters wells at distance k."""
+        b = ctypes.c_size_t()
+        self._ck(self._lib.wd_tile_near_dups_workspace(int(n_clusters), int(n_tiles), int(k), ctypes.byref(b)))
+        return b.value
+
+    def tile_near_dups(self, planes: Sequence[Sequence[int]], filters: Sequence[int], n_clusters: int, k: int,
+                       workspace: int, workspace_bytes: int, labels: Optional[Sequence[int]] = None, hash_bits: int = 0,
+                       pair_budget: int = 0, tables=None, L=None):
+        """The near-duplicate clusters of every tile (wd_tile_near_dups, include/welldup_tilenear.h): PF wells
+        linked by Hamming distance <= k wherever on the tile they lie; needs every well as a target.  labels:
+        n_tiles device addresses of N uint32 each, or None.  Returns rows [n_tiles, 5 + 2*levels + 8]: [PF wells,
+        Clusters, InClusters, Redundant, NearPairs, Local[levels], RingWells[levels], size bins 2..8, 9+].  A tile
+        with more candidate pairs in a segment than pair_budget (0 = the default) raises RuntimeError."""
+        n_tiles = len(filters)
+        if L is None:
+            L = len(planes[0]) if n_tiles else 0
+        pt, ft = tables if tables is not None else self._tables(planes, filters, L)
+        rows = np.zeros((n_tiles, 5 + 2 * self.levels + _lib.DUPSET_SIZE_BINS), dtype=np.int64)
+        lt = (ctypes.c_void_p * max(1, n_tiles))(*[int(p) for p in labels]) if labels is not None else None
+        self._ck(self._lib.wd_tile_near_dups(
+            self._ctx, n_tiles, L, pt, ft, int(n_clusters), int(k), ctypes.c_void_p(workspace), int(workspace_bytes),
+            int(hash_bits), int(pair_budget), rows.ctypes.data_as(ctypes.c_void_p), lt))
+        return rows
+
     def scan_async(self, tables, n_tiles: int, L: int, n_clusters: int, mode: int, k: int,
                    out_tile_dev: int, out_per_target_dev: Optional[int] = None):
         pt, ft = tables
@@ -508,6 +533,11 @@ class TileBatch:
         if reuse is not None and reuse.sc is scanner and reuse.d_tdups:
             self.d_tdups, self._tdups_cap = reuse.d_tdups, reuse._tdups_cap
             reuse.d_tdups = 0
+        # near-duplicate clusters (tile_near_dups): the same again
+        self.d_tnear, self._tnear_cap = 0, 0
+        if reuse is not None and reuse.sc is scanner and reuse.d_tnear:
+            self.d_tnear, self._tnear_cap = reuse.d_tnear, reuse._tnear_cap
+            reuse.d_tnear = 0
 
     def plane_ptr(self, tile: int, cycle: int) -> int:
         """Address of well 0 of the cycle (wells are `interleave` bytes apart)."""
@@ -620,8 +650,32 @@ class TileBatch:
             lab = self.sc.d2h(d_lbl, lbl_bytes, np.uint32).reshape(self.n_tiles, self.N)
         return rows, lab
 
+    def tile_near_dups(self, k: int, labels: bool = False, pair_budget: int = 0, hash_bits: int = 0):
+        """The near-duplicate clusters (Hamming distance <= k) of every tile of the batch (Scanner.tile_near_dups;
+        every well must be a target, the batch a plane per cycle).  -> (rows, labels uint32 [n_tiles, N] or None)."""
+        ws = self.sc.tile_near_dups_workspace_bytes(self.N, self.n_tiles, k)
+        lbl_bytes = 4 * self.N * self.n_tiles if labels else 0
+        if not self.d_tnear or self._tnear_cap < ws + lbl_bytes:
+            if self.d_tnear:
+                self.sc.free(self.d_tnear)
+                self.d_tnear = 0
+            self._tnear_cap = ws + lbl_bytes
+            self.d_tnear = self.sc.malloc(max(1, self._tnear_cap))
+        d_lbl = self.d_tnear + ws if labels else 0
+        lbl_ptrs = [d_lbl + 4 * self.N * i for i in range(self.n_tiles)] if labels else None
+        self.sc.set_option("well_stride", self.interleave)
+        try:
+            rows = self.sc.tile_near_dups(None, self.filter_ptrs(), self.N, k, self.d_tnear, ws, labels=lbl_ptrs,
+                                          hash_bits=hash_bits, pair_budget=pair_budget, tables=self.tables, L=self.L)
+        finally:
+            self.sc.set_option("well_stride", 1)
+        lab = None
+        if labels:
+            lab = self.sc.d2h(d_lbl, lbl_bytes, np.uint32).reshape(self.n_tiles, self.N)
+        return rows, lab
+
     def free(self):
-        for ptr in (self.d_planes, self.d_filters, self.d_tmp, self.d_sets, self.d_tdups):
+        for ptr in (self.d_planes, self.d_filters, self.d_tmp, self.d_sets, self.d_tdups, self.d_tnear):
             if ptr:
                 self.sc.free(ptr)
-        self.d_planes = self.d_filters = self.d_tmp = self.d_sets = self.d_tdups = 0
+        self.d_planes = self.d_filters = self.d_tmp = self.d_sets = self.d_tdups = self.d_tnear = 0
