@@ -5,7 +5,7 @@
 
 The numbers are the compiler's own (the AMDGPU metadata note of the code object: llvm-readelf
 --notes), so they describe exactly the binary that ships - no GPU needed.  Patterns are substrings
-of the demangled kernel names (default: the scan kernels)."""
+of the demangled kernel names (default: the scan kernels and the lane-duplicate kernels, k_ld_*)."""
 import json
 import os
 import re
@@ -68,7 +68,7 @@ def main(argv):
         i = argv.index("--json")
         js = argv[i + 1]
         argv = argv[:i] + argv[i + 2:]
-    pats = argv or ["k_scan_q", "k_scan_lines", "k_dense_"]
+    pats = argv or ["k_scan_q", "k_scan_lines", "k_dense_", "k_ld_"]
     ks = kernels()
     sel = {k: v for k, v in sorted(ks.items()) if any(p in k for p in pats)}
     print("%-58s %5s %5s %6s %6s %7s %8s" % ("kernel", "vgpr", "sgpr", "s.spill", "v.spill", "lds", "scratch"))

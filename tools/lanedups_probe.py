@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""Read classes of a whole lane (scanner.LaneDups, include/welldup_lanedups.h) beside what they sit next to: a
+lane of `--tiles` full-size tiles fed in batches of `--batch` through two TileBatches that take turns, as the
+CLI streams a lane (the buffers of a batch are overwritten two batches later).  Wall clock per call (all are
+synchronous), in the same process and on the same resident batches: LaneDups.add and, at the end,
+LaneDups.finish; TileBatch.tile_dups; the equality scan (TileBatch.count); and the rate of a kernel that only
+reads the planes (Scanner.stream_read_gbs) - k_ld_pack reads exactly those bytes once.  The tiles are those of
+tools/tiledups_probe.py (seed 5, tiles 1101.., 2 % planted inside each tile), which share no read; with `--cross`
+every odd tile repeats the tile before it but for the first cycle, so that a quarter of its wells have a
+classmate there and the lane's table is joined as often as claimed.
+`--equal` adds a lane of three tiles whose reads are all equal (one slot takes every well: the worst case).
+For per-kernel times run it under
+
+    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/lanedups_probe.py
+
+(the k_ld_* rows of the stats are this stage, k_td_* the per-tile classes, k_dense_* the scan)."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from well_duplicates_amd import synth, workload                  # noqa: E402
+from well_duplicates_amd.scanner import LaneDups, Scanner, TileBatch       # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--rows", type=int, default=workload.HISEQ4000_ROWS)
+ap.add_argument("--cols", type=int, default=workload.HISEQ4000_COLS)
+ap.add_argument("--levels", type=int, default=3)
+ap.add_argument("--cycles", type=int, default=150)
+ap.add_argument("--tiles", type=int, default=32)
+ap.add_argument("--batch", type=int, default=8)
+ap.add_argument("--plant", type=int, default=1311, help="planted wells per 65536 inside a tile (1311 = 2 %%)")
+ap.add_argument("--cross", action="store_true", help="every odd tile repeats the tile before it but for the first cycle")
+ap.add_argument("--equal", action="store_true", help="also time a lane of three tiles whose reads are all equal")
+a = ap.parse_args()
+
+n = a.rows * a.cols
+x, y = synth.honeycomb_pixels(a.rows, a.cols)
+sc = Scanner(0)
+T, P = sc.targets_from_coords(x, y, None, levels=a.levels)
+spec = synth.SynthSpec(seed=5, n_clusters=n, row=a.cols, plant_per_64k=a.plant)
+ws = sc.lane_dups_workspace_bytes(n, a.tiles, a.cycles)
+print("lane of %d tiles of %d wells, %d cycles, batches of %d; %.2f %% planted inside a tile%s; workspace %.2f GB"
+      % (a.tiles, n, a.cycles, a.batch, 100.0 * a.plant / 65536,
+         ", odd tiles repeat the tile before but for cycle 0" if a.cross else "", ws / 1e9))
+
+
+def clock(fn):
+    t0 = time.perf_counter()
+    out = fn()
+    return out, (time.perf_counter() - t0) * 1e3
+
+
+def fill(tb, tiles):
+    """tools/tiledups_probe.py's tiles; with --cross every odd tile has the planes of the tile before it but for
+    cycle 0, and a filter of its own: the wells whose first base happens to agree (a quarter) are copies"""
+    for s, t in enumerate(tiles):
+        own = 1101 + t
+        base = own - 1 if (a.cross and t % 2) else own
+        sc.synth_filter(tb.filter_ptr(s), spec, 1, own)
+        for c in range(a.cycles):
+            sc.synth_plane(tb.plane_ptr(s, c), spec, 1, own if c == 0 else base, c)
+    sc.synchronize()
+
+
+batches = [list(range(b0, min(a.tiles, b0 + a.batch))) for b0 in range(0, a.tiles, a.batch)]
+tbs = [TileBatch(sc, a.batch, a.cycles, n), TileBatch(sc, a.batch, a.cycles, n)] if a.tiles else []
+ld = LaneDups(sc, n, a.tiles, a.cycles)
+t_add = t_td = t_cnt = t_read = 0.0
+read_gbs = []
+td_pf = td_red = 0
+for bi, tiles in enumerate(batches):
+    tb = tbs[bi % 2]
+    if len(tiles) != tb.n_tiles:                     # a short last batch
+        tb = TileBatch(sc, len(tiles), a.cycles, n, reuse=tb)
+        tbs[bi % 2] = tb
+    fill(tb, tiles)
+    if bi == 0:                                      # warm-up of every path, on a lane that is dropped
+        warm = LaneDups(sc, n, len(tiles), a.cycles)
+        warm.add(tb, list(range(len(tiles))))
+        warm.finish()
+        warm.close()
+        tb.tile_dups()
+        tb.count(0, 0)
+    _, dt = clock(lambda: ld.add(tb, tiles))
+    t_add += dt
+    (rows, _), dt = clock(lambda: tb.tile_dups())
+    t_td += dt
+    td_pf += int(rows[:, 0].sum())
+    td_red += int(rows[:, 3].sum())
+    _, dt = clock(lambda: tb.count(0, 0))
+    t_cnt += dt
+    gbs = sc.stream_read_gbs(tb.d_planes, tb.plane_bytes)
+    read_gbs.append(gbs)
+    t_read += tb.plane_bytes / gbs / 1e6
+(lane, trow, _), t_fin = clock(lambda: ld.finish())
+ld.close()
+for tb in tbs:
+    tb.free()
+
+k = max(1, a.tiles)
+wells = lane[0]
+print("%d PF wells, %d classes (%d across tiles), %d wells in them; lane duplication %.3f %% (within tiles %d, across "
+      "tiles %d); the tiles one by one: %.3f %%" % (wells, lane[1], lane[4], lane[2], 100.0 * lane[3] / max(1, wells),
+                                                   lane[2] - lane[5], lane[5] - lane[1], 100.0 * td_red / max(1, td_pf)))
+assert trow[:, 3].sum() == td_red and wells == td_pf, "TileRedundant differs from tile_dups' Redundant"
+print("  %-22s %9.3f ms  (%.4f ms per tile, %.2f G wells/s)" % ("lane_dups add", t_add, t_add / k, a.tiles * n / t_add / 1e6))
+print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("lane_dups finish", t_fin, t_fin / k))
+print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("add + finish", t_add + t_fin, (t_add + t_fin) / k))
+print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("tile_dups", t_td, t_td / k))
+print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("count", t_cnt, t_cnt / k))
+print("  %-22s %9.3f ms  (%.4f ms per tile, %.0f GB/s)" % ("pure read of the planes", t_read, t_read / k,
+                                                            float(np.mean(read_gbs)) if read_gbs else 0.0))
+print("  (add + finish) / tile_dups = %.2f; add / pure read = %.2f" % ((t_add + t_fin) / t_td, t_add / t_read))
+
+if a.equal:
+    three = TileBatch(sc, 3, a.cycles, n)
+    for s in range(3):
+        three.upload_tile(s, [np.full(n, 0x42 + (c % 4), dtype=np.uint8) for c in range(a.cycles)], np.ones(n, dtype=np.uint8))
+    eq = LaneDups(sc, n, 3, a.cycles)
+    _, e_add = clock(lambda: eq.add(three, [0, 1, 2]))
+    (lane, trow, _), e_fin = clock(lambda: eq.finish())
+    assert lane[:6].tolist() == [3 * n, 1, 3 * n, 3 * n - 1, 1, 3]
+    print("every read equal, three tiles: add %.3f ms, finish %.3f ms" % (e_add, e_fin))
+    eq.close()
+    three.free()
+sc.close()

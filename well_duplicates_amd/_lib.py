@@ -119,6 +119,17 @@ TILENEAR_PROTOTYPES = {
 }
 TILENEAR_MAX_K = 3
 
+# name -> (restype, argtypes); every symbol include/welldup_lanedups.h declares beyond the four above
+LANEDUPS_PROTOTYPES = {
+    "wd_lane_dups_workspace": (_i, [_i64, _i, _i, ctypes.POINTER(_sz)]),
+    "wd_lane_dups_begin": (_i, [_vp, _i64, _i, _i, _vp, _sz, _i, _pp]),
+    "wd_lane_dups_add": (_i, [_vp, _i, ctypes.POINTER(_i), _pp, _pp]),
+    "wd_lane_dups_finish": (_i, [_vp, _vp, _vp, _pp]),
+    "wd_lane_dups_end": (None, [_vp]),
+}
+LANEDUPS_LANE_COLS = 6 + DUPSET_SIZE_BINS
+LANEDUPS_TILE_COLS = 5
+
 _lib = None
 
 
@@ -144,7 +155,7 @@ def _deps(path: str, seen=None) -> set:
 
 def source_build_id() -> str:
     """sha256 over the library's sources (csrc/*, include/welldup.h, include/welldup_sets.h,
-    include/welldup_tiledups.h, include/welldup_tilenear.h): what `wd_build_id()` of a library
+    include/welldup_tiledups.h, include/welldup_tilenear.h, include/welldup_lanedups.h): what `wd_build_id()` of a library
     built from this tree returns.  Counter profiles and resource tables carry it (tools/pmc_collect.py),
     so that evidence is tied to the code that produced it, not to a kernel's name."""
     import hashlib
@@ -155,6 +166,7 @@ def source_build_id() -> str:
     files.append(os.path.join(INCLUDE, "welldup_sets.h"))
     files.append(os.path.join(INCLUDE, "welldup_tiledups.h"))
     files.append(os.path.join(INCLUDE, "welldup_tilenear.h"))
+    files.append(os.path.join(INCLUDE, "welldup_lanedups.h"))
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         with open(f, "rb") as fh:
@@ -204,7 +216,7 @@ def unit_of_kernel(kernel: str) -> str:
         return "ingest"
     if kernel.startswith("k_sets"):
         return "sets"
-    if kernel.startswith(("k_td_", "k_tn_")):
+    if kernel.startswith(("k_td_", "k_tn_", "k_ld_")):
         return "tiledups"
     return "scan"
 
@@ -264,7 +276,7 @@ def load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the scan path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     for name, (res, args) in list(PROTOTYPES.items()) + list(SETS_PROTOTYPES.items()) + list(TILEDUPS_PROTOTYPES.items()) + \
-            list(TILENEAR_PROTOTYPES.items()):
+            list(TILENEAR_PROTOTYPES.items()) + list(LANEDUPS_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

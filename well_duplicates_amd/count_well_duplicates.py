@@ -22,13 +22,17 @@ Differences from the reference, all deliberate:
     intends (its own message formatting raises NameError first);
   * extra flags: --device, --dist-backend, --tile-batch, --threads, --strict, -o/--output,
     --all-wells, --slocs, --layout, --serial-ingest, --dup-sets, --dup-sets-out, --tile-dups, --tile-dups-out,
-    --tile-dups-hamming, --tile-dups-pair-budget;
+    --tile-dups-hamming, --tile-dups-pair-budget, --lane-dups, --lane-dups-out;
   * --all-wells --dup-sets groups every tile's wells into duplicate sets and follows each lane's report
     with their counts and the exact duplication (report.write_dup_sets);
   * --all-wells --tile-dups groups every tile's PF wells into classes of equal reads, wherever on the tile they
     lie, and follows each lane's report with the duplication of the tiles as a whole and the share of it
     that lies inside the rings (report.write_tile_dups); --tile-dups-hamming K adds the same for the clusters of
     reads within Hamming distance K of each other (report.write_tile_near_dups);
+  * --all-wells --lane-dups groups the PF wells of a whole lane into classes of equal reads, on whatever tiles they
+    lie (a LaneDups accumulator is fed every batch before its buffers are reused), and closes each lane's output
+    with the duplication of the lane, split into the part within tiles and the part across tiles, and the
+    library size it lets one estimate (report.write_lane_dups);
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
@@ -44,7 +48,7 @@ import numpy as np
 from . import bcl as bcl_direct_reader
 from . import _lib, report, workload
 from .report import LENGTH, TALLY, output_writer  # noqa: F401  (reference module surface)
-from .scanner import INVALID_TARGET, Scanner, TileBatch, compare_mode
+from .scanner import INVALID_TARGET, LaneDups, Scanner, TileBatch, compare_mode
 from .targets import load_targets, load_targets_csr
 
 __VERSION__ = 0.3        # report format version of the reference this mirrors (:4)
@@ -154,6 +158,16 @@ def parse_args(argv=None):
                    help="with --tile-dups-hamming: the most candidate pairs one segment of one tile may have before "
                         "the run is refused (reads of low diversity: amplicons, a shared adaptor); 0 = the "
                         "library's default, max(16 x wells, 2^24)")
+    p.add_argument("--lane-dups", action="store_true",
+                   help="with --all-wells: group the PF wells of every tile of a lane into classes of equal reads over "
+                        "the scanned cycles, on whatever tiles they lie, and print, after each lane's report and its "
+                        "other blocks, the classes, the redundant wells within tiles and across tiles, the duplication "
+                        "of the lane (redundant / PF wells) and the library size estimated from it.  A packed copy of "
+                        "every PF read of the lane stays in GPU memory until the lane is done: a lane that does not "
+                        "fit is refused before anything is loaded (single process only)")
+    p.add_argument("--lane-dups-out", default=None, metavar="PATH",
+                   help="with --lane-dups: write lane, tile, well, class_tile and class_well (tile and well of the "
+                        "first well of its class) of every well in a lane class to this TSV file")
     args = p.parse_args(argv)
     if not args.coord_file and not args.all_wells:
         p.error("the following arguments are required: -f/--coord_file (or --all-wells)")
@@ -179,6 +193,13 @@ def parse_args(argv=None):
         p.error("--tile-dups-pair-budget must not be negative")
     if args.tile_dups_pair_budget and args.tile_dups_hamming is None:
         p.error("--tile-dups-pair-budget needs --tile-dups-hamming")
+    if args.lane_dups and not args.all_wells:
+        p.error("--lane-dups needs --all-wells (the resident layout of every well, a plane per cycle)")
+    if args.lane_dups_out and not args.lane_dups:
+        p.error("--lane-dups-out needs --lane-dups")
+    if args.lane_dups and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        p.error("--lane-dups runs in a single process only: under WORLD_SIZE > 1 a lane's tiles are spread over the "
+                "ranks, and the classes of a lane need all of them in one GPU's table")
     return args
 
 
@@ -263,9 +284,30 @@ def set_members(labels: np.ndarray):
     return wells, labels[wells]
 
 
+def lane_members(labels: np.ndarray):
+    """A lane's labels [tiles, N] (LaneDups.finish) -> (tile index, well, class tile index, class well) of the
+    wells in a lane class, by tile index and well."""
+    n = labels.shape[1]
+    flat = labels.reshape(-1)
+    ids = np.flatnonzero(flat != INVALID_TARGET)
+    lab = flat[ids].astype(np.int64)
+    size = np.bincount(lab, minlength=flat.shape[0])
+    keep = size[lab] >= 2
+    ids, lab = ids[keep], lab[keep]
+    return ids // n, ids % n, lab // n, lab % n
+
+
+def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int):
+    """--lane-dups: the accumulator's workspace against the free device memory, before anything is loaded."""
+    if need > free:
+        raise MemoryError("--lane-dups needs %.2f GB of device memory for a lane of %d tiles x %d wells x %d cycles "
+                          "(%d bytes), and %.2f GB (%d bytes) are free" % (need / 1e9, tiles, wells, cycles, need,
+                                                                          free / 1e9, free))
+
+
 def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells, tile_batch,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
-               dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0):
+               dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
@@ -274,6 +316,11 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     batch after the scan: into["tdups"][(lane, tile)] = TileDupCounts, into["tmembers"][(lane, tile)].
     tile_near = K > 0 (with tile_dups): and the clusters at Hamming distance <= K (TileBatch.tile_near_dups):
     into["tnear"][(lane, tile)] = TileNearCounts, into["tnmembers"][(lane, tile)] = (wells, classes, clusters).
+    lane_dups (needs `into`, batches a plane per cycle): the read classes of every lane as a whole - a LaneDups
+    accumulator is begun at a lane's first batch, fed every batch after its scan and before its buffers are
+    released, and finished at the lane's last batch: into["ldups"][lane] = LaneDupCounts; 2 = and the members,
+    into["lmembers"][lane] = (tile names by index,) + lane_members(labels).  A tile index is the tile's place
+    in the lane's list.
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -311,6 +358,8 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     last_batch_of = {lane: bi for bi, (lane, _) in enumerate(batches)}
     pool = ThreadPoolExecutor(max_workers=max(1, threads))
     live = []                               # TileBatches not yet freed
+    lane_acc = {"ld": None, "lane": None}   # the LaneDups of the lane being scanned
+    tiles_of_lane = {lane: list(tiles) for lane, tiles in lane_tiles}
     spare = []                              # finished ones whose buffers the next batch takes over
 
     def start(batch):
@@ -439,6 +488,26 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                             ws, clusters = set_members(tn_labels[i])
                             into["tnmembers"][(lane, t)] = (ws, td_labels[i][ws], clusters)
                     _lap("batch %d: read clusters" % bi)
+            if lane_dups:
+                names = tiles_of_lane[lane]
+                ld = lane_acc["ld"]
+                if lane_acc["lane"] != lane:
+                    if ld is not None and (ld.N, ld.max_tiles, ld.L) == (n_clusters, len(names), len(cycle_list)):
+                        ld.restart()            # (the workspace of the lane before: freeing it would wait for the loaders)
+                    else:
+                        if ld is not None:
+                            ld.close()
+                        lane_acc["ld"] = None
+                        ld = lane_acc["ld"] = LaneDups(sc, n_clusters, len(names), len(cycle_list))
+                    lane_acc["lane"] = lane
+                ld.add(tb, [names.index(t) for t in chunk])
+                if last_batch_of[lane] == bi:
+                    lane_row, tile_rows, lane_labels = ld.finish(labels=lane_dups > 1)
+                    into["ldups"][lane] = report.LaneDupCounts.from_rows(lane_row, tile_rows, names)
+                    if lane_labels is not None:
+                        into["lmembers"][lane] = (names,) + lane_members(lane_labels)
+                        del lane_labels
+                _lap("batch %d: lane classes" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
             if want_log:
                 hits, total = sc.hitlog_fetch(max(1024, int(nbr.size) * len(chunk)))
@@ -481,6 +550,8 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     finally:
         # queued loads are dropped, running ones finish - only then may their targets go
         pool.shutdown(wait=True, cancel_futures=True)
+        if lane_acc["ld"] is not None:      # finished or half built
+            lane_acc["ld"].close()
         for tb in list(live):
             release(tb)
         for tb in spare:
@@ -507,6 +578,18 @@ def write_cluster_members(path, members):
             wells, classes, clusters = members[(lane, tile)]
             fh.writelines("%s\t%s\t%d\t%d\t%d\n" % (lane, tile, w, c, s)
                           for w, c, s in zip(wells.tolist(), classes.tolist(), clusters.tolist()))
+
+
+def write_lane_members(path, members):
+    """--lane-dups-out: lane, tile, well, class_tile, class_well of every well in a lane class, by lane, then in
+    the order of the lane's tiles, then by well.  members[lane] = (tile names by index, tile index, well, class
+    tile index, class well)."""
+    with open(path, "w") as fh:
+        fh.write("lane\ttile\twell\tclass_tile\tclass_well\n")
+        for lane in sorted(members, key=str):
+            names, ti, w, cti, cw = members[lane]
+            fh.writelines("%s\t%s\t%d\t%s\t%d\n" % (lane, names[a], b, names[c], d)
+                          for a, b, c, d in zip(ti.tolist(), w.tolist(), cti.tolist(), cw.tolist()))
 
 
 def main(argv=None, exiting=False):
@@ -669,13 +752,15 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                         equal = equal + tds[t]
                     report.write_tile_near_dups(lane, near_k, tns, verbose=not args.summary_only, out=out_fh,
                                                 levels=levels, equal=equal)
+                if args.lane_dups:          # (single process: the lane's counts never travel through `block`)
+                    report.write_lane_dups(lane, results["ldups"][lane], verbose=not args.summary_only, out=out_fh)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
                 where = {item: i for i, item in enumerate(mine)}
                 # scan_lanes fills these, lane_done reads them
                 results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
-                           "tnear": {}, "tnmembers": {}}
+                           "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}}
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
@@ -693,6 +778,11 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                     if world == 1:          # as the reference: a lane is reported when it is done
                         emit(lane, rows)
 
+                if err is None and args.lane_dups:
+                    # before anything is loaded: a lane's accumulator has to fit beside the batches
+                    import torch
+                    check_lane_dups_fits(sc.lane_dups_workspace_bytes(n_targets, len(tiles), len(cycle_list)),
+                                         torch.cuda.mem_get_info(device)[0], len(tiles), n_targets, len(cycle_list))
                 if err is None:             # (a rank whose setup failed has nothing to scan: it goes to the flag)
                     scan_lanes(sc, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                                max(0, args.tile_batch), args.threads,
@@ -702,13 +792,16 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                gpu_inflate=not args.host_inflate, lane_done=lane_done, into=results,
                                dup_sets=(2 if args.dup_sets_out else 1) if args.dup_sets else 0,
                                tile_dups=(2 if args.tile_dups_out else 1) if args.tile_dups else 0,
-                               tile_near=near_k, pair_budget=args.tile_dups_pair_budget)
+                               tile_near=near_k, pair_budget=args.tile_dups_pair_budget,
+                               lane_dups=(2 if args.lane_dups_out else 1) if args.lane_dups else 0)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
                     if args.tile_dups_out and near_k:
                         write_cluster_members(args.tile_dups_out, results["tnmembers"])
                     elif args.tile_dups_out:
                         write_set_members(args.tile_dups_out, results["tmembers"], column="class")
+                    if args.lane_dups_out:
+                        write_lane_members(args.lane_dups_out, results["lmembers"])
             except Exception as e:          # noqa: BLE001 - re-raised below, on every rank
                 err = e
             if world > 1:

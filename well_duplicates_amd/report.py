@@ -20,6 +20,7 @@ This printer reports 0.00 % instead; pass strict=True to get the reference's exc
 """
 from __future__ import annotations
 
+import math
 import sys
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
@@ -434,3 +435,105 @@ def write_tile_near_dups(lane, k: int, counts: Dict[str, TileNearCounts], verbos
         line += "\tby equality: {:.2%}".format(equal.tile_duplication())
     print(line, file=out)
     print("Local share at level {} (Local/InClusters): {:.2%}".format(levels, tot.local_share()), file=out)
+
+
+LANE_ROW_COLS = 6 + len(CLASS_BIN_NAMES)
+LANE_TILE_COLS = 5
+
+
+def library_size(reads: int, distinct: int) -> Optional[float]:
+    """The Lander-Waterman estimate other duplicate markers print: the X that solves
+    distinct / X = 1 - exp(-reads / X), found by bisection; None when no read is redundant (no X is large
+    enough) or there is no read at all."""
+    n, c = float(reads), float(distinct)
+    if c <= 0 or c >= n:
+        return None
+    f = lambda x: -x * math.expm1(-n / x) - c        # increasing in x; f(c) < 0, f(x) -> n - c > 0
+    lo, hi = c, 2.0 * c
+    while f(hi) <= 0.0:
+        lo, hi = hi, 2.0 * hi
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if mid <= lo or mid >= hi:
+            break
+        if f(mid) <= 0.0:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
+
+
+@dataclass
+class LaneDupCounts:
+    """Read classes across all tiles of a lane (include/welldup_lanedups.h, the LaneDups accumulator): the lane
+    row's columns, and per tile (by the tile's name) [PF, InLane, InTile, TileRedundant, LaneRedundant]."""
+    pf: int = 0
+    classes: int = 0
+    in_classes: int = 0
+    redundant: int = 0
+    cross_tile_classes: int = 0
+    tile_spans: int = 0
+    sizes: List[int] = field(default_factory=lambda: [0] * len(CLASS_BIN_NAMES))
+    tiles: Dict[str, List[int]] = field(default_factory=dict)
+
+    @classmethod
+    def from_rows(cls, lane_row: Sequence[int], tile_rows: Sequence[Sequence[int]], tile_names: Sequence) -> "LaneDupCounts":
+        """lane_row and tile_rows as LaneDups.finish returns them; tile_names[i]: the name of tile index i (an
+        index beyond the names, or a name of None, was never a tile of the lane and is left out)."""
+        b = [int(v) for v in lane_row]
+        assert len(b) == LANE_ROW_COLS
+        tiles = {}
+        for name, row in zip(tile_names, tile_rows):
+            assert len(row) == LANE_TILE_COLS
+            if name is not None:
+                tiles[name] = [int(v) for v in row]
+        return cls(b[0], b[1], b[2], b[3], b[4], b[5], b[6:], tiles)
+
+    def to_rows(self):
+        """-> (lane row, tile rows in sorted order of the tiles' names)"""
+        return ([self.pf, self.classes, self.in_classes, self.redundant, self.cross_tile_classes, self.tile_spans] +
+                list(self.sizes), [list(self.tiles[t]) for t in sorted(self.tiles)])
+
+    @property
+    def within_tiles(self) -> int:
+        """Redundant wells with a classmate of smaller well index on their own tile: InClasses - TileSpans."""
+        return self.in_classes - self.tile_spans
+
+    @property
+    def across_tiles(self) -> int:
+        """The rest of Redundant, TileSpans - Classes: first wells of their class on a tile it did not begin on."""
+        return self.tile_spans - self.classes
+
+    def lane_duplication(self) -> float:
+        """Redundant wells / PF wells (0 without PF wells)."""
+        return self.redundant / self.pf if self.pf else 0.0
+
+    def library_size(self) -> Optional[float]:
+        return library_size(self.pf, self.pf - self.redundant)
+
+
+def write_lane_dups(lane, counts: LaneDupCounts, verbose: bool = False, out=None) -> None:
+    """The block that follows a lane's report (and its --dup-sets / --tile-dups blocks) under --lane-dups: per-tile
+    lines (verbose, in sorted tile order as write_report), the lane's classes, their sizes, the redundant wells
+    split into those within tiles and those across tiles, the duplication of the lane and the library size it
+    lets one estimate."""
+    out = out or sys.stdout
+    c = counts
+    print(file=out)
+    if verbose:
+        for tile in sorted(c.tiles):
+            t = c.tiles[tile]
+            print("LaneDups: %s\tTile: %s\tPF wells: %i\tInLane: %i\tInTile: %i\tTileRedundant: %i\tLaneRedundant: %i" % (
+                lane, tile, t[0], t[1], t[2], t[3], t[4]), file=out)
+    print("LaneDupsSummary: %s\tTiles: %i\tPF wells: %i\tClasses: %i\tInClasses: %i (%.5f)\tRedundant: %i (%.5f)\t"
+          "CrossTileClasses: %i\tTileSpans: %i" % (
+              lane, len(c.tiles), c.pf, c.classes, c.in_classes, c.in_classes / c.pf if c.pf else 0.0, c.redundant,
+              c.redundant / c.pf if c.pf else 0.0, c.cross_tile_classes, c.tile_spans), file=out)
+    print("ClassSizes: %s" % "\t".join("%s: %i" % (name, n) for name, n in zip(CLASS_BIN_NAMES, c.sizes)), file=out)
+    share = lambda v: v / c.redundant if c.redundant else 0.0
+    print("Redundant within tiles: %i (%.5f of Redundant)\tacross tiles: %i (%.5f of Redundant)" % (
+        c.within_tiles, share(c.within_tiles), c.across_tiles, share(c.across_tiles)), file=out)
+    print("Lane duplication (Redundant/PF wells): {:.2%}".format(c.lane_duplication()), file=out)
+    size = c.library_size()
+    print("Estimated library size (distinct/X = 1 - exp(-PF/X)): %s" % ("n/a" if size is None else "%.0f" % size),
+          file=out)

@@ -304,6 +304,13 @@ class Scanner:
             int(hash_bits), int(pair_budget), rows.ctypes.data_as(ctypes.c_void_p), lt))
         return rows
 
+    def lane_dups_workspace_bytes(self, n_clusters: int, max_tiles: int, L: int) -> int:
+        """Device bytes a LaneDups accumulator needs for max_tiles tiles of n_clusters wells and L cycles
+        (wd_lane_dups_workspace; a lane of 2^32 - 1 wells or more raises RuntimeError)."""
+        b = ctypes.c_size_t()
+        self._ck(self._lib.wd_lane_dups_workspace(int(n_clusters), int(max_tiles), int(L), ctypes.byref(b)))
+        return b.value
+
     def scan_async(self, tables, n_tiles: int, L: int, n_clusters: int, mode: int, k: int,
                    out_tile_dev: int, out_per_target_dev: Optional[int] = None):
         pt, ft = tables
@@ -485,6 +492,92 @@ class Scanner:
         s = self._spec_c(spec, tile)
         self._ck(self._lib.wd_synth_filter(self._ctx, ctypes.c_void_p(dst), ctypes.byref(s),
                                            int(lane), int(tile)))
+
+
+class LaneDups:
+    """The read classes across all tiles of a lane (include/welldup_lanedups.h): an accumulator the batches of
+    a lane are fed to one after the other.  It owns its workspace: a packed copy of every read and the lane's
+    table, so a batch's planes may be reused as soon as `add` returns."""
+
+    def __init__(self, scanner: Scanner, n_clusters: int, max_tiles: int, L: int, hash_bits: int = 0):
+        self.sc = scanner
+        self.N, self.max_tiles, self.L, self.hash_bits = int(n_clusters), int(max_tiles), int(L), int(hash_bits)
+        self.ws_bytes = scanner.lane_dups_workspace_bytes(self.N, self.max_tiles, self.L)
+        self.d_ws = scanner.malloc(self.ws_bytes)
+        self.d_labels = 0
+        self._h = None
+        try:
+            self._begin(self.d_ws, self.ws_bytes)
+        except Exception:
+            self.close()
+            raise
+
+    def _begin(self, workspace: int, workspace_bytes: int):
+        h = ctypes.c_void_p()
+        self.sc._ck(self.sc._lib.wd_lane_dups_begin(self.sc._ctx, self.N, self.max_tiles, self.L, ctypes.c_void_p(workspace),
+                                                    int(workspace_bytes), self.hash_bits, ctypes.byref(h)))
+        self._h = h
+
+    def restart(self):
+        """Drops what has been added and begins another lane of the same shape in the same workspace."""
+        self._end()
+        self._begin(self.d_ws, self.ws_bytes)
+
+    def add(self, tb: "TileBatch", tile_indices: Sequence[int]):
+        """Adds the tiles of a resident batch (a plane per cycle); tile_indices[i]: slot i's number in the lane,
+        0 .. max_tiles - 1, each used once.  A bad index, the interleaved layout or a call after finish raises
+        ValueError and changes nothing."""
+        idx = [int(t) for t in tile_indices]
+        if len(idx) != tb.n_tiles or tb.L != self.L or tb.N != self.N:
+            raise ValueError("the batch has %d tiles of %d wells and %d cycles; %d indices for a lane of %d wells and "
+                             "%d cycles" % (tb.n_tiles, tb.N, tb.L, len(idx), self.N, self.L))
+        self.add_tables(idx, tb.tables, well_stride=tb.interleave)
+
+    def add_tables(self, tile_indices: Sequence[int], tables, well_stride: int = 1):
+        """add() from the ctypes pointer tables Scanner._tables makes (planes n x L, filters n)."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        pt, ft = tables
+        ti = (ctypes.c_int * max(1, len(tile_indices)))(*tile_indices)
+        self.sc.set_option("well_stride", well_stride)
+        try:
+            self.sc._ck(self.sc._lib.wd_lane_dups_add(self._h, len(tile_indices), ti, pt, ft))
+        finally:
+            self.sc.set_option("well_stride", 1)
+
+    def finish(self, labels: bool = False):
+        """Once.  -> (lane row int64 [14]: [PF, Classes, InClasses, Redundant, CrossTileClasses, TileSpans, size
+        bins 2..8, 9+], tile rows int64 [max_tiles, 5]: [PF, InLane, InTile, TileRedundant, LaneRedundant],
+        labels uint32 [max_tiles, N] or None)."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        lane_row = np.zeros(_lib.LANEDUPS_LANE_COLS, dtype=np.int64)
+        tile_rows = np.zeros((self.max_tiles, _lib.LANEDUPS_TILE_COLS), dtype=np.int64)
+        lt = None
+        lbl_bytes = 4 * self.N * self.max_tiles
+        if labels:
+            if not self.d_labels:
+                self.d_labels = self.sc.malloc(max(1, lbl_bytes))
+            lt = (ctypes.c_void_p * max(1, self.max_tiles))(*[self.d_labels + 4 * self.N * i for i in range(self.max_tiles)])
+        self.sc._ck(self.sc._lib.wd_lane_dups_finish(self._h, lane_row.ctypes.data_as(ctypes.c_void_p),
+                                                     tile_rows.ctypes.data_as(ctypes.c_void_p), lt))
+        lab = None
+        if labels:
+            lab = self.sc.d2h(self.d_labels, lbl_bytes, np.uint32).reshape(self.max_tiles, self.N)
+        return lane_row, tile_rows, lab
+
+    def _end(self):
+        if self._h is not None:
+            self.sc._lib.wd_lane_dups_end(self._h)
+            self._h = None
+
+    def close(self):
+        """Drops the lane, finished or not, and frees the workspace."""
+        self._end()
+        for ptr in (self.d_ws, self.d_labels):
+            if ptr:
+                self.sc.free(ptr)
+        self.d_ws = self.d_labels = 0
 
 
 class TileBatch:
