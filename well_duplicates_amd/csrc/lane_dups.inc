@@ -1,13 +1,14 @@
 // lane_dups.inc - read classes across all tiles of a lane (include/welldup_lanedups.h): an accumulator that
 // outlives the batches a lane is streamed through device memory in, and stays exact.  Included at the end of
-// welldup_tiledups.hip: it uses that unit's fingerprint (Fp, mix64), code_of, block size and the free-slot word.
+// welldup_tiledups.hip: it uses read_classes.inc (plane_pass, claim_or_join, wave_grouped, the spread counters)
+// and that unit's block size and host checks.
 //
 // In the caller's workspace, for W = max_tiles * N wells of capacity (a well's place is its global id
 // g = tile_index * N + well): one table for the lane, the packed rows [W][R] (R = ceil(L / 10) words of ten 3-bit
 // codes), aux [W] uint64 (fingerprint, then slot, then slot of the second table), label [W], members [W].
 //
 // wd_lane_dups_add, per batch of tiles (grid y = tile of the batch):
-//   k_ld_pack        k_td_fingerprint's pass over the planes; the 30-bit words it folds are also stored as the
+//   k_ld_pack        the pass of k_td_fingerprint over the planes; the 30-bit words it folds are also stored as the
 //                    well's packed row - after this kernel nothing reads the planes again
 //   k_ld_insert      one lane per PF well into the lane's table; equality is decided on the packed rows
 // wd_lane_dups_finish, over the tiles that were added:
@@ -67,29 +68,12 @@ LdLayout ld_layout_of(int64_t N, int max_tiles, int L)
 
 __device__ inline unsigned long long *ld_tile_cnt(unsigned long long *cnt_t, int tile_index)
 {
-    return cnt_t + ((size_t)tile_index * kSpread + blockIdx.x % kSpread) * kLdTileCnt;
-}
-
-// The lanes of a wave that name the same word as the first active one add once, the others one each: what
-// this lane has to add (wells of one class lie side by side when every read is equal - k_td_resolve).  Every
-// lane of the wave must call it.
-__device__ inline uint32_t ld_grouped(bool active, uint32_t key)
-{
-    const unsigned long long act = __ballot(active);
-    if (!act)
-        return 0;
-    const int lane = threadIdx.x & (kWave - 1), leader = __ffsll((long long)act) - 1;
-    const uint32_t key0 = (uint32_t)__shfl((int)key, leader);
-    const bool same = active && key == key0;
-    const unsigned long long group = __ballot(same);
-    if (lane == leader)
-        return (uint32_t)__popcll(group);
-    return active && !same ? 1u : 0u;
+    return spread_row(cnt_t, (size_t)tile_index, kLdTileCnt);
 }
 
 // ---- pack ---------------------------------------------------------------------------------------
-// k_td_fingerprint's loop - dword loads of four wells, ten planes in flight, the plane pointers through the
-// scalar cache - with the 30-bit words stored as the wells' rows as well.  Also clears the wells' members
+// The words of plane_pass (plane_word4 one at a time: the wave stops every kLdChunk words) stored as the wells'
+// rows as well.  Also clears the wells' members
 // (k_ld_resolve counts into them).
 // A lane that stored its four wells' words as they come writes four bytes each to four rows, 64 rows per
 // store instruction: at 150 cycles that is 69 M four-byte write requests per tile, and they, not the bytes,
@@ -105,42 +89,16 @@ constexpr int kLdChunk = 8;                        // words of a row staged befo
 constexpr int kLdWaveWells = 4 * kWave;            // wells of a workgroup of k_ld_pack<true>
 constexpr int kLdStride = kLdWaveWells + 32 / kLdChunk;
 
-// one word of four wells: planes c .. c + n - 1 (n = kFpCycles but for the last word of a row)
-__device__ inline void ld_word4(const uint8_t *const *pl, int c, int n, int64_t w0, uint32_t acc[4])
-{
-    if (n == kFpCycles) {
-        uint32_t v[kFpCycles];
-#pragma unroll
-        for (int j = 0; j < kFpCycles; j++)                 // (non-temporal: the planes are streamed)
-            v[j] = __builtin_nontemporal_load((const uint32_t *)(pl[c + j] + w0));
-#pragma unroll
-        for (int j = 0; j < kFpCycles; j++)
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                acc[q] |= code_of((v[j] >> (8 * q)) & 0xFFu) << (3 * j);
-        return;
-    }
-    for (int j = 0; j < n; j++) {
-        const uint32_t v = __builtin_nontemporal_load((const uint32_t *)(pl[c + j] + w0));
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-            acc[q] |= code_of((v >> (8 * q)) & 0xFFu) << (3 * j);
-    }
-}
-
 // one well, byte loads: unaligned planes, and the last N % 4 wells of a tile
 __device__ inline void ld_pack_well(const uint8_t *const *pl, int L, int words, int64_t w, size_t g,
                                     uint32_t *__restrict__ rows, unsigned long long *__restrict__ fp,
                                     uint32_t *__restrict__ members)
 {
     Fp h;
-    for (int c = 0, k = 0; c < L; c += kFpCycles, k++) {
-        uint32_t acc = 0;
-        for (int j = 0; j < kFpCycles && c + j < L; j++)
-            acc |= code_of(pl[c + j][w]) << (3 * j);
-        h.fold(acc);
-        rows[g * words + k] = acc;
-    }
+    plane_pass<false>(pl, 0, L, w, [&](int k, const uint32_t(&acc)[1]) {
+        h.fold(acc[0]);
+        rows[g * words + k] = acc[0];
+    });
     fp[g] = h.value();
     members[g] = 0;
 }
@@ -175,8 +133,11 @@ __global__ void __launch_bounds__(VEC4 ? kWave : kTdBlock) k_ld_pack(const uint8
         int kc = 0;                                                        // words staged (the same for every lane)
         for (; kc < kLdChunk && c < L; kc++, c += kFpCycles) {
             if (quad) {
-                uint32_t acc[4] = {0, 0, 0, 0};
-                ld_word4(pl, c, min(kFpCycles, L - c), w0, acc);
+                uint32_t acc[4];
+                if (c + kFpCycles <= L)
+                    plane_word4<true>(pl, c, L, w0, acc);
+                else
+                    plane_word4<false>(pl, c, L, w0, acc);
 #pragma unroll
                 for (int q = 0; q < 4; q++)
                     h[q].fold(acc[q]);
@@ -211,25 +172,13 @@ __global__ void __launch_bounds__(VEC4 ? kWave : kTdBlock) k_ld_pack(const uint8
 }
 
 // ---- the lane's table -----------------------------------------------------------------------------
-// A slot is (tag << 32) | global id, all ones = free, and is only touched by agent-scope atomics inside a
-// kernel, as in k_td_insert: a relaxed load first, a CAS that claims a free slot with tag and own id at once,
-// an atomic min that lowers the representative.  The argument of welldup_tiledups.hip carries over with
-// "global id" for "well index".  Why the outcome does not depend on the order of execution:
-//   - a slot is claimed once and never freed, and every well that joins it has been compared with its
-//     representative on the packed rows and found equal: all wells a slot ever names belong to one class, so
-//     a stale representative is still a member of that class and decides a comparison the same way;
-//   - a load that sees a free slot is followed by the CAS, which fails on a slot claimed meanwhile and
-//     returns what it holds: the lane then treats the slot as it would have, had it seen that value;
-//   - every well of a class therefore passes the same slots (those of other classes on its probe path, which
-//     never change class) and stops at the first that is free or its own class's: a class has exactly one
-//     slot, and the min leaves its smallest global id there, whichever lane came first.
-// Across wd_lane_dups_add calls in any order: none of the three points speaks of when a lane runs.  The table
-// persists between the calls and is never cleared or rehashed before the finish, so the lanes of a later call
-// are to those of an earlier one what late lanes of one launch are to early ones - and the order of lanes
-// inside a launch is already arbitrary.  What a comparison reads is fixed before it runs: the packed rows of
+// claim_or_join with id = global id, equality decided on the packed rows (rows_equal).
+// Across wd_lane_dups_add calls in any order: none of the three points of its argument speaks of when a lane
+// runs.  The table persists between the calls and is never cleared or rehashed before the finish, so the lanes
+// of a later call are to those of an earlier one what late lanes of one launch are to early ones - and the
+// order of lanes inside a launch is already arbitrary.  What a comparison reads is fixed before it runs: the packed rows of
 // this batch and of every earlier one were written by k_ld_pack launches that ended before this kernel began,
 // and no kernel writes a row twice (a tile index is taken once).
-// Equality is decided by rows_equal, never by the tag: a tag only saves comparisons.
 __device__ inline bool rows_equal(const uint32_t *__restrict__ rows, int words, uint32_t a, uint32_t b)
 {
     const uint32_t *x = rows + (size_t)a * words, *y = rows + (size_t)b * words;
@@ -273,22 +222,10 @@ __global__ void __launch_bounds__(kTdBlock) k_ld_insert(const uint8_t *const *__
     }
     const uint32_t g = (uint32_t)g64;                                  // (max_tiles * N < 2^32 - 1)
     const unsigned long long m = mix64(aux[g64] & fp_mask);
-    const unsigned long long tag = m & 0xFFFFFFFF00000000ull, mine = tag | g;
-    unsigned long long s = m & slot_mask;
-    for (;;) {
-        unsigned long long cur = __hip_atomic_load(table + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == kEmpty &&
-            __hip_atomic_compare_exchange_strong(table + s, &cur, mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT))
-            break;                                                     // claimed (else cur = what the slot holds now)
-        if ((cur & 0xFFFFFFFF00000000ull) == tag && rows_equal(rows, words, g, (uint32_t)cur)) {
-            if (g < (uint32_t)cur)                                     // (the word only ever goes down)
-                __hip_atomic_fetch_min(table + s, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-        }
-        s = (s + 1) & slot_mask;                                       // the table has >= 2 W slots: a free one comes
-    }
-    aux[g64] = s;
+    const unsigned long long tag = m & 0xFFFFFFFF00000000ull;
+    aux[g64] = claim_or_join(table, slot_mask, m, tag, g, [=](unsigned long long cur) {             // (>= 2 W slots)
+        return (cur & 0xFFFFFFFF00000000ull) == tag && rows_equal(rows, words, g, (uint32_t)cur);
+    });
 }
 
 // ---- finish ---------------------------------------------------------------------------------------
@@ -318,7 +255,7 @@ __global__ void __launch_bounds__(kTdBlock) k_ld_resolve(const unsigned long lon
         if (labels_out && labels_out[ti])
             labels_out[ti][w] = lab;
     }
-    const uint32_t add = ld_grouped(lab != kInvalid && lab != (uint32_t)g, lab);
+    const uint32_t add = wave_grouped(lab != kInvalid && lab != (uint32_t)g, lab);
     if (add)
         atomicAdd(members + lab, add);
     const unsigned long long pf = __ballot(lab != kInvalid);
@@ -331,8 +268,8 @@ __global__ void __launch_bounds__(kTdBlock) k_ld_resolve(const unsigned long lon
 
 // Classes, size bins, InLane, LaneRedundant.  A well in a class enters the second table: a slot is
 // (label << 32) | the smallest global id of the (label, tile) group seen so far.  The tile of an entry is that of
-// the id it holds, so two groups of one class are told apart by where that id lies; the discipline and the
-// argument are those of k_ld_insert, with equality of (label, tile) decided exactly on the word itself.
+// the id it holds, so two groups of one class are told apart by where that id lies: claim_or_join again, with
+// equality of (label, tile) decided exactly on the word itself.
 // aux[g] = the group's slot, kNoSlot for a well in no class.
 __global__ void __launch_bounds__(kTdBlock) k_ld_classes(const int *__restrict__ tile_idx, int64_t N,
                                                           const uint32_t *__restrict__ label,
@@ -361,22 +298,12 @@ __global__ void __launch_bounds__(kTdBlock) k_ld_classes(const int *__restrict__
                 atomicAdd(&s_sum[2], 1u);
             }
             const unsigned long long base = (unsigned long long)ti * (unsigned long long)N;
-            const unsigned long long key = (unsigned long long)lab << 32, mine = key | g;
-            s = mix64(key | (uint32_t)ti) & slot_mask;
-            for (;;) {
-                unsigned long long cur = __hip_atomic_load(table + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (cur == kEmpty &&
-                    __hip_atomic_compare_exchange_strong(table + s, &cur, mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                         __HIP_MEMORY_SCOPE_AGENT))
-                    break;
+            const unsigned long long key = (unsigned long long)lab << 32;
+            // (groups <= wells in classes <= W: a free slot comes; & not &&: one branch for the three tests)
+            s = claim_or_join(table, slot_mask, mix64(key | (uint32_t)ti), key, g, [=](unsigned long long cur) {
                 const unsigned long long id = cur & 0xFFFFFFFFull;
-                if ((cur >> 32) == lab && id >= base && id - base < (unsigned long long)N) {
-                    if (g < (uint32_t)id)
-                        __hip_atomic_fetch_min(table + s, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    break;
-                }
-                s = (s + 1) & slot_mask;                               // groups <= wells in classes <= W: a free one comes
-            }
+                return ((cur >> 32) == lab) & (id >= base) & (id - base < (unsigned long long)N);
+            });
         }
         aux[g64] = s;
     }
@@ -387,7 +314,7 @@ __global__ void __launch_bounds__(kTdBlock) k_ld_classes(const int *__restrict__
         if (i == 1 || i == 2)
             atomicAdd(ld_tile_cnt(cnt_t, ti) + (i == 1 ? kLdInLane : kLdLaneRed), v);
         else
-            atomicAdd(cnt_l + (size_t)(blockIdx.x % kSpread) * kLdLaneCnt + (i == 0 ? kLdClasses : kLdBins + (i - 3)), v);
+            atomicAdd(spread_row(cnt_l, 0, kLdLaneCnt) + (i == 0 ? kLdClasses : kLdBins + (i - 3)), v);
     }
 }
 
@@ -408,7 +335,7 @@ __global__ void __launch_bounds__(kTdBlock) k_ld_span_count(const int *__restric
             gmin = (uint32_t)__hip_atomic_load(table + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // (a group has one slot and one smallest member: lanes that name the same one name the same slot)
-    const uint32_t add = ld_grouped(s != kNoSlot && gmin != (uint32_t)g64, gmin);
+    const uint32_t add = wave_grouped(s != kNoSlot && gmin != (uint32_t)g64, gmin);
     if (add)
         __hip_atomic_fetch_add(table + s, (unsigned long long)add << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -451,7 +378,7 @@ __global__ void __launch_bounds__(kTdBlock) k_ld_span_sum(const int *__restrict_
     if (threadIdx.x < 4 && s_sum[threadIdx.x]) {
         const unsigned long long v = s_sum[threadIdx.x];
         if (threadIdx.x < 2)
-            atomicAdd(cnt_l + (size_t)(blockIdx.x % kSpread) * kLdLaneCnt + (threadIdx.x == 0 ? kLdSpans : kLdCross), v);
+            atomicAdd(spread_row(cnt_l, 0, kLdLaneCnt) + (threadIdx.x == 0 ? kLdSpans : kLdCross), v);
         else
             atomicAdd(ld_tile_cnt(cnt_t, ti) + (threadIdx.x == 2 ? kLdInTile : kLdTileRed), v);
     }
@@ -553,15 +480,9 @@ try {
             return fail(ctx, WD_ERR_ARG, "lane duplicates: tile index " + std::to_string(t) + " used twice");
         seen[t] = 1;
     }
-    bool aligned4 = true;
-    for (size_t i = 0; i < (size_t)n_tiles * L; i++) {
-        if (!planes[i])
-            return fail(ctx, WD_ERR_ARG, "null plane pointer");
-        aligned4 = aligned4 && ((uintptr_t)planes[i] & 3u) == 0;
-    }
-    for (int i = 0; i < n_tiles; i++)
-        if (!filter[i] || !on_device(filter[i]) || (L > 0 && !on_device(planes[(size_t)i * L])))
-            return fail(ctx, WD_ERR_ARG, "lane duplicates: planes and filters must be in device memory");
+    bool aligned4;
+    if (const int rc = check_tables(ctx, "lane duplicates: ", n_tiles, L, planes, filter, nullptr, &aligned4))
+        return rc;
     if (bind_device(ctx))
         return WD_ERR_HIP;
     if (N > 0) {
@@ -572,10 +493,8 @@ try {
         int *d_tidx = (int *)(ws + lay.tidx);
         uint32_t *rows = (uint32_t *)(ws + lay.rows);
         unsigned long long *aux = (unsigned long long *)(ws + lay.aux);
-        if (L > 0)
-            WD_HIP(ctx, hipMemcpyAsync(d_planes, planes, (size_t)n_tiles * L * sizeof(void *), hipMemcpyHostToDevice,
-                                       ctx->stream));
-        WD_HIP(ctx, hipMemcpyAsync(d_filt, filter, n_tiles * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
+        if (const int rc = upload_tables(ctx, n_tiles, L, planes, d_planes, filter, d_filt))
+            return rc;
         WD_HIP(ctx, hipMemcpyAsync(d_tidx, tile_index, n_tiles * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
         const dim3 wgrid((unsigned)((N + kTdBlock - 1) / kTdBlock), (unsigned)n_tiles);
         if (aligned4)
@@ -655,26 +574,24 @@ try {
     WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
     for (int t = 0; t < T; t++) {
+        unsigned long long c[kLdTileCnt];
+        sum_spread(h_t.data(), (size_t)t, kLdTileCnt, c);
         int64_t *o = tile_rows + (size_t)t * WD_LANEDUPS_TILE_COLS;
-        for (int r = 0; r < kSpread; r++) {
-            const unsigned long long *c = h_t.data() + ((size_t)t * kSpread + r) * kLdTileCnt;
-            o[0] += (int64_t)c[kLdPf];
-            o[1] += (int64_t)c[kLdInLane];
-            o[2] += (int64_t)c[kLdInTile];
-            o[3] += (int64_t)c[kLdTileRed];
-            o[4] += (int64_t)c[kLdLaneRed];
-        }
+        o[0] = (int64_t)c[kLdPf];
+        o[1] = (int64_t)c[kLdInLane];
+        o[2] = (int64_t)c[kLdInTile];
+        o[3] = (int64_t)c[kLdTileRed];
+        o[4] = (int64_t)c[kLdLaneRed];
         lane_row[0] += o[0];
         lane_row[2] += o[1];
     }
-    for (int r = 0; r < kSpread; r++) {
-        const unsigned long long *c = h_l.data() + (size_t)r * kLdLaneCnt;
-        lane_row[1] += (int64_t)c[kLdClasses];
-        lane_row[4] += (int64_t)c[kLdCross];
-        lane_row[5] += (int64_t)c[kLdSpans];
-        for (int b = 0; b < kBins; b++)
-            lane_row[6 + b] += (int64_t)c[kLdBins + b];
-    }
+    unsigned long long c[kLdLaneCnt];
+    sum_spread(h_l.data(), 0, kLdLaneCnt, c);
+    lane_row[1] = (int64_t)c[kLdClasses];
+    lane_row[4] = (int64_t)c[kLdCross];
+    lane_row[5] = (int64_t)c[kLdSpans];
+    for (int b = 0; b < kBins; b++)
+        lane_row[6 + b] = (int64_t)c[kLdBins + b];
     lane_row[3] = lane_row[2] - lane_row[1];
     return WD_OK;
 } WD_CATCH

@@ -1,7 +1,7 @@
 // tile_near.inc - near-duplicate read clusters of every tile (include/welldup_tilenear.h): PF wells linked by
 // Hamming distance <= K anywhere on the tile, single linkage.  Included at the end of welldup_tiledups.hip:
-// it uses that unit's fingerprint words, table, code_of, k_td_insert / k_td_resolve / k_td_local / k_td_levels
-// and counter layout.
+// it uses read_classes.inc (plane_pass, compare_wells, wave_grouped), that unit's k_td_insert / k_td_resolve /
+// k_td_local / k_td_levels, its counter layout and its host helpers.
 //
 // Per batch of tiles (grid y = tile):
 //   k_tn_fingerprint  the pass of k_td_fingerprint, cut at K + 1 segment boundaries: a 32-bit fingerprint per
@@ -24,8 +24,6 @@
 
 namespace {
 
-constexpr int kCntNear = kCntRing + kMaxLevels;    // pairs of distinct reads within K (a spare counter of the row)
-static_assert(kCntNear < kCnt, "the counter row has no room for NearPairs");
 constexpr int kTnMaxK = 3;
 constexpr uint32_t kTnLong = 32;                   // chains up to this length are one lane's walk
 constexpr uint32_t kNil = 0xFFFFFFFFu;             // end of a chain
@@ -53,7 +51,7 @@ __host__ __device__ inline int seg_begin(int L, int nseg, int s) { return (int)(
 
 __device__ inline uint32_t seg_slot(uint32_t f, uint32_t slot_mask) { return (uint32_t)mix64(f) & slot_mask; }
 
-// grid as k_td_fingerprint.  segfp[s][tile * N + w]; also clears the members array.
+// grid as k_td_fingerprint: its pass, once per segment.  segfp[s][tile * N + w]; also clears the members array.
 template <bool VEC4>
 __global__ void __launch_bounds__(kTdBlock) k_tn_fingerprint(const uint8_t *const *__restrict__ planes, int L, int nseg,
                                                               int64_t N, size_t seg_stride,
@@ -72,36 +70,13 @@ __global__ void __launch_bounds__(kTdBlock) k_tn_fingerprint(const uint8_t *cons
     if (VEC4 && w0 + 4 <= N) {
         Fp whole[4];
         for (int s = 0; s < nseg; s++) {
-            const int end = seg_begin(L, nseg, s + 1);
-            int c = seg_begin(L, nseg, s);
+            const int end = seg_begin(L, nseg, s + 1);       // (the 30-bit word is flushed at the segment's end)
             Fp g[4];
-            for (; c + kFpCycles <= end; c += kFpCycles) {
-                uint32_t v[kFpCycles];
-#pragma unroll
-                for (int j = 0; j < kFpCycles; j++)
-                    v[j] = __builtin_nontemporal_load((const uint32_t *)(pl[c + j] + w0));
-                uint32_t acc[4] = {0, 0, 0, 0};
-#pragma unroll
-                for (int j = 0; j < kFpCycles; j++)
-#pragma unroll
-                    for (int q = 0; q < 4; q++)
-                        acc[q] |= code_of((v[j] >> (8 * q)) & 0xFFu) << (3 * j);
+            plane_pass<true>(pl, seg_begin(L, nseg, s), end, w0, [&](int, const uint32_t(&acc)[4]) {
 #pragma unroll
                 for (int q = 0; q < 4; q++)
                     g[q].fold(acc[q]);
-            }
-            if (c < end) {                                   // the 30-bit word is flushed at the segment's end
-                uint32_t acc[4] = {0, 0, 0, 0};
-                for (int j = 0; c + j < end; j++) {
-                    const uint32_t v = __builtin_nontemporal_load((const uint32_t *)(pl[c + j] + w0));
-#pragma unroll
-                    for (int q = 0; q < 4; q++)
-                        acc[q] |= code_of((v >> (8 * q)) & 0xFFu) << (3 * j);
-                }
-#pragma unroll
-                for (int q = 0; q < 4; q++)
-                    g[q].fold(acc[q]);
-            }
+            });
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 segfp[s * seg_stride + w0 + q] = g[q].a ^ (g[q].b * 0x9E3779B1u);
@@ -121,12 +96,7 @@ __global__ void __launch_bounds__(kTdBlock) k_tn_fingerprint(const uint8_t *cons
         for (int s = 0; s < nseg; s++) {
             const int end = seg_begin(L, nseg, s + 1);
             Fp g;
-            for (int c = seg_begin(L, nseg, s); c < end; c += kFpCycles) {
-                uint32_t acc = 0;
-                for (int j = 0; j < kFpCycles && c + j < end; j++)
-                    acc |= code_of(pl[c + j][w]) << (3 * j);
-                g.fold(acc);
-            }
+            plane_pass<false>(pl, seg_begin(L, nseg, s), end, w, [&](int, const uint32_t(&acc)[1]) { g.fold(acc[0]); });
             segfp[s * seg_stride + w] = g.a ^ (g.b * 0x9E3779B1u);
             whole.fold(g.a);
             whole.fold(g.b);
@@ -221,35 +191,11 @@ __global__ void __launch_bounds__(kTdBlock) k_tn_scatter(const uint32_t *__restr
         list[base + slots[2 * (sbase + s)] + rank[base + w]] = w;            // (ranges add up to <= N per tile)
 }
 
-// mismatching cycles of wells a and b, counted no further than the block in which they pass k
-__device__ inline int hamming_upto(const uint8_t *const *pl, int L, uint32_t a, uint32_t b, int k)
-{
-    int d = 0, c = 0;
-    for (; c + kCmpCycles <= L; c += kCmpCycles) {
-        uint32_t x[kCmpCycles], y[kCmpCycles];
-#pragma unroll
-        for (int j = 0; j < kCmpCycles; j++) {
-            const uint8_t *p = pl[c + j];
-            x[j] = p[a];
-            y[j] = p[b];
-        }
-#pragma unroll
-        for (int j = 0; j < kCmpCycles; j++)
-            d += code_of(x[j]) != code_of(y[j]);
-        if (d > k)
-            return d;
-    }
-    for (; c < L; c++) {
-        const uint8_t *p = pl[c];
-        d += code_of(p[a]) != code_of(p[b]);
-    }
-    return d;
-}
-
 // Union-find on the label array, as the parent pointers of welldup_sets.hip (the argument there holds word
 // for word: a pointer only ever names a smaller index of the same tree, every read inside the kernel is an
 // agent-scope atomic, a successful CAS hooks a root under a smaller root of another tree).  Before the first
 // segment label[w] is the representative of w's class: representatives are the roots, and only they are united.
+// (tn_find / tn_unite are a copy of that unit's: sharing them would change the sets unit and detach its evidence)
 __device__ inline uint32_t tn_load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __device__ inline uint32_t tn_find(uint32_t *par, uint32_t x)         // (splits the path on the way)
@@ -394,8 +340,7 @@ __global__ void __launch_bounds__(kTdBlock) k_tn_compress(uint32_t *label, int64
     first[(size_t)tile * N + w] = kNoLevel;
 }
 
-// grid (ceil(N / 256), n_tiles): members counted at the roots (lanes of a wave that name the root of the
-// first of them add once, as k_td_resolve), labels out
+// grid (ceil(N / 256), n_tiles): members counted at the roots (wave_grouped, as k_td_resolve), labels out
 __global__ void __launch_bounds__(kTdBlock) k_tn_members(const uint32_t *__restrict__ label, int64_t N, uint32_t *members,
                                                           uint32_t *const *__restrict__ labels_out)
 {
@@ -408,18 +353,9 @@ __global__ void __launch_bounds__(kTdBlock) k_tn_members(const uint32_t *__restr
         if (labels_out)
             labels_out[tile][w] = lab;
     }
-    const bool member = lab != kInvalid && lab != (uint32_t)w;
-    const unsigned long long joiners = __ballot(member);
-    if (joiners) {
-        const int lane = threadIdx.x & (kWave - 1), leader = __ffsll((long long)joiners) - 1;
-        const uint32_t lab0 = (uint32_t)__shfl((int)lab, leader);
-        const bool same = member && lab == lab0;
-        const unsigned long long group = __ballot(same);
-        if (lane == leader)
-            atomicAdd(members + base + lab0, (uint32_t)__popcll(group));
-        else if (member && !same)
-            atomicAdd(members + base + lab, 1u);
-    }
+    const uint32_t add = wave_grouped(lab != kInvalid && lab != (uint32_t)w, lab);
+    if (add)
+        atomicAdd(members + base + lab, add);
 }
 
 }  // namespace
@@ -441,8 +377,6 @@ try {
     if (!ctx || !out_rows || n_tiles < 0 || N < 0 || L < 0 || hash_bits < 0 || hash_bits > 32 || k < 0 ||
         k > kTnMaxK || L < k + 1 || pair_budget < 0)
         return WD_ERR_ARG;
-    if (!ctx->has_targets)
-        return fail(ctx, WD_ERR_STATE, "wd_set_targets has not been called");
     const int levels = ctx->levels;
     const size_t nrow_eq = 4 + 2 * (size_t)levels + kBins, nrow = nrow_eq + 1;
     if (k == 0) {                                                      // the classes, NearPairs = 0
@@ -460,96 +394,59 @@ try {
         }
         return WD_OK;
     }
-    if ((int64_t)ctx->T != N || levels < 1)
-        return fail(ctx, WD_ERR_ARG, "tile duplicates need every well as a target (T == N)");
-    if (ctx->well_stride != 1)
-        return fail(ctx, WD_ERR_UNSUPPORTED, "tile duplicates read a plane per cycle (well_stride 1)");
-    if (N >= ((int64_t)1 << 31))
-        return fail(ctx, WD_ERR_UNSUPPORTED, "tile duplicates: more than 2^31 - 1 wells");
-    if (L > kMaxCycles)
-        return fail(ctx, WD_ERR_UNSUPPORTED, "tile duplicates: more than 1024 cycles");
-    if (n_tiles > 65535)
-        return fail(ctx, WD_ERR_UNSUPPORTED, "tile duplicates: more than 65535 tiles in one call");
+    if (const int rc = check_tile_call(ctx, n_tiles, L, N, planes, filter, workspace_dev, workspace_bytes,
+                                       [&] { return near_layout_of(N, n_tiles, k).bytes; }, "wd_tile_near_dups_workspace"))
+        return rc;
     const NearLayout nl = near_layout_of(N, n_tiles, k);
     const Layout &lay = nl.base;
-    if (n_tiles > 0 && (!workspace_dev || workspace_bytes < nl.bytes))
-        return fail(ctx, WD_ERR_ARG, "workspace smaller than wd_tile_near_dups_workspace");
-    if (n_tiles > 0 && (!filter || !planes))
-        return fail(ctx, WD_ERR_ARG, "null plane or filter table");
-    if (ctx->T > 0 && n_tiles > 0 && (ctx->idx_min < 0 || ctx->idx_max >= N))
-        return fail(ctx, WD_ERR_INDEX, "a target names a well outside the tile");
-    if (bind_device(ctx))
-        return WD_ERR_HIP;
     memset(out_rows, 0, (size_t)n_tiles * nrow * sizeof(int64_t));
     if (n_tiles == 0 || N == 0)
         return WD_OK;
-    bool aligned4 = true;
-    for (size_t i = 0; i < (size_t)n_tiles * L; i++) {
-        if (!planes[i])
-            return fail(ctx, WD_ERR_ARG, "null plane pointer");
-        aligned4 = aligned4 && ((uintptr_t)planes[i] & 3u) == 0;
-    }
-    for (int i = 0; i < n_tiles; i++) {
-        if (!filter[i] || !on_device(filter[i]) || !on_device(planes[(size_t)i * L]))
-            return fail(ctx, WD_ERR_ARG, "tile duplicates: planes and filters must be in device memory");
-        if (labels_dev && !labels_dev[i])
-            return fail(ctx, WD_ERR_ARG, "null label pointer");
-    }
+    bool aligned4;
+    if (const int rc = check_tables(ctx, "tile duplicates: ", n_tiles, L, planes, filter, labels_dev, &aligned4))
+        return rc;
     // the default budget: DESIGN 5.9 (the worst admitted segment stays well under a second per tile)
     const int64_t budget = pair_budget > 0 ? pair_budget : std::max<int64_t>(16 * N, (int64_t)1 << 24);
 
-    uint8_t *ws = (uint8_t *)workspace_dev;
-    unsigned long long *cnt = (unsigned long long *)(ws + lay.cnt);
-    uint32_t *flags = (uint32_t *)(ws + lay.flags);
-    const uint8_t **d_planes = (const uint8_t **)(ws + lay.planes);
-    const uint8_t **d_filt = (const uint8_t **)(ws + lay.filt);
-    uint32_t **d_lbl = (uint32_t **)(ws + lay.lbl);
-    unsigned long long *table = (unsigned long long *)(ws + lay.table);
-    unsigned long long *fp = (unsigned long long *)(ws + lay.fp);
-    uint32_t *label = (uint32_t *)(ws + lay.label);
-    uint32_t *members = (uint32_t *)(ws + lay.members);
-    uint32_t *first = (uint32_t *)(ws + lay.first);
-    unsigned long long *aux = (unsigned long long *)(ws + nl.aux);
-    uint32_t *segfp = (uint32_t *)(ws + nl.segfp);
+    const View v(lay, workspace_dev);
+    unsigned long long *aux = (unsigned long long *)((uint8_t *)workspace_dev + nl.aux);
+    uint32_t *segfp = (uint32_t *)((uint8_t *)workspace_dev + nl.segfp);
     const size_t wells = (size_t)n_tiles * N, all_slots = (size_t)n_tiles * lay.slots;
-    uint32_t *slots = (uint32_t *)table;                               // the table's bytes, once it is resolved
-    uint32_t *next = (uint32_t *)fp, *rank = next + wells;             // the fingerprints' bytes, once inserted
-    uint32_t *list = first;
-    const uint32_t slot_mask = (uint32_t)(lay.slots - 1);
+    uint32_t *slots = (uint32_t *)v.table;                             // the table's bytes, once it is resolved
+    uint32_t *next = (uint32_t *)v.fp, *rank = next + wells;           // the fingerprints' bytes, once inserted
+    uint32_t *list = v.first;
+    const uint32_t slot_mask = v.slot_mask;
     const unsigned long long fp_mask = hash_bits == 0 ? ~0ull : (1ull << hash_bits) - 1;
     const uint32_t fmask = hash_bits == 0 || hash_bits == 32 ? ~0u : (1u << hash_bits) - 1;
     const int nseg = k + 1;
 
-    std::vector<uint32_t *> h_lbl(n_tiles, nullptr);
-    if (labels_dev)
-        for (int i = 0; i < n_tiles; i++)
-            h_lbl[i] = labels_dev[i];
-    WD_HIP(ctx, hipMemsetAsync(ws + lay.cnt, 0, lay.planes - lay.cnt, ctx->stream));          // counters and flags
+    if (const int rc = clear_workspace(ctx, lay, v, n_tiles))
+        return rc;
     WD_HIP(ctx, hipMemsetAsync(aux, 0, (size_t)nseg * n_tiles * 2 * 8, ctx->stream));
-    WD_HIP(ctx, hipMemsetAsync(table, 0xFF, all_slots * 8, ctx->stream));                      // every slot free
-    WD_HIP(ctx, hipMemcpyAsync(d_planes, planes, (size_t)n_tiles * L * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
-    WD_HIP(ctx, hipMemcpyAsync(d_filt, filter, n_tiles * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
-    WD_HIP(ctx, hipMemcpyAsync(d_lbl, h_lbl.data(), n_tiles * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
+    std::vector<uint32_t *> h_lbl;
+    if (const int rc = upload_tables(ctx, n_tiles, L, planes, v.planes, filter, v.filt, labels_dev, v.lbl, &h_lbl))
+        return rc;
 
     const unsigned wblocks = (unsigned)((N + kTdBlock - 1) / kTdBlock);
     const dim3 wgrid(wblocks, (unsigned)n_tiles), blk(kTdBlock);
     const dim3 sgrid((unsigned)((lay.slots + kTnBoundSlots - 1) / kTnBoundSlots), (unsigned)n_tiles);
-    hipLaunchKernelGGL(k_td_check_centres, dim3(wblocks), blk, 0, ctx->stream, ctx->d_centre, ctx->T, flags);
+    hipLaunchKernelGGL(k_td_check_centres, dim3(wblocks), blk, 0, ctx->stream, ctx->d_centre, ctx->T, v.flags);
     if (aligned4)
         hipLaunchKernelGGL(k_tn_fingerprint<true>, dim3((unsigned)((N + 4 * kTdBlock - 1) / (4 * kTdBlock)), (unsigned)n_tiles),
-                           blk, 0, ctx->stream, d_planes, L, nseg, N, wells, fp, segfp, members);
+                           blk, 0, ctx->stream, v.planes, L, nseg, N, wells, v.fp, segfp, v.members);
     else
-        hipLaunchKernelGGL(k_tn_fingerprint<false>, wgrid, blk, 0, ctx->stream, d_planes, L, nseg, N, wells, fp, segfp,
-                           members);
-    hipLaunchKernelGGL(k_td_insert, wgrid, blk, 0, ctx->stream, d_planes, d_filt, L, N, fp, fp_mask, table, slot_mask, label);
-    hipLaunchKernelGGL(k_td_resolve, wgrid, blk, 0, ctx->stream, table, slot_mask, N, label, members, first,
-                       (uint32_t *const *)nullptr, cnt);
+        hipLaunchKernelGGL(k_tn_fingerprint<false>, wgrid, blk, 0, ctx->stream, v.planes, L, nseg, N, wells, v.fp, segfp,
+                           v.members);
+    hipLaunchKernelGGL(k_td_insert, wgrid, blk, 0, ctx->stream, v.planes, v.filt, L, N, v.fp, fp_mask, v.table, slot_mask,
+                       v.label);
+    hipLaunchKernelGGL(k_td_resolve, wgrid, blk, 0, ctx->stream, v.table, slot_mask, N, v.label, v.members, v.first,
+                       (uint32_t *const *)nullptr, v.cnt);
     std::vector<unsigned long long> h_aux((size_t)n_tiles * 2);
     for (int seg = 0; seg < nseg; seg++) {
         unsigned long long *aux_s = aux + (size_t)seg * n_tiles * 2;
         const uint32_t *segfp_s = segfp + (size_t)seg * wells;
         WD_HIP(ctx, hipMemsetAsync(slots, 0xFF, all_slots * 8, ctx->stream));
-        hipLaunchKernelGGL(k_tn_bucket, wgrid, blk, 0, ctx->stream, label, seg, N, segfp_s, fmask, slot_mask, slots, next,
+        hipLaunchKernelGGL(k_tn_bucket, wgrid, blk, 0, ctx->stream, v.label, seg, N, segfp_s, fmask, slot_mask, slots, next,
                            rank);
         hipLaunchKernelGGL(k_tn_bound, sgrid, blk, 0, ctx->stream, slots, slot_mask, aux_s);
         WD_HIP(ctx, hipGetLastError());
@@ -569,50 +466,20 @@ try {
         if (longest > 0)
             hipLaunchKernelGGL(k_tn_scatter, wgrid, blk, 0, ctx->stream, next, N, segfp_s, fmask, slot_mask, slots, rank,
                                list);
-        hipLaunchKernelGGL(k_tn_pairs, wgrid, blk, 0, ctx->stream, d_planes, L, k, seg, N, segfp, wells, fmask, slot_mask,
-                           slots, next, label, cnt);
+        hipLaunchKernelGGL(k_tn_pairs, wgrid, blk, 0, ctx->stream, v.planes, L, k, seg, N, segfp, wells, fmask, slot_mask,
+                           slots, next, v.label, v.cnt);
         if (longest > 0)
             hipLaunchKernelGGL(k_tn_pairs_long,
                                dim3((unsigned)((longest + kTdBlock / kWave - 1) / (kTdBlock / kWave)), (unsigned)n_tiles),
-                               blk, 0, ctx->stream, d_planes, L, k, seg, N, segfp, wells, fmask, slot_mask, slots, list, aux_s,
-                               label, cnt);
+                               blk, 0, ctx->stream, v.planes, L, k, seg, N, segfp, wells, fmask, slot_mask, slots, list, aux_s,
+                               v.label, v.cnt);
     }
-    hipLaunchKernelGGL(k_tn_compress, wgrid, blk, 0, ctx->stream, label, N, members, first);
-    hipLaunchKernelGGL(k_tn_members, wgrid, blk, 0, ctx->stream, label, N, members, labels_dev ? d_lbl : nullptr);
-    hipLaunchKernelGGL(k_td_local, wgrid, blk, 0, ctx->stream, label, members, N, ctx->d_lvl_off, ctx->d_nbr, levels, first,
-                       cnt);
-    hipLaunchKernelGGL(k_td_levels, wgrid, blk, 0, ctx->stream, first, N, levels, cnt);
-    WD_HIP(ctx, hipGetLastError());
-    std::vector<unsigned long long> h_cnt((size_t)n_tiles * kSpread * kCnt);
-    uint32_t h_flags[4] = {0, 0, 0, 0};
-    WD_HIP(ctx, hipMemcpyAsync(h_cnt.data(), cnt, h_cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                               ctx->stream));
-    WD_HIP(ctx, hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, ctx->stream));
-    WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (h_flags[kFlagCentres])
-        return fail(ctx, WD_ERR_ARG, "tile duplicates need target t to be centred on well t");
-
-    for (int i = 0; i < n_tiles; i++) {
-        unsigned long long c[kCnt] = {};
-        for (int r = 0; r < kSpread; r++)
-            for (int f = 0; f < kCnt; f++)
-                c[f] += h_cnt[((size_t)i * kSpread + r) * kCnt + f];
-        int64_t *o = out_rows + (size_t)i * nrow;
-        o[0] = (int64_t)c[kCntPf];
-        o[1] = (int64_t)c[kCntClasses];
-        o[2] = (int64_t)c[kCntInClasses];
-        o[3] = o[2] - o[1];
-        o[4] = (int64_t)c[kCntNear];
-        int64_t local = 0;
-        for (int l = 0; l < levels; l++) {
-            local += (int64_t)c[kCntFirst + l];
-            o[5 + l] = local;
-            o[5 + levels + l] = (int64_t)c[kCntRing + l];
-        }
-        for (int b = 0; b < kBins; b++)
-            o[5 + 2 * levels + b] = (int64_t)c[kCntBins + b];
-    }
-    return WD_OK;
+    hipLaunchKernelGGL(k_tn_compress, wgrid, blk, 0, ctx->stream, v.label, N, v.members, v.first);
+    hipLaunchKernelGGL(k_tn_members, wgrid, blk, 0, ctx->stream, v.label, N, v.members, labels_dev ? v.lbl : nullptr);
+    hipLaunchKernelGGL(k_td_local, wgrid, blk, 0, ctx->stream, v.label, v.members, N, ctx->d_lvl_off, ctx->d_nbr, levels,
+                       v.first, v.cnt);
+    hipLaunchKernelGGL(k_td_levels, wgrid, blk, 0, ctx->stream, v.first, N, levels, v.cnt);
+    return finish_tile_rows(ctx, v, n_tiles, true, out_rows);
 } WD_CATCH
 
 }  // extern "C"

@@ -21,26 +21,23 @@
 #endif
 namespace wd { const char *unit_id_tiledups() { return WD_UNIT_ID; } }      // hash of this unit's sources (wd_build_id)
 
-namespace {
+#include "read_classes.inc"    // the encoding, the plane pass, the table, the compare loop, the grouped add, the counters
 
-using namespace wd;
+namespace {
 
 constexpr uint32_t kInvalid = WD_INVALID_TARGET;   // label of a non-PF well; slot of a well not in the table
 constexpr uint32_t kNoLevel = 0xFFFFFFFFu;         // first level of a well with no classmate in any ring
-constexpr unsigned long long kEmpty = ~0ull;       // a free slot (no entry looks like it: a well index is < kInvalid)
 constexpr int kBins = WD_DUPSET_SIZE_BINS;
 constexpr int kTdBlock = 256;
-constexpr int kFpCycles = 10;                      // cycles folded per 30-bit word, and planes in flight per lane
 
-// per-tile counters in the workspace, [n_tiles][kSpread][kCnt] uint64: a workgroup adds its sums to copy
-// blockIdx.x % kSpread and the host adds the copies up (one copy per tile serialises the ~17 000
-// workgroups of a 4.3 M-well tile on a few addresses: welldup_sets.hip)
-constexpr int kSpread = 64;
+// per-tile counters in the workspace, [n_tiles][kSpread][kCnt] uint64 (spread_row)
 constexpr int kCntPf = 0, kCntClasses = 1, kCntInClasses = 2;
 constexpr int kCntBins = 3;                        // classes of size 2..8, >= 9
 constexpr int kCntFirst = kCntBins + kBins;        // wells whose first level is l (histogram)
 constexpr int kCntRing = kCntFirst + kMaxLevels;   // RingWells[l]
+constexpr int kCntNear = kCntRing + kMaxLevels;    // pairs of distinct reads within K (tile_near.inc)
 constexpr int kCnt = (kCntRing + kMaxLevels + 7) / 8 * 8;
+static_assert(kCntNear < kCnt, "the counter row has no room for NearPairs");
 
 // flags[0]: a centre is not its own target index
 constexpr int kFlagCentres = 0;
@@ -78,43 +75,36 @@ Layout layout_of(int64_t N, int n_tiles)
     return l;
 }
 
-__device__ inline unsigned long long *cnt_row(unsigned long long *cnt, int tile)
-{
-    return cnt + ((size_t)tile * kSpread + blockIdx.x % kSpread) * kCnt;
-}
-
-// the reference's alphabet: byte 0 is N (4), any other byte its low two bits (bcl_direct_reader.py:352-361)
-__device__ inline uint32_t code_of(uint32_t byte) { return byte ? (byte & 3u) : 4u; }
-
-// ---- fingerprint ------------------------------------------------------------------------------
-// Ten cycles, three bits each, make a 30-bit word; the words of a read go through two 32-bit
-// multiplicative hashes (a 64-bit multiply per word and well would make the pass compute bound).
-// Whatever this hash cannot tell apart is told apart on the reads by k_td_insert.
-struct Fp {
-    uint32_t a = 0x811C9DC5u, b = 0x01000193u;
-    __device__ inline void fold(uint32_t w)
+// the typed pointers of a workspace laid out by layout_of
+struct View {
+    unsigned long long *cnt;
+    uint32_t *flags;
+    const uint8_t **planes, **filt;
+    uint32_t **lbl;
+    unsigned long long *table, *fp;
+    uint32_t *label, *members, *first;
+    uint32_t slot_mask;
+    View(const Layout &l, void *workspace)
     {
-        a = (a ^ w) * 0x9E3779B1u;
-        a ^= a >> 15;
-        b = (b + w) * 0x85EBCA6Bu;
-        b ^= b >> 13;
+        uint8_t *ws = (uint8_t *)workspace;
+        cnt = (unsigned long long *)(ws + l.cnt);
+        flags = (uint32_t *)(ws + l.flags);
+        planes = (const uint8_t **)(ws + l.planes);
+        filt = (const uint8_t **)(ws + l.filt);
+        lbl = (uint32_t **)(ws + l.lbl);
+        table = (unsigned long long *)(ws + l.table);
+        fp = (unsigned long long *)(ws + l.fp);
+        label = (uint32_t *)(ws + l.label);
+        members = (uint32_t *)(ws + l.members);
+        first = (uint32_t *)(ws + l.first);
+        slot_mask = (uint32_t)(l.slots - 1);
     }
-    __device__ inline unsigned long long value() const { return ((unsigned long long)a << 32) | b; }
 };
 
-__device__ inline unsigned long long mix64(unsigned long long x)      // (the murmur3 finaliser)
-{
-    x ^= x >> 33;
-    x *= 0xFF51AFD7ED558CCDull;
-    x ^= x >> 33;
-    x *= 0xC4CEB9FE1A85EC53ull;
-    x ^= x >> 33;
-    return x;
-}
+__device__ inline unsigned long long *cnt_row(unsigned long long *cnt, int tile) { return spread_row(cnt, (size_t)tile, kCnt); }
 
 // grid (ceil(N / (V * 256)), n_tiles).  VEC4: every plane is 4-byte aligned, a lane folds wells 4 i .. 4 i + 3
-// from dword loads.  The plane pointers are the same for every lane: they come through the scalar cache.
-// Also clears the members array (k_td_resolve counts into it).
+// (plane_pass).  Also clears the members array (k_td_resolve counts into it).
 template <bool VEC4>
 __global__ void __launch_bounds__(kTdBlock) k_td_fingerprint(const uint8_t *const *__restrict__ planes, int L,
                                                               int64_t N, unsigned long long *__restrict__ fp,
@@ -130,34 +120,11 @@ __global__ void __launch_bounds__(kTdBlock) k_td_fingerprint(const uint8_t *cons
     members += (size_t)tile * N;
     if (VEC4 && w0 + 4 <= N) {
         Fp h[4];
-        int c = 0;
-        for (; c + kFpCycles <= L; c += kFpCycles) {
-            uint32_t v[kFpCycles];
-#pragma unroll
-            for (int j = 0; j < kFpCycles; j++)             // (non-temporal: the planes are streamed)
-                v[j] = __builtin_nontemporal_load((const uint32_t *)(pl[c + j] + w0));
-            uint32_t acc[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int j = 0; j < kFpCycles; j++)
-#pragma unroll
-                for (int q = 0; q < 4; q++)
-                    acc[q] |= code_of((v[j] >> (8 * q)) & 0xFFu) << (3 * j);
+        plane_pass<true>(pl, 0, L, w0, [&](int, const uint32_t(&acc)[4]) {
 #pragma unroll
             for (int q = 0; q < 4; q++)
                 h[q].fold(acc[q]);
-        }
-        if (c < L) {
-            uint32_t acc[4] = {0, 0, 0, 0};
-            for (int j = 0; c + j < L; j++) {
-                const uint32_t v = __builtin_nontemporal_load((const uint32_t *)(pl[c + j] + w0));
-#pragma unroll
-                for (int q = 0; q < 4; q++)
-                    acc[q] |= code_of((v >> (8 * q)) & 0xFFu) << (3 * j);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                h[q].fold(acc[q]);
-        }
+        });
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             fp[w0 + q] = h[q].value();
@@ -167,63 +134,14 @@ __global__ void __launch_bounds__(kTdBlock) k_td_fingerprint(const uint8_t *cons
     }
     for (int64_t w = w0; w < N && w < w0 + V; w++) {         // unaligned planes, and the last wells of a tile
         Fp h;
-        for (int c = 0; c < L; c += kFpCycles) {
-            uint32_t acc = 0;
-            for (int j = 0; j < kFpCycles && c + j < L; j++)
-                acc |= code_of(pl[c + j][w]) << (3 * j);
-            h.fold(acc);
-        }
+        plane_pass<false>(pl, 0, L, w, [&](int, const uint32_t(&acc)[1]) { h.fold(acc[0]); });
         fp[w] = h.value();
         members[w] = 0;
     }
 }
 
-// ---- the table ----------------------------------------------------------------------------------
-// A slot is one 64-bit word (tag << 32) | representative, all ones = free.  Memory model as for the parent
-// pointers of welldup_sets.hip (per-XCD L2s, L1s that other CUs' stores never refresh): inside the kernel a
-// slot is only touched by agent-scope atomics - a relaxed load, a CAS that claims a free slot with tag and
-// own index at once, an atomic min that lowers the representative.  Why the outcome does not depend on the
-// order of execution:
-//   - a slot is claimed once and never freed, and every well that joins it has been compared with its
-//     representative on the reads and found equal: all wells a slot ever names belong to one class, so a
-//     stale representative is still a member of that class and decides a comparison the same way;
-//   - a load that sees a free slot is followed by the CAS, which fails on a slot claimed meanwhile and
-//     returns what it holds: the lane then treats the same slot as it would have, had it seen that value;
-//   - every well of a class therefore passes the same slots (those of other classes on its probe path,
-//     which never change class) and stops at the first that is free or its own class's: a class has
-//     exactly one slot, and the min leaves its smallest index there, whichever lane came first.
-// Equality is decided by reads_equal, never by the tag: a tag only saves comparisons.
-// (kCmpCycles cycles of both wells are loaded before the first is looked at: a lane that compared cycle by
-// cycle waited for two dependent loads 150 times over, and its wave with it)
-constexpr int kCmpCycles = 16;
-
-__device__ inline bool reads_equal(const uint8_t *const *pl, int L, uint32_t a, uint32_t b)
-{
-    int c = 0;
-    for (; c + kCmpCycles <= L; c += kCmpCycles) {
-        uint32_t x[kCmpCycles], y[kCmpCycles];
-#pragma unroll
-        for (int j = 0; j < kCmpCycles; j++) {
-            const uint8_t *p = pl[c + j];
-            x[j] = p[a];
-            y[j] = p[b];
-        }
-        uint32_t diff = 0;
-#pragma unroll
-        for (int j = 0; j < kCmpCycles; j++)
-            diff |= code_of(x[j]) ^ code_of(y[j]);
-        if (diff)
-            return false;
-    }
-    for (; c < L; c++) {
-        const uint8_t *p = pl[c];
-        if (code_of(p[a]) != code_of(p[b]))
-            return false;
-    }
-    return true;
-}
-
-// grid (ceil(N / 256), n_tiles); slot_of[w] = the well's slot, kInvalid for a non-PF well
+// grid (ceil(N / 256), n_tiles), one lane per PF well into the tile's table (claim_or_join: id = well index,
+// equality decided on the reads); slot_of[w] = the well's slot, kInvalid for a non-PF well
 __global__ void __launch_bounds__(kTdBlock) k_td_insert(const uint8_t *const *__restrict__ planes,
                                                          const uint8_t *const *__restrict__ filt, int L, int64_t N,
                                                          const unsigned long long *__restrict__ fp,
@@ -243,24 +161,10 @@ __global__ void __launch_bounds__(kTdBlock) k_td_insert(const uint8_t *const *__
     const uint8_t *const *pl = planes + (size_t)tile * L;
     unsigned long long *tab = table + (size_t)tile * ((size_t)slot_mask + 1);
     const unsigned long long m = mix64(fp[base + w] & fp_mask);
-    const unsigned long long tag = m & 0xFFFFFFFF00000000ull, mine = tag | w;
-    uint32_t s = (uint32_t)m & slot_mask;
-    for (;;) {
-        // (a load first: a CAS straight away saved 6 % of this kernel on a tile of mostly unique reads, and
-        // on a tile of equal reads put 4.3 M of them on one word - 49 ms instead of 3)
-        unsigned long long cur = __hip_atomic_load(tab + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == kEmpty &&
-            __hip_atomic_compare_exchange_strong(tab + s, &cur, mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT))
-            break;                                                     // claimed (else cur = what the slot holds now)
-        if ((cur & 0xFFFFFFFF00000000ull) == tag && reads_equal(pl, L, w, (uint32_t)cur)) {
-            if (w < (uint32_t)cur)                                     // (the word only ever goes down)
-                __hip_atomic_fetch_min(tab + s, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-        }
-        s = (s + 1) & slot_mask;                                       // the table has >= 2 N slots: a free one comes
-    }
-    slot_of[base + w] = s;
+    const unsigned long long tag = m & 0xFFFFFFFF00000000ull;
+    slot_of[base + w] = claim_or_join(tab, slot_mask, m, tag, w, [=](unsigned long long cur) {       // (>= 2 N slots)
+        return (cur & 0xFFFFFFFF00000000ull) == tag && reads_equal(pl, L, w, (uint32_t)cur);
+    });
 }
 
 // grid (ceil(N / 256), n_tiles): slot -> label (in place), members counted at the representative
@@ -288,20 +192,9 @@ __global__ void __launch_bounds__(kTdBlock) k_td_resolve(const unsigned long lon
         if (labels_out)
             labels_out[tile][w] = lab;
     }
-    // members: the lanes of a wave that name the same representative as the first of them add once (wells
-    // of one class lie side by side when a tile's reads are all equal: 4.3 M adds to one word took 49 ms)
-    const bool member = lab != kInvalid && lab != (uint32_t)w;
-    const unsigned long long joiners = __ballot(member);
-    if (joiners) {
-        const int lane = threadIdx.x & (kWave - 1), leader = __ffsll((long long)joiners) - 1;
-        const uint32_t lab0 = (uint32_t)__shfl((int)lab, leader);
-        const bool same = member && lab == lab0;
-        const unsigned long long group = __ballot(same);
-        if (lane == leader)
-            atomicAdd(members + base + lab0, (uint32_t)__popcll(group));
-        else if (member && !same)
-            atomicAdd(members + base + lab, 1u);
-    }
+    const uint32_t add = wave_grouped(lab != kInvalid && lab != (uint32_t)w, lab);
+    if (add)
+        atomicAdd(members + base + lab, add);
     const unsigned long long pf = __ballot(s != kInvalid);
     if ((threadIdx.x & (kWave - 1)) == 0 && pf)
         atomicAdd(&s_pf, (uint32_t)__popcll(pf));
@@ -421,6 +314,121 @@ bool on_device(const void *p)
     return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
 }
 
+// ---- host: what the entry points of the unit share ------------------------------------------------------
+// Every plane, filter and (if asked for) label pointer of a call: none null, planes and filters in device
+// memory.  aligned4: every plane is 4-byte aligned.  prefix is "tile duplicates: " or "lane duplicates: ".
+int check_tables(wd_ctx *ctx, const char *prefix, int n_tiles, int L, const uint8_t *const *planes,
+                 const uint8_t *const *filter, uint32_t *const *labels, bool *aligned4)
+{
+    *aligned4 = true;
+    for (size_t i = 0; i < (size_t)n_tiles * L; i++) {
+        if (!planes[i])
+            return fail(ctx, WD_ERR_ARG, "null plane pointer");
+        *aligned4 = *aligned4 && ((uintptr_t)planes[i] & 3u) == 0;
+    }
+    for (int i = 0; i < n_tiles; i++) {
+        if (!filter[i] || !on_device(filter[i]) || (L > 0 && !on_device(planes[(size_t)i * L])))
+            return fail(ctx, WD_ERR_ARG, std::string(prefix) + "planes and filters must be in device memory");
+        if (labels && !labels[i])
+            return fail(ctx, WD_ERR_ARG, "null label pointer");
+    }
+    return WD_OK;
+}
+
+// What wd_tile_dups and wd_tile_near_dups ask before anything runs: every well a target, a plane per cycle,
+// the limits, a workspace of need() bytes (asked once the limits hold; size_fn names the function that
+// states them), tables, targets inside the tile.  Binds the device.
+template <class Need>
+int check_tile_call(wd_ctx *ctx, int n_tiles, int L, int64_t N, const uint8_t *const *planes,
+                    const uint8_t *const *filter, const void *workspace, size_t workspace_bytes, Need &&need,
+                    const char *size_fn)
+{
+    if (!ctx->has_targets)
+        return fail(ctx, WD_ERR_STATE, "wd_set_targets has not been called");
+    if ((int64_t)ctx->T != N || ctx->levels < 1)
+        return fail(ctx, WD_ERR_ARG, "tile duplicates need every well as a target (T == N)");
+    if (ctx->well_stride != 1)
+        return fail(ctx, WD_ERR_UNSUPPORTED, "tile duplicates read a plane per cycle (well_stride 1)");
+    if (N >= ((int64_t)1 << 31))
+        return fail(ctx, WD_ERR_UNSUPPORTED, "tile duplicates: more than 2^31 - 1 wells");
+    if (L > kMaxCycles)
+        return fail(ctx, WD_ERR_UNSUPPORTED, "tile duplicates: more than 1024 cycles");
+    if (n_tiles > 65535)
+        return fail(ctx, WD_ERR_UNSUPPORTED, "tile duplicates: more than 65535 tiles in one call");
+    if (n_tiles > 0 && (!workspace || workspace_bytes < need()))
+        return fail(ctx, WD_ERR_ARG, std::string("workspace smaller than ") + size_fn);
+    if (n_tiles > 0 && (!filter || (L > 0 && !planes)))
+        return fail(ctx, WD_ERR_ARG, "null plane or filter table");
+    if (ctx->T > 0 && n_tiles > 0 && (ctx->idx_min < 0 || ctx->idx_max >= N))
+        return fail(ctx, WD_ERR_INDEX, "a target names a well outside the tile");
+    return bind_device(ctx) ? WD_ERR_HIP : WD_OK;
+}
+
+// The pointer tables of a call into the workspace.  With d_lbl, the label table goes too (all null if labels is
+// null), from h_lbl, which the caller keeps until it has synchronised the stream.
+int upload_tables(wd_ctx *ctx, int n_tiles, int L, const uint8_t *const *planes, const uint8_t **d_planes,
+                  const uint8_t *const *filter, const uint8_t **d_filt, uint32_t *const *labels = nullptr,
+                  uint32_t **d_lbl = nullptr, std::vector<uint32_t *> *h_lbl = nullptr)
+{
+    if (L > 0)
+        WD_HIP(ctx, hipMemcpyAsync(d_planes, planes, (size_t)n_tiles * L * sizeof(void *), hipMemcpyHostToDevice,
+                                   ctx->stream));
+    WD_HIP(ctx, hipMemcpyAsync(d_filt, filter, n_tiles * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
+    if (d_lbl) {
+        h_lbl->assign(n_tiles, nullptr);
+        if (labels)
+            std::copy(labels, labels + n_tiles, h_lbl->begin());
+        WD_HIP(ctx, hipMemcpyAsync(d_lbl, h_lbl->data(), n_tiles * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
+    }
+    return WD_OK;
+}
+
+// counters and flags clear, every slot of the tables free
+int clear_workspace(wd_ctx *ctx, const Layout &lay, const View &v, int n_tiles)
+{
+    WD_HIP(ctx, hipMemsetAsync(v.cnt, 0, lay.planes - lay.cnt, ctx->stream));
+    WD_HIP(ctx, hipMemsetAsync(v.table, 0xFF, (size_t)n_tiles * lay.slots * 8, ctx->stream));
+    return WD_OK;
+}
+
+// The end of a per-tile call: counters and flags come down, the centres are checked, the copies summed and
+// the rows filled - [PF, Classes, InClasses, Redundant, (NearPairs if near,) Local[levels], RingWells[levels],
+// bins].
+int finish_tile_rows(wd_ctx *ctx, const View &v, int n_tiles, bool near, int64_t *out_rows)
+{
+    const int levels = ctx->levels;
+    WD_HIP(ctx, hipGetLastError());
+    std::vector<unsigned long long> h_cnt((size_t)n_tiles * kSpread * kCnt);
+    uint32_t h_flags[4] = {0, 0, 0, 0};
+    WD_HIP(ctx, hipMemcpyAsync(h_cnt.data(), v.cnt, h_cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    WD_HIP(ctx, hipMemcpyAsync(h_flags, v.flags, sizeof(h_flags), hipMemcpyDeviceToHost, ctx->stream));
+    WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (h_flags[kFlagCentres])
+        return fail(ctx, WD_ERR_ARG, "tile duplicates need target t to be centred on well t");
+    const size_t first = near ? 5 : 4, nrow = first + 2 * (size_t)levels + kBins;
+    for (int i = 0; i < n_tiles; i++) {
+        unsigned long long c[kCnt];
+        sum_spread(h_cnt.data(), (size_t)i, kCnt, c);
+        int64_t *o = out_rows + (size_t)i * nrow;
+        o[0] = (int64_t)c[kCntPf];
+        o[1] = (int64_t)c[kCntClasses];
+        o[2] = (int64_t)c[kCntInClasses];
+        o[3] = o[2] - o[1];
+        if (near)
+            o[4] = (int64_t)c[kCntNear];
+        int64_t local = 0;
+        for (int l = 0; l < levels; l++) {
+            local += (int64_t)c[kCntFirst + l];
+            o[first + l] = local;
+            o[first + levels + l] = (int64_t)c[kCntRing + l];
+        }
+        for (int b = 0; b < kBins; b++)
+            o[first + 2 * levels + b] = (int64_t)c[kCntBins + b];
+    }
+    return WD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -439,116 +447,41 @@ int wd_tile_dups(wd_ctx *ctx, int n_tiles, int L, const uint8_t *const *planes, 
 try {
     if (!ctx || !out_rows || n_tiles < 0 || N < 0 || L < 0 || hash_bits < 0 || hash_bits > 32)
         return WD_ERR_ARG;
-    if (!ctx->has_targets)
-        return fail(ctx, WD_ERR_STATE, "wd_set_targets has not been called");
-    const int levels = ctx->levels;
-    if ((int64_t)ctx->T != N || levels < 1)
-        return fail(ctx, WD_ERR_ARG, "tile duplicates need every well as a target (T == N)");
-    if (ctx->well_stride != 1)
-        return fail(ctx, WD_ERR_UNSUPPORTED, "tile duplicates read a plane per cycle (well_stride 1)");
-    if (N >= ((int64_t)1 << 31))
-        return fail(ctx, WD_ERR_UNSUPPORTED, "tile duplicates: more than 2^31 - 1 wells");
-    if (L > kMaxCycles)
-        return fail(ctx, WD_ERR_UNSUPPORTED, "tile duplicates: more than 1024 cycles");
-    if (n_tiles > 65535)
-        return fail(ctx, WD_ERR_UNSUPPORTED, "tile duplicates: more than 65535 tiles in one call");
+    if (const int rc = check_tile_call(ctx, n_tiles, L, N, planes, filter, workspace_dev, workspace_bytes,
+                                       [&] { return layout_of(N, n_tiles).bytes; }, "wd_tile_dups_workspace"))
+        return rc;
     const Layout lay = layout_of(N, n_tiles);
-    if (n_tiles > 0 && (!workspace_dev || workspace_bytes < lay.bytes))
-        return fail(ctx, WD_ERR_ARG, "workspace smaller than wd_tile_dups_workspace");
-    if (n_tiles > 0 && (!filter || (L > 0 && !planes)))
-        return fail(ctx, WD_ERR_ARG, "null plane or filter table");
-    if (ctx->T > 0 && n_tiles > 0 && (ctx->idx_min < 0 || ctx->idx_max >= N))
-        return fail(ctx, WD_ERR_INDEX, "a target names a well outside the tile");
-    if (bind_device(ctx))
-        return WD_ERR_HIP;
-    const size_t nrow = 4 + 2 * (size_t)levels + kBins;
-    memset(out_rows, 0, (size_t)n_tiles * nrow * sizeof(int64_t));
+    const int levels = ctx->levels;
+    memset(out_rows, 0, (size_t)n_tiles * (4 + 2 * (size_t)levels + kBins) * sizeof(int64_t));
     if (n_tiles == 0 || N == 0)
         return WD_OK;
-    bool aligned4 = true;
-    for (size_t i = 0; i < (size_t)n_tiles * L; i++) {
-        if (!planes[i])
-            return fail(ctx, WD_ERR_ARG, "null plane pointer");
-        aligned4 = aligned4 && ((uintptr_t)planes[i] & 3u) == 0;
-    }
-    for (int i = 0; i < n_tiles; i++) {
-        if (!filter[i] || !on_device(filter[i]) || (L > 0 && !on_device(planes[(size_t)i * L])))
-            return fail(ctx, WD_ERR_ARG, "tile duplicates: planes and filters must be in device memory");
-        if (labels_dev && !labels_dev[i])
-            return fail(ctx, WD_ERR_ARG, "null label pointer");
-    }
-
-    uint8_t *ws = (uint8_t *)workspace_dev;
-    unsigned long long *cnt = (unsigned long long *)(ws + lay.cnt);
-    uint32_t *flags = (uint32_t *)(ws + lay.flags);
-    const uint8_t **d_planes = (const uint8_t **)(ws + lay.planes);
-    const uint8_t **d_filt = (const uint8_t **)(ws + lay.filt);
-    uint32_t **d_lbl = (uint32_t **)(ws + lay.lbl);
-    unsigned long long *table = (unsigned long long *)(ws + lay.table);
-    unsigned long long *fp = (unsigned long long *)(ws + lay.fp);
-    uint32_t *label = (uint32_t *)(ws + lay.label);
-    uint32_t *members = (uint32_t *)(ws + lay.members);
-    uint32_t *first = (uint32_t *)(ws + lay.first);
-    const uint32_t slot_mask = (uint32_t)(lay.slots - 1);
+    bool aligned4;
+    if (const int rc = check_tables(ctx, "tile duplicates: ", n_tiles, L, planes, filter, labels_dev, &aligned4))
+        return rc;
+    const View v(lay, workspace_dev);
     const unsigned long long fp_mask = hash_bits == 0 ? ~0ull : (1ull << hash_bits) - 1;
-
-    std::vector<uint32_t *> h_lbl(n_tiles, nullptr);
-    if (labels_dev)
-        for (int i = 0; i < n_tiles; i++)
-            h_lbl[i] = labels_dev[i];
-    WD_HIP(ctx, hipMemsetAsync(ws + lay.cnt, 0, lay.planes - lay.cnt, ctx->stream));          // counters and flags
-    WD_HIP(ctx, hipMemsetAsync(table, 0xFF, (size_t)n_tiles * lay.slots * 8, ctx->stream));   // every slot free
-    if (L > 0)
-        WD_HIP(ctx, hipMemcpyAsync(d_planes, planes, (size_t)n_tiles * L * sizeof(void *), hipMemcpyHostToDevice,
-                                   ctx->stream));
-    WD_HIP(ctx, hipMemcpyAsync(d_filt, filter, n_tiles * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
-    WD_HIP(ctx, hipMemcpyAsync(d_lbl, h_lbl.data(), n_tiles * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
+    if (const int rc = clear_workspace(ctx, lay, v, n_tiles))
+        return rc;
+    std::vector<uint32_t *> h_lbl;
+    if (const int rc = upload_tables(ctx, n_tiles, L, planes, v.planes, filter, v.filt, labels_dev, v.lbl, &h_lbl))
+        return rc;
 
     const unsigned wblocks = (unsigned)((N + kTdBlock - 1) / kTdBlock);
-    const dim3 wgrid(wblocks, (unsigned)n_tiles);
-    hipLaunchKernelGGL(k_td_check_centres, dim3(wblocks), dim3(kTdBlock), 0, ctx->stream, ctx->d_centre, ctx->T, flags);
+    const dim3 wgrid(wblocks, (unsigned)n_tiles), blk(kTdBlock);
+    hipLaunchKernelGGL(k_td_check_centres, dim3(wblocks), blk, 0, ctx->stream, ctx->d_centre, ctx->T, v.flags);
     if (aligned4)
         hipLaunchKernelGGL(k_td_fingerprint<true>, dim3((unsigned)((N + 4 * kTdBlock - 1) / (4 * kTdBlock)), (unsigned)n_tiles),
-                           dim3(kTdBlock), 0, ctx->stream, d_planes, L, N, fp, members);
+                           blk, 0, ctx->stream, v.planes, L, N, v.fp, v.members);
     else
-        hipLaunchKernelGGL(k_td_fingerprint<false>, wgrid, dim3(kTdBlock), 0, ctx->stream, d_planes, L, N, fp, members);
-    hipLaunchKernelGGL(k_td_insert, wgrid, dim3(kTdBlock), 0, ctx->stream, d_planes, d_filt, L, N, fp, fp_mask, table,
-                       slot_mask, label);
-    hipLaunchKernelGGL(k_td_resolve, wgrid, dim3(kTdBlock), 0, ctx->stream, table, slot_mask, N, label, members, first,
-                       labels_dev ? d_lbl : nullptr, cnt);
-    hipLaunchKernelGGL(k_td_local, wgrid, dim3(kTdBlock), 0, ctx->stream, label, members, N, ctx->d_lvl_off, ctx->d_nbr,
-                       levels, first, cnt);
-    hipLaunchKernelGGL(k_td_levels, wgrid, dim3(kTdBlock), 0, ctx->stream, first, N, levels, cnt);
-    WD_HIP(ctx, hipGetLastError());
-    std::vector<unsigned long long> h_cnt((size_t)n_tiles * kSpread * kCnt);
-    uint32_t h_flags[4] = {0, 0, 0, 0};
-    WD_HIP(ctx, hipMemcpyAsync(h_cnt.data(), cnt, h_cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                               ctx->stream));
-    WD_HIP(ctx, hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, ctx->stream));
-    WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (h_flags[kFlagCentres])
-        return fail(ctx, WD_ERR_ARG, "tile duplicates need target t to be centred on well t");
-
-    for (int i = 0; i < n_tiles; i++) {
-        unsigned long long c[kCnt] = {};
-        for (int r = 0; r < kSpread; r++)
-            for (int f = 0; f < kCnt; f++)
-                c[f] += h_cnt[((size_t)i * kSpread + r) * kCnt + f];
-        int64_t *o = out_rows + (size_t)i * nrow;
-        o[0] = (int64_t)c[kCntPf];
-        o[1] = (int64_t)c[kCntClasses];
-        o[2] = (int64_t)c[kCntInClasses];
-        o[3] = o[2] - o[1];
-        int64_t local = 0;
-        for (int l = 0; l < levels; l++) {
-            local += (int64_t)c[kCntFirst + l];
-            o[4 + l] = local;
-            o[4 + levels + l] = (int64_t)c[kCntRing + l];
-        }
-        for (int b = 0; b < kBins; b++)
-            o[4 + 2 * levels + b] = (int64_t)c[kCntBins + b];
-    }
-    return WD_OK;
+        hipLaunchKernelGGL(k_td_fingerprint<false>, wgrid, blk, 0, ctx->stream, v.planes, L, N, v.fp, v.members);
+    hipLaunchKernelGGL(k_td_insert, wgrid, blk, 0, ctx->stream, v.planes, v.filt, L, N, v.fp, fp_mask, v.table, v.slot_mask,
+                       v.label);
+    hipLaunchKernelGGL(k_td_resolve, wgrid, blk, 0, ctx->stream, v.table, v.slot_mask, N, v.label, v.members, v.first,
+                       labels_dev ? v.lbl : nullptr, v.cnt);
+    hipLaunchKernelGGL(k_td_local, wgrid, blk, 0, ctx->stream, v.label, v.members, N, ctx->d_lvl_off, ctx->d_nbr, levels,
+                       v.first, v.cnt);
+    hipLaunchKernelGGL(k_td_levels, wgrid, blk, 0, ctx->stream, v.first, N, levels, v.cnt);
+    return finish_tile_rows(ctx, v, n_tiles, false, out_rows);
 } WD_CATCH
 
 }  // extern "C"

@@ -229,11 +229,26 @@ class Scanner:
             pto.ctypes.data_as(ctypes.c_void_p) if per_target else None))
         return blocks, pto
 
+    def _workspace_bytes(self, fn, *args) -> int:
+        b = ctypes.c_size_t()
+        self._ck(fn(*[int(a) for a in args], ctypes.byref(b)))
+        return b.value
+
+    def _tile_call(self, planes, filters, labels, tables, L, row_cols: int, call):
+        """What tile_dups and tile_near_dups share: the pointer tables, a zeroed int64 [n_tiles, row_cols], the label
+        table (or None), then call(n_tiles, L, plane table, filter table, rows pointer, label table) -> rc."""
+        n_tiles = len(filters)
+        if L is None:
+            L = len(planes[0]) if n_tiles else 0
+        pt, ft = tables if tables is not None else self._tables(planes, filters, L)
+        rows = np.zeros((n_tiles, row_cols), dtype=np.int64)
+        lt = (ctypes.c_void_p * max(1, n_tiles))(*[int(p) for p in labels]) if labels is not None else None
+        self._ck(call(n_tiles, L, pt, ft, rows.ctypes.data_as(ctypes.c_void_p), lt))
+        return rows
+
     def dup_sets_workspace_bytes(self, n_clusters: int, n_tiles: int) -> int:
         """Device bytes wd_dup_sets needs as its workspace for n_tiles tiles of n_clusters wells."""
-        b = ctypes.c_size_t()
-        self._ck(self._lib.wd_dup_sets_workspace(int(n_clusters), int(n_tiles), ctypes.byref(b)))
-        return b.value
+        return self._workspace_bytes(self._lib.wd_dup_sets_workspace, n_clusters, n_tiles)
 
     def dup_sets(self, planes: Sequence[Sequence[int]], filters: Sequence[int], n_clusters: int, mode: int, k: int,
                  workspace: int, workspace_bytes: int, labels: Optional[Sequence[int]] = None, edge_cap: int = 0,
@@ -258,9 +273,7 @@ class Scanner:
 
     def tile_dups_workspace_bytes(self, n_clusters: int, n_tiles: int) -> int:
         """Device bytes wd_tile_dups needs as its workspace for n_tiles tiles of n_clusters wells."""
-        b = ctypes.c_size_t()
-        self._ck(self._lib.wd_tile_dups_workspace(int(n_clusters), int(n_tiles), ctypes.byref(b)))
-        return b.value
+        return self._workspace_bytes(self._lib.wd_tile_dups_workspace, n_clusters, n_tiles)
 
     def tile_dups(self, planes: Sequence[Sequence[int]], filters: Sequence[int], n_clusters: int, workspace: int,
                   workspace_bytes: int, labels: Optional[Sequence[int]] = None, hash_bits: int = 0, tables=None, L=None):
@@ -268,22 +281,15 @@ class Scanner:
         wherever on the tile they lie; needs every well as a target.  labels: n_tiles device addresses of N
         uint32 each, or None.  Returns rows [n_tiles, 4 + 2*levels + 8]: [PF wells, Classes, InClasses,
         Redundant, Local[levels], RingWells[levels], size bins 2..8, 9+]."""
-        n_tiles = len(filters)
-        if L is None:
-            L = len(planes[0]) if n_tiles else 0
-        pt, ft = tables if tables is not None else self._tables(planes, filters, L)
-        rows = np.zeros((n_tiles, 4 + 2 * self.levels + _lib.DUPSET_SIZE_BINS), dtype=np.int64)
-        lt = (ctypes.c_void_p * max(1, n_tiles))(*[int(p) for p in labels]) if labels is not None else None
-        self._ck(self._lib.wd_tile_dups(
-            self._ctx, n_tiles, L, pt, ft, int(n_clusters), ctypes.c_void_p(workspace), int(workspace_bytes),
-            int(hash_bits), rows.ctypes.data_as(ctypes.c_void_p), lt))
-        return rows
+        return self._tile_call(
+            planes, filters, labels, tables, L, 4 + 2 * self.levels + _lib.DUPSET_SIZE_BINS,
+            lambda n_tiles, L, pt, ft, rows, lt: self._lib.wd_tile_dups(
+                self._ctx, n_tiles, L, pt, ft, int(n_clusters), ctypes.c_void_p(workspace), int(workspace_bytes),
+                int(hash_bits), rows, lt))
 
     def tile_near_dups_workspace_bytes(self, n_clusters: int, n_tiles: int, k: int) -> int:
         """Device bytes wd_tile_near_dups needs as its workspace for n_tiles tiles of n_clusters wells at distance k."""
-        b = ctypes.c_size_t()
-        self._ck(self._lib.wd_tile_near_dups_workspace(int(n_clusters), int(n_tiles), int(k), ctypes.byref(b)))
-        return b.value
+        return self._workspace_bytes(self._lib.wd_tile_near_dups_workspace, n_clusters, n_tiles, k)
 
     def tile_near_dups(self, planes: Sequence[Sequence[int]], filters: Sequence[int], n_clusters: int, k: int,
                        workspace: int, workspace_bytes: int, labels: Optional[Sequence[int]] = None, hash_bits: int = 0,
@@ -293,23 +299,16 @@ class Scanner:
         n_tiles device addresses of N uint32 each, or None.  Returns rows [n_tiles, 5 + 2*levels + 8]: [PF wells,
         Clusters, InClusters, Redundant, NearPairs, Local[levels], RingWells[levels], size bins 2..8, 9+].  A tile
         with more candidate pairs in a segment than pair_budget (0 = the default) raises RuntimeError."""
-        n_tiles = len(filters)
-        if L is None:
-            L = len(planes[0]) if n_tiles else 0
-        pt, ft = tables if tables is not None else self._tables(planes, filters, L)
-        rows = np.zeros((n_tiles, 5 + 2 * self.levels + _lib.DUPSET_SIZE_BINS), dtype=np.int64)
-        lt = (ctypes.c_void_p * max(1, n_tiles))(*[int(p) for p in labels]) if labels is not None else None
-        self._ck(self._lib.wd_tile_near_dups(
-            self._ctx, n_tiles, L, pt, ft, int(n_clusters), int(k), ctypes.c_void_p(workspace), int(workspace_bytes),
-            int(hash_bits), int(pair_budget), rows.ctypes.data_as(ctypes.c_void_p), lt))
-        return rows
+        return self._tile_call(
+            planes, filters, labels, tables, L, 5 + 2 * self.levels + _lib.DUPSET_SIZE_BINS,
+            lambda n_tiles, L, pt, ft, rows, lt: self._lib.wd_tile_near_dups(
+                self._ctx, n_tiles, L, pt, ft, int(n_clusters), int(k), ctypes.c_void_p(workspace), int(workspace_bytes),
+                int(hash_bits), int(pair_budget), rows, lt))
 
     def lane_dups_workspace_bytes(self, n_clusters: int, max_tiles: int, L: int) -> int:
         """Device bytes a LaneDups accumulator needs for max_tiles tiles of n_clusters wells and L cycles
         (wd_lane_dups_workspace; a lane of 2^32 - 1 wells or more raises RuntimeError)."""
-        b = ctypes.c_size_t()
-        self._ck(self._lib.wd_lane_dups_workspace(int(n_clusters), int(max_tiles), int(L), ctypes.byref(b)))
-        return b.value
+        return self._workspace_bytes(self._lib.wd_lane_dups_workspace, n_clusters, max_tiles, L)
 
     def scan_async(self, tables, n_tiles: int, L: int, n_clusters: int, mode: int, k: int,
                    out_tile_dev: int, out_per_target_dev: Optional[int] = None):
@@ -616,21 +615,17 @@ class TileBatch:
             self.d_tmp = scanner.malloc(tmp_bytes) if tmp_bytes else 0
             self._cap = (self.plane_bytes, self.filter_bytes, tmp_bytes)
         self.tables = Scanner._tables(self.plane_ptrs(), self.filter_ptrs(), L)
-        # duplicate sets (dup_sets): workspace and labels, allocated on first use, kept with the buffers
-        self.d_sets, self.sets_bytes, self.edges = 0, 0, 0
-        if reuse is not None and reuse.sc is scanner and reuse.d_sets:
-            self.d_sets, self.sets_bytes, self._sets_cap = reuse.d_sets, reuse.sets_bytes, reuse._sets_cap
-            reuse.d_sets = 0
-        # read classes (tile_dups): the same, with a buffer of its own
-        self.d_tdups, self._tdups_cap = 0, 0
-        if reuse is not None and reuse.sc is scanner and reuse.d_tdups:
-            self.d_tdups, self._tdups_cap = reuse.d_tdups, reuse._tdups_cap
-            reuse.d_tdups = 0
-        # near-duplicate clusters (tile_near_dups): the same again
-        self.d_tnear, self._tnear_cap = 0, 0
-        if reuse is not None and reuse.sc is scanner and reuse.d_tnear:
-            self.d_tnear, self._tnear_cap = reuse.d_tnear, reuse._tnear_cap
-            reuse.d_tnear = 0
+        # dup_sets, tile_dups, tile_near_dups: a workspace each (a caller may interleave the calls) with the labels
+        # behind it, allocated on first use, kept with the buffers: name -> [device address, capacity in bytes]
+        self._ws = {name: [0, 0] for name in ("sets", "tdups", "tnear")}
+        self.sets_bytes, self.edges = 0, 0
+        if reuse is not None and reuse.sc is scanner:
+            self.sets_bytes = reuse.sets_bytes if reuse.d_sets else 0
+            self._ws, reuse._ws = reuse._ws, self._ws
+
+    d_sets = property(lambda self: self._ws["sets"][0])
+    d_tdups = property(lambda self: self._ws["tdups"][0])
+    d_tnear = property(lambda self: self._ws["tnear"][0])
 
     def plane_ptr(self, tile: int, cycle: int) -> int:
         """Address of well 0 of the cycle (wells are `interleave` bytes apart)."""
@@ -694,81 +689,54 @@ class TileBatch:
         finally:
             self.sc.set_option("well_stride", 1)
 
-    def dup_sets(self, mode: int, k: int, labels: bool = False, edge_cap: int = 0):
-        """count() plus the duplicate sets of every tile (Scanner.dup_sets; every well must be a target).
-        -> (blocks, sets rows, labels uint32 [n_tiles, N] or None).  edges_processed is left in self.edges."""
-        ws = self.sc.dup_sets_workspace_bytes(self.N, self.n_tiles)
+    def _with_workspace(self, name: str, ws: int, labels: bool, call):
+        """Grows the workspace `name` to ws bytes plus the labels behind it and runs call(workspace address, label
+        addresses or None) under this batch's well_stride.  -> (its result, labels uint32 [n_tiles, N] or None)."""
+        w = self._ws[name]
         lbl_bytes = 4 * self.N * self.n_tiles if labels else 0
-        if not self.d_sets or self._sets_cap < ws + lbl_bytes:
-            if self.d_sets:
-                self.sc.free(self.d_sets)
-                self.d_sets = 0
-            self._sets_cap = ws + lbl_bytes
-            self.d_sets = self.sc.malloc(max(1, self._sets_cap))
-        self.sets_bytes = ws
-        d_lbl = self.d_sets + ws if labels else 0
+        if not w[0] or w[1] < ws + lbl_bytes:
+            if w[0]:
+                self.sc.free(w[0])
+                w[0] = 0
+            w[1] = ws + lbl_bytes
+            w[0] = self.sc.malloc(max(1, w[1]))
+        d_lbl = w[0] + ws
         lbl_ptrs = [d_lbl + 4 * self.N * i for i in range(self.n_tiles)] if labels else None
         self.sc.set_option("well_stride", self.interleave)
         try:
-            blocks, sets, self.edges = self.sc.dup_sets(None, self.filter_ptrs(), self.N, mode, k, self.d_sets, ws,
-                                                        labels=lbl_ptrs, edge_cap=edge_cap, tables=self.tables, L=self.L)
+            out = call(w[0], lbl_ptrs)
         finally:
             self.sc.set_option("well_stride", 1)
-        lab = None
-        if labels:
-            lab = self.sc.d2h(d_lbl, lbl_bytes, np.uint32).reshape(self.n_tiles, self.N)
+        return out, (self.sc.d2h(d_lbl, lbl_bytes, np.uint32).reshape(self.n_tiles, self.N) if labels else None)
+
+    def dup_sets(self, mode: int, k: int, labels: bool = False, edge_cap: int = 0):
+        """count() plus the duplicate sets of every tile (Scanner.dup_sets; every well must be a target).
+        -> (blocks, sets rows, labels uint32 [n_tiles, N] or None).  edges_processed is left in self.edges."""
+        ws = self.sets_bytes = self.sc.dup_sets_workspace_bytes(self.N, self.n_tiles)
+        (blocks, sets, self.edges), lab = self._with_workspace("sets", ws, labels, lambda d_ws, lbl_ptrs: self.sc.dup_sets(
+            None, self.filter_ptrs(), self.N, mode, k, d_ws, ws, labels=lbl_ptrs, edge_cap=edge_cap, tables=self.tables,
+            L=self.L))
         return blocks, sets, lab
 
     def tile_dups(self, labels: bool = False, hash_bits: int = 0):
         """The read classes of every tile of the batch (Scanner.tile_dups; every well must be a target, the
         batch a plane per cycle).  -> (rows, labels uint32 [n_tiles, N] or None)."""
         ws = self.sc.tile_dups_workspace_bytes(self.N, self.n_tiles)
-        lbl_bytes = 4 * self.N * self.n_tiles if labels else 0
-        if not self.d_tdups or self._tdups_cap < ws + lbl_bytes:
-            if self.d_tdups:
-                self.sc.free(self.d_tdups)
-                self.d_tdups = 0
-            self._tdups_cap = ws + lbl_bytes
-            self.d_tdups = self.sc.malloc(max(1, self._tdups_cap))
-        d_lbl = self.d_tdups + ws if labels else 0
-        lbl_ptrs = [d_lbl + 4 * self.N * i for i in range(self.n_tiles)] if labels else None
-        self.sc.set_option("well_stride", self.interleave)
-        try:
-            rows = self.sc.tile_dups(None, self.filter_ptrs(), self.N, self.d_tdups, ws, labels=lbl_ptrs,
-                                     hash_bits=hash_bits, tables=self.tables, L=self.L)
-        finally:
-            self.sc.set_option("well_stride", 1)
-        lab = None
-        if labels:
-            lab = self.sc.d2h(d_lbl, lbl_bytes, np.uint32).reshape(self.n_tiles, self.N)
-        return rows, lab
+        return self._with_workspace("tdups", ws, labels, lambda d_ws, lbl_ptrs: self.sc.tile_dups(
+            None, self.filter_ptrs(), self.N, d_ws, ws, labels=lbl_ptrs, hash_bits=hash_bits, tables=self.tables, L=self.L))
 
     def tile_near_dups(self, k: int, labels: bool = False, pair_budget: int = 0, hash_bits: int = 0):
         """The near-duplicate clusters (Hamming distance <= k) of every tile of the batch (Scanner.tile_near_dups;
         every well must be a target, the batch a plane per cycle).  -> (rows, labels uint32 [n_tiles, N] or None)."""
         ws = self.sc.tile_near_dups_workspace_bytes(self.N, self.n_tiles, k)
-        lbl_bytes = 4 * self.N * self.n_tiles if labels else 0
-        if not self.d_tnear or self._tnear_cap < ws + lbl_bytes:
-            if self.d_tnear:
-                self.sc.free(self.d_tnear)
-                self.d_tnear = 0
-            self._tnear_cap = ws + lbl_bytes
-            self.d_tnear = self.sc.malloc(max(1, self._tnear_cap))
-        d_lbl = self.d_tnear + ws if labels else 0
-        lbl_ptrs = [d_lbl + 4 * self.N * i for i in range(self.n_tiles)] if labels else None
-        self.sc.set_option("well_stride", self.interleave)
-        try:
-            rows = self.sc.tile_near_dups(None, self.filter_ptrs(), self.N, k, self.d_tnear, ws, labels=lbl_ptrs,
-                                          hash_bits=hash_bits, pair_budget=pair_budget, tables=self.tables, L=self.L)
-        finally:
-            self.sc.set_option("well_stride", 1)
-        lab = None
-        if labels:
-            lab = self.sc.d2h(d_lbl, lbl_bytes, np.uint32).reshape(self.n_tiles, self.N)
-        return rows, lab
+        return self._with_workspace("tnear", ws, labels, lambda d_ws, lbl_ptrs: self.sc.tile_near_dups(
+            None, self.filter_ptrs(), self.N, k, d_ws, ws, labels=lbl_ptrs, hash_bits=hash_bits, pair_budget=pair_budget,
+            tables=self.tables, L=self.L))
 
     def free(self):
-        for ptr in (self.d_planes, self.d_filters, self.d_tmp, self.d_sets, self.d_tdups, self.d_tnear):
+        for ptr in [self.d_planes, self.d_filters, self.d_tmp] + [w[0] for w in self._ws.values()]:
             if ptr:
                 self.sc.free(ptr)
-        self.d_planes = self.d_filters = self.d_tmp = self.d_sets = self.d_tdups = self.d_tnear = 0
+        self.d_planes = self.d_filters = self.d_tmp = 0
+        for w in self._ws.values():
+            w[0] = 0
