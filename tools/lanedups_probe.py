@@ -9,6 +9,11 @@ tools/tiledups_probe.py (seed 5, tiles 1101.., 2 % planted inside each tile), wh
 every odd tile repeats the tile before it but for the first cycle, so that a quarter of its wells have a
 classmate there and the lane's table is joined as often as claimed.
 `--equal` adds a lane of three tiles whose reads are all equal (one slot takes every well: the worst case).
+`--hamming K` feeds a second accumulator the same batches and times LaneDups.finish(hamming=K) - the near-duplicate
+clusters of the lane, include/welldup_lanenear.h - beside the equality finish, and TileBatch.tile_near_dups at the
+same K beside tile_dups on every batch: the near finish less the equality finish is held against tile_near_dups
+less tile_dups.  `--heavy M` adds a lane of four tiles with M distinct reads in all that share their first segment
+(one bucket, M (M - 1) / 2 candidate pairs: the pair rate on packed rows).
 For per-kernel times run it under
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/lanedups_probe.py
@@ -35,6 +40,9 @@ ap.add_argument("--batch", type=int, default=8)
 ap.add_argument("--plant", type=int, default=1311, help="planted wells per 65536 inside a tile (1311 = 2 %%)")
 ap.add_argument("--cross", action="store_true", help="every odd tile repeats the tile before it but for the first cycle")
 ap.add_argument("--equal", action="store_true", help="also time a lane of three tiles whose reads are all equal")
+ap.add_argument("--hamming", type=int, default=0, metavar="K", help="also time the near finish at Hamming distance <= K")
+ap.add_argument("--heavy", type=int, default=0, metavar="M",
+                help="also time a lane of M distinct reads that share their first segment (needs --hamming)")
 a = ap.parse_args()
 
 n = a.rows * a.cols
@@ -69,7 +77,8 @@ def fill(tb, tiles):
 batches = [list(range(b0, min(a.tiles, b0 + a.batch))) for b0 in range(0, a.tiles, a.batch)]
 tbs = [TileBatch(sc, a.batch, a.cycles, n), TileBatch(sc, a.batch, a.cycles, n)] if a.tiles else []
 ld = LaneDups(sc, n, a.tiles, a.cycles)
-t_add = t_td = t_cnt = t_read = 0.0
+ldn = LaneDups(sc, n, a.tiles, a.cycles) if a.hamming else None
+t_add = t_td = t_cnt = t_read = t_tn = 0.0
 read_gbs = []
 td_pf = td_red = 0
 for bi, tiles in enumerate(batches):
@@ -85,8 +94,18 @@ for bi, tiles in enumerate(batches):
         warm.close()
         tb.tile_dups()
         tb.count(0, 0)
+        if a.hamming:
+            warm = LaneDups(sc, n, len(tiles), a.cycles)
+            warm.add(tb, list(range(len(tiles))))
+            warm.finish(hamming=a.hamming)
+            warm.close()
+            tb.tile_near_dups(a.hamming)
     _, dt = clock(lambda: ld.add(tb, tiles))
     t_add += dt
+    if a.hamming:
+        ldn.add(tb, tiles)
+        _, dt = clock(lambda: tb.tile_near_dups(a.hamming))
+        t_tn += dt
     (rows, _), dt = clock(lambda: tb.tile_dups())
     t_td += dt
     td_pf += int(rows[:, 0].sum())
@@ -98,6 +117,10 @@ for bi, tiles in enumerate(batches):
     t_read += tb.plane_bytes / gbs / 1e6
 (lane, trow, _), t_fin = clock(lambda: ld.finish())
 ld.close()
+if a.hamming:
+    near, t_near = clock(lambda: ldn.finish(hamming=a.hamming))
+    ldn.close()
+    assert (near[0] == lane).all() and (near[1] == trow).all(), "the near finish delivers other classes"
 for tb in tbs:
     tb.free()
 
@@ -115,6 +138,40 @@ print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("count", t_cnt, t_cnt / k))
 print("  %-22s %9.3f ms  (%.4f ms per tile, %.0f GB/s)" % ("pure read of the planes", t_read, t_read / k,
                                                             float(np.mean(read_gbs)) if read_gbs else 0.0))
 print("  (add + finish) / tile_dups = %.2f; add / pure read = %.2f" % ((t_add + t_fin) / t_td, t_add / t_read))
+
+if a.hamming:
+    nl = near[3]
+    print("Hamming <= %d: %d clusters (%d across tiles), %d wells in them, %d near pairs of distinct reads; lane duplication "
+          "%.3f %% (by equality %.3f %%)" % (a.hamming, nl[1], nl[4], nl[2], nl[6], 100.0 * nl[3] / max(1, wells),
+                                             100.0 * lane[3] / max(1, wells)))
+    print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("lane near finish", t_near, t_near / k))
+    print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("  less the finish", t_near - t_fin, (t_near - t_fin) / k))
+    print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("tile_near_dups", t_tn, t_tn / k))
+    print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("  less tile_dups", t_tn - t_td, (t_tn - t_td) / k))
+    print("  (near finish - finish) / (tile_near_dups - tile_dups) = %.2f" % ((t_near - t_fin) / (t_tn - t_td)))
+
+if a.heavy and a.hamming:
+    m4 = (a.heavy + 3) // 4
+    rng = np.random.default_rng(7)
+    head = (a.cycles + a.hamming) // (a.hamming + 1)                    # covers the first segment
+    four = TileBatch(sc, 4, a.cycles, m4)
+    for s in range(4):
+        reads = rng.integers(1, 256, (m4, a.cycles)).astype(np.uint8)
+        reads[:, :head] = 0x41
+        four.upload_tile(s, [np.ascontiguousarray(reads[:, c]) for c in range(a.cycles)], np.ones(m4, dtype=np.uint8))
+    pairs = 4 * m4 * (4 * m4 - 1) // 2
+    times = []
+    for hamming in (0, a.hamming, 0, a.hamming):
+        hv = LaneDups(sc, m4, 4, a.cycles)
+        hv.add(four, [0, 1, 2, 3])
+        got, dt = clock(lambda: hv.finish(hamming=hamming, pair_budget=pairs if hamming else 0))
+        hv.close()
+        times.append(dt)
+    assert got[0][1] == 0, "the heavy lane's reads are not distinct"
+    dt = times[3] - times[2]
+    print("heavy: %d distinct reads on four tiles share cycles 0..%d: %d candidate pairs; finish %.3f ms, near finish "
+          "%.3f ms: %.3g pairs per second" % (4 * m4, head - 1, pairs, times[2], times[3], pairs / (dt * 1e-3)))
+    four.free()
 
 if a.equal:
     three = TileBatch(sc, 3, a.cycles, n)

@@ -130,6 +130,14 @@ LANEDUPS_PROTOTYPES = {
 LANEDUPS_LANE_COLS = 6 + DUPSET_SIZE_BINS
 LANEDUPS_TILE_COLS = 5
 
+# name -> (restype, argtypes); every symbol include/welldup_lanenear.h declares beyond the five above
+LANENEAR_PROTOTYPES = {
+    "wd_lane_near_dups_scratch": (_i, [_i64, _i, _i, _i, ctypes.POINTER(_sz)]),
+    "wd_lane_near_dups_finish": (_i, [_vp, _i, _vp, _sz, _i64, _vp, _vp, _pp, _vp, _vp, _pp]),
+}
+LANENEAR_MAX_K = TILENEAR_MAX_K
+LANENEAR_LANE_COLS = 7 + DUPSET_SIZE_BINS
+
 _lib = None
 
 
@@ -216,7 +224,7 @@ def unit_of_kernel(kernel: str) -> str:
         return "ingest"
     if kernel.startswith("k_sets"):
         return "sets"
-    if kernel.startswith(("k_td_", "k_tn_", "k_ld_")):
+    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_")):
         return "tiledups"
     return "scan"
 
@@ -276,7 +284,7 @@ def load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the scan path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     for name, (res, args) in list(PROTOTYPES.items()) + list(SETS_PROTOTYPES.items()) + list(TILEDUPS_PROTOTYPES.items()) + \
-            list(TILENEAR_PROTOTYPES.items()) + list(LANEDUPS_PROTOTYPES.items()):
+            list(TILENEAR_PROTOTYPES.items()) + list(LANEDUPS_PROTOTYPES.items()) + list(LANENEAR_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -168,6 +168,17 @@ def parse_args(argv=None):
     p.add_argument("--lane-dups-out", default=None, metavar="PATH",
                    help="with --lane-dups: write lane, tile, well, class_tile and class_well (tile and well of the "
                         "first well of its class) of every well in a lane class to this TSV file")
+    p.add_argument("--lane-dups-hamming", type=int, default=None, metavar="K",
+                   help="with --lane-dups: also group the PF wells of every tile of a lane into clusters of reads "
+                        "linked by Hamming distance <= K (1..%d; single linkage, exact, on whatever tiles the wells lie) "
+                        "and print a second block of the same shape for them, with the pairs of distinct reads of the "
+                        "lane within K, the duplication of the lane at Hamming <= K beside the one by equality and the "
+                        "library size estimated from the clusters; --lane-dups-out then lists the wells in a lane "
+                        "cluster, with cluster_tile and cluster_well columns.  Hamming only" % _lib.LANENEAR_MAX_K)
+    p.add_argument("--lane-dups-pair-budget", type=int, default=0, metavar="N",
+                   help="with --lane-dups-hamming: the most candidate pairs one segment of a lane may have before the "
+                        "run is refused (reads of low diversity); 0 = the library's default, max(16 x the lane's "
+                        "wells, 2^24)")
     args = p.parse_args(argv)
     if not args.coord_file and not args.all_wells:
         p.error("the following arguments are required: -f/--coord_file (or --all-wells)")
@@ -197,6 +208,14 @@ def parse_args(argv=None):
         p.error("--lane-dups needs --all-wells (the resident layout of every well, a plane per cycle)")
     if args.lane_dups_out and not args.lane_dups:
         p.error("--lane-dups-out needs --lane-dups")
+    if args.lane_dups_hamming is not None and not args.lane_dups:
+        p.error("--lane-dups-hamming needs --lane-dups")
+    if args.lane_dups_hamming is not None and not 1 <= args.lane_dups_hamming <= _lib.LANENEAR_MAX_K:
+        p.error("--lane-dups-hamming takes 1..%d" % _lib.LANENEAR_MAX_K)
+    if args.lane_dups_pair_budget < 0:
+        p.error("--lane-dups-pair-budget must not be negative")
+    if args.lane_dups_pair_budget and args.lane_dups_hamming is None:
+        p.error("--lane-dups-pair-budget needs --lane-dups-hamming")
     if args.lane_dups and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         p.error("--lane-dups runs in a single process only: under WORLD_SIZE > 1 a lane's tiles are spread over the "
                 "ranks, and the classes of a lane need all of them in one GPU's table")
@@ -297,17 +316,28 @@ def lane_members(labels: np.ndarray):
     return ids // n, ids % n, lab // n, lab % n
 
 
-def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int):
-    """--lane-dups: the accumulator's workspace against the free device memory, before anything is loaded."""
+def lane_cluster_members(class_labels: np.ndarray, cluster_labels: np.ndarray):
+    """A lane's class and cluster labels [tiles, N] (LaneDups.finish(hamming=K)) -> (tile index, well, class tile
+    index, class well, cluster tile index, cluster well) of the wells in a lane cluster, by tile index and well."""
+    ti, w, cti, cw = lane_members(cluster_labels)
+    lab = class_labels.reshape(-1)[ti * class_labels.shape[1] + w].astype(np.int64)
+    return ti, w, lab // class_labels.shape[1], lab % class_labels.shape[1], cti, cw
+
+
+def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0):
+    """--lane-dups: the accumulator's workspace - with --lane-dups-hamming plus the scratch of the near finish -
+    against the free device memory, before anything is loaded."""
+    need += scratch
     if need > free:
         raise MemoryError("--lane-dups needs %.2f GB of device memory for a lane of %d tiles x %d wells x %d cycles "
-                          "(%d bytes), and %.2f GB (%d bytes) are free" % (need / 1e9, tiles, wells, cycles, need,
-                                                                          free / 1e9, free))
+                          "(%d bytes%s), and %.2f GB (%d bytes) are free" % (
+                              need / 1e9, tiles, wells, cycles, need,
+                              ", %d of them for --lane-dups-hamming" % scratch if scratch else "", free / 1e9, free))
 
 
 def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells, tile_batch,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
-               dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0):
+               dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0, lane_near=0, lane_pair_budget=0):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
@@ -321,6 +351,8 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     released, and finished at the lane's last batch: into["ldups"][lane] = LaneDupCounts; 2 = and the members,
     into["lmembers"][lane] = (tile names by index,) + lane_members(labels).  A tile index is the tile's place
     in the lane's list.
+    lane_near = K > 0 (with lane_dups): and the lane's clusters at Hamming distance <= K (LaneDups.finish(hamming=K)):
+    into["lnear"][lane] = LaneNearCounts, and into["lmembers"][lane] = (names,) + lane_cluster_members(...).
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -502,11 +534,16 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                     lane_acc["lane"] = lane
                 ld.add(tb, [names.index(t) for t in chunk])
                 if last_batch_of[lane] == bi:
-                    lane_row, tile_rows, lane_labels = ld.finish(labels=lane_dups > 1)
+                    got = ld.finish(labels=lane_dups > 1, hamming=lane_near, pair_budget=lane_pair_budget)
+                    lane_row, tile_rows, lane_labels = got[:3]
                     into["ldups"][lane] = report.LaneDupCounts.from_rows(lane_row, tile_rows, names)
-                    if lane_labels is not None:
+                    if lane_near:
+                        into["lnear"][lane] = report.LaneNearCounts.from_rows(got[3], got[4], names)
+                        if lane_labels is not None:
+                            into["lmembers"][lane] = (names,) + lane_cluster_members(lane_labels, got[5])
+                    elif lane_labels is not None:
                         into["lmembers"][lane] = (names,) + lane_members(lane_labels)
-                        del lane_labels
+                    del lane_labels, got
                 _lap("batch %d: lane classes" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
             if want_log:
@@ -583,13 +620,18 @@ def write_cluster_members(path, members):
 def write_lane_members(path, members):
     """--lane-dups-out: lane, tile, well, class_tile, class_well of every well in a lane class, by lane, then in
     the order of the lane's tiles, then by well.  members[lane] = (tile names by index, tile index, well, class
-    tile index, class well)."""
+    tile index, class well) - or, under --lane-dups-hamming, those and (cluster tile index, cluster well) of every
+    well in a lane cluster, which makes two more columns."""
     with open(path, "w") as fh:
-        fh.write("lane\ttile\twell\tclass_tile\tclass_well\n")
+        near = any(len(m) == 7 for m in members.values())
+        fh.write("lane\ttile\twell\tclass_tile\tclass_well%s\n" % ("\tcluster_tile\tcluster_well" if near else ""))
         for lane in sorted(members, key=str):
-            names, ti, w, cti, cw = members[lane]
-            fh.writelines("%s\t%s\t%d\t%s\t%d\n" % (lane, names[a], b, names[c], d)
-                          for a, b, c, d in zip(ti.tolist(), w.tolist(), cti.tolist(), cw.tolist()))
+            names, cols = members[lane][0], [c.tolist() for c in members[lane][1:]]
+            if near:        # (--lane-dups-hamming: the wells in a lane cluster, their class and their cluster)
+                fh.writelines("%s\t%s\t%d\t%s\t%d\t%s\t%d\n" % (lane, names[a], b, names[c], d, names[e], f)
+                              for a, b, c, d, e, f in zip(*cols))
+            else:
+                fh.writelines("%s\t%s\t%d\t%s\t%d\n" % (lane, names[a], b, names[c], d) for a, b, c, d in zip(*cols))
 
 
 def main(argv=None, exiting=False):
@@ -724,6 +766,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
             ntd = 4 + 2 * levels + len(report.CLASS_BIN_NAMES) if args.tile_dups else 0
             # --tile-dups-hamming: and the clusters' behind those
             near_k = args.tile_dups_hamming or 0
+            lane_near_k = args.lane_dups_hamming or 0
             ntn = 5 + 2 * levels + len(report.CLASS_BIN_NAMES) if near_k else 0
             rows = np.zeros((len(mine), ncnt + nsets + ntd + ntn), dtype=np.int64)
             logs = {}
@@ -754,13 +797,16 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                                 levels=levels, equal=equal)
                 if args.lane_dups:          # (single process: the lane's counts never travel through `block`)
                     report.write_lane_dups(lane, results["ldups"][lane], verbose=not args.summary_only, out=out_fh)
+                if lane_near_k:
+                    report.write_lane_near_dups(lane, lane_near_k, results["lnear"][lane], verbose=not args.summary_only,
+                                                out=out_fh, equal=results["ldups"][lane])
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
                 where = {item: i for i, item in enumerate(mine)}
                 # scan_lanes fills these, lane_done reads them
                 results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
-                           "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}}
+                           "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}, "lnear": {}}
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
@@ -782,7 +828,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                     # before anything is loaded: a lane's accumulator has to fit beside the batches
                     import torch
                     check_lane_dups_fits(sc.lane_dups_workspace_bytes(n_targets, len(tiles), len(cycle_list)),
-                                         torch.cuda.mem_get_info(device)[0], len(tiles), n_targets, len(cycle_list))
+                                         torch.cuda.mem_get_info(device)[0], len(tiles), n_targets, len(cycle_list),
+                                         scratch=sc.lane_near_scratch_bytes(n_targets, len(tiles), len(cycle_list),
+                                                                            lane_near_k))
                 if err is None:             # (a rank whose setup failed has nothing to scan: it goes to the flag)
                     scan_lanes(sc, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                                max(0, args.tile_batch), args.threads,
@@ -793,7 +841,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                dup_sets=(2 if args.dup_sets_out else 1) if args.dup_sets else 0,
                                tile_dups=(2 if args.tile_dups_out else 1) if args.tile_dups else 0,
                                tile_near=near_k, pair_budget=args.tile_dups_pair_budget,
-                               lane_dups=(2 if args.lane_dups_out else 1) if args.lane_dups else 0)
+                               lane_dups=(2 if args.lane_dups_out else 1) if args.lane_dups else 0,
+                               lane_near=lane_near_k, lane_pair_budget=args.lane_dups_pair_budget)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
                     if args.tile_dups_out and near_k:

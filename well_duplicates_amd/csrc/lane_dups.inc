@@ -11,7 +11,7 @@
 //   k_ld_pack        the pass of k_td_fingerprint over the planes; the 30-bit words it folds are also stored as the
 //                    well's packed row - after this kernel nothing reads the planes again
 //   k_ld_insert      one lane per PF well into the lane's table; equality is decided on the packed rows
-// wd_lane_dups_finish, over the tiles that were added:
+// wd_lane_dups_finish (ld_equality, which lane_near.inc calls too), over the tiles that were added:
 //   k_ld_resolve     slot -> label; members counted at the representative; PF per tile
 //   (the table is dead now: it is cleared and used again, keyed by (label, tile))
 //   k_ld_classes     classes, size bins, InLane, LaneRedundant; a well in a class enters the second table, whose
@@ -396,7 +396,158 @@ struct wd_lane_dups {
     unsigned long long fp_mask;
     std::vector<char> added;                       // by tile index
     bool finished;
+    // the classes, once k_ld_resolve has run (lane_near.inc delivers them again after a refusal)
+    bool resolved;
+    std::vector<int64_t> eq_lane, eq_tiles;
 };
+
+namespace {
+
+int ld_check_labels(wd_lane_dups *ld, uint32_t *const *labels_dev)
+{
+    if (labels_dev)
+        for (int t = 0; t < ld->max_tiles; t++)
+            if (labels_dev[t] && ld->N > 0 && !on_device(labels_dev[t]))
+                return fail(ld->ctx, WD_ERR_ARG, "lane duplicates: labels must be in device memory");
+    return WD_OK;
+}
+
+std::vector<int> ld_tiles_added(const wd_lane_dups *ld)
+{
+    std::vector<int> tiles;
+    for (int t = 0; t < ld->max_tiles; t++)
+        if (ld->added[t])
+            tiles.push_back(t);
+    return tiles;
+}
+
+// The rows of the label array as it stands (class representatives, or the cluster roots of lane_near.inc, with
+// the members counted at them), over the tiles in d_tidx: the table is cleared and keyed by (label, tile),
+// k_ld_classes / k_ld_span_count / k_ld_span_sum add to the counters, which come down and are summed.  PF per
+// tile is what the counters hold (k_ld_resolve's).  Synchronises the stream.
+int ld_count_rows(wd_lane_dups *ld, const std::vector<int> &tiles, int64_t *lane_row, int64_t *tile_rows)
+{
+    wd_ctx *ctx = ld->ctx;
+    const int64_t N = ld->N;
+    const int T = ld->max_tiles;
+    const LdLayout &lay = ld->lay;
+    uint8_t *ws = ld->ws;
+    unsigned long long *cnt_t = (unsigned long long *)(ws + lay.cnt_t);
+    unsigned long long *cnt_l = (unsigned long long *)(ws + lay.cnt_l);
+    std::vector<unsigned long long> h_t((size_t)T * kSpread * kLdTileCnt, 0), h_l((size_t)kSpread * kLdLaneCnt, 0);
+    if (!tiles.empty()) {
+        int *d_tidx = (int *)(ws + lay.tidx);
+        unsigned long long *table = (unsigned long long *)(ws + lay.table);
+        unsigned long long *aux = (unsigned long long *)(ws + lay.aux);
+        uint32_t *label = (uint32_t *)(ws + lay.label);
+        uint32_t *members = (uint32_t *)(ws + lay.members);
+        const unsigned long long slot_mask = lay.slots - 1;
+        const dim3 wgrid((unsigned)((N + kTdBlock - 1) / kTdBlock), (unsigned)tiles.size());
+        WD_HIP(ctx, hipMemsetAsync(table, 0xFF, lay.slots * 8, ctx->stream));        // the second table: every slot free
+        hipLaunchKernelGGL(k_ld_classes, wgrid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, label, members, aux, table,
+                           slot_mask, cnt_t, cnt_l);
+        hipLaunchKernelGGL(k_ld_span_count, wgrid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, aux, table);
+        hipLaunchKernelGGL(k_ld_span_sum, wgrid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, aux, table, label, members,
+                           cnt_t, cnt_l);
+        WD_HIP(ctx, hipGetLastError());
+        WD_HIP(ctx, hipMemcpyAsync(h_t.data(), cnt_t, h_t.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        WD_HIP(ctx, hipMemcpyAsync(h_l.data(), cnt_l, h_l.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+
+    memset(lane_row, 0, WD_LANEDUPS_LANE_COLS * sizeof(int64_t));
+    for (int t = 0; t < T; t++) {
+        unsigned long long c[kLdTileCnt];
+        sum_spread(h_t.data(), (size_t)t, kLdTileCnt, c);
+        int64_t *o = tile_rows + (size_t)t * WD_LANEDUPS_TILE_COLS;
+        o[0] = (int64_t)c[kLdPf];
+        o[1] = (int64_t)c[kLdInLane];
+        o[2] = (int64_t)c[kLdInTile];
+        o[3] = (int64_t)c[kLdTileRed];
+        o[4] = (int64_t)c[kLdLaneRed];
+        lane_row[0] += o[0];
+        lane_row[2] += o[1];
+    }
+    unsigned long long c[kLdLaneCnt];
+    sum_spread(h_l.data(), 0, kLdLaneCnt, c);
+    lane_row[1] = (int64_t)c[kLdClasses];
+    lane_row[4] = (int64_t)c[kLdCross];
+    lane_row[5] = (int64_t)c[kLdSpans];
+    for (int b = 0; b < kBins; b++)
+        lane_row[6 + b] = (int64_t)c[kLdBins + b];
+    lane_row[3] = lane_row[2] - lane_row[1];
+    return WD_OK;
+}
+
+// labels_dev[t] = the label array's part of tile index t (all ones for an index never added); not synchronised
+int ld_copy_labels(wd_lane_dups *ld, uint32_t *const *labels_dev, bool added_too)
+{
+    wd_ctx *ctx = ld->ctx;
+    const size_t bytes = (size_t)ld->N * 4;
+    const uint32_t *label = (const uint32_t *)(ld->ws + ld->lay.label);
+    if (labels_dev && bytes)
+        for (int t = 0; t < ld->max_tiles; t++) {
+            if (!labels_dev[t])
+                continue;
+            if (!ld->added[t])                                         // a tile index never added has no PF well
+                WD_HIP(ctx, hipMemsetAsync(labels_dev[t], 0xFF, bytes, ctx->stream));
+            else if (added_too)
+                WD_HIP(ctx, hipMemcpyAsync(labels_dev[t], label + (size_t)t * ld->N, bytes, hipMemcpyDeviceToDevice,
+                                           ctx->stream));
+        }
+    return WD_OK;
+}
+
+// The classes of the lane: rows to host memory, labels to labels_dev (checked by the caller).  The first call
+// resolves the table (k_ld_resolve: from then on the label array holds the class representatives) and keeps the
+// rows; a later one - lane_near.inc calls again after a refusal - delivers the same rows and labels from them.
+int ld_equality(wd_lane_dups *ld, int64_t *lane_row, int64_t *tile_rows, uint32_t *const *labels_dev)
+{
+    wd_ctx *ctx = ld->ctx;
+    const int64_t N = ld->N;
+    const int T = ld->max_tiles;
+    const size_t lane_bytes = WD_LANEDUPS_LANE_COLS * sizeof(int64_t);
+    const size_t tile_bytes = (size_t)T * WD_LANEDUPS_TILE_COLS * sizeof(int64_t);
+    memset(lane_row, 0, lane_bytes);
+    memset(tile_rows, 0, tile_bytes);
+    if (N == 0 || T == 0)
+        return WD_OK;
+    if (bind_device(ctx))
+        return WD_ERR_HIP;
+    if (ld->resolved) {
+        memcpy(lane_row, ld->eq_lane.data(), lane_bytes);
+        memcpy(tile_rows, ld->eq_tiles.data(), tile_bytes);
+        if (const int rc = ld_copy_labels(ld, labels_dev, true))
+            return rc;
+        WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return WD_OK;
+    }
+    if (const int rc = ld_copy_labels(ld, labels_dev, false))
+        return rc;
+    const std::vector<int> tiles = ld_tiles_added(ld);
+    const LdLayout &lay = ld->lay;
+    uint8_t *ws = ld->ws;
+    if (!tiles.empty()) {
+        uint32_t **d_lbl = (uint32_t **)(ws + lay.lbl);
+        int *d_tidx = (int *)(ws + lay.tidx);
+        if (labels_dev)
+            WD_HIP(ctx, hipMemcpyAsync(d_lbl, labels_dev, T * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
+        WD_HIP(ctx, hipMemcpyAsync(d_tidx, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        const dim3 wgrid((unsigned)((N + kTdBlock - 1) / kTdBlock), (unsigned)tiles.size());
+        hipLaunchKernelGGL(k_ld_resolve, wgrid, dim3(kTdBlock), 0, ctx->stream, (unsigned long long *)(ws + lay.table),
+                           d_tidx, N, (unsigned long long *)(ws + lay.aux), (uint32_t *)(ws + lay.label),
+                           (uint32_t *)(ws + lay.members), labels_dev ? d_lbl : nullptr,
+                           (unsigned long long *)(ws + lay.cnt_t));
+    }
+    if (const int rc = ld_count_rows(ld, tiles, lane_row, tile_rows))
+        return rc;
+    ld->eq_lane.assign(lane_row, lane_row + WD_LANEDUPS_LANE_COLS);
+    ld->eq_tiles.assign(tile_rows, tile_rows + (size_t)T * WD_LANEDUPS_TILE_COLS);
+    ld->resolved = true;
+    return WD_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -440,6 +591,7 @@ try {
     ld->fp_mask = hash_bits == 0 ? ~0ull : (1ull << hash_bits) - 1;
     ld->added.assign((size_t)max_tiles, 0);
     ld->finished = false;
+    ld->resolved = false;
     hipError_t e = hipMemsetAsync(ld->ws + ld->lay.cnt_t, 0, ld->lay.planes - ld->lay.cnt_t, ctx->stream);      // counters
     if (e == hipSuccess)
         e = hipMemsetAsync(ld->ws + ld->lay.table, 0xFF, ld->lay.slots * 8, ctx->stream);                       // every slot free
@@ -461,7 +613,7 @@ try {
     wd_ctx *ctx = ld->ctx;
     const int L = ld->L;
     const int64_t N = ld->N;
-    if (ld->finished)
+    if (ld->finished || ld->resolved)                                  // (resolved: a near finish was refused)
         return fail(ctx, WD_ERR_ARG, "lane duplicates: add after finish");
     if (ctx->well_stride != 1)
         return fail(ctx, WD_ERR_ARG, "lane duplicates read a plane per cycle (well_stride 1)");
@@ -521,79 +673,10 @@ try {
     wd_ctx *ctx = ld->ctx;
     if (ld->finished)
         return fail(ctx, WD_ERR_ARG, "lane duplicates: finish is called once");
-    const int64_t N = ld->N;
-    const int T = ld->max_tiles;
-    if (labels_dev)
-        for (int t = 0; t < T; t++)
-            if (labels_dev[t] && N > 0 && !on_device(labels_dev[t]))
-                return fail(ctx, WD_ERR_ARG, "lane duplicates: labels must be in device memory");
+    if (const int rc = ld_check_labels(ld, labels_dev))
+        return rc;
     ld->finished = true;
-    memset(lane_row, 0, WD_LANEDUPS_LANE_COLS * sizeof(int64_t));
-    memset(tile_rows, 0, (size_t)T * WD_LANEDUPS_TILE_COLS * sizeof(int64_t));
-    std::vector<int> tiles;
-    for (int t = 0; t < T; t++)
-        if (ld->added[t])
-            tiles.push_back(t);
-    if (N == 0 || T == 0)
-        return WD_OK;
-    if (bind_device(ctx))
-        return WD_ERR_HIP;
-    if (labels_dev)                                 // a tile index never added has no PF well
-        for (int t = 0; t < T; t++)
-            if (labels_dev[t] && !ld->added[t])
-                WD_HIP(ctx, hipMemsetAsync(labels_dev[t], 0xFF, (size_t)N * 4, ctx->stream));
-    const LdLayout &lay = ld->lay;
-    uint8_t *ws = ld->ws;
-    unsigned long long *cnt_t = (unsigned long long *)(ws + lay.cnt_t);
-    unsigned long long *cnt_l = (unsigned long long *)(ws + lay.cnt_l);
-    std::vector<unsigned long long> h_t((size_t)T * kSpread * kLdTileCnt, 0), h_l((size_t)kSpread * kLdLaneCnt, 0);
-    if (!tiles.empty()) {
-        uint32_t **d_lbl = (uint32_t **)(ws + lay.lbl);
-        int *d_tidx = (int *)(ws + lay.tidx);
-        unsigned long long *table = (unsigned long long *)(ws + lay.table);
-        unsigned long long *aux = (unsigned long long *)(ws + lay.aux);
-        uint32_t *label = (uint32_t *)(ws + lay.label);
-        uint32_t *members = (uint32_t *)(ws + lay.members);
-        const unsigned long long slot_mask = lay.slots - 1;
-        if (labels_dev)
-            WD_HIP(ctx, hipMemcpyAsync(d_lbl, labels_dev, T * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
-        WD_HIP(ctx, hipMemcpyAsync(d_tidx, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        const dim3 wgrid((unsigned)((N + kTdBlock - 1) / kTdBlock), (unsigned)tiles.size());
-        hipLaunchKernelGGL(k_ld_resolve, wgrid, dim3(kTdBlock), 0, ctx->stream, table, d_tidx, N, aux, label, members,
-                           labels_dev ? d_lbl : nullptr, cnt_t);
-        WD_HIP(ctx, hipMemsetAsync(table, 0xFF, lay.slots * 8, ctx->stream));        // the second table: every slot free
-        hipLaunchKernelGGL(k_ld_classes, wgrid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, label, members, aux, table,
-                           slot_mask, cnt_t, cnt_l);
-        hipLaunchKernelGGL(k_ld_span_count, wgrid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, aux, table);
-        hipLaunchKernelGGL(k_ld_span_sum, wgrid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, aux, table, label, members,
-                           cnt_t, cnt_l);
-        WD_HIP(ctx, hipGetLastError());
-        WD_HIP(ctx, hipMemcpyAsync(h_t.data(), cnt_t, h_t.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        WD_HIP(ctx, hipMemcpyAsync(h_l.data(), cnt_l, h_l.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-
-    for (int t = 0; t < T; t++) {
-        unsigned long long c[kLdTileCnt];
-        sum_spread(h_t.data(), (size_t)t, kLdTileCnt, c);
-        int64_t *o = tile_rows + (size_t)t * WD_LANEDUPS_TILE_COLS;
-        o[0] = (int64_t)c[kLdPf];
-        o[1] = (int64_t)c[kLdInLane];
-        o[2] = (int64_t)c[kLdInTile];
-        o[3] = (int64_t)c[kLdTileRed];
-        o[4] = (int64_t)c[kLdLaneRed];
-        lane_row[0] += o[0];
-        lane_row[2] += o[1];
-    }
-    unsigned long long c[kLdLaneCnt];
-    sum_spread(h_l.data(), 0, kLdLaneCnt, c);
-    lane_row[1] = (int64_t)c[kLdClasses];
-    lane_row[4] = (int64_t)c[kLdCross];
-    lane_row[5] = (int64_t)c[kLdSpans];
-    for (int b = 0; b < kBins; b++)
-        lane_row[6 + b] = (int64_t)c[kLdBins + b];
-    lane_row[3] = lane_row[2] - lane_row[1];
-    return WD_OK;
+    return ld_equality(ld, lane_row, tile_rows, labels_dev);
 } WD_CATCH
 
 void wd_lane_dups_end(wd_lane_dups *ld)

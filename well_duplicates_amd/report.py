@@ -537,3 +537,57 @@ def write_lane_dups(lane, counts: LaneDupCounts, verbose: bool = False, out=None
     size = c.library_size()
     print("Estimated library size (distinct/X = 1 - exp(-PF/X)): %s" % ("n/a" if size is None else "%.0f" % size),
           file=out)
+
+
+LANE_NEAR_ROW_COLS = LANE_ROW_COLS + 1
+
+
+@dataclass
+class LaneNearCounts(LaneDupCounts):
+    """Near-duplicate read clusters across all tiles of a lane (include/welldup_lanenear.h): LaneDupCounts with
+    "class" read as "cluster" (classes = Clusters, in_classes = InClusters, cross_tile_classes =
+    CrossTileClusters), and the pairs of distinct reads of the lane within the distance."""
+    near_pairs: int = 0
+
+    @classmethod
+    def from_rows(cls, lane_row: Sequence[int], tile_rows: Sequence[Sequence[int]], tile_names: Sequence) -> "LaneNearCounts":
+        """lane_row (NearPairs in front of the size bins) and tile_rows as LaneDups.finish(hamming=K) returns them"""
+        b = [int(v) for v in lane_row]
+        assert len(b) == LANE_NEAR_ROW_COLS
+        base = LaneDupCounts.from_rows(b[:6] + b[7:], tile_rows, tile_names)
+        return cls(base.pf, base.classes, base.in_classes, base.redundant, base.cross_tile_classes, base.tile_spans,
+                   base.sizes, base.tiles, b[6])
+
+    def to_rows(self):
+        lane, tiles = LaneDupCounts.to_rows(self)
+        return lane[:6] + [self.near_pairs] + lane[6:], tiles
+
+
+def write_lane_near_dups(lane, k: int, counts: LaneNearCounts, verbose: bool = False, out=None,
+                         equal: Optional[LaneDupCounts] = None) -> None:
+    """The block that follows a lane's --lane-dups block under --lane-dups-hamming K, of the same shape, for the
+    clusters at Hamming distance <= K.  equal: the lane's classes, whose duplication is printed beside that of the
+    clusters."""
+    out = out or sys.stdout
+    c = counts
+    print(file=out)
+    if verbose:
+        for tile in sorted(c.tiles):
+            t = c.tiles[tile]
+            print("LaneNearDups: %s\tTile: %s\tHamming: %i\tPF wells: %i\tInLane: %i\tInTile: %i\tTileRedundant: %i\t"
+                  "LaneRedundant: %i" % (lane, tile, k, t[0], t[1], t[2], t[3], t[4]), file=out)
+    print("LaneNearDupsSummary: %s\tTiles: %i\tHamming: %i\tPF wells: %i\tClusters: %i\tInClusters: %i (%.5f)\t"
+          "Redundant: %i (%.5f)\tCrossTileClusters: %i\tTileSpans: %i\tNearPairs: %i" % (
+              lane, len(c.tiles), k, c.pf, c.classes, c.in_classes, c.in_classes / c.pf if c.pf else 0.0, c.redundant,
+              c.redundant / c.pf if c.pf else 0.0, c.cross_tile_classes, c.tile_spans, c.near_pairs), file=out)
+    print("ClusterSizes: %s" % "\t".join("%s: %i" % (name, n) for name, n in zip(CLASS_BIN_NAMES, c.sizes)), file=out)
+    share = lambda v: v / c.redundant if c.redundant else 0.0
+    print("Redundant within tiles: %i (%.5f of Redundant)\tacross tiles: %i (%.5f of Redundant)" % (
+        c.within_tiles, share(c.within_tiles), c.across_tiles, share(c.across_tiles)), file=out)
+    line = "Lane duplication at Hamming <= {} (Redundant/PF wells): {:.2%}".format(k, c.lane_duplication())
+    if equal is not None:
+        line += "\tby equality: {:.2%}".format(equal.lane_duplication())
+    print(line, file=out)
+    size = c.library_size()
+    print("Estimated library size (distinct/X = 1 - exp(-PF/X)): %s" % ("n/a" if size is None else "%.0f" % size),
+          file=out)

@@ -310,6 +310,11 @@ class Scanner:
         (wd_lane_dups_workspace; a lane of 2^32 - 1 wells or more raises RuntimeError)."""
         return self._workspace_bytes(self._lib.wd_lane_dups_workspace, n_clusters, max_tiles, L)
 
+    def lane_near_scratch_bytes(self, n_clusters: int, max_tiles: int, L: int, k: int) -> int:
+        """Device bytes LaneDups.finish(hamming=k) needs beside the accumulator's workspace
+        (wd_lane_near_dups_scratch; 0 for k = 0)."""
+        return self._workspace_bytes(self._lib.wd_lane_near_dups_scratch, n_clusters, max_tiles, L, k)
+
     def scan_async(self, tables, n_tiles: int, L: int, n_clusters: int, mode: int, k: int,
                    out_tile_dev: int, out_per_target_dev: Optional[int] = None):
         pt, ft = tables
@@ -503,7 +508,8 @@ class LaneDups:
         self.N, self.max_tiles, self.L, self.hash_bits = int(n_clusters), int(max_tiles), int(L), int(hash_bits)
         self.ws_bytes = scanner.lane_dups_workspace_bytes(self.N, self.max_tiles, self.L)
         self.d_ws = scanner.malloc(self.ws_bytes)
-        self.d_labels = 0
+        self.d_labels = self.d_near_labels = 0
+        self.refused = None
         self._h = None
         try:
             self._begin(self.d_ws, self.ws_bytes)
@@ -544,26 +550,52 @@ class LaneDups:
         finally:
             self.sc.set_option("well_stride", 1)
 
-    def finish(self, labels: bool = False):
+    def _label_table(self, attr: str):
+        lbl_bytes = 4 * self.N * self.max_tiles
+        if not getattr(self, attr):
+            setattr(self, attr, self.sc.malloc(max(1, lbl_bytes)))
+        base = getattr(self, attr)
+        return (ctypes.c_void_p * max(1, self.max_tiles))(*[base + 4 * self.N * i for i in range(self.max_tiles)])
+
+    def finish(self, labels: bool = False, hamming: int = 0, pair_budget: int = 0):
         """Once.  -> (lane row int64 [14]: [PF, Classes, InClasses, Redundant, CrossTileClasses, TileSpans, size
         bins 2..8, 9+], tile rows int64 [max_tiles, 5]: [PF, InLane, InTile, TileRedundant, LaneRedundant],
-        labels uint32 [max_tiles, N] or None)."""
+        labels uint32 [max_tiles, N] or None).
+        With hamming = K > 0 (wd_lane_near_dups_finish, include/welldup_lanenear.h) three more follow, for the
+        clusters at Hamming distance <= K: near lane row int64 [15] (NearPairs before the size bins), near tile rows
+        and near labels.  The scratch is allocated for the call and released.  A lane with more candidate pairs in
+        a segment than pair_budget (0 = the default) raises RuntimeError: `refused` then holds the equality
+        results, which are valid, and finish may be called again."""
         if self._h is None:
             raise ValueError("the accumulator is closed")
+        if hamming == 0 and pair_budget:
+            raise ValueError("a pair budget needs hamming > 0")
         lane_row = np.zeros(_lib.LANEDUPS_LANE_COLS, dtype=np.int64)
         tile_rows = np.zeros((self.max_tiles, _lib.LANEDUPS_TILE_COLS), dtype=np.int64)
-        lt = None
         lbl_bytes = 4 * self.N * self.max_tiles
-        if labels:
-            if not self.d_labels:
-                self.d_labels = self.sc.malloc(max(1, lbl_bytes))
-            lt = (ctypes.c_void_p * max(1, self.max_tiles))(*[self.d_labels + 4 * self.N * i for i in range(self.max_tiles)])
-        self.sc._ck(self.sc._lib.wd_lane_dups_finish(self._h, lane_row.ctypes.data_as(ctypes.c_void_p),
-                                                     tile_rows.ctypes.data_as(ctypes.c_void_p), lt))
-        lab = None
-        if labels:
-            lab = self.sc.d2h(self.d_labels, lbl_bytes, np.uint32).reshape(self.max_tiles, self.N)
-        return lane_row, tile_rows, lab
+        lt = self._label_table("d_labels") if labels else None
+        fetch = lambda ptr: self.sc.d2h(ptr, lbl_bytes, np.uint32).reshape(self.max_tiles, self.N) if labels else None
+        if hamming == 0:
+            self.sc._ck(self.sc._lib.wd_lane_dups_finish(self._h, lane_row.ctypes.data_as(ctypes.c_void_p),
+                                                         tile_rows.ctypes.data_as(ctypes.c_void_p), lt))
+            return lane_row, tile_rows, fetch(self.d_labels)
+        near_lane = np.zeros(_lib.LANENEAR_LANE_COLS, dtype=np.int64)
+        near_tiles = np.zeros((self.max_tiles, _lib.LANEDUPS_TILE_COLS), dtype=np.int64)
+        nlt = self._label_table("d_near_labels") if labels else None
+        self.refused = None
+        sbytes = self.sc.lane_near_scratch_bytes(self.N, self.max_tiles, self.L, hamming)     # (a bad K raises here)
+        d_scratch = self.sc.malloc(max(1, sbytes))
+        try:
+            rc = self.sc._lib.wd_lane_near_dups_finish(
+                self._h, int(hamming), ctypes.c_void_p(d_scratch), sbytes, int(pair_budget),
+                lane_row.ctypes.data_as(ctypes.c_void_p), tile_rows.ctypes.data_as(ctypes.c_void_p), lt,
+                near_lane.ctypes.data_as(ctypes.c_void_p), near_tiles.ctypes.data_as(ctypes.c_void_p), nlt)
+            if rc == _lib.ERR_UNSUPPORTED:
+                self.refused = (lane_row, tile_rows, fetch(self.d_labels))
+            self.sc._ck(rc)
+        finally:
+            self.sc.free(d_scratch)
+        return lane_row, tile_rows, fetch(self.d_labels), near_lane, near_tiles, fetch(self.d_near_labels)
 
     def _end(self):
         if self._h is not None:
@@ -573,10 +605,10 @@ class LaneDups:
     def close(self):
         """Drops the lane, finished or not, and frees the workspace."""
         self._end()
-        for ptr in (self.d_ws, self.d_labels):
+        for ptr in (self.d_ws, self.d_labels, self.d_near_labels):
             if ptr:
                 self.sc.free(ptr)
-        self.d_ws = self.d_labels = 0
+        self.d_ws = self.d_labels = self.d_near_labels = 0
 
 
 class TileBatch:
