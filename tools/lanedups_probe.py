@@ -14,11 +14,17 @@ clusters of the lane, include/welldup_lanenear.h - beside the equality finish, a
 same K beside tile_dups on every batch: the near finish less the equality finish is held against tile_near_dups
 less tile_dups.  `--heavy M` adds a lane of four tiles with M distinct reads in all that share their first segment
 (one bucket, M (M - 1) / 2 candidate pairs: the pair rate on packed rows).
+`--index I [--libraries M]` times the lane's duplication per index read (include/welldup_laneindex.h): the lane is
+streamed again into an accumulator with an index part of I cycles, once per case - M libraries of equal size, one
+library (every counter on one row: the hottest case), and uniform random index reads (the most groups) - and
+LaneDups.index_add per tile and LaneDups.index_finish are printed beside the equality add and finish on the same
+batches.
 For per-kernel times run it under
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/lanedups_probe.py
 
-(the k_ld_* rows of the stats are this stage, k_td_* the per-tile classes, k_dense_* the scan)."""
+(the k_ld_* rows of the stats are this stage, k_li_* the index part, k_td_* the per-tile classes, k_dense_* the
+scan)."""
 import argparse
 import os
 import sys
@@ -43,6 +49,8 @@ ap.add_argument("--equal", action="store_true", help="also time a lane of three 
 ap.add_argument("--hamming", type=int, default=0, metavar="K", help="also time the near finish at Hamming distance <= K")
 ap.add_argument("--heavy", type=int, default=0, metavar="M",
                 help="also time a lane of M distinct reads that share their first segment (needs --hamming)")
+ap.add_argument("--index", type=int, default=0, metavar="I", help="also time the index part with I index cycles (1..20)")
+ap.add_argument("--libraries", type=int, default=96, metavar="M", help="libraries of the pooled lane (with --index)")
 a = ap.parse_args()
 
 n = a.rows * a.cols
@@ -172,6 +180,45 @@ if a.heavy and a.hamming:
     print("heavy: %d distinct reads on four tiles share cycles 0..%d: %d candidate pairs; finish %.3f ms, near finish "
           "%.3f ms: %.3g pairs per second" % (4 * m4, head - 1, pairs, times[2], times[3], pairs / (dt * 1e-3)))
     four.free()
+
+if a.index:
+    I = a.index
+    iws = sc.lane_index_workspace_bytes(n, a.tiles, I)
+    print("index part: %d index cycles, workspace %.2f GB" % (I, iws / 1e9))
+    rng = np.random.default_rng(11)
+    tb, itb = TileBatch(sc, a.batch, a.cycles, n), TileBatch(sc, a.batch, I, n)
+    for name, m in (("%d libraries of equal size" % a.libraries, a.libraries), ("one library", 1), ("random index reads", 0)):
+        lib = rng.integers(1, 256, (max(1, m), I)).astype(np.uint8)
+        li = LaneDups(sc, n, a.tiles, a.cycles)
+        li.index_begin(I)
+        i_add = i_iadd = 0.0
+        for tiles in batches:
+            if len(tiles) != tb.n_tiles:
+                tb, itb = TileBatch(sc, len(tiles), a.cycles, n, reuse=tb), TileBatch(sc, len(tiles), I, n, reuse=itb)
+            fill(tb, tiles)
+            for s_ in range(len(tiles)):
+                reads = lib[rng.integers(0, m, n)] if m else rng.integers(1, 256, (n, I)).astype(np.uint8)
+                for c in range(I):
+                    sc.h2d(itb.plane_ptr(s_, c), np.ascontiguousarray(reads[:, c]))
+            _, dt = clock(lambda: li.add(tb, tiles))
+            i_add += dt
+            _, dt = clock(lambda: li.index_add(itb, tiles))
+            i_iadd += dt
+        (ilane, _, _), i_fin = clock(lambda: li.finish())
+        pf = int(ilane[0])
+        (irow, other, rows, _), i_ifin = clock(lambda: li.index_finish(max(1, -(-pf // 1000)), 1001))
+        _, i_again = clock(lambda: li.index_finish(max(1, -(-pf // 1000)), 1001))
+        li.close()
+        assert rows[:, 0].sum() + other[0] == pf and (ilane[:4] == lane[:4]).all(), "the index rows do not add up"
+        print("%s: %d groups, %d listed, %d mixed classes of %d" % (name, irow[0], irow[1], irow[3], ilane[1]))
+        print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("lane_dups add", i_add, i_add / k))
+        print("  %-22s %9.3f ms  (%.4f ms per tile; add x I / L = %.4f)" % ("index_add", i_iadd, i_iadd / k,
+                                                                          i_add / k * I / a.cycles))
+        print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("lane_dups finish", i_fin, i_fin / k))
+        print("  %-22s %9.3f ms  (%.4f ms per tile; again, the listing only: %.3f ms)" % ("index_finish", i_ifin, i_ifin / k,
+                                                                                        i_again))
+    tb.free()
+    itb.free()
 
 if a.equal:
     three = TileBatch(sc, 3, a.cycles, n)

@@ -138,6 +138,17 @@ LANENEAR_PROTOTYPES = {
 LANENEAR_MAX_K = TILENEAR_MAX_K
 LANENEAR_LANE_COLS = 7 + DUPSET_SIZE_BINS
 
+# name -> (restype, argtypes); every symbol include/welldup_laneindex.h declares beyond the six above
+LANEINDEX_PROTOTYPES = {
+    "wd_lane_index_workspace": (_i, [_i64, _i, _i, ctypes.POINTER(_sz)]),
+    "wd_lane_index_begin": (_i, [_vp, _i, _vp, _sz]),
+    "wd_lane_index_add": (_i, [_vp, _i, ctypes.POINTER(_i), _pp]),
+    "wd_lane_index_finish": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(_i64)]),
+}
+LANEINDEX_MAX_CYCLES = 20
+LANEINDEX_GROUP_COLS = 5
+LANEINDEX_LANE_COLS = 5
+
 _lib = None
 
 
@@ -224,7 +235,7 @@ def unit_of_kernel(kernel: str) -> str:
         return "ingest"
     if kernel.startswith("k_sets"):
         return "sets"
-    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_")):
+    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_")):
         return "tiledups"
     return "scan"
 
@@ -284,7 +295,8 @@ def load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the scan path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     for name, (res, args) in list(PROTOTYPES.items()) + list(SETS_PROTOTYPES.items()) + list(TILEDUPS_PROTOTYPES.items()) + \
-            list(TILENEAR_PROTOTYPES.items()) + list(LANEDUPS_PROTOTYPES.items()) + list(LANENEAR_PROTOTYPES.items()):
+            list(TILENEAR_PROTOTYPES.items()) + list(LANEDUPS_PROTOTYPES.items()) + list(LANENEAR_PROTOTYPES.items()) + \
+            list(LANEINDEX_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

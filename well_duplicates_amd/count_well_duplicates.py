@@ -32,12 +32,15 @@ Differences from the reference, all deliberate:
   * --all-wells --lane-dups groups the PF wells of a whole lane into classes of equal reads, on whatever tiles they
     lie (a LaneDups accumulator is fed every batch before its buffers are reused), and closes each lane's output
     with the duplication of the lane, split into the part within tiles and the part across tiles, and the
-    library size it lets one estimate (report.write_lane_dups);
+    library size it lets one estimate (report.write_lane_dups); --lane-dups-index RANGES groups the lane's PF wells
+    by the bases of the index cycles as well - the libraries of a pooled lane - and adds the duplication and the
+    library size of each, and the classes that span more than one index read (report.write_lane_index_dups);
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
 from __future__ import annotations
 
+import math
 import os
 import sys
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
@@ -179,6 +182,19 @@ def parse_args(argv=None):
                    help="with --lane-dups-hamming: the most candidate pairs one segment of a lane may have before the "
                         "run is refused (reads of low diversity); 0 = the library's default, max(16 x the lane's "
                         "wells, 2^24)")
+    p.add_argument("--lane-dups-index", default=None, metavar="RANGES",
+                   help="with --lane-dups: the index cycles of the run, as --cycles takes them (eg. 151-159,159-167; "
+                        "%d cycles at most).  The PF wells of a lane are grouped by the bases of these cycles - its "
+                        "libraries, found without a sample sheet - and a third block gives, per library, its share "
+                        "of the lane, the redundant wells inside it, the library size estimated from them and the wells "
+                        "whose class reaches into another library; then the redundancy within and across libraries "
+                        "and the classes that span more than one (index hopping, cross-contamination).  With "
+                        "--lane-dups-hamming the block is computed on the clusters; --lane-dups-out gains an index "
+                        "column" % _lib.LANEINDEX_MAX_CYCLES)
+    p.add_argument("--lane-dups-index-min-share", type=float, default=0.001, metavar="F",
+                   help="with --lane-dups-index: an index read is listed as a library when it holds at least this "
+                        "share of the lane's PF wells, in (0, 1]; all others (reads with a sequencing error in the "
+                        "index, mostly) are summed into one Other line")
     args = p.parse_args(argv)
     if not args.coord_file and not args.all_wells:
         p.error("the following arguments are required: -f/--coord_file (or --all-wells)")
@@ -216,6 +232,20 @@ def parse_args(argv=None):
         p.error("--lane-dups-pair-budget must not be negative")
     if args.lane_dups_pair_budget and args.lane_dups_hamming is None:
         p.error("--lane-dups-pair-budget needs --lane-dups-hamming")
+    if args.lane_dups_index is not None and not args.lane_dups:
+        p.error("--lane-dups-index needs --lane-dups")
+    if args.lane_dups_index is not None:
+        try:
+            ranges = workload.parse_cycles(0, 0, args.lane_dups_index)
+        except ValueError:
+            ranges = [(0, 0)]
+        if any(not 0 <= a < b for a, b in ranges):
+            p.error("--lane-dups-index takes ranges of cycles as --cycles does, eg. 151-159,159-167")
+        n_index = sum(b - a for a, b in ranges)
+        if not 1 <= n_index <= _lib.LANEINDEX_MAX_CYCLES:
+            p.error("--lane-dups-index takes 1..%d cycles, not %d" % (_lib.LANEINDEX_MAX_CYCLES, n_index))
+    if not 0.0 < args.lane_dups_index_min_share <= 1.0:
+        p.error("--lane-dups-index-min-share takes a share in (0, 1], not %g" % args.lane_dups_index_min_share)
     if args.lane_dups and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         p.error("--lane-dups runs in a single process only: under WORLD_SIZE > 1 a lane's tiles are spread over the "
                 "ranks, and the classes of a lane need all of them in one GPU's table")
@@ -324,20 +354,28 @@ def lane_cluster_members(class_labels: np.ndarray, cluster_labels: np.ndarray):
     return ti, w, lab // class_labels.shape[1], lab % class_labels.shape[1], cti, cw
 
 
-def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0):
-    """--lane-dups: the accumulator's workspace - with --lane-dups-hamming plus the scratch of the near finish -
-    against the free device memory, before anything is loaded."""
-    need += scratch
+def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0, index: int = 0):
+    """--lane-dups: the accumulator's workspace - with --lane-dups-hamming plus the scratch of the near finish, with
+    --lane-dups-index plus the index workspace - against the free device memory, before anything is loaded."""
+    need += scratch + index
     if need > free:
         raise MemoryError("--lane-dups needs %.2f GB of device memory for a lane of %d tiles x %d wells x %d cycles "
-                          "(%d bytes%s), and %.2f GB (%d bytes) are free" % (
+                          "(%d bytes%s%s), and %.2f GB (%d bytes) are free" % (
                               need / 1e9, tiles, wells, cycles, need,
-                              ", %d of them for --lane-dups-hamming" % scratch if scratch else "", free / 1e9, free))
+                              ", %d of them for --lane-dups-hamming" % scratch if scratch else "",
+                              ", %d of them for --lane-dups-index" % index if index else "", free / 1e9, free))
+
+
+def index_listing(min_share: float, pf: int):
+    """--lane-dups-index-min-share F and a lane's PF wells -> (min_pf, cap) of LaneDups.index_finish: a group is
+    listed from ceil(F x PF) wells on, and no more than floor(1 / F) groups can each hold a share F of the reads."""
+    return max(1, int(math.ceil(min_share * pf))), int(math.floor(1.0 / min_share)) + 1
 
 
 def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells, tile_batch,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
-               dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0, lane_near=0, lane_pair_budget=0):
+               dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0, lane_near=0, lane_pair_budget=0,
+               lane_index=None):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
@@ -353,6 +391,11 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     in the lane's list.
     lane_near = K > 0 (with lane_dups): and the lane's clusters at Hamming distance <= K (LaneDups.finish(hamming=K)):
     into["lnear"][lane] = LaneNearCounts, and into["lmembers"][lane] = (names,) + lane_cluster_members(...).
+    lane_index = (index cycles, cycles per index range, min share) (with lane_dups): every batch gets a second
+    TileBatch of the index cycles, whose files are appended to the batch's job list - one call loads both, through
+    the GPU decoder and the .cbcl path alike - and which is fed to LaneDups.index_add, reused and released with the
+    scan batch; after the lane's finish into["lindex"][lane] = LaneIndexCounts (on the clusters under lane_near), and
+    with the members into["lmindex"][lane] = the index read of every row of into["lmembers"][lane].
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -365,6 +408,8 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     """
     centre, lvl_off, nbr = csr
     levels = lvl_off.shape[1] - 1
+    index_cycles, index_lengths, index_share = lane_index if lane_index else ([], [], 1.0)
+    assert not index_cycles or (lane_dups and interleave == 1)
     counts, logs = (into["counts"], into["logs"]) if into else ({}, {})
     batches = []                            # (lane, [tiles]), never across a lane's end: an error stays its lane's (start_ahead)
     for lane, tiles in lane_tiles:
@@ -383,7 +428,7 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                     room = 700
             except (OSError, IndexError, RuntimeError, AssertionError):
                 pass                            # (whatever is wrong with the first tile is reported when it is loaded)
-            per = max(1, room // max(1, len(cycle_list) + 1))
+            per = max(1, room // max(1, len(cycle_list) + len(index_cycles) + 1))
             n_batches = max(1, -(-len(tiles) // per))
             tb_n = max(1, -(-len(tiles) // n_batches))
         batches += [(lane, tiles[b0:b0 + tb_n]) for b0 in range(0, len(tiles), tb_n)]
@@ -393,6 +438,7 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     lane_acc = {"ld": None, "lane": None}   # the LaneDups of the lane being scanned
     tiles_of_lane = {lane: list(tiles) for lane, tiles in lane_tiles}
     spare = []                              # finished ones whose buffers the next batch takes over
+    index_tb, index_spare = {}, []          # id(scan batch) -> its batch of index cycles; finished ones
 
     def start(batch):
         """Submit every load of a batch; returns at once."""
@@ -411,12 +457,19 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
         tb = TileBatch(sc, len(chunk), len(cycle_list), n_clusters, interleave=interleave,
                        reuse=spare.pop() if spare else None)
         live.append(tb)
+        if index_cycles:
+            index_tb[id(tb)] = TileBatch(sc, len(chunk), len(index_cycles), n_clusters,
+                                         reuse=index_spare.pop() if index_spare else None)
         _lap("  batch of %d tiles: buffers" % len(chunk))
         # ingest: every (tile, cycle) file is gunzipped into pinned memory and copied to the GPU
         # by libwelldup (wd_load_bcl_gz).  Runs without .bcl.gz files are NovaSeq runs: the
         # tile's block of the lane/surface .cbcl is gunzipped on the host and expanded on the
         # GPU (wd_load_cbcl_tile), which needs the tile's filter first.
-        jobs = [(i, c) for i in range(len(handles)) for c in range(len(cycle_list))]
+        # a job: (slot, cycle, where its plane goes); the index cycles' planes go to the batch of their own
+        jobs = [(i, cycle_list[c], tb.plane_ptr(i, c)) for i in range(len(handles)) for c in range(len(cycle_list))]
+        if index_cycles:
+            itb = index_tb[id(tb)]
+            jobs += [(i, cyc, itb.plane_ptr(i, c)) for i in range(len(handles)) for c, cyc in enumerate(index_cycles)]
         batch = None                        # which files the GPU decoder gets as one batch
         if gpu_inflate and jobs:
             if os.path.exists(handles[0].plane_path(cycle_list[0])):
@@ -427,38 +480,38 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
         filt = [] if batch else [pool.submit(sc.load_filter, h.filter_file, tb.filter_ptr(i), n_clusters)
                                  for i, h in enumerate(handles)]
 
-        def load(i, c):
+        def load(i, cyc, dst):
             try:
-                sc.load_bcl_gz(handles[i].plane_path(cycle_list[c]), tb.plane_ptr(i, c), n_clusters, interleave)
+                sc.load_bcl_gz(handles[i].plane_path(cyc), dst, n_clusters, interleave)
             except FileNotFoundError:       # only a missing file: a corrupt one is reported as such
                 if filt:
                     filt[i].result()
-                sc.load_cbcl_tile(handles[i].cbcl_path(cycle_list[c]), int(handles[i].tile),
-                                  tb.filter_ptr(i), n_clusters, tb.plane_ptr(i, c), interleave)
+                sc.load_cbcl_tile(handles[i].cbcl_path(cyc), int(handles[i].tile),
+                                  tb.filter_ptr(i), n_clusters, dst, interleave)
         if batch == "cbcl":
             # NovaSeq: the filters first (the expansion of a tile's blocks needs its filter in HBM),
             # then every (tile, cycle) block of the batch through one launch of the GPU decoder
             def load_all():
                 sc.load_bcl_gz_batch([], [], n_clusters, threads=max(1, threads),
                                      filters=[(h.filter_file, tb.filter_ptr(i)) for i, h in enumerate(handles)])
-                sc.load_cbcl_batch([(handles[i].cbcl_path(cycle_list[c]), int(handles[i].tile), tb.filter_ptr(i),
-                                     tb.plane_ptr(i, c)) for i, c in jobs], n_clusters, threads=max(1, threads),
+                sc.load_cbcl_batch([(handles[i].cbcl_path(cyc), int(handles[i].tile), tb.filter_ptr(i), dst)
+                                    for i, cyc, dst in jobs], n_clusters, threads=max(1, threads),
                                    well_stride=interleave)
             planes = [pool.submit(load_all)]
         elif batch:
             # the whole batch - planes and filters - goes through one call: the library's threads read
             # the files, the GPU inflates the .bcl.gz ones (wd_load_tile_files_batch)
             def load_all():
-                missing = sc.load_bcl_gz_batch([handles[i].plane_path(cycle_list[c]) for i, c in jobs],
-                                               [tb.plane_ptr(i, c) for i, c in jobs], n_clusters,
+                missing = sc.load_bcl_gz_batch([handles[i].plane_path(cyc) for i, cyc, _ in jobs],
+                                               [dst for _, _, dst in jobs], n_clusters,
                                                threads=max(1, threads), missing_ok=True, well_stride=interleave,
                                                filters=[(h.filter_file, tb.filter_ptr(i)) for i, h in enumerate(handles)],
-                                               tile_of=[i for i, _ in jobs] + list(range(len(handles))))
+                                               tile_of=[i for i, _, _ in jobs] + list(range(len(handles))))
                 for j in missing:           # (a run is .bcl.gz or .cbcl, never both: this loop is for the odd file)
                     load(*jobs[j])
             planes = [pool.submit(load_all)]
         else:
-            planes = [pool.submit(load, i, c) for i, c in jobs]
+            planes = [pool.submit(load, *job) for job in jobs]
         return _Loading((lane, chunk), handles, tb, filt + planes)
 
     def start_ahead(batch):
@@ -474,10 +527,15 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
 
     def release(tb, keep=False):
         live.remove(tb)
+        itb = index_tb.pop(id(tb), None)
         if keep:
             spare.append(tb)
+            if itb is not None:
+                index_spare.append(itb)
         else:
             tb.free()
+            if itb is not None:
+                itb.free()
 
     try:
         # three batches on their way at any time: one's files are read and copied while the one before
@@ -531,8 +589,12 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                             ld.close()
                         lane_acc["ld"] = None
                         ld = lane_acc["ld"] = LaneDups(sc, n_clusters, len(names), len(cycle_list))
+                        if index_cycles:
+                            ld.index_begin(len(index_cycles))
                     lane_acc["lane"] = lane
                 ld.add(tb, [names.index(t) for t in chunk])
+                if index_cycles:
+                    ld.index_add(index_tb[id(tb)], [names.index(t) for t in chunk])
                 if last_batch_of[lane] == bi:
                     got = ld.finish(labels=lane_dups > 1, hamming=lane_near, pair_budget=lane_pair_budget)
                     lane_row, tile_rows, lane_labels = got[:3]
@@ -543,6 +605,13 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                             into["lmembers"][lane] = (names,) + lane_cluster_members(lane_labels, got[5])
                     elif lane_labels is not None:
                         into["lmembers"][lane] = (names,) + lane_members(lane_labels)
+                    if index_cycles:
+                        final = got[3] if lane_near else lane_row      # the row of the labels the lane was left with
+                        into["lindex"][lane] = report.LaneIndexCounts.from_rows(
+                            *ld.index_finish(*index_listing(index_share, int(final[0]))), index_lengths, final[0], final[1])
+                        if lane_labels is not None:
+                            m = into["lmembers"][lane]
+                            into["lmindex"][lane] = ld.index_keys()[m[1] * n_clusters + m[2]]
                     del lane_labels, got
                 _lap("batch %d: lane classes" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
@@ -591,7 +660,7 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
             lane_acc["ld"].close()
         for tb in list(live):
             release(tb)
-        for tb in spare:
+        for tb in spare + index_spare:
             tb.free()
     return counts, logs
 
@@ -617,16 +686,25 @@ def write_cluster_members(path, members):
                           for w, c, s in zip(wells.tolist(), classes.tolist(), clusters.tolist()))
 
 
-def write_lane_members(path, members):
+def write_lane_members(path, members, index=None):
     """--lane-dups-out: lane, tile, well, class_tile, class_well of every well in a lane class, by lane, then in
     the order of the lane's tiles, then by well.  members[lane] = (tile names by index, tile index, well, class
     tile index, class well) - or, under --lane-dups-hamming, those and (cluster tile index, cluster well) of every
-    well in a lane cluster, which makes two more columns."""
+    well in a lane cluster, which makes two more columns.  index (--lane-dups-index) = (cycles per index range,
+    {lane: the index key of every row}): a last column `index`, the well's index read as bases."""
     with open(path, "w") as fh:
         near = any(len(m) == 7 for m in members.values())
-        fh.write("lane\ttile\twell\tclass_tile\tclass_well%s\n" % ("\tcluster_tile\tcluster_well" if near else ""))
+        fh.write("lane\ttile\twell\tclass_tile\tclass_well%s%s\n" % ("\tcluster_tile\tcluster_well" if near else "",
+                                                                   "\tindex" if index else ""))
         for lane in sorted(members, key=str):
             names, cols = members[lane][0], [c.tolist() for c in members[lane][1:]]
+            if index:
+                reads = {int(k): report.index_bases(k, index[0]) for k in np.unique(index[1][lane])}
+                cols.append([reads[k] for k in index[1][lane].tolist()])
+                fmt = "%s\t%s\t%d\t%s\t%d" + ("\t%s\t%d" if near else "") + "\t%s\n"
+                fh.writelines(fmt % ((lane, names[r[0]], r[1], names[r[2]], r[3]) +
+                                     ((names[r[4]], r[5]) if near else ()) + (r[-1],)) for r in zip(*cols))
+                continue
             if near:        # (--lane-dups-hamming: the wells in a lane cluster, their class and their cluster)
                 fh.writelines("%s\t%s\t%d\t%s\t%d\t%s\t%d\n" % (lane, names[a], b, names[c], d, names[e], f)
                               for a, b, c, d, e, f in zip(*cols))
@@ -767,6 +845,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
             # --tile-dups-hamming: and the clusters' behind those
             near_k = args.tile_dups_hamming or 0
             lane_near_k = args.lane_dups_hamming or 0
+            index_ranges = workload.parse_cycles(0, 0, args.lane_dups_index) if args.lane_dups_index else []
+            index_cycles = [c for s, e in index_ranges for c in range(s, e)]
             ntn = 5 + 2 * levels + len(report.CLASS_BIN_NAMES) if near_k else 0
             rows = np.zeros((len(mine), ncnt + nsets + ntd + ntn), dtype=np.int64)
             logs = {}
@@ -800,13 +880,16 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 if lane_near_k:
                     report.write_lane_near_dups(lane, lane_near_k, results["lnear"][lane], verbose=not args.summary_only,
                                                 out=out_fh, equal=results["ldups"][lane])
+                if index_cycles:
+                    report.write_lane_index_dups(lane, results["lindex"][lane], hamming=lane_near_k, out=out_fh)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
                 where = {item: i for i, item in enumerate(mine)}
                 # scan_lanes fills these, lane_done reads them
                 results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
-                           "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}, "lnear": {}}
+                           "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}, "lnear": {}, "lindex": {},
+                           "lmindex": {}}
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
@@ -830,7 +913,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                     check_lane_dups_fits(sc.lane_dups_workspace_bytes(n_targets, len(tiles), len(cycle_list)),
                                          torch.cuda.mem_get_info(device)[0], len(tiles), n_targets, len(cycle_list),
                                          scratch=sc.lane_near_scratch_bytes(n_targets, len(tiles), len(cycle_list),
-                                                                            lane_near_k))
+                                                                            lane_near_k),
+                                         index=sc.lane_index_workspace_bytes(n_targets, len(tiles), len(index_cycles))
+                                         if index_cycles else 0)
                 if err is None:             # (a rank whose setup failed has nothing to scan: it goes to the flag)
                     scan_lanes(sc, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                                max(0, args.tile_batch), args.threads,
@@ -842,7 +927,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                tile_dups=(2 if args.tile_dups_out else 1) if args.tile_dups else 0,
                                tile_near=near_k, pair_budget=args.tile_dups_pair_budget,
                                lane_dups=(2 if args.lane_dups_out else 1) if args.lane_dups else 0,
-                               lane_near=lane_near_k, lane_pair_budget=args.lane_dups_pair_budget)
+                               lane_near=lane_near_k, lane_pair_budget=args.lane_dups_pair_budget,
+                               lane_index=(index_cycles, [e - s for s, e in index_ranges],
+                                           args.lane_dups_index_min_share) if index_cycles else None)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
                     if args.tile_dups_out and near_k:
@@ -850,7 +937,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                     elif args.tile_dups_out:
                         write_set_members(args.tile_dups_out, results["tmembers"], column="class")
                     if args.lane_dups_out:
-                        write_lane_members(args.lane_dups_out, results["lmembers"])
+                        write_lane_members(args.lane_dups_out, results["lmembers"],
+                                           index=([e - s for s, e in index_ranges], results["lmindex"])
+                                           if index_cycles else None)
             except Exception as e:          # noqa: BLE001 - re-raised below, on every rank
                 err = e
             if world > 1:

@@ -386,6 +386,8 @@ __global__ void __launch_bounds__(kTdBlock) k_ld_span_sum(const int *__restrict_
 
 }  // namespace
 
+struct wd_lane_index;                              // lane_index.inc: the index part of an accumulator
+
 // the host side of an accumulator (the device side is the caller's workspace)
 struct wd_lane_dups {
     wd_ctx *ctx;
@@ -399,6 +401,7 @@ struct wd_lane_dups {
     // the classes, once k_ld_resolve has run (lane_near.inc delivers them again after a refusal)
     bool resolved;
     std::vector<int64_t> eq_lane, eq_tiles;
+    std::shared_ptr<wd_lane_index> index;          // null unless wd_lane_index_begin has been called
 };
 
 namespace {

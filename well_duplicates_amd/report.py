@@ -591,3 +591,84 @@ def write_lane_near_dups(lane, k: int, counts: LaneNearCounts, verbose: bool = F
     size = c.library_size()
     print("Estimated library size (distinct/X = 1 - exp(-PF/X)): %s" % ("n/a" if size is None else "%.0f" % size),
           file=out)
+
+
+LANE_INDEX_GROUP_COLS = 5
+LANE_INDEX_LANE_COLS = 5
+
+
+def index_bases(key: int, lengths: Sequence[int]) -> str:
+    """An index key (include/welldup_laneindex.h: ten 3-bit codes per 32-bit word, the first word low) as bases,
+    the index cycle ranges - lengths[i] cycles each - joined by '+'."""
+    codes = [(int(key) >> (32 * (c // 10) + 3 * (c % 10))) & 7 for c in range(sum(lengths))]
+    text = "".join("ACGTN"[min(c, 4)] for c in codes)
+    parts, at = [], 0
+    for n in lengths:
+        parts.append(text[at:at + n])
+        at += n
+    return "+".join(parts)
+
+
+@dataclass
+class LaneIndexCounts:
+    """A lane's duplication per index read (include/welldup_laneindex.h, LaneDups.index_finish): the lane index
+    row's columns, the listed groups - (index read as bases, [PF, InLane, InGroup, GroupRedundant, Mixed]) by
+    (-PF, key) - the Other row, and from the lane row the labels belong to its PF wells and its classes."""
+    groups: int = 0
+    listed: int = 0
+    group_spans: int = 0
+    mixed_classes: int = 0
+    mixed_wells: int = 0
+    other: List[int] = field(default_factory=lambda: [0] * LANE_INDEX_GROUP_COLS)
+    rows: List = field(default_factory=list)
+    pf: int = 0
+    classes: int = 0
+
+    @classmethod
+    def from_rows(cls, lane_index_row: Sequence[int], other: Sequence[int], group_rows: Sequence[Sequence[int]],
+                  keys: Sequence[int], lengths: Sequence[int], pf: int, classes: int) -> "LaneIndexCounts":
+        """The four results of LaneDups.index_finish, in any order of the groups; lengths: the cycles of every
+        index range; pf, classes: the lane row's PF wells and classes (clusters under --lane-dups-hamming)."""
+        b = [int(v) for v in lane_index_row]
+        assert len(b) == LANE_INDEX_LANE_COLS and len(other) == LANE_INDEX_GROUP_COLS and len(group_rows) == len(keys)
+        order = sorted(range(len(keys)), key=lambda i: (-int(group_rows[i][0]), int(keys[i])))
+        rows = []
+        for i in order:
+            assert len(group_rows[i]) == LANE_INDEX_GROUP_COLS
+            rows.append((index_bases(keys[i], lengths), [int(v) for v in group_rows[i]]))
+        assert b[1] == len(rows)
+        return cls(b[0], b[1], b[2], b[3], b[4], [int(v) for v in other], rows, int(pf), int(classes))
+
+    @property
+    def within_libraries(self) -> int:
+        """The sum of GroupRedundant: wells with a classmate of smaller global id in their own group."""
+        return sum(r[3] for _, r in self.rows) + self.other[3]
+
+    @property
+    def across_libraries(self) -> int:
+        """GroupSpans - Classes: first wells of their class in a group the class did not begin in."""
+        return self.group_spans - self.classes
+
+
+def write_lane_index_dups(lane, counts: LaneIndexCounts, hamming: int = 0, out=None) -> None:
+    """The block that follows a lane's other blocks under --lane-dups-index: a line per listed group (library), the
+    Other line, the summary.  hamming = K > 0: computed on the clusters at Hamming distance <= K, and says so."""
+    out = out or sys.stdout
+    c = counts
+    ham = "\tHamming: %i" % hamming if hamming else ""
+    share = lambda v, of: v / of if of else 0.0
+
+    def line(name, r, size):
+        print("LaneIndexDups: %s%s\tIndex: %s\tPF wells: %i (%.5f)\tInGroup: %i\tGroupRedundant: %i (%.5f)\t"
+              "Library size: %s\tMixed: %i (%.5f)" % (lane, ham, name, r[0], share(r[0], c.pf), r[2], r[3], share(r[3], r[0]),
+                                                      size, r[4], share(r[4], r[0])), file=out)
+    print(file=out)
+    for name, r in c.rows:
+        size = library_size(r[0], r[0] - r[3])
+        line(name, r, "n/a" if size is None else "%.0f" % size)
+    line("Other", c.other, "n/a")
+    red = c.within_libraries + c.across_libraries
+    print("LaneIndexDupsSummary: %s%s\tGroups: %i\tListed: %i\tRedundant within libraries: %i (%.5f of Redundant)\t"
+          "across libraries: %i (%.5f of Redundant)\tMixed%s: %i" % (
+              lane, ham, c.groups, c.listed, c.within_libraries, share(c.within_libraries, red), c.across_libraries,
+              share(c.across_libraries, red), "Clusters" if hamming else "Classes", c.mixed_classes), file=out)

@@ -315,6 +315,11 @@ class Scanner:
         (wd_lane_near_dups_scratch; 0 for k = 0)."""
         return self._workspace_bytes(self._lib.wd_lane_near_dups_scratch, n_clusters, max_tiles, L, k)
 
+    def lane_index_workspace_bytes(self, n_clusters: int, max_tiles: int, I: int) -> int:
+        """Device bytes the index part of a LaneDups accumulator needs for I index cycles
+        (wd_lane_index_workspace; I outside 1..20 raises ValueError)."""
+        return self._workspace_bytes(self._lib.wd_lane_index_workspace, n_clusters, max_tiles, I)
+
     def scan_async(self, tables, n_tiles: int, L: int, n_clusters: int, mode: int, k: int,
                    out_tile_dev: int, out_per_target_dev: Optional[int] = None):
         pt, ft = tables
@@ -509,6 +514,7 @@ class LaneDups:
         self.ws_bytes = scanner.lane_dups_workspace_bytes(self.N, self.max_tiles, self.L)
         self.d_ws = scanner.malloc(self.ws_bytes)
         self.d_labels = self.d_near_labels = 0
+        self.d_index, self.index_bytes, self.I, self.index_listed = 0, 0, 0, 0
         self.refused = None
         self._h = None
         try:
@@ -527,6 +533,83 @@ class LaneDups:
         """Drops what has been added and begins another lane of the same shape in the same workspace."""
         self._end()
         self._begin(self.d_ws, self.ws_bytes)
+        if self.I:
+            self._index_begin()
+
+    # ---- the lane's duplication per index read (include/welldup_laneindex.h)
+    def index_begin(self, I: int):
+        """Gives the lane an index part of I cycles (1..20), before any finish; the accumulator owns and frees its
+        workspace."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        if self.I:
+            raise ValueError("index_begin is called once")
+        nbytes = self.sc.lane_index_workspace_bytes(self.N, self.max_tiles, int(I))
+        self.d_index, self.index_bytes = self.sc.malloc(max(1, nbytes)), nbytes
+        try:
+            self.I = int(I)
+            self._index_begin()
+        except Exception:
+            self.sc.free(self.d_index)
+            self.d_index, self.index_bytes, self.I = 0, 0, 0
+            raise
+
+    def _index_begin(self):
+        self.sc._ck(self.sc._lib.wd_lane_index_begin(self._h, self.I, ctypes.c_void_p(self.d_index), self.index_bytes))
+
+    def index_add(self, tables, tile_indices: Sequence[int], well_stride: int = 1):
+        """Packs the index keys of resident tiles.  tables: a TileBatch of the I index cycles, or the ctypes pointer
+        tables Scanner._tables makes (the planes n x I; the filters are not looked at); tile_indices as `add`
+        takes them.  Independent of `add` in order and batching."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        idx = [int(t) for t in tile_indices]
+        if isinstance(tables, TileBatch):
+            tb = tables
+            if len(idx) != tb.n_tiles or tb.L != self.I or tb.N != self.N:
+                raise ValueError("the batch has %d tiles of %d wells and %d cycles; %d indices for a lane of %d wells "
+                                 "and %d index cycles" % (tb.n_tiles, tb.N, tb.L, len(idx), self.N, self.I))
+            tables, well_stride = tb.tables, tb.interleave
+        pt = tables[0]
+        if self.I and len(pt) < len(idx) * self.I:
+            raise ValueError("the plane table must hold n_tiles x I pointers")
+        ti = (ctypes.c_int * max(1, len(idx)))(*idx)
+        self.sc.set_option("well_stride", well_stride)
+        try:
+            self.sc._ck(self.sc._lib.wd_lane_index_add(self._h, len(idx), ti, pt))
+        finally:
+            self.sc.set_option("well_stride", 1)
+
+    def index_keys(self) -> np.ndarray:
+        """uint64 [max_tiles * N]: the index key of every well that got index planes (the key array of the index
+        workspace; it lies where include/welldup_laneindex.h's arithmetic puts it: behind the counters, the plane
+        pointers and the tile indices)."""
+        up = lambda v: (v + 255) // 256 * 256
+        at = 4096 + 4096 + 256 + up(8 * self.max_tiles * self.I) + up(4 * self.max_tiles)
+        return self.sc.d2h(self.d_index + at, 8 * self.N * self.max_tiles, np.uint64)
+
+    def index_finish(self, min_pf: int = 1, cap: int = 1 << 16):
+        """After finish(), any number of times.  -> (lane index row int64 [5]: [Groups, Listed, GroupSpans,
+        MixedClasses, MixedWells], Other row int64 [5], group rows int64 [listed, 5]: [PF, InLane, InGroup,
+        GroupRedundant, Mixed], keys uint64 [listed]), the groups of at least min_pf PF wells sorted by (-PF, key).
+        More than cap such groups raise RuntimeError; `index_listed` then holds their number."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        cap = int(cap)
+        lane_row = np.zeros(_lib.LANEINDEX_LANE_COLS, dtype=np.int64)
+        other = np.zeros(_lib.LANEINDEX_GROUP_COLS, dtype=np.int64)
+        rows = np.zeros((max(cap, 0), _lib.LANEINDEX_GROUP_COLS), dtype=np.int64)
+        keys = np.zeros(max(cap, 0), dtype=np.uint64)
+        n = ctypes.c_int64(0)
+        rc = self.sc._lib.wd_lane_index_finish(self._h, int(min_pf), cap, lane_row.ctypes.data_as(ctypes.c_void_p),
+                                               other.ctypes.data_as(ctypes.c_void_p),
+                                               rows.ctypes.data_as(ctypes.c_void_p) if cap > 0 else None,
+                                               keys.ctypes.data_as(ctypes.c_void_p) if cap > 0 else None, ctypes.byref(n))
+        self.index_listed = n.value
+        self.sc._ck(rc)
+        rows, keys = rows[:n.value], keys[:n.value]
+        order = np.lexsort((keys, -rows[:, 0]))
+        return lane_row, other, rows[order], keys[order]
 
     def add(self, tb: "TileBatch", tile_indices: Sequence[int]):
         """Adds the tiles of a resident batch (a plane per cycle); tile_indices[i]: slot i's number in the lane,
@@ -605,10 +688,10 @@ class LaneDups:
     def close(self):
         """Drops the lane, finished or not, and frees the workspace."""
         self._end()
-        for ptr in (self.d_ws, self.d_labels, self.d_near_labels):
+        for ptr in (self.d_ws, self.d_labels, self.d_near_labels, self.d_index):
             if ptr:
                 self.sc.free(ptr)
-        self.d_ws = self.d_labels = self.d_near_labels = 0
+        self.d_ws = self.d_labels = self.d_near_labels = self.d_index = 0
 
 
 class TileBatch:
