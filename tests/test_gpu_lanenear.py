@@ -15,7 +15,7 @@ from lanedups_ref import check_identities, lane_dups
 from lanenear_ref import (HAND, NEAR_PAIRS, check_near_identities, coarser, hand_made_lane, lane_near_dups, lay_end_to_end,
                           near_row)
 from tiledups_ref import INVALID
-from tilenear_ref import distinct_reads
+from tilenear_ref import distinct_reads, long_boundary_check, long_boundary_reads
 from well_duplicates_amd import _lib
 from well_duplicates_amd import count_well_duplicates as cwd
 from well_duplicates_amd import report, synth, workload
@@ -416,6 +416,31 @@ def test_heavy_bucket_refusal_and_retry(sc):
         finally:
             ld.close()
     finally:
+        tb.free()
+
+
+def test_lane_clusters_at_the_long_slot_boundary(sc):
+    """The reads of test_gpu_tilenear's boundary test dealt alternately onto two tiles of a lane of three indices,
+    a tile per add call: slots of 31 and 32 distinct reads (the chain walk) and of 33 and 34 (the rank path), every
+    one of them on both tiles.  All six outputs of the all-pairs reference; NearPairs and the size bins of
+    tile_near_dups on the undealt reads."""
+    reads, groups = long_boundary_reads()
+    n, index = reads.shape[0] // 2, [2, 0]                             # (index 1 is never added)
+    assert all(0 < int((g % 2).sum()) < g.size for g in groups)
+    x, y = synth.honeycomb_pixels(16, 16)
+    sc.targets_from_coords(x, y, None, levels=3)
+    whole = _upload(sc, [reads], [np.ones(2 * n, dtype=np.uint8)])
+    tb = _upload(sc, [reads[0::2], reads[1::2]], [np.ones(n, dtype=np.uint8)] * 2)
+    try:
+        want_eq, want = _reference(tb, index, 3, 1)
+        well = np.arange(2 * n)
+        long_boundary_check(want[2][np.array(index)[well % 2], well // 2], groups)
+        got = _feed(sc, tb, index, 3, [[0], [1]], 1)
+        _same(got, want_eq, want)
+        tn_rows, _ = whole.tile_near_dups(1)
+        assert got[3][NEAR_PAIRS] == tn_rows[0, 4] and (got[3][NEAR_PAIRS + 1:] == tn_rows[0, -8:]).all()
+    finally:
+        whole.free()
         tb.free()
 
 

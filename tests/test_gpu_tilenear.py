@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from tiledups_ref import INVALID, tile_dups
-from tilenear_ref import HAND, hand_made_tile, tile_near_dups
+from tilenear_ref import HAND, hand_made_tile, long_boundary_check, long_boundary_reads, tile_near_dups
 from well_duplicates_amd import _lib
 from well_duplicates_amd import count_well_duplicates as cwd
 from well_duplicates_amd import report, synth, workload
@@ -269,6 +269,23 @@ def test_near_dups_heavy_bucket_and_refusal(sc):
         assert (again == want_rows).all() and (again_labels == want_labels).all()
         eq, _ = tb.tile_dups()                                                 # ... and so does everything else
         assert eq[1, 0] == n
+    finally:
+        tb.free()
+
+
+def test_near_dups_at_the_long_slot_boundary(sc):
+    """K = 1, 20 cycles, one tile of 16 x 16 PF wells: slots of 31 and 32 distinct reads (the chain walk, at most 31
+    steps) and of 33 and 34 (the rank path), each with planted pairs at one mismatch - rows and labels of the
+    all-pairs reference."""
+    csr = _honeycomb(sc, 16, 16)
+    reads, groups = long_boundary_reads()
+    tb = _upload(sc, reads, np.ones(reads.shape[0], dtype=np.uint8))
+    try:
+        want_rows, want_labels = _reference(tb, csr, 1)
+        long_boundary_check(want_labels[0], groups)
+        rows, labels = tb.tile_near_dups(1, labels=True)
+        assert (labels == want_labels).all()
+        assert (rows == want_rows).all(), (rows, want_rows)
     finally:
         tb.free()
 

@@ -141,7 +141,7 @@ def test_lanedups_header_and_binding_agree():
 
 def test_build_id_covers_the_new_sources():
     deps = {os.path.basename(f) for f in _lib._deps(os.path.join(_lib.CSRC, "welldup_tiledups.hip"))}
-    assert {"lane_dups.inc", "welldup_lanedups.h", "tile_near.inc", "read_classes.inc", "welldup_tiledups.h"} <= deps
+    assert {"lane_dups.inc", "welldup_lanedups.h", "tile_near.inc", "near_core.inc", "read_classes.inc", "welldup_tiledups.h"} <= deps
     for u in _lib.UNITS[:-1]:
         other = {os.path.basename(f) for f in _lib._deps(os.path.join(_lib.CSRC, "welldup_%s.hip" % u))}
         assert not {"lane_dups.inc", "welldup_lanedups.h"} & other

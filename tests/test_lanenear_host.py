@@ -90,7 +90,7 @@ def test_lanenear_header_and_binding_agree():
                    "k_ln_members"):
         assert _lib.unit_of_kernel(kernel) == "tiledups"
     deps = {os.path.basename(f) for f in _lib._deps(os.path.join(_lib.CSRC, "welldup_tiledups.hip"))}
-    assert {"lane_near.inc", "welldup_lanenear.h", "lane_dups.inc", "tile_near.inc", "read_classes.inc"} <= deps
+    assert {"lane_near.inc", "welldup_lanenear.h", "lane_dups.inc", "tile_near.inc", "near_core.inc", "read_classes.inc"} <= deps
     _lib.build()
     lib = _lib.load()
     for s in syms:

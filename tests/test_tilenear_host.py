@@ -92,7 +92,7 @@ def test_tilenear_header_and_binding_agree():
 
 def test_build_id_covers_the_new_sources():
     deps = {os.path.basename(f) for f in _lib._deps(os.path.join(_lib.CSRC, "welldup_tiledups.hip"))}
-    assert {"tile_near.inc", "read_classes.inc", "welldup_tilenear.h", "welldup_tiledups.h"} <= deps
+    assert {"tile_near.inc", "near_core.inc", "read_classes.inc", "welldup_tilenear.h", "welldup_tiledups.h"} <= deps
     for u in _lib.UNITS[:-1]:
         other = {os.path.basename(f) for f in _lib._deps(os.path.join(_lib.CSRC, "welldup_%s.hip" % u))}
         assert not {"tile_near.inc", "welldup_tilenear.h"} & other

@@ -219,3 +219,43 @@ HAND = {
     2: dict(labels=[0, 0, 2, 3, 4, 5, 3, 0, 8, 3, 10, 5, 12, 12, 14, INVALID, 12, 12, 18, 14, 20, 3, 22, 5],
             head=[23, 5, 16, 11, 10], local=[11, 13], ring_wells=[50, 89], bins=[1, 2, 2, 0, 0, 0, 0, 0]),
 }
+
+
+# ---- reads at the boundary between the chain walk and the rank path (GPU tests of both near passes) ----
+LONG_GROUPS = (31, 32, 33, 34)      # a slot of up to 32 distinct reads is walked as a chain, a larger one goes by ranks
+
+
+def long_boundary_reads(seed=23, n=256, cycles=20):
+    """-> (reads uint8 [n, cycles], groups: the wells of each), for K = 1 (segments: cycles 0..9 and 10..19).
+    Four groups of 31, 32, 33 and 34 distinct reads at random wells; a group shares its own cycles 0..9 - one slot
+    of segment 0 - and is random in cycles 10..19 but for five planted pairs, which differ in exactly one cycle
+    of 10..19.  The other wells are random; no two reads of the tile are equal.
+    What the tests built on this cannot see: which path a group went down on the GPU.  A random well whose segment
+    fingerprint falls into a group's slot makes 32 vertices 33, and a chain's order is the order of arrival, so the
+    planted pairs lie at arbitrary steps of a walk: a bound one step short would be caught only by chance."""
+    rng = np.random.default_rng(seed)
+    half = cycles // 2
+    reads = (0x40 | rng.integers(0, 4, (n, cycles))).astype(np.uint8)
+    wells = rng.permutation(n)
+    groups, at = [], 0
+    for size in LONG_GROUPS:
+        g = wells[at:at + size]
+        at += size
+        reads[g, :half] = reads[g[0], :half]
+        for a, b in ((0, 1), (2, 3), (4, 5), (size - 4, size - 3), (size - 2, size - 1)):
+            reads[g[b], half:] = reads[g[a], half:]
+            reads[g[b], half + a % half] ^= 1                          # another base, the same quality bits
+        groups.append(g)
+    assert np.unique(reads, axis=0).shape[0] == n
+    return reads, groups
+
+
+def long_boundary_check(labels, groups):
+    """labels [n]: the reference's cluster label of every read above.  Every group holds a near pair and no near
+    pair joins two groups, so each of the four slots is decided on its own path."""
+    owner = {}
+    for i, g in enumerate(groups):
+        labs, count = np.unique(labels[g], return_counts=True)
+        assert (count >= 2).any(), i
+        for lab in labs.tolist():
+            assert owner.setdefault(lab, i) == i, (lab, i)

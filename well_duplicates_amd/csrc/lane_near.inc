@@ -1,40 +1,26 @@
 // lane_near.inc - near-duplicate read clusters of a lane (include/welldup_lanenear.h): the PF wells of all tiles
-// of a lane linked by Hamming distance <= K, single linkage.  Included at the end of welldup_tiledups.hip: it uses
-// read_classes.inc (Fp, mix64, wave_grouped, the spread counters), tile_near.inc (seg_begin, the union-find on a
-// label array, kTnLong, kNil, kTnBoundSlots) and lane_dups.inc (the accumulator, ld_equality, ld_count_rows).
+// of a lane linked by Hamming distance <= K, single linkage.  Included at the end of welldup_tiledups.hip: the
+// method, its kernels' bodies and the argument for its exactness stand in near_core.inc.  Here are the lane's
+// space, its kernels and its host call; it also uses read_classes.inc (Fp, mix64, the spread counters) and
+// lane_dups.inc (the accumulator, ld_equality, ld_count_rows).
 //
-// wd_lane_near_dups_finish, over the tiles that were added (grid y = tile, a well's place is its global id g):
-//   ld_equality       the classes, as wd_lane_dups_finish: after k_ld_resolve label[g] is the representative of g's
-//                     class (label[g] <= g, a representative its own label) - the parent array of the union-find.
-//                     The lane's table and the 8-byte word per well (aux) are dead from there on: the table takes
-//                     the buckets of a segment, aux[g] = {next, rank} of g's chain
-//   then, only the representatives being vertices, for every segment s = K..0 (nothing quadratic, no label changed):
-//   k_ln_bucket       the segment's fingerprint from the packed row (masks at the segment's ends), then
-//                     rank = count[slot]++, next = exchange(head[slot], g)
-//   k_ln_bound        sum over slots of c (c - 1) / 2; a slot of more than kTnLong gets a range of the member array
-//   (the host refuses the call here if a segment exceeds the budget; segment 0's buckets are still in the table)
+// wd_lane_near_dups_finish, over the tiles that were added (grid y = tile):
+//   ld_equality       the classes, as wd_lane_dups_finish; their representatives are the vertices.  The lane's table
+//                     and aux, dead from there on, take a segment's buckets and {next, rank} of every well's chain
+//   then for every segment s = K..0: k_ln_bucket, k_ln_bound, and the host refuses a lane over budget
 //   then per segment s = 0..K (s > 0: k_ln_bucket again, and k_ln_bound if the segment has a long slot):
-//   k_ln_scatter      members of long slots into their range, at their rank
-//   k_ln_pairs        a lane per representative of a short slot walks the chain behind itself
-//   k_ln_pairs_long   a wave per member of a long slot, its lanes over the members of lower rank
-//   k_ln_compress, k_ln_members   label = root, members recounted at the roots
-//   k_ld_classes, k_ld_span_count, k_ld_span_sum   unchanged, on zeroed counters: they are keyed by label only
-//
-// Why it is exact.  (1) Completeness: two reads within K mismatches agree on one of K + 1 segments (pigeonhole),
-// hence on that segment's masked words of the packed row, hence on its fingerprint (masked by hash_bits or not),
-// hence on a slot; within the slot either the chain walk (every member meets every member behind it) or the ranks
-// (every member meets every member of lower rank) visit each unordered pair once per segment, and the rule "the
-// first segment whose fingerprints agree" picks exactly one of those visits: each true pair is united and counted
-// once.  (2) Soundness: distance is counted on the packed rows, a bijective image of the decoded reads; a fingerprint only saves
-// comparisons.  (3) The union-find is that of tile_near.inc with "global id" for "well index": pointers only ever
-// name a smaller id of the same tree, every access to a parent inside a kernel is an agent-scope atomic, a
-// successful CAS hooks a root under a smaller root of another tree - roots are smallest ids and the components do
-// not depend on the order.  Non-representatives point at their representative and are not touched before
-// k_ln_compress.  (4) Every loop is bounded: the chain walk by kTnLong, the long path by the budget, find / unite by
-// the forest's depth.  Chains, ranks, bounds and rows are read only after the kernel that wrote them.
-// Tiles that arrived in different wd_lane_dups_add calls: nothing changes.  Bucketing happens entirely inside this
-// call, from the packed rows and the resolved labels, neither of which records when a tile came; a bucket's
-// members lie on any tiles and every kernel takes global ids throughout.
+//   k_ln_scatter, k_ln_pairs, k_ln_pairs_long
+//   k_ln_compress, k_ln_members, then k_ld_classes, k_ld_span_count, k_ld_span_sum on zeroed counters (by label only)
+// The lane's space: a vertex id is the well's global id g = tile index * N + well and every array is the lane's,
+// so a bucket's members lie on any tiles.  Particular to it:
+// - Bounds before any label changes.  All K + 1 bounds are taken first, nothing quadratic run and no label
+//   touched, so a refused call leaves the equality results valid; going down leaves segment 0's buckets in the
+//   table for the pairs.
+// - No stored fingerprints.  A segment's fingerprint is folded from the packed row whenever it is asked for, so
+//   a pair is tested on the distance first: nearly every candidate fails it, and only a pair within K pays for
+//   the fingerprints.
+// - Tiles from different wd_lane_dups_add calls: nothing changes.  Bucketing happens entirely inside this call,
+//   from the packed rows and the resolved labels, neither of which records when a tile came.
 #include "welldup_lanenear.h"
 
 namespace {
@@ -67,88 +53,6 @@ __device__ inline uint32_t ln_seg_fp(const uint32_t *__restrict__ row, int L, in
         g.fold(row[k] & ((1u << (3 * hi)) - 1u) & ~((1u << (3 * lo)) - 1u));
     }
     return g.a ^ (g.b * 0x9E3779B1u);
-}
-
-__device__ inline unsigned long long ln_slot(uint32_t f, uint32_t fmask, unsigned long long slot_mask)
-{
-    return mix64(f & fmask) & slot_mask;
-}
-
-// A slot of a segment's table: tile_near.inc's word - [0] the head of its chain, [1] all ones minus the number of
-// its members, one 0xFF fill empties the table - in the bytes of the lane's table.  link[2 g] = next, [2 g + 1] =
-// rank, in the bytes of aux.  grid (ceil(N / 256), tiles added): the representatives into the chains of `seg`.
-// Vertices are the representatives: label[g] == g as long as no union has run (by_label).  The unions move
-// labels, so every pass marks the other wells with next == g, which no chain produces, and the passes after the
-// first union go by that mark.
-__global__ void __launch_bounds__(kTdBlock) k_ln_bucket(const int *__restrict__ tile_idx, int64_t N, int L, int nseg,
-                                                         int seg, bool by_label, const uint32_t *__restrict__ label,
-                                                         const uint32_t *__restrict__ rows, int words, uint32_t fmask,
-                                                         unsigned long long slot_mask, uint32_t *slots,
-                                                         uint32_t *__restrict__ link)
-{
-    const int64_t w = (int64_t)blockIdx.x * kTdBlock + threadIdx.x;
-    if (w >= N)
-        return;
-    const size_t g64 = (size_t)tile_idx[blockIdx.y] * (size_t)N + (size_t)w;
-    const uint32_t g = (uint32_t)g64;                                  // (max_tiles * N < 2^32 - 1)
-    uint32_t *nx = link + 2 * g64;
-    if (by_label ? label[g64] != g : nx[0] == g) {
-        nx[0] = g;
-        return;
-    }
-    uint32_t *slot = slots + 2 * ln_slot(ln_seg_fp(rows + g64 * words, L, nseg, seg), fmask, slot_mask);
-    nx[1] = ~__hip_atomic_fetch_sub(slot + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    nx[0] = __hip_atomic_exchange(slot, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// grid (ceil(slots / kTnBoundSlots)), a lane two slots per 16-byte load, sixteen slots in all.  aux = {sum of
-// c (c - 1) / 2, members of long slots}, 64-bit (one slot of a whole lane is about 1.2e17 pairs); the head of a long slot
-// becomes the start of its range in the member array (its chain is not walked).
-__global__ void __launch_bounds__(kTdBlock) k_ln_bound(uint32_t *__restrict__ slots, unsigned long long slot_mask,
-                                                        unsigned long long *aux)
-{
-    __shared__ unsigned long long s_sum;
-    if (threadIdx.x == 0)
-        s_sum = 0;
-    __syncthreads();
-    unsigned long long sum = 0;
-    for (uint32_t i = 2 * threadIdx.x; i < kTnBoundSlots; i += 2 * kTdBlock) {
-        const unsigned long long s = (unsigned long long)blockIdx.x * kTnBoundSlots + i;      // (slots: a multiple of 64)
-        if (s > slot_mask)
-            break;
-        const uint4 v = *(const uint4 *)(slots + 2 * s);
-        const unsigned long long c[2] = {~v.y, ~v.w};
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-            if (c[j] > 1) {
-                sum += c[j] * (c[j] - 1) / 2;
-                if (c[j] > kTnLong)
-                    slots[2 * (s + j)] = (uint32_t)atomicAdd(aux + 1, c[j]);       // (ranges add up to <= W < 2^32)
-            }
-    }
-    if (sum)
-        atomicAdd(&s_sum, sum);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_sum)
-        atomicAdd(aux, s_sum);
-}
-
-// grid as k_ln_bucket: members of long slots into list[head[slot] + rank]
-__global__ void __launch_bounds__(kTdBlock) k_ln_scatter(const int *__restrict__ tile_idx, int64_t N, int L, int nseg,
-                                                          int seg, const uint32_t *__restrict__ rows, int words,
-                                                          uint32_t fmask, unsigned long long slot_mask,
-                                                          const uint32_t *__restrict__ slots,
-                                                          const uint32_t *__restrict__ link, uint32_t *__restrict__ list)
-{
-    const int64_t w = (int64_t)blockIdx.x * kTdBlock + threadIdx.x;
-    if (w >= N)
-        return;
-    const size_t g64 = (size_t)tile_idx[blockIdx.y] * (size_t)N + (size_t)w;
-    if (link[2 * g64] == (uint32_t)g64)                                // no vertex
-        return;
-    const unsigned long long s = ln_slot(ln_seg_fp(rows + g64 * words, L, nseg, seg), fmask, slot_mask);
-    if (slot_count(slots, s) > kTnLong)
-        list[(size_t)slots[2 * s] + link[2 * g64 + 1]] = (uint32_t)g64;            // (a range holds its slot's ranks)
 }
 
 // Mismatching cycles of two packed rows, counted no further than the piece in which they pass k: XOR, the three
@@ -197,62 +101,78 @@ __device__ inline int rows_hamming_upto(const uint32_t *__restrict__ rows, int w
     return d;
 }
 
-// The pair (a, b) of one slot of segment seg.  True if the reads are within k and the pair is this segment's: the
-// fingerprints of seg agree and those of no earlier segment do (then united).  The distance comes first: nearly
-// every candidate fails it, and only a pair within k pays for the fingerprints.
-__device__ inline bool ln_pair(const uint32_t *__restrict__ rows, int words, int L, int k, int seg, uint32_t fmask,
-                               uint32_t a, uint32_t b, uint32_t *par)
+// The lane's space, for the tile of blockIdx.y (max_tiles * N < 2^32 - 1).  link[2 g] = next, link[2 g + 1] = rank,
+// in the bytes of aux: the kernels hand the bodies link and link + 1.  A kernel fills what its body asks for and
+// leaves the rest zero: bound slot_mask alone; bucket and scatter tile_idx .. nseg; pairs all but labels_out;
+// pairs_long, which never asks for id(), slot_mask .. cnt; compress tile_idx and N; members those and labels_out.
+struct LnSpace {
+    using slot_t = unsigned long long;
+    static constexpr bool kDistanceFirst = true;
+    static constexpr bool kChainFirst = true;
+    const int *tile_idx;
+    int64_t N;
+    unsigned long long slot_mask;
+    uint32_t fmask;
+    const uint32_t *rows;
+    int words, L, nseg;
+    unsigned long long *cnt;
+    uint32_t *const *labels_out;
+
+    __device__ uint32_t id(int64_t w) const { return (uint32_t)((size_t)tile_idx[blockIdx.y] * (size_t)N + (size_t)w); }
+    __device__ size_t at(uint32_t id) const { return id; }
+    __device__ size_t link(uint32_t id) const { return 2 * (size_t)id; }
+    __device__ size_t slot_base() const { return 0; }
+    __device__ size_t aux_at() const { return 0; }
+    __device__ unsigned long long *near() const { return spread_row(cnt, 0, 1); }
+    __device__ uint32_t seg_fp(uint32_t id, int seg) const { return ln_seg_fp(rows + (size_t)id * words, L, nseg, seg); }
+    __device__ const uint32_t *reads() const { return rows; }
+    __device__ int distance_upto(const uint32_t *r, uint32_t a, uint32_t b, int k) const
+    {
+        return rows_hamming_upto(r, words, a, b, k);
+    }
+    __device__ void clear_more(size_t) const {}
+    __device__ void label_out(int64_t w, uint32_t lab) const
+    {
+        const int ti = tile_idx[blockIdx.y];
+        if (labels_out && labels_out[ti])
+            labels_out[ti][w] = lab;
+    }
+};
+
+// The slots are the bytes of the lane's table; the grids are near_core.inc's, y over the tiles added.
+__global__ void __launch_bounds__(kTdBlock) k_ln_bucket(const int *__restrict__ tile_idx, int64_t N, int L, int nseg,
+                                                         int seg, bool by_label, const uint32_t *__restrict__ label,
+                                                         const uint32_t *__restrict__ rows, int words, uint32_t fmask,
+                                                         unsigned long long slot_mask, uint32_t *slots,
+                                                         uint32_t *__restrict__ link)
 {
-    if (rows_hamming_upto(rows, words, a, b, k) > k)
-        return false;
-    const uint32_t *x = rows + (size_t)a * words, *y = rows + (size_t)b * words;
-    if ((ln_seg_fp(x, L, k + 1, seg) ^ ln_seg_fp(y, L, k + 1, seg)) & fmask)
-        return false;
-    for (int s = 0; s < seg; s++)
-        if (!((ln_seg_fp(x, L, k + 1, s) ^ ln_seg_fp(y, L, k + 1, s)) & fmask))
-            return false;                                              // visited at segment s
-    tn_unite(par, a, b);
-    return true;
+    near_bucket(LnSpace{tile_idx, N, slot_mask, fmask, rows, words, L, nseg}, seg, by_label, label, slots, link, link + 1);
 }
 
-__device__ inline void ln_add_near(uint32_t *s_near, uint32_t found, unsigned long long *near)
+__global__ void __launch_bounds__(kTdBlock) k_ln_bound(uint32_t *__restrict__ slots, unsigned long long slot_mask,
+                                                        unsigned long long *aux)
 {
-    if (found)
-        atomicAdd(s_near, found);
-    __syncthreads();
-    if (threadIdx.x == 0 && *s_near)
-        atomicAdd(spread_row(near, 0, 1), (unsigned long long)*s_near);
+    near_bound(LnSpace{nullptr, 0, slot_mask}, slots, aux);
 }
 
-// grid as k_ln_bucket: at most kTnLong - 1 steps per lane
+__global__ void __launch_bounds__(kTdBlock) k_ln_scatter(const int *__restrict__ tile_idx, int64_t N, int L, int nseg,
+                                                          int seg, const uint32_t *__restrict__ rows, int words,
+                                                          uint32_t fmask, unsigned long long slot_mask,
+                                                          const uint32_t *__restrict__ slots,
+                                                          const uint32_t *__restrict__ link, uint32_t *__restrict__ list)
+{
+    near_scatter(LnSpace{tile_idx, N, slot_mask, fmask, rows, words, L, nseg}, seg, link, link + 1, slots, list);
+}
+
 __global__ void __launch_bounds__(kTdBlock) k_ln_pairs(const int *__restrict__ tile_idx, int64_t N, int L, int k, int seg,
                                                         const uint32_t *__restrict__ rows, int words, uint32_t fmask,
                                                         unsigned long long slot_mask, const uint32_t *__restrict__ slots,
                                                         const uint32_t *__restrict__ link, uint32_t *label,
                                                         unsigned long long *near)
 {
-    __shared__ uint32_t s_near;
-    if (threadIdx.x == 0)
-        s_near = 0;
-    __syncthreads();
-    const int64_t w = (int64_t)blockIdx.x * kTdBlock + threadIdx.x;
-    uint32_t found = 0;
-    if (w < N) {
-        const size_t g64 = (size_t)tile_idx[blockIdx.y] * (size_t)N + (size_t)w;
-        const uint32_t g = (uint32_t)g64, first = link[2 * g64];
-        if (first != g && first != kNil) {                             // a vertex with a member behind it
-            const uint32_t c = slot_count(slots, ln_slot(ln_seg_fp(rows + g64 * words, L, k + 1, seg), fmask, slot_mask));
-            if (c <= kTnLong) {
-                uint32_t steps = 0;
-                for (uint32_t m = first; m != kNil && steps < kTnLong; m = link[2 * (size_t)m], steps++)
-                    found += ln_pair(rows, words, L, k, seg, fmask, g, m, label);
-            }
-        }
-    }
-    ln_add_near(&s_near, found, near);
+    near_pairs(LnSpace{tile_idx, N, slot_mask, fmask, rows, words, L, k + 1, near}, k, seg, slots, link, label);
 }
 
-// grid (ceil(members of long slots / 4)), a wave per member of a long slot
 __global__ void __launch_bounds__(kTdBlock) k_ln_pairs_long(int L, int k, int seg, const uint32_t *__restrict__ rows,
                                                              int words, uint32_t fmask, unsigned long long slot_mask,
                                                              const uint32_t *__restrict__ slots,
@@ -260,69 +180,22 @@ __global__ void __launch_bounds__(kTdBlock) k_ln_pairs_long(int L, int k, int se
                                                              const unsigned long long *__restrict__ aux, uint32_t *label,
                                                              unsigned long long *near)
 {
-    __shared__ uint32_t s_near;
-    if (threadIdx.x == 0)
-        s_near = 0;
-    __syncthreads();
-    const unsigned long long i = (unsigned long long)blockIdx.x * (kTdBlock / kWave) + threadIdx.x / kWave;
-    uint32_t found = 0;
-    if (i < aux[1]) {
-        const uint32_t a = list[i];
-        const uint32_t off = slots[2 * ln_slot(ln_seg_fp(rows + (size_t)a * words, L, k + 1, seg), fmask, slot_mask)];
-        const uint32_t r = (uint32_t)i - off;                          // a's rank: the members before it
-        for (uint32_t j = threadIdx.x & (kWave - 1); j < r; j += kWave)
-            found += ln_pair(rows, words, L, k, seg, fmask, a, list[(size_t)off + j], label);
-    }
-    ln_add_near(&s_near, found, near);
+    near_pairs_long(LnSpace{nullptr, 0, slot_mask, fmask, rows, words, L, k + 1, near}, k, seg, slots, list, aux, label);
 }
 
-// grid as k_ln_bucket: label = root (only well g's lane writes label[g]; what it writes is an ancestor), members
-// cleared for the recount
 __global__ void __launch_bounds__(kTdBlock) k_ln_compress(const int *__restrict__ tile_idx, int64_t N, uint32_t *label,
                                                            uint32_t *__restrict__ members)
 {
-    const int64_t w = (int64_t)blockIdx.x * kTdBlock + threadIdx.x;
-    if (w >= N)
-        return;
-    const size_t g64 = (size_t)tile_idx[blockIdx.y] * (size_t)N + (size_t)w;
-    const uint32_t p = tn_load(label + g64);
-    if (p != kInvalid && p != (uint32_t)g64) {
-        uint32_t x = p, y = tn_load(label + x);
-        while (y != x) {
-            x = y;
-            y = tn_load(label + x);
-        }
-        if (x != p)
-            __hip_atomic_store(label + g64, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    members[g64] = 0;
+    near_compress(LnSpace{tile_idx, N}, label, members);
 }
 
-// grid as k_ln_bucket: members counted at the roots, once per wave and root (as k_ld_resolve), labels out
 __global__ void __launch_bounds__(kTdBlock) k_ln_members(const int *__restrict__ tile_idx, int64_t N,
                                                           const uint32_t *__restrict__ label, uint32_t *members,
                                                           uint32_t *const *__restrict__ labels_out)
 {
-    const int ti = tile_idx[blockIdx.y];
-    const int64_t w = (int64_t)blockIdx.x * kTdBlock + threadIdx.x;
-    const size_t g = (size_t)ti * (size_t)N + (size_t)w;
-    uint32_t lab = kInvalid;
-    if (w < N) {
-        lab = label[g];
-        if (labels_out && labels_out[ti])
-            labels_out[ti][w] = lab;
-    }
-    const uint32_t add = wave_grouped(lab != kInvalid && lab != (uint32_t)g, lab);
-    if (add)
-        atomicAdd(members + lab, add);
-}
-
-// the cluster rows from the class rows' layout: NearPairs goes in front of the size bins
-void ln_near_row(const int64_t *lane_row, int64_t near_pairs, int64_t *near_lane_row)
-{
-    std::copy(lane_row, lane_row + 6, near_lane_row);
-    near_lane_row[6] = near_pairs;
-    std::copy(lane_row + 6, lane_row + WD_LANEDUPS_LANE_COLS, near_lane_row + 7);
+    LnSpace sp{tile_idx, N};
+    sp.labels_out = labels_out;
+    near_members(sp, label, members);
 }
 
 }  // namespace
@@ -373,7 +246,7 @@ try {
     const std::vector<int> tiles = ld_tiles_added(ld);
     if (k == 0 || wells == 0 || tiles.empty()) {                       // the classes, NearPairs = 0
         ld->finished = true;
-        ln_near_row(lane_row, 0, near_lane_row);
+        near_row(lane_row, 6, WD_LANEDUPS_LANE_COLS, 0, near_lane_row);
         std::copy(tile_rows, tile_rows + (size_t)T * WD_LANEDUPS_TILE_COLS, near_tile_rows);
         if (wells > 0) {
             if (const int rc = ld_copy_labels(ld, near_labels_dev, true))
@@ -382,9 +255,7 @@ try {
         }
         return WD_OK;
     }
-    // the default budget: the per-tile rule of tile_near.inc at lane scale (DESIGN 5.12)
-    const unsigned long long budget =
-        pair_budget > 0 ? (unsigned long long)pair_budget : std::max<unsigned long long>(16ull * wells, 1ull << 24);
+    const unsigned long long budget = near_budget(pair_budget, wells);      // the per-tile rule at lane scale
 
     const LdLayout &lay = ld->lay;
     uint8_t *ws = ld->ws, *sc = (uint8_t *)scratch_dev;
@@ -420,11 +291,7 @@ try {
     WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int seg = 0; seg < nseg; seg++)
         if (h_aux[2 * seg] > budget)
-            return fail(ctx, WD_ERR_UNSUPPORTED,
-                        "lane near-duplicates: segment " + std::to_string(seg) + " (cycles " +
-                            std::to_string(seg_begin(L, nseg, seg)) + ".." + std::to_string(seg_begin(L, nseg, seg + 1) - 1) +
-                            "): " + std::to_string(h_aux[2 * seg]) + " candidate pairs exceed the pair budget of " +
-                            std::to_string(budget) + " (reads of low diversity in that segment)");
+            return fail(ctx, WD_ERR_UNSUPPORTED, near_refusal("lane near-duplicates: ", L, nseg, seg, h_aux[2 * seg], budget));
 
     ld->finished = true;                                               // from here on the labels change
     for (int seg = 0; seg < nseg; seg++) {
@@ -469,7 +336,7 @@ try {
     cluster_row[0] = lane_row[0];
     unsigned long long near_pairs = 0;
     sum_spread(h_near, 0, 1, &near_pairs);
-    ln_near_row(cluster_row, (int64_t)near_pairs, near_lane_row);
+    near_row(cluster_row, 6, WD_LANEDUPS_LANE_COLS, (int64_t)near_pairs, near_lane_row);
     return WD_OK;
 } WD_CATCH
 

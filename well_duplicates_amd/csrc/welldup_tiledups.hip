@@ -10,10 +10,10 @@
 //                     and the level of every classmate met there is taken for both ends
 //   k_td_levels       histogram of the first levels (the host accumulates it into Local)
 // This unit reads the context (targets, stream) and keeps no state in it.
-// tile_near.inc (included at the end) builds the near-duplicate clusters of welldup_tilenear.h on these parts,
-// lane_dups.inc (after it) the classes across all tiles of a lane of welldup_lanedups.h, lane_near.inc (after it) the
-// near-duplicate clusters of a lane of welldup_lanenear.h, lane_index.inc (last) a lane's duplication per index read
-// of welldup_laneindex.h.
+// tile_near.inc (included at the end, after the near_core.inc it shares with lane_near.inc) builds the
+// near-duplicate clusters of welldup_tilenear.h on these parts, lane_dups.inc (after it) the classes across all
+// tiles of a lane of welldup_lanedups.h, lane_near.inc (after it) the near-duplicate clusters of a lane of
+// welldup_lanenear.h, lane_index.inc (last) a lane's duplication per index read of welldup_laneindex.h.
 #include <memory>
 
 #include "wd_ctx.h"
@@ -490,6 +490,7 @@ try {
 
 }  // extern "C"
 
+#include "near_core.inc"      // what the two near-duplicate passes below share: the method, its kernels' bodies
 #include "tile_near.inc"      // near-duplicate clusters (include/welldup_tilenear.h) on the parts above
 #include "lane_dups.inc"      // read classes across the tiles of a lane (include/welldup_lanedups.h)
 #include "lane_near.inc"      // near-duplicate clusters of a lane (include/welldup_lanenear.h) on all of the above
