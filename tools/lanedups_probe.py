@@ -19,11 +19,16 @@ streamed again into an accumulator with an index part of I cycles, once per case
 library (every counter on one row: the hottest case), and uniform random index reads (the most groups) - and
 LaneDups.index_add per tile and LaneDups.index_finish are printed beside the equality add and finish on the same
 batches.
+`--hamming K --mismatches` times LaneDups.mismatches(K) (where the lane's duplicate copies differ,
+include/welldup_lanemismatch.h) per tile of the lane beside the equality finish on the same batches, on three
+inputs: the planted lane (after the near finish), the `--equal` lane (every well a pair of one root, every pair in
+Dist[0]) and a lane of three tiles whose copies all differ from their original at one and the same cycle, by the
+same substitution (one entry of Sub takes every add: the contended histogram entry).
 For per-kernel times run it under
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/lanedups_probe.py
 
-(the k_ld_* rows of the stats are this stage, k_li_* the index part, k_td_* the per-tile classes, k_dense_* the
+(the k_ld_* rows of the stats are this stage, k_li_* the index part, k_lm_* the mismatch pass, k_td_* the per-tile classes, k_dense_* the
 scan)."""
 import argparse
 import os
@@ -51,7 +56,11 @@ ap.add_argument("--heavy", type=int, default=0, metavar="M",
                 help="also time a lane of M distinct reads that share their first segment (needs --hamming)")
 ap.add_argument("--index", type=int, default=0, metavar="I", help="also time the index part with I index cycles (1..20)")
 ap.add_argument("--libraries", type=int, default=96, metavar="M", help="libraries of the pooled lane (with --index)")
+ap.add_argument("--mismatches", action="store_true",
+                help="also time LaneDups.mismatches(K) beside the equality finish (needs --hamming; three inputs)")
 a = ap.parse_args()
+if a.mismatches and not a.hamming:
+    ap.error("--mismatches needs --hamming K")
 
 n = a.rows * a.cols
 x, y = synth.honeycomb_pixels(a.rows, a.cols)
@@ -127,6 +136,10 @@ for bi, tiles in enumerate(batches):
 ld.close()
 if a.hamming:
     near, t_near = clock(lambda: ldn.finish(hamming=a.hamming))
+    if a.mismatches:
+        ldn.mismatches(a.hamming)                    # (the first call of a kernel pays for loading it)
+        mm, t_mm = clock(lambda: ldn.mismatches(a.hamming))
+        assert mm[0][0] == near[3][3] and mm[0][4:].sum() == mm[0][0], "Pairs is not the near finish's Redundant"
     ldn.close()
     assert (near[0] == lane).all() and (near[1] == trow).all(), "the near finish delivers other classes"
 for tb in tbs:
@@ -157,6 +170,12 @@ if a.hamming:
     print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("tile_near_dups", t_tn, t_tn / k))
     print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("  less tile_dups", t_tn - t_td, (t_tn - t_td) / k))
     print("  (near finish - finish) / (tile_near_dups - tile_dups) = %.2f" % ((t_near - t_fin) / (t_tn - t_td)))
+
+if a.mismatches:
+    row = mm[0]
+    print("mismatches, max_d %d: %d pairs, %d profiled, %d mismatches (%d with N); Dist %s"
+          % (a.hamming, row[0], row[1], row[2], row[3], " ".join(str(v) for v in row[4:])))
+    print("  %-22s %9.3f ms  (%.4f ms per tile; the equality finish: %.4f)" % ("lane mismatches", t_mm, t_mm / k, t_fin / k))
 
 if a.heavy and a.hamming:
     m4 = (a.heavy + 3) // 4
@@ -229,6 +248,35 @@ if a.equal:
     (lane, trow, _), e_fin = clock(lambda: eq.finish())
     assert lane[:6].tolist() == [3 * n, 1, 3 * n, 3 * n - 1, 1, 3]
     print("every read equal, three tiles: add %.3f ms, finish %.3f ms" % (e_add, e_fin))
+    if a.mismatches:
+        eq.mismatches(a.hamming)
+        em, e_mm = clock(lambda: eq.mismatches(a.hamming))
+        assert em[0].tolist() == [3 * n - 1, 3 * n - 1, 0, 0, 3 * n - 1] + [0] * 8
+        print("  %-22s %9.3f ms  (%.4f ms per tile; the equality finish: %.4f)" % ("lane mismatches", e_mm, e_mm / 3, e_fin / 3))
     eq.close()
+    three.free()
+
+if a.mismatches:
+    # tile 0: the planted tile 1101 with G at cycle `at` of every well; tiles 1 and 2: the same with T there
+    at = a.cycles // 2
+    three = TileBatch(sc, 3, a.cycles, n)
+    for s in range(3):
+        sc.h2d(three.filter_ptr(s), np.ones(n, dtype=np.uint8))
+        for c in range(a.cycles):
+            if c == at:
+                sc.h2d(three.plane_ptr(s, c), np.full(n, 0x42 if s == 0 else 0x43, dtype=np.uint8))
+            else:
+                sc.synth_plane(three.plane_ptr(s, c), spec, 1, 1101, c)
+    sc.synchronize()
+    one = LaneDups(sc, n, 3, a.cycles)
+    one.add(three, [0, 1, 2])
+    (_, _, _, onear, _, _), o_near = clock(lambda: one.finish(hamming=1))
+    one.mismatches(1)
+    om, o_mm = clock(lambda: one.mismatches(1))
+    assert om[0][5] >= 2 * n and om[2][at, 2, 3] >= 2 * n, "the copies are not one cycle from their originals"
+    print("every copy G>T at cycle %d of its original, three tiles: %d pairs, %d of them at distance 1, Sub[%d][G][T] = %d; "
+          "near finish %.3f ms" % (at, om[0][0], om[0][5], at, om[2][at, 2, 3], o_near))
+    print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("lane mismatches", o_mm, o_mm / 3))
+    one.close()
     three.free()
 sc.close()

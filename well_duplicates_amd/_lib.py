@@ -149,6 +149,16 @@ LANEINDEX_MAX_CYCLES = 20
 LANEINDEX_GROUP_COLS = 5
 LANEINDEX_LANE_COLS = 5
 
+# name -> (restype, argtypes); every symbol include/welldup_lanemismatch.h declares beyond the seven above
+LANEMISMATCH_PROTOTYPES = {
+    "wd_lane_mismatch_scratch": (_i, [_i, _i, ctypes.POINTER(_sz)]),
+    "wd_lane_mismatches": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp]),
+}
+LANEMISMATCH_MAX_D = 7
+LANEMISMATCH_DIST_BINS = 9
+LANEMISMATCH_LANE_COLS = 4 + LANEMISMATCH_DIST_BINS
+LANEMISMATCH_TILE_COLS = 4
+
 _lib = None
 
 
@@ -235,7 +245,7 @@ def unit_of_kernel(kernel: str) -> str:
         return "ingest"
     if kernel.startswith("k_sets"):
         return "sets"
-    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_")):
+    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_")):
         return "tiledups"
     return "scan"
 
@@ -296,7 +306,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     for name, (res, args) in list(PROTOTYPES.items()) + list(SETS_PROTOTYPES.items()) + list(TILEDUPS_PROTOTYPES.items()) + \
             list(TILENEAR_PROTOTYPES.items()) + list(LANEDUPS_PROTOTYPES.items()) + list(LANENEAR_PROTOTYPES.items()) + \
-            list(LANEINDEX_PROTOTYPES.items()):
+            list(LANEINDEX_PROTOTYPES.items()) + list(LANEMISMATCH_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -35,6 +35,8 @@ Differences from the reference, all deliberate:
     library size it lets one estimate (report.write_lane_dups); --lane-dups-index RANGES groups the lane's PF wells
     by the bases of the index cycles as well - the libraries of a pooled lane - and adds the duplication and the
     library size of each, and the classes that span more than one index read (report.write_lane_index_dups);
+    --lane-dups-mismatches (with --lane-dups-hamming) compares every redundant well with the first of its cluster
+    and says how far apart the copies lie and at which cycles they differ (report.write_lane_mismatches);
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
@@ -195,6 +197,22 @@ def parse_args(argv=None):
                    help="with --lane-dups-index: an index read is listed as a library when it holds at least this "
                         "share of the lane's PF wells, in (0, 1]; all others (reads with a sequencing error in the "
                         "index, mostly) are summed into one Other line")
+    p.add_argument("--lane-dups-mismatches", action="store_true",
+                   help="with --lane-dups-hamming K: compare every redundant well of a lane's clusters with the first "
+                        "well of its cluster and print, after every other block of the lane, how many cycles apart the "
+                        "copies lie (0..7, >= 8: mass in the last distance within K says K is too small, pairs far "
+                        "beyond K that unrelated reads are being chained), the mismatches per pair, per scanned cycle "
+                        "and per tile, and the substitutions with either direction summed.  Copies of one molecule "
+                        "should be identical, so the cycles at which they differ are sequencing errors (no-calls where "
+                        "a read has N): an error profile of the lane without a spike-in or an alignment.  The implied "
+                        "rate per base, Mismatches / (2 x Profiled x cycles), assumes both copies carry errors alike "
+                        "and is truncated from above: the clusters only link within K, so copies with more errors "
+                        "are never compared")
+    p.add_argument("--lane-dups-mismatches-max-d", type=int, default=None, metavar="D",
+                   help="with --lane-dups-mismatches: only pairs at most D cycles apart (0..%d, default K) enter the "
+                        "mismatch and substitution counts - a chain member far from the first well of its cluster is "
+                        "probably another molecule; the distances themselves are counted for every pair"
+                        % _lib.LANEMISMATCH_MAX_D)
     args = p.parse_args(argv)
     if not args.coord_file and not args.all_wells:
         p.error("the following arguments are required: -f/--coord_file (or --all-wells)")
@@ -244,6 +262,14 @@ def parse_args(argv=None):
         n_index = sum(b - a for a, b in ranges)
         if not 1 <= n_index <= _lib.LANEINDEX_MAX_CYCLES:
             p.error("--lane-dups-index takes 1..%d cycles, not %d" % (_lib.LANEINDEX_MAX_CYCLES, n_index))
+    if args.lane_dups_mismatches and args.lane_dups_hamming is None:
+        p.error("--lane-dups-mismatches needs --lane-dups-hamming K with K >= 1 (under equality every copy is identical "
+                "to the first well of its class: there is nothing to profile)")
+    if args.lane_dups_mismatches_max_d is not None and not args.lane_dups_mismatches:
+        p.error("--lane-dups-mismatches-max-d needs --lane-dups-mismatches")
+    if args.lane_dups_mismatches_max_d is not None and not 0 <= args.lane_dups_mismatches_max_d <= _lib.LANEMISMATCH_MAX_D:
+        p.error("--lane-dups-mismatches-max-d takes 0..%d, not %d" % (_lib.LANEMISMATCH_MAX_D,
+                                                                     args.lane_dups_mismatches_max_d))
     if not 0.0 < args.lane_dups_index_min_share <= 1.0:
         p.error("--lane-dups-index-min-share takes a share in (0, 1], not %g" % args.lane_dups_index_min_share)
     if args.lane_dups and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -354,16 +380,19 @@ def lane_cluster_members(class_labels: np.ndarray, cluster_labels: np.ndarray):
     return ti, w, lab // class_labels.shape[1], lab % class_labels.shape[1], cti, cw
 
 
-def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0, index: int = 0):
+def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0, index: int = 0,
+                         mismatch: int = 0):
     """--lane-dups: the accumulator's workspace - with --lane-dups-hamming plus the scratch of the near finish, with
-    --lane-dups-index plus the index workspace - against the free device memory, before anything is loaded."""
-    need += scratch + index
+    --lane-dups-index plus the index workspace, with --lane-dups-mismatches plus that pass's scratch - against the
+    free device memory, before anything is loaded."""
+    need += scratch + index + mismatch
     if need > free:
         raise MemoryError("--lane-dups needs %.2f GB of device memory for a lane of %d tiles x %d wells x %d cycles "
-                          "(%d bytes%s%s), and %.2f GB (%d bytes) are free" % (
+                          "(%d bytes%s%s%s), and %.2f GB (%d bytes) are free" % (
                               need / 1e9, tiles, wells, cycles, need,
                               ", %d of them for --lane-dups-hamming" % scratch if scratch else "",
-                              ", %d of them for --lane-dups-index" % index if index else "", free / 1e9, free))
+                              ", %d of them for --lane-dups-index" % index if index else "",
+                              ", %d of them for --lane-dups-mismatches" % mismatch if mismatch else "", free / 1e9, free))
 
 
 def index_listing(min_share: float, pf: int):
@@ -375,7 +404,7 @@ def index_listing(min_share: float, pf: int):
 def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells, tile_batch,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
                dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0, lane_near=0, lane_pair_budget=0,
-               lane_index=None):
+               lane_index=None, lane_mismatch=None):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
@@ -396,6 +425,8 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     the GPU decoder and the .cbcl path alike - and which is fed to LaneDups.index_add, reused and released with the
     scan batch; after the lane's finish into["lindex"][lane] = LaneIndexCounts (on the clusters under lane_near), and
     with the members into["lmindex"][lane] = the index read of every row of into["lmembers"][lane].
+    lane_mismatch = D (with lane_near): after the lane's finish, and after its index finish, LaneDups.mismatches(D):
+    into["lmismatch"][lane] = LaneMismatchCounts, its cycles numbered by cycle_list.
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -612,6 +643,9 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                         if lane_labels is not None:
                             m = into["lmembers"][lane]
                             into["lmindex"][lane] = ld.index_keys()[m[1] * n_clusters + m[2]]
+                    if lane_mismatch is not None:
+                        into["lmismatch"][lane] = report.LaneMismatchCounts.from_rows(
+                            *ld.mismatches(lane_mismatch), names, lane_near, lane_mismatch, cycle_list)
                     del lane_labels, got
                 _lap("batch %d: lane classes" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
@@ -847,6 +881,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
             lane_near_k = args.lane_dups_hamming or 0
             index_ranges = workload.parse_cycles(0, 0, args.lane_dups_index) if args.lane_dups_index else []
             index_cycles = [c for s, e in index_ranges for c in range(s, e)]
+            mismatch_d = None
+            if args.lane_dups_mismatches:
+                mismatch_d = lane_near_k if args.lane_dups_mismatches_max_d is None else args.lane_dups_mismatches_max_d
             ntn = 5 + 2 * levels + len(report.CLASS_BIN_NAMES) if near_k else 0
             rows = np.zeros((len(mine), ncnt + nsets + ntd + ntn), dtype=np.int64)
             logs = {}
@@ -882,6 +919,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                                 out=out_fh, equal=results["ldups"][lane])
                 if index_cycles:
                     report.write_lane_index_dups(lane, results["lindex"][lane], hamming=lane_near_k, out=out_fh)
+                if args.lane_dups_mismatches:
+                    report.write_lane_mismatches(lane, results["lmismatch"][lane], verbose=not args.summary_only, out=out_fh)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
@@ -889,7 +928,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 # scan_lanes fills these, lane_done reads them
                 results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
                            "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}, "lnear": {}, "lindex": {},
-                           "lmindex": {}}
+                           "lmindex": {}, "lmismatch": {}}
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
@@ -915,7 +954,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                          scratch=sc.lane_near_scratch_bytes(n_targets, len(tiles), len(cycle_list),
                                                                             lane_near_k),
                                          index=sc.lane_index_workspace_bytes(n_targets, len(tiles), len(index_cycles))
-                                         if index_cycles else 0)
+                                         if index_cycles else 0,
+                                         mismatch=sc.lane_mismatch_scratch_bytes(len(tiles), len(cycle_list))
+                                         if mismatch_d is not None else 0)
                 if err is None:             # (a rank whose setup failed has nothing to scan: it goes to the flag)
                     scan_lanes(sc, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                                max(0, args.tile_batch), args.threads,
@@ -929,7 +970,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                lane_dups=(2 if args.lane_dups_out else 1) if args.lane_dups else 0,
                                lane_near=lane_near_k, lane_pair_budget=args.lane_dups_pair_budget,
                                lane_index=(index_cycles, [e - s for s, e in index_ranges],
-                                           args.lane_dups_index_min_share) if index_cycles else None)
+                                           args.lane_dups_index_min_share) if index_cycles else None,
+                               lane_mismatch=mismatch_d)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
                     if args.tile_dups_out and near_k:

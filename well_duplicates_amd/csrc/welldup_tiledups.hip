@@ -13,7 +13,8 @@
 // tile_near.inc (included at the end, after the near_core.inc it shares with lane_near.inc) builds the
 // near-duplicate clusters of welldup_tilenear.h on these parts, lane_dups.inc (after it) the classes across all
 // tiles of a lane of welldup_lanedups.h, lane_near.inc (after it) the near-duplicate clusters of a lane of
-// welldup_lanenear.h, lane_index.inc (last) a lane's duplication per index read of welldup_laneindex.h.
+// welldup_lanenear.h, lane_index.inc (after it) a lane's duplication per index read of welldup_laneindex.h,
+// lane_mismatch.inc (last) where a lane's duplicate copies differ of welldup_lanemismatch.h.
 #include <memory>
 
 #include "wd_ctx.h"
@@ -495,3 +496,4 @@ try {
 #include "lane_dups.inc"      // read classes across the tiles of a lane (include/welldup_lanedups.h)
 #include "lane_near.inc"      // near-duplicate clusters of a lane (include/welldup_lanenear.h) on all of the above
 #include "lane_index.inc"     // a lane's classes split by index read (include/welldup_laneindex.h)
+#include "lane_mismatch.inc"  // where a lane's duplicate copies differ (include/welldup_lanemismatch.h)

@@ -672,3 +672,104 @@ def write_lane_index_dups(lane, counts: LaneIndexCounts, hamming: int = 0, out=N
           "across libraries: %i (%.5f of Redundant)\tMixed%s: %i" % (
               lane, ham, c.groups, c.listed, c.within_libraries, share(c.within_libraries, red), c.across_libraries,
               share(c.across_libraries, red), "Clusters" if hamming else "Classes", c.mixed_classes), file=out)
+
+
+LANE_MISMATCH_MAX_D = 7
+LANE_MISMATCH_DIST_NAMES = ["0", "1", "2", "3", "4", "5", "6", "7", ">=8"]
+LANE_MISMATCH_LANE_COLS = 4 + len(LANE_MISMATCH_DIST_NAMES)
+LANE_MISMATCH_TILE_COLS = 4
+CODE_NAMES = "ACGTN"
+
+
+@dataclass
+class LaneMismatchCounts:
+    """Where a lane's duplicate copies differ (include/welldup_lanemismatch.h, LaneDups.mismatches): every redundant
+    well against its root under the clusters at Hamming distance <= k.  The lane row's columns, per tile (by the
+    tile's name) [Pairs, Profiled, Mismatches, WithN], sub[c][a][b] over the pairs with d <= max_d, and the number
+    of every scanned cycle as --cycles counts them."""
+    k: int = 0
+    max_d: int = 0
+    pairs: int = 0
+    profiled: int = 0
+    mismatches: int = 0
+    with_n: int = 0
+    dist: List[int] = field(default_factory=lambda: [0] * len(LANE_MISMATCH_DIST_NAMES))
+    tiles: Dict[str, List[int]] = field(default_factory=dict)
+    sub: List = field(default_factory=list)
+    cycles: List[int] = field(default_factory=list)
+
+    @classmethod
+    def from_rows(cls, lane_row: Sequence[int], tile_rows: Sequence[Sequence[int]], sub, tile_names: Sequence, k: int,
+                  max_d: int, cycles: Optional[Sequence[int]] = None) -> "LaneMismatchCounts":
+        """The three results of LaneDups.mismatches(max_d); tile_names as LaneDupCounts.from_rows takes them; cycles:
+        the scanned cycles' numbers (default 0, 1, ..)."""
+        b = [int(v) for v in lane_row]
+        assert len(b) == LANE_MISMATCH_LANE_COLS and 0 <= max_d <= LANE_MISMATCH_MAX_D
+        tiles = {}
+        for name, row in zip(tile_names, tile_rows):
+            assert len(row) == LANE_MISMATCH_TILE_COLS
+            if name is not None:
+                tiles[name] = [int(v) for v in row]
+        sub = [[[int(v) for v in row] for row in cell] for cell in sub]
+        assert all(len(cell) == 5 and all(len(row) == 5 for row in cell) for cell in sub)
+        cycles = list(range(len(sub))) if cycles is None else [int(c) for c in cycles]
+        assert len(cycles) == len(sub)
+        return cls(int(k), int(max_d), b[0], b[1], b[2], b[3], b[4:], tiles, sub, cycles)
+
+    def per_cycle(self):
+        """-> [(mismatches, of which with N)] per scanned cycle"""
+        return [(sum(map(sum, cell)), sum(cell[4]) + sum(row[4] for row in cell[:4])) for cell in self.sub]
+
+    def symmetric(self, a: int, b: int) -> int:
+        """The profiled pairs with codes a and b, either way round, summed over the cycles."""
+        return sum(cell[a][b] + cell[b][a] for cell in self.sub)
+
+    def per_pair(self) -> float:
+        """Mismatches per profiled pair (0 without one)."""
+        return self.mismatches / self.profiled if self.profiled else 0.0
+
+    def error_rate(self) -> float:
+        """Mismatches / (2 x Profiled x cycles): what a base's error rate would be if both copies of a pair carried
+        errors alike.  Truncated from above: pairs further apart than the clusters link are never seen."""
+        den = 2 * self.profiled * len(self.sub)
+        return self.mismatches / den if den else 0.0
+
+
+def write_lane_mismatches(lane, counts: LaneMismatchCounts, verbose: bool = False, out=None) -> None:
+    """The block that follows every other block of a lane under --lane-dups-mismatches: per-tile and per-cycle lines
+    (verbose; tiles in sorted order as write_report, cycles numbered as --cycles), then the summary: the distances of
+    the redundant wells from their roots, the mismatches per profiled pair and the per-base rate they imply, the
+    substitutions with either direction summed, and the share of the last distance the clusters still link."""
+    out = out or sys.stdout
+    c = counts
+    share = lambda v, of: v / of if of else 0.0
+    print(file=out)
+    if verbose:
+        for tile in sorted(c.tiles):
+            t = c.tiles[tile]
+            print("LaneMismatches: %s\tTile: %s\tPairs: %i\tProfiled: %i\tMismatches: %i\tWithN: %i" % (
+                lane, tile, t[0], t[1], t[2], t[3]), file=out)
+        for cycle, (n, with_n) in zip(c.cycles, c.per_cycle()):
+            print("LaneMismatches: %s\tCycle: %i\tMismatches: %i (%.6f per profiled pair)\tWithN: %i" % (
+                lane, cycle, n, share(n, c.profiled), with_n), file=out)
+    print("LaneMismatchesSummary: %s\tTiles: %i\tHamming: %i\tMaxD: %i\tPairs: %i\tProfiled: %i (%.5f)\tMismatches: %i\t"
+          "WithN: %i" % (lane, len(c.tiles), c.k, c.max_d, c.pairs, c.profiled, share(c.profiled, c.pairs), c.mismatches,
+                         c.with_n), file=out)
+    print("Dist: %s" % "\t".join("%s: %i (%.5f)" % (name, n, share(n, c.pairs))
+                                 for name, n in zip(LANE_MISMATCH_DIST_NAMES, c.dist)), file=out)
+    print("Mismatches per profiled pair: %.5f" % c.per_pair(), file=out)
+    print("Implied error rate per base (Mismatches / (2 x Profiled x %i cycles)): %.3e" % (len(c.sub), c.error_rate()),
+          file=out)
+    for a in range(4):
+        for b in range(a + 1, 4):
+            n = c.symmetric(a, b)
+            print("Substitution: %s<>%s\t%i (%.5f of Mismatches)" % (CODE_NAMES[a], CODE_NAMES[b], n, share(n, c.mismatches)),
+                  file=out)
+    for a in range(4):
+        n = c.symmetric(a, 4)
+        print("Substitution: %s<>N\t%i (%.5f of Mismatches)" % (CODE_NAMES[a], n, share(n, c.mismatches)), file=out)
+    last = min(c.k, len(c.dist) - 1)
+    near = sum(c.dist[1:last + 1])
+    print("Pairs at distance %i, the last the clusters link: %i (%.5f of the pairs at 1..%i, %.5f of Pairs)" % (
+        last, c.dist[last] if last else 0, share(c.dist[last] if last else 0, near), last, share(c.dist[last] if last else 0, c.pairs)),
+          file=out)

@@ -320,6 +320,11 @@ class Scanner:
         (wd_lane_index_workspace; I outside 1..20 raises ValueError)."""
         return self._workspace_bytes(self._lib.wd_lane_index_workspace, n_clusters, max_tiles, I)
 
+    def lane_mismatch_scratch_bytes(self, max_tiles: int, L: int) -> int:
+        """Device bytes LaneDups.mismatches needs beside the accumulator's workspace (wd_lane_mismatch_scratch;
+        it does not depend on the wells of a tile)."""
+        return self._workspace_bytes(self._lib.wd_lane_mismatch_scratch, max_tiles, L)
+
     def scan_async(self, tables, n_tiles: int, L: int, n_clusters: int, mode: int, k: int,
                    out_tile_dev: int, out_per_target_dev: Optional[int] = None):
         pt, ft = tables
@@ -679,6 +684,28 @@ class LaneDups:
         finally:
             self.sc.free(d_scratch)
         return lane_row, tile_rows, fetch(self.d_labels), near_lane, near_tiles, fetch(self.d_near_labels)
+
+    def mismatches(self, max_d: int):
+        """After finish(), any number of times, before or after index_finish (wd_lane_mismatches,
+        include/welldup_lanemismatch.h): every redundant well against its root under the labels the finish left.
+        -> (lane row int64 [13]: [Pairs, Profiled, Mismatches, WithN, Dist d = 0..7 and >= 8], tile rows int64
+        [max_tiles, 4]: [Pairs, Profiled, Mismatches, WithN] by the member's tile, sub int64 [L, 5, 5]:
+        [cycle][root's code][member's code] over the pairs with d <= max_d).  The scratch is allocated for the
+        call and released.  max_d outside 0..7 or a call before a successful finish raises ValueError."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        lane_row = np.zeros(_lib.LANEMISMATCH_LANE_COLS, dtype=np.int64)
+        tile_rows = np.zeros((self.max_tiles, _lib.LANEMISMATCH_TILE_COLS), dtype=np.int64)
+        sub = np.zeros((self.L, 5, 5), dtype=np.int64)
+        sbytes = self.sc.lane_mismatch_scratch_bytes(self.max_tiles, self.L)
+        d_scratch = self.sc.malloc(sbytes)
+        try:
+            self.sc._ck(self.sc._lib.wd_lane_mismatches(
+                self._h, int(max_d), ctypes.c_void_p(d_scratch), sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
+                tile_rows.ctypes.data_as(ctypes.c_void_p), sub.ctypes.data_as(ctypes.c_void_p)))
+        finally:
+            self.sc.free(d_scratch)
+        return lane_row, tile_rows, sub
 
     def _end(self):
         if self._h is not None:
