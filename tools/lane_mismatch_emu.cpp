@@ -8,71 +8,13 @@
 // says anything about time.
 //
 //   g++ -O1 -g -std=c++17 -fsanitize=undefined -Iinclude tools/lane_mismatch_emu.cpp -o lane_mismatch_emu
-#include <ucontext.h>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-#include <algorithm>
-using std::min; using std::max;
-struct uint4 { uint32_t x, y, z, w; };
-struct D3 { unsigned x, y, z; };
-constexpr int kTdBlock = 256, kWave = 64, kSpread = 64, kFpCycles = 10, kLdCmpWords = 8;
-constexpr uint32_t kInvalid = 0xFFFFFFFFu;
-constexpr int kMaxCycles = 1024;
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-// ---- fibers: one per lane of a workgroup, switched at collectives
-struct Fiber { ucontext_t ctx; bool done; char *stack; };
-static Fiber fib[kTdBlock]; static ucontext_t sched; static int cur;
-static D3 g_block;
-#define threadIdx (D3{(unsigned)cur, 0, 0})
-#define blockIdx g_block
-static void yield_() { swapcontext(&fib[cur].ctx, &sched); }
-static int bar_count = 0; static long bar_gen = 0;
-static void __syncthreads() { long g = bar_gen; if (++bar_count == kTdBlock) { bar_count = 0; bar_gen++; } else while (bar_gen == g) yield_(); }
-struct WaveSync { int count = 0; long gen = 0; unsigned long long pred[2] = {0, 0}; int val[2][kWave]; };
-static WaveSync ws[kTdBlock / kWave];
-static unsigned long long __ballot(bool p) {
-    WaveSync &w = ws[cur / kWave]; long g = w.gen; int par = g & 1, lane = cur % kWave;
-    if (w.count == 0) w.pred[par] = 0;
-    if (p) w.pred[par] |= 1ull << lane;
-    if (++w.count == kWave) { w.count = 0; w.gen++; } else while (w.gen == g) yield_();
-    return w.pred[par];
-}
-static int __shfl(int v, int src) {
-    WaveSync &w = ws[cur / kWave]; long g = w.gen; int par = g & 1, lane = cur % kWave;
-    w.val[par][lane] = v;
-    if (++w.count == kWave) { w.count = 0; w.gen++; } else while (w.gen == g) yield_();
-    return w.val[par][src];
-}
-#define __popcll __builtin_popcountll
-#define __ffsll __builtin_ffsll
-#define __popc __builtin_popcount
-#define __ffs __builtin_ffs
-template <class T, class U> static T atomicAdd(T *p, U v) { T o = *p; *p += (T)v; return o; }
-static unsigned long long *spread_row(unsigned long long *cnt, size_t row, int width) { return cnt + (row * kSpread + blockIdx.x % kSpread) * width; }
-#define __device__
-#define __global__
-#define __shared__ static
-#define __launch_bounds__(x)
-#define __restrict__
+#include "wave_emu.h"
 #define WD_LANE_MISMATCH_EMU
 #include "../well_duplicates_amd/csrc/lane_mismatch.inc"
 
 struct Args { const int *tile_idx; int64_t N; const uint32_t *label, *rows; int words, L, max_d; unsigned long long *cnt_t, *cnt_l, *sub; };
 static Args A;
-static void entry() { k_lm_tally(A.tile_idx, A.N, A.label, A.rows, A.words, A.L, A.max_d, A.cnt_t, A.cnt_l, A.sub); fib[cur].done = true; swapcontext(&fib[cur].ctx, &sched); }
-static void run_block(unsigned bx, unsigned by) {
-    g_block = D3{bx, by, 0};
-    for (int t = 0; t < kTdBlock; t++) {
-        if (!fib[t].stack) fib[t].stack = (char *)malloc(1 << 16);
-        getcontext(&fib[t].ctx); fib[t].ctx.uc_stack.ss_sp = fib[t].stack; fib[t].ctx.uc_stack.ss_size = 1 << 16; fib[t].ctx.uc_link = &sched;
-        fib[t].done = false; makecontext(&fib[t].ctx, entry, 0);
-    }
-    int left = kTdBlock;
-    while (left) for (int t = 0; t < kTdBlock; t++) if (!fib[t].done) { cur = t; swapcontext(&sched, &fib[t].ctx); if (fib[t].done) left--; }
-}
+static void entry() { k_lm_tally(A.tile_idx, A.N, A.label, A.rows, A.words, A.L, A.max_d, A.cnt_t, A.cnt_l, A.sub); }
 int main() {
     srand(3);
     for (int trial = 0; trial < 12; trial++) {
@@ -104,7 +46,7 @@ int main() {
         for (size_t g = 0; g < W; g++) if (!code[g].empty()) for (int c = 0; c < L; c++) rows[g * words + c / 10] |= (uint32_t)code[g][c] << (3 * (c % 10));
         std::vector<unsigned long long> cnt_t((size_t)T * kSpread * kLmTileCnt, 0), cnt_l(kSpread * kLmLaneCnt, 0), sub((size_t)L * 25, 0);
         A = Args{tiles, N, label.data(), rows.data(), words, L, max_d, cnt_t.data(), cnt_l.data(), sub.data()};
-        for (unsigned by = 0; by < 2; by++) for (unsigned bx = 0; bx < (unsigned)((N + kLmRun - 1) / kLmRun); bx++) run_block(bx, by);
+        for (unsigned by = 0; by < 2; by++) for (unsigned bx = 0; bx < (unsigned)((N + kLmRun - 1) / kLmRun); bx++) run_block(bx, by, entry);
         // the definitions, directly
         std::vector<long long> wt((size_t)T * 4, 0), wd(9, 0), wsub((size_t)L * 25, 0);
         for (int ti : tiles) for (int64_t w = 0; w < N; w++) {

@@ -24,11 +24,18 @@ include/welldup_lanemismatch.h) per tile of the lane beside the equality finish 
 inputs: the planted lane (after the near finish), the `--equal` lane (every well a pair of one root, every pair in
 Dist[0]) and a lane of three tiles whose copies all differ from their original at one and the same cycle, by the
 same substitution (one entry of Sub takes every add: the contended histogram entry).
+`--distance [--radius R]` times LaneDups.distances (how far apart the lane's duplicate copies lie,
+include/welldup_lanedistance.h) per tile of the lane beside the equality finish and LaneDups.mismatches on the same
+batches and the same (equality) labels, on three inputs: the planted lane, the `--equal` lane (every pair on one root:
+one bin and one root tile take every add of a wave) and a lane of three tiles whose wells of odd index all repeat
+their left neighbour (everything in Dist[0] and Local).  The call includes the host's check, interleaving and upload
+of the coordinates (8 bytes per well of a tile, once per call whatever the tiles): the kernel's own time is the
+k_lg_tally row of the trace below, the rest of the call is that host part.
 For per-kernel times run it under
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/lanedups_probe.py
 
-(the k_ld_* rows of the stats are this stage, k_li_* the index part, k_lm_* the mismatch pass, k_td_* the per-tile classes, k_dense_* the
+(the k_ld_* rows of the stats are this stage, k_li_* the index part, k_lm_* the mismatch pass, k_lg_* the distance pass, k_td_* the per-tile classes, k_dense_* the
 scan)."""
 import argparse
 import os
@@ -58,6 +65,9 @@ ap.add_argument("--index", type=int, default=0, metavar="I", help="also time the
 ap.add_argument("--libraries", type=int, default=96, metavar="M", help="libraries of the pooled lane (with --index)")
 ap.add_argument("--mismatches", action="store_true",
                 help="also time LaneDups.mismatches(K) beside the equality finish (needs --hamming; three inputs)")
+ap.add_argument("--distance", action="store_true",
+                help="also time LaneDups.distances beside the equality finish and mismatches (three inputs with --equal)")
+ap.add_argument("--radius", type=int, default=2500, metavar="R", help="the radius of --distance")
 a = ap.parse_args()
 if a.mismatches and not a.hamming:
     ap.error("--mismatches needs --hamming K")
@@ -133,6 +143,28 @@ for bi, tiles in enumerate(batches):
     read_gbs.append(gbs)
     t_read += tb.plane_bytes / gbs / 1e6
 (lane, trow, _), t_fin = clock(lambda: ld.finish())
+
+
+def time_distances(acc, tiles_n, t_finish, what):
+    """LaneDups.distances and, on the same labels, LaneDups.mismatches(0), each after a first call that pays for
+    loading the kernel; and the call without the matrix"""
+    acc.distances(x, y, a.radius)
+    dg, t_dg = clock(lambda: acc.distances(x, y, a.radius))
+    _, t_dg0 = clock(lambda: acc.distances(x, y, a.radius, matrix=False))
+    acc.mismatches(0)
+    dm, t_dm = clock(lambda: acc.mismatches(0))
+    row = dg[0]
+    assert row[0] == dm[0][0] and row[3:].sum() == row[1] and (dg[1].sum(axis=0) == row[:3]).all(), "the rows do not add up"
+    print("%s: distances, R = %d: %d pairs, %d on the root's tile, %d local; Dist %s; root tiles met per tile: %.1f"
+          % (what, a.radius, row[0], row[1], row[2], " ".join(str(v) for v in row[3:]),
+             float((dg[2] > 0).sum()) / max(1, tiles_n)))
+    print("  %-22s %9.3f ms  (%.4f ms per tile; without the matrix %.4f; mismatches(0): %.4f; the equality finish: %.4f)"
+          % ("lane distances", t_dg, t_dg / tiles_n, t_dg0 / tiles_n, t_dm / tiles_n, t_finish / tiles_n))
+    return row
+
+
+if a.distance:
+    time_distances(ld, max(1, a.tiles), t_fin, "the planted lane")
 ld.close()
 if a.hamming:
     near, t_near = clock(lambda: ldn.finish(hamming=a.hamming))
@@ -253,6 +285,9 @@ if a.equal:
         em, e_mm = clock(lambda: eq.mismatches(a.hamming))
         assert em[0].tolist() == [3 * n - 1, 3 * n - 1, 0, 0, 3 * n - 1] + [0] * 8
         print("  %-22s %9.3f ms  (%.4f ms per tile; the equality finish: %.4f)" % ("lane mismatches", e_mm, e_mm / 3, e_fin / 3))
+    if a.distance:
+        row = time_distances(eq, 3, e_fin, "every read equal, three tiles")
+        assert row[:2].tolist() == [3 * n - 1, n - 1], "the equal lane's pairs are not all on well 0 of tile 0"
     eq.close()
     three.free()
 
@@ -278,5 +313,25 @@ if a.mismatches:
           "near finish %.3f ms" % (at, om[0][0], om[0][5], at, om[2][at, 2, 3], o_near))
     print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("lane mismatches", o_mm, o_mm / 3))
     one.close()
+    three.free()
+if a.distance:
+    # three tiles without planted copies whose wells of odd index repeat the well to their left, cycle by cycle
+    bare = synth.SynthSpec(seed=5, n_clusters=n, row=a.cols, plant_per_64k=0)
+    three = TileBatch(sc, 3, a.cycles, n)
+    for s in range(3):
+        sc.h2d(three.filter_ptr(s), np.ones(n, dtype=np.uint8))
+        for c in range(a.cycles):
+            sc.synth_plane(three.plane_ptr(s, c), bare, 1, 1101 + s, c)
+            sc.synchronize()
+            plane = sc.d2h(three.plane_ptr(s, c), n, np.uint8).copy()
+            plane[1::2] = plane[0::2][:plane[1::2].size]
+            sc.h2d(three.plane_ptr(s, c), plane)
+    sc.synchronize()
+    nb = LaneDups(sc, n, 3, a.cycles)
+    nb.add(three, [0, 1, 2])
+    (nlane, _, _), n_fin = clock(lambda: nb.finish())
+    row = time_distances(nb, 3, n_fin, "every odd well a copy of its left neighbour, three tiles")
+    assert row[0] >= 3 * (n // 2) and row[3] >= 0.99 * row[1], "the copies do not sit beside their originals"
+    nb.close()
     three.free()
 sc.close()

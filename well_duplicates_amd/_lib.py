@@ -159,6 +159,18 @@ LANEMISMATCH_DIST_BINS = 9
 LANEMISMATCH_LANE_COLS = 4 + LANEMISMATCH_DIST_BINS
 LANEMISMATCH_TILE_COLS = 4
 
+# name -> (restype, argtypes); every symbol include/welldup_lanedistance.h declares beyond the eight above
+LANEDISTANCE_PROTOTYPES = {
+    "wd_lane_distance_scratch": (_i, [_i64, _i, _i, ctypes.POINTER(_sz)]),
+    "wd_lane_distances": (_i, [_vp, _vp, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),
+}
+LANEDISTANCE_DIST_BINS = 11
+LANEDISTANCE_LANE_COLS = 3 + LANEDISTANCE_DIST_BINS
+LANEDISTANCE_TILE_COLS = 3
+LANEDISTANCE_MAX_COORD = (1 << 24) - 1
+LANEDISTANCE_MAX_RADIUS = 1 << 25
+LANEDISTANCE_MATRIX_MAX_TILES = 4096
+
 _lib = None
 
 
@@ -245,7 +257,7 @@ def unit_of_kernel(kernel: str) -> str:
         return "ingest"
     if kernel.startswith("k_sets"):
         return "sets"
-    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_")):
+    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_")):
         return "tiledups"
     return "scan"
 
@@ -306,7 +318,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     for name, (res, args) in list(PROTOTYPES.items()) + list(SETS_PROTOTYPES.items()) + list(TILEDUPS_PROTOTYPES.items()) + \
             list(TILENEAR_PROTOTYPES.items()) + list(LANEDUPS_PROTOTYPES.items()) + list(LANENEAR_PROTOTYPES.items()) + \
-            list(LANEINDEX_PROTOTYPES.items()) + list(LANEMISMATCH_PROTOTYPES.items()):
+            list(LANEINDEX_PROTOTYPES.items()) + list(LANEMISMATCH_PROTOTYPES.items()) + \
+            list(LANEDISTANCE_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -22,7 +22,8 @@ Differences from the reference, all deliberate:
     intends (its own message formatting raises NameError first);
   * extra flags: --device, --dist-backend, --tile-batch, --threads, --strict, -o/--output,
     --all-wells, --slocs, --layout, --serial-ingest, --dup-sets, --dup-sets-out, --tile-dups, --tile-dups-out,
-    --tile-dups-hamming, --tile-dups-pair-budget, --lane-dups, --lane-dups-out;
+    --tile-dups-hamming, --tile-dups-pair-budget, --lane-dups, --lane-dups-out,
+    --lane-dups-hamming, --lane-dups-index, --lane-dups-mismatches, --lane-dups-distance;
   * --all-wells --dup-sets groups every tile's wells into duplicate sets and follows each lane's report
     with their counts and the exact duplication (report.write_dup_sets);
   * --all-wells --tile-dups groups every tile's PF wells into classes of equal reads, wherever on the tile they
@@ -37,6 +38,9 @@ Differences from the reference, all deliberate:
     library size of each, and the classes that span more than one index read (report.write_lane_index_dups);
     --lane-dups-mismatches (with --lane-dups-hamming) compares every redundant well with the first of its cluster
     and says how far apart the copies lie and at which cycles they differ (report.write_lane_mismatches);
+    --lane-dups-distance holds every redundant well against the first of its class or cluster by where the two sit:
+    on the same tile or not, how far apart, and how many closer than --lane-dups-distance-radius, the local copies
+    that the library size should not count (report.write_lane_distances);
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
@@ -213,6 +217,20 @@ def parse_args(argv=None):
                         "mismatch and substitution counts - a chain member far from the first well of its cluster is "
                         "probably another molecule; the distances themselves are counted for every pair"
                         % _lib.LANEMISMATCH_MAX_D)
+    p.add_argument("--lane-dups-distance", action="store_true",
+                   help="with --lane-dups: hold every redundant well of a lane against the first well of its class (of its "
+                        "cluster with --lane-dups-hamming) by where the two sit, and print, after every other block of the "
+                        "lane: the pairs on one tile and across tiles, the distances of the former in bins that double "
+                        "from 32 units to 16 384 beside what uniformly placed copies would give (do the copies fall off "
+                        "like a local process or lie flat like PCR copies?), the cross-tile pairs by where the other "
+                        "tile lies, and the library size estimated without the local copies.  A well is paired with "
+                        "the first well of its class, not with its nearest classmate: the block says which share of the "
+                        "within-tile redundancy that covers")
+    p.add_argument("--lane-dups-distance-radius", type=int, default=2500, metavar="R",
+                   help="with --lane-dups-distance: a copy closer than R to the first well of its class on the same tile "
+                        "is a local copy (0..%d).  R is in the units of the FASTQ header's coordinates, "
+                        "int(10 x the s.locs position + 1000.5), the units of Picard's OPTICAL_DUPLICATE_PIXEL_DISTANCE, "
+                        "whose documentation gives 2500 for patterned flowcells" % _lib.LANEDISTANCE_MAX_RADIUS)
     args = p.parse_args(argv)
     if not args.coord_file and not args.all_wells:
         p.error("the following arguments are required: -f/--coord_file (or --all-wells)")
@@ -270,6 +288,11 @@ def parse_args(argv=None):
     if args.lane_dups_mismatches_max_d is not None and not 0 <= args.lane_dups_mismatches_max_d <= _lib.LANEMISMATCH_MAX_D:
         p.error("--lane-dups-mismatches-max-d takes 0..%d, not %d" % (_lib.LANEMISMATCH_MAX_D,
                                                                      args.lane_dups_mismatches_max_d))
+    if args.lane_dups_distance and not args.lane_dups:
+        p.error("--lane-dups-distance needs --lane-dups")
+    if not 0 <= args.lane_dups_distance_radius <= _lib.LANEDISTANCE_MAX_RADIUS:
+        p.error("--lane-dups-distance-radius takes 0..%d, not %d" % (_lib.LANEDISTANCE_MAX_RADIUS,
+                                                                    args.lane_dups_distance_radius))
     if not 0.0 < args.lane_dups_index_min_share <= 1.0:
         p.error("--lane-dups-index-min-share takes a share in (0, 1], not %g" % args.lane_dups_index_min_share)
     if args.lane_dups and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -381,18 +404,19 @@ def lane_cluster_members(class_labels: np.ndarray, cluster_labels: np.ndarray):
 
 
 def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0, index: int = 0,
-                         mismatch: int = 0):
+                         mismatch: int = 0, distance: int = 0):
     """--lane-dups: the accumulator's workspace - with --lane-dups-hamming plus the scratch of the near finish, with
-    --lane-dups-index plus the index workspace, with --lane-dups-mismatches plus that pass's scratch - against the
-    free device memory, before anything is loaded."""
-    need += scratch + index + mismatch
+    --lane-dups-index plus the index workspace, with --lane-dups-mismatches or --lane-dups-distance plus that pass's
+    scratch - against the free device memory, before anything is loaded."""
+    need += scratch + index + mismatch + distance
     if need > free:
         raise MemoryError("--lane-dups needs %.2f GB of device memory for a lane of %d tiles x %d wells x %d cycles "
-                          "(%d bytes%s%s%s), and %.2f GB (%d bytes) are free" % (
+                          "(%d bytes%s%s%s%s), and %.2f GB (%d bytes) are free" % (
                               need / 1e9, tiles, wells, cycles, need,
                               ", %d of them for --lane-dups-hamming" % scratch if scratch else "",
                               ", %d of them for --lane-dups-index" % index if index else "",
-                              ", %d of them for --lane-dups-mismatches" % mismatch if mismatch else "", free / 1e9, free))
+                              ", %d of them for --lane-dups-mismatches" % mismatch if mismatch else "",
+                              ", %d of them for --lane-dups-distance" % distance if distance else "", free / 1e9, free))
 
 
 def index_listing(min_share: float, pf: int):
@@ -404,7 +428,7 @@ def index_listing(min_share: float, pf: int):
 def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells, tile_batch,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
                dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0, lane_near=0, lane_pair_budget=0,
-               lane_index=None, lane_mismatch=None):
+               lane_index=None, lane_mismatch=None, lane_distance=None):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
@@ -427,6 +451,9 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     with the members into["lmindex"][lane] = the index read of every row of into["lmembers"][lane].
     lane_mismatch = D (with lane_near): after the lane's finish, and after its index finish, LaneDups.mismatches(D):
     into["lmismatch"][lane] = LaneMismatchCounts, its cycles numbered by cycle_list.
+    lane_distance = (x, y, radius) (with lane_dups; x, y: the coordinates of a tile's wells): after everything else
+    of the lane LaneDups.distances(x, y, radius), with TilePairs up to 4096 tiles: into["ldistance"][lane] =
+    LaneDistanceCounts, on the labels the lane was left with.
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -646,6 +673,12 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                     if lane_mismatch is not None:
                         into["lmismatch"][lane] = report.LaneMismatchCounts.from_rows(
                             *ld.mismatches(lane_mismatch), names, lane_near, lane_mismatch, cycle_list)
+                    if lane_distance is not None:
+                        lx, ly, radius = lane_distance
+                        area = float(int(lx.max()) - int(lx.min())) * float(int(ly.max()) - int(ly.min())) if len(lx) else 0.0
+                        into["ldistance"][lane] = report.LaneDistanceCounts.from_rows(
+                            *ld.distances(lx, ly, radius, matrix=len(names) <= _lib.LANEDISTANCE_MATRIX_MAX_TILES), names,
+                            radius, into["lnear"][lane] if lane_near else into["ldups"][lane], area)
                     del lane_labels, got
                 _lap("batch %d: lane classes" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
@@ -921,6 +954,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                     report.write_lane_index_dups(lane, results["lindex"][lane], hamming=lane_near_k, out=out_fh)
                 if args.lane_dups_mismatches:
                     report.write_lane_mismatches(lane, results["lmismatch"][lane], verbose=not args.summary_only, out=out_fh)
+                if args.lane_dups_distance:
+                    report.write_lane_distances(lane, results["ldistance"][lane], verbose=not args.summary_only, out=out_fh)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
@@ -928,7 +963,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 # scan_lanes fills these, lane_done reads them
                 results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
                            "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}, "lnear": {}, "lindex": {},
-                           "lmindex": {}, "lmismatch": {}}
+                           "lmindex": {}, "lmismatch": {}, "ldistance": {}}
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
@@ -956,7 +991,10 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                          index=sc.lane_index_workspace_bytes(n_targets, len(tiles), len(index_cycles))
                                          if index_cycles else 0,
                                          mismatch=sc.lane_mismatch_scratch_bytes(len(tiles), len(cycle_list))
-                                         if mismatch_d is not None else 0)
+                                         if mismatch_d is not None else 0,
+                                         distance=sc.lane_distance_scratch_bytes(
+                                             n_targets, len(tiles), len(tiles) <= _lib.LANEDISTANCE_MATRIX_MAX_TILES)
+                                         if args.lane_dups_distance else 0)
                 if err is None:             # (a rank whose setup failed has nothing to scan: it goes to the flag)
                     scan_lanes(sc, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                                max(0, args.tile_batch), args.threads,
@@ -971,7 +1009,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                lane_near=lane_near_k, lane_pair_budget=args.lane_dups_pair_budget,
                                lane_index=(index_cycles, [e - s for s, e in index_ranges],
                                            args.lane_dups_index_min_share) if index_cycles else None,
-                               lane_mismatch=mismatch_d)
+                               lane_mismatch=mismatch_d,
+                               lane_distance=(xy[0], xy[1], args.lane_dups_distance_radius)
+                               if args.lane_dups_distance else None)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
                     if args.tile_dups_out and near_k:

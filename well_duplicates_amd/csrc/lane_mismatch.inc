@@ -10,7 +10,8 @@
 // refuses after a finish); label by k_ld_resolve (ld_equality, once: `resolved`) and by k_ln_pairs /
 // k_ln_pairs_long / k_ln_compress (lane_near.inc, all inside the one successful wd_lane_near_dups_finish);
 // ld_count_rows, li_tally and wd_lane_index_finish (lane_index.inc) write the table, aux and the index workspace,
-// and read label - which is why this pass keeps away from the table and aux.
+// and read label - which is why this pass keeps away from the table and aux; k_lg_tally (lane_distance.inc) reads
+// label only.
 #include "welldup_lanemismatch.h"
 
 namespace {

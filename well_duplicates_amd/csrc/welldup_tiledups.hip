@@ -14,7 +14,8 @@
 // near-duplicate clusters of welldup_tilenear.h on these parts, lane_dups.inc (after it) the classes across all
 // tiles of a lane of welldup_lanedups.h, lane_near.inc (after it) the near-duplicate clusters of a lane of
 // welldup_lanenear.h, lane_index.inc (after it) a lane's duplication per index read of welldup_laneindex.h,
-// lane_mismatch.inc (last) where a lane's duplicate copies differ of welldup_lanemismatch.h.
+// lane_mismatch.inc (after it) where a lane's duplicate copies differ of welldup_lanemismatch.h, lane_distance.inc
+// (last) how far apart they lie of welldup_lanedistance.h.
 #include <memory>
 
 #include "wd_ctx.h"
@@ -497,3 +498,4 @@ try {
 #include "lane_near.inc"      // near-duplicate clusters of a lane (include/welldup_lanenear.h) on all of the above
 #include "lane_index.inc"     // a lane's classes split by index read (include/welldup_laneindex.h)
 #include "lane_mismatch.inc"  // where a lane's duplicate copies differ (include/welldup_lanemismatch.h)
+#include "lane_distance.inc"  // how far apart a lane's duplicate copies lie (include/welldup_lanedistance.h)

@@ -773,3 +773,129 @@ def write_lane_mismatches(lane, counts: LaneMismatchCounts, verbose: bool = Fals
     print("Pairs at distance %i, the last the clusters link: %i (%.5f of the pairs at 1..%i, %.5f of Pairs)" % (
         last, c.dist[last] if last else 0, share(c.dist[last] if last else 0, near), last, share(c.dist[last] if last else 0, c.pairs)),
           file=out)
+
+
+LANE_DISTANCE_EDGES = [32 << b for b in range(10)]                     # 32, 64, .., 16384: where a Dist bin ends
+LANE_DISTANCE_DIST_NAMES = (["<32"] + ["%i-%i" % (e, 2 * e) for e in LANE_DISTANCE_EDGES[:-1]] +
+                            [">=%i" % LANE_DISTANCE_EDGES[-1]])
+LANE_DISTANCE_LANE_COLS = 3 + len(LANE_DISTANCE_DIST_NAMES)
+LANE_DISTANCE_TILE_COLS = 3
+LANE_DISTANCE_MAX_RADIUS = 1 << 25
+LANE_DISTANCE_CROSS_NAMES = ["adjacent tile of the swath", "same surface otherwise", "other surface"]
+
+
+def cross_tile_category(a: str, b: str) -> int:
+    """Where tile b lies seen from tile a, by their names S W TT (surface, swath, tile; workload.tiles_for_stype):
+    0 = same surface and swath and the next tile number, 1 = same surface otherwise, 2 = the other surface (or a
+    name that is not of that form)."""
+    a, b = str(a), str(b)
+    if len(a) < 3 or len(b) < 3 or not (a.isdigit() and b.isdigit()) or a[0] != b[0]:
+        return 2
+    return 0 if a[1] == b[1] and abs(int(a[2:]) - int(b[2:])) == 1 else 1
+
+
+@dataclass
+class LaneDistanceCounts:
+    """How far apart a lane's duplicate copies lie (include/welldup_lanedistance.h, LaneDups.distances): every
+    redundant well against its root.  The lane row's columns, per tile (by the tile's name) [Pairs, SameTile, Local],
+    the cross-tile pairs by where the root's tile lies (cross_tile_category; None without TilePairs) beside the share
+    each category would have if copies fell on tiles in proportion to their PF wells, the area of the coordinates'
+    bounding box, and from the lane row the labels belong to: PF wells, Redundant and InClasses - TileSpans."""
+    radius: int = 0
+    pairs: int = 0
+    same_tile: int = 0
+    local: int = 0
+    dist: List[int] = field(default_factory=lambda: [0] * len(LANE_DISTANCE_DIST_NAMES))
+    tiles: Dict[str, List[int]] = field(default_factory=dict)
+    cross: Optional[List[int]] = None
+    cross_by_pf: Optional[List[float]] = None
+    area: float = 0.0
+    pf: int = 0
+    redundant: int = 0
+    within_tiles: int = 0
+
+    @classmethod
+    def from_rows(cls, lane_row: Sequence[int], tile_rows: Sequence[Sequence[int]], tile_pairs, tile_names: Sequence,
+                  radius: int, final: "LaneDupCounts", area: float) -> "LaneDistanceCounts":
+        """The three results of LaneDups.distances(x, y, radius) (tile_pairs may be None); tile_names as
+        LaneDupCounts.from_rows takes them; final: the LaneDupCounts (LaneNearCounts under --lane-dups-hamming) of
+        the labels the lane was left with; area: (max x - min x) * (max y - min y) of the coordinates."""
+        b = [int(v) for v in lane_row]
+        assert len(b) == LANE_DISTANCE_LANE_COLS and 0 <= radius <= LANE_DISTANCE_MAX_RADIUS
+        tiles = {}
+        for name, row in zip(tile_names, tile_rows):
+            assert len(row) == LANE_DISTANCE_TILE_COLS
+            if name is not None:
+                tiles[name] = [int(v) for v in row]
+        cross = by_pf = None
+        if tile_pairs is not None:
+            named = [(i, name) for i, name in enumerate(tile_names) if name is not None and i < len(tile_pairs)]
+            cross, weight = [0, 0, 0], [0.0, 0.0, 0.0]
+            for i, a in named:
+                for j, c in named:
+                    if i < j:
+                        cat = cross_tile_category(a, c)
+                        cross[cat] += int(tile_pairs[i][j]) + int(tile_pairs[j][i])
+                        weight[cat] += float(final.tiles[a][0] if a in final.tiles else 0) * \
+                            float(final.tiles[c][0] if c in final.tiles else 0)
+            total = sum(weight)
+            by_pf = [w / total if total else 0.0 for w in weight]
+        return cls(int(radius), b[0], b[1], b[2], b[3:], tiles, cross, by_pf, float(area), final.pf, final.redundant,
+                   final.within_tiles)
+
+    @property
+    def cross_tile(self) -> int:
+        return self.pairs - self.same_tile
+
+    def coverage(self) -> float:
+        """SameTile / (InClasses - TileSpans): the share of the redundant wells with an earlier classmate on their own
+        tile that the pairing with the root sees as same-tile pairs (the rest: their root lies on another tile)."""
+        return self.same_tile / self.within_tiles if self.within_tiles else 0.0
+
+    def uniform_shares(self) -> List[float]:
+        """Per Dist bin the share a copy placed uniformly over the tile would have: pi (hi^2 - lo^2) / area, without
+        an edge correction, capped so that the bins sum to at most 1 (the open bin takes what is left); zeros
+        without an area."""
+        edges = [0.0] + [float(e) for e in LANE_DISTANCE_EDGES] + [math.inf]
+        if self.area <= 0:                               # (no wells, or all on a line: nothing to hold against)
+            return [0.0] * len(LANE_DISTANCE_DIST_NAMES)
+        out, left = [], 1.0
+        for lo, hi in zip(edges, edges[1:]):
+            raw = math.pi * (hi * hi - lo * lo) / self.area if hi < math.inf else math.inf
+            out.append(min(raw, left))
+            left -= out[-1]
+        return out
+
+    def library_size_without_local(self) -> Optional[float]:
+        """library_size with the local copies taken out of the reads, as other duplicate markers take out their
+        optical duplicates: (PF - Local) reads, PF - Redundant of them distinct."""
+        return library_size(self.pf - self.local, self.pf - self.redundant)
+
+
+def write_lane_distances(lane, counts: LaneDistanceCounts, verbose: bool = False, out=None) -> None:
+    """The block that closes a lane's output under --lane-dups-distance: per-tile lines (verbose, in sorted tile
+    order as write_report), then the summary: the redundant wells by where their root lies, the distances of the
+    same-tile pairs beside what uniformly placed copies would give, the cross-tile pairs by where the root's tile
+    lies beside what the tiles' PF wells would give, and the library size without the local copies."""
+    out = out or sys.stdout
+    c = counts
+    share = lambda v, of: v / of if of else 0.0
+    print(file=out)
+    if verbose:
+        for tile in sorted(c.tiles):
+            t = c.tiles[tile]
+            print("LaneDistances: %s\tTile: %s\tPairs: %i\tSameTile: %i\tLocal: %i" % (lane, tile, t[0], t[1], t[2]), file=out)
+    print("LaneDistancesSummary: %s\tTiles: %i\tR: %i\tPairs: %i\tSameTile: %i (%.5f)\tLocal: %i (%.5f)\t"
+          "SameTile of the wells with an earlier classmate on their tile: %.5f" % (
+              lane, len(c.tiles), c.radius, c.pairs, c.same_tile, share(c.same_tile, c.pairs), c.local,
+              share(c.local, c.pairs), c.coverage()), file=out)
+    print("Dist (share of SameTile; uniform~: a copy placed uniformly over the tile, an approximation without edges): %s" %
+          "\t".join("%s: %i (%.5f, uniform~ %.5f)" % (name, n, share(n, c.same_tile), u)
+                    for name, n, u in zip(LANE_DISTANCE_DIST_NAMES, c.dist, c.uniform_shares())), file=out)
+    if c.cross is not None:
+        print("Cross-tile pairs: %i\t%s" % (c.cross_tile, "\t".join(
+            "%s: %i (%.5f, by PF wells %.5f)" % (name, n, share(n, c.cross_tile), p)
+            for name, n, p in zip(LANE_DISTANCE_CROSS_NAMES, c.cross, c.cross_by_pf))), file=out)
+    size = c.library_size_without_local()
+    print("Estimated library size without local copies (R = %i; distinct/X = 1 - exp(-(PF - Local)/X)): %s" % (
+        c.radius, "n/a" if size is None else "%.0f" % size), file=out)

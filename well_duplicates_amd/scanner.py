@@ -325,6 +325,12 @@ class Scanner:
         it does not depend on the wells of a tile)."""
         return self._workspace_bytes(self._lib.wd_lane_mismatch_scratch, max_tiles, L)
 
+    def lane_distance_scratch_bytes(self, n_clusters: int, max_tiles: int, matrix: bool = True) -> int:
+        """Device bytes LaneDups.distances needs beside the accumulator's workspace (wd_lane_distance_scratch: the
+        coordinates of a tile's wells, the counters, and with `matrix` TilePairs; more than 4096 tiles with the
+        matrix raise RuntimeError)."""
+        return self._workspace_bytes(self._lib.wd_lane_distance_scratch, n_clusters, max_tiles, int(bool(matrix)))
+
     def scan_async(self, tables, n_tiles: int, L: int, n_clusters: int, mode: int, k: int,
                    out_tile_dev: int, out_per_target_dev: Optional[int] = None):
         pt, ft = tables
@@ -706,6 +712,39 @@ class LaneDups:
         finally:
             self.sc.free(d_scratch)
         return lane_row, tile_rows, sub
+
+    def distances(self, x, y, radius: int, matrix: bool = True):
+        """After finish(), any number of times, before or after index_finish and mismatches (wd_lane_distances,
+        include/welldup_lanedistance.h): every redundant well against its root under the labels the finish left, by
+        where the two lie.  x, y: the coordinates of a tile's N wells, each 0 .. 2^24 - 1.
+        -> (lane row int64 [14]: [Pairs, SameTile, Local, Dist[0..10]], tile rows int64 [max_tiles, 3]: [Pairs,
+        SameTile, Local] by the member's tile, tile pairs int64 [max_tiles, max_tiles]: [root's tile][member's tile],
+        or None without `matrix`).  The scratch is allocated for the call and released.  A radius outside 0 .. 2^25,
+        a coordinate out of range or a call before a successful finish raises ValueError."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        xs, ys = (np.asarray(v) for v in (x, y))
+        if xs.shape != (self.N,) or ys.shape != (self.N,):
+            raise ValueError("x and y hold a coordinate per well of a tile: %d each" % self.N)
+        for v in (xs, ys):                               # (what int32 cannot hold is out of range as well)
+            if v.size and (int(v.min()) < 0 or int(v.max()) > _lib.LANEDISTANCE_MAX_COORD):
+                w = int(np.flatnonzero((v < 0) | (v > _lib.LANEDISTANCE_MAX_COORD))[0])
+                raise ValueError("well %d lies at (%d, %d), outside 0..%d" % (w, xs[w], ys[w], _lib.LANEDISTANCE_MAX_COORD))
+        xs, ys = np.ascontiguousarray(xs, dtype=np.int32), np.ascontiguousarray(ys, dtype=np.int32)
+        lane_row = np.zeros(_lib.LANEDISTANCE_LANE_COLS, dtype=np.int64)
+        tile_rows = np.zeros((self.max_tiles, _lib.LANEDISTANCE_TILE_COLS), dtype=np.int64)
+        tile_pairs = np.zeros((self.max_tiles, self.max_tiles), dtype=np.int64) if matrix else None
+        sbytes = self.sc.lane_distance_scratch_bytes(self.N, self.max_tiles, matrix)
+        d_scratch = self.sc.malloc(max(1, sbytes))
+        try:
+            self.sc._ck(self.sc._lib.wd_lane_distances(
+                self._h, xs.ctypes.data_as(ctypes.c_void_p), ys.ctypes.data_as(ctypes.c_void_p), int(radius),
+                ctypes.c_void_p(d_scratch), sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
+                tile_rows.ctypes.data_as(ctypes.c_void_p),
+                tile_pairs.ctypes.data_as(ctypes.c_void_p) if matrix else None))
+        finally:
+            self.sc.free(d_scratch)
+        return lane_row, tile_rows, tile_pairs
 
     def _end(self):
         if self._h is not None:
