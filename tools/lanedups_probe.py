@@ -31,12 +31,18 @@ one bin and one root tile take every add of a wave) and a lane of three tiles wh
 their left neighbour (everything in Dist[0] and Local).  The call includes the host's check, interleaving and upload
 of the coordinates (8 bytes per well of a tile, once per call whatever the tiles): the kernel's own time is the
 k_lg_tally row of the trace below, the rest of the call is that host part.
+`--hamming K --quality` times the lane's reported base quality against its copies (include/welldup_lanequality.h):
+LaneDups.qual_add per tile beside add on the same batches, and LaneDups.qualities(K) per tile beside mismatches(K) and
+the equality finish, on three inputs: the planted lane (39 quality levels, the CLI's default bins), the `--equal` lane,
+whose bases all carry one quality value (every well a profiled pair, every observation in one cell of Obs: the case the
+counting inside a lane is there for), and the `--equal` lane with random qualities (every cell of Obs, no two
+neighbouring cycles alike).
 For per-kernel times run it under
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/lanedups_probe.py
 
-(the k_ld_* rows of the stats are this stage, k_li_* the index part, k_lm_* the mismatch pass, k_lg_* the distance pass, k_td_* the per-tile classes, k_dense_* the
-scan)."""
+(the k_ld_* rows of the stats are this stage, k_li_* the index part, k_lm_* the mismatch pass, k_lg_* the distance pass,
+k_lq_* the quality part, k_td_* the per-tile classes, k_dense_* the scan)."""
 import argparse
 import os
 import sys
@@ -68,9 +74,15 @@ ap.add_argument("--mismatches", action="store_true",
 ap.add_argument("--distance", action="store_true",
                 help="also time LaneDups.distances beside the equality finish and mismatches (three inputs with --equal)")
 ap.add_argument("--radius", type=int, default=2500, metavar="R", help="the radius of --distance")
+ap.add_argument("--quality", action="store_true",
+                help="also time LaneDups.qual_add beside add and LaneDups.qualities(K) beside mismatches(K) (needs "
+                     "--hamming; three inputs with --equal)")
 a = ap.parse_args()
 if a.mismatches and not a.hamming:
     ap.error("--mismatches needs --hamming K")
+if a.quality and not a.hamming:
+    ap.error("--quality needs --hamming K")
+QUALITY_BINS = [0, 2, 10, 20, 25, 30, 35, 40]         # the CLI's default
 
 n = a.rows * a.cols
 x, y = synth.honeycomb_pixels(a.rows, a.cols)
@@ -105,7 +117,10 @@ batches = [list(range(b0, min(a.tiles, b0 + a.batch))) for b0 in range(0, a.tile
 tbs = [TileBatch(sc, a.batch, a.cycles, n), TileBatch(sc, a.batch, a.cycles, n)] if a.tiles else []
 ld = LaneDups(sc, n, a.tiles, a.cycles)
 ldn = LaneDups(sc, n, a.tiles, a.cycles) if a.hamming else None
-t_add = t_td = t_cnt = t_read = t_tn = 0.0
+if a.quality:
+    print("quality part: workspace %.2f GB" % (sc.lane_qual_workspace_bytes(n, a.tiles, a.cycles) / 1e9))
+    ldn.qual_begin(QUALITY_BINS)
+t_add = t_td = t_cnt = t_read = t_tn = t_qadd = 0.0
 read_gbs = []
 td_pf = td_red = 0
 for bi, tiles in enumerate(batches):
@@ -123,6 +138,9 @@ for bi, tiles in enumerate(batches):
         tb.count(0, 0)
         if a.hamming:
             warm = LaneDups(sc, n, len(tiles), a.cycles)
+            if a.quality:
+                warm.qual_begin(QUALITY_BINS)
+                warm.qual_add(tb, list(range(len(tiles))))
             warm.add(tb, list(range(len(tiles))))
             warm.finish(hamming=a.hamming)
             warm.close()
@@ -131,6 +149,9 @@ for bi, tiles in enumerate(batches):
     t_add += dt
     if a.hamming:
         ldn.add(tb, tiles)
+        if a.quality:
+            _, dt = clock(lambda: ldn.qual_add(tb, tiles))
+            t_qadd += dt
         _, dt = clock(lambda: tb.tile_near_dups(a.hamming))
         t_tn += dt
     (rows, _), dt = clock(lambda: tb.tile_dups())
@@ -163,6 +184,26 @@ def time_distances(acc, tiles_n, t_finish, what):
     return row
 
 
+def time_qualities(acc, tiles_n, t_finish, t_qual_add, t_plain_add, what):
+    """LaneDups.qualities(K) and, on the same labels, LaneDups.mismatches(K), each after a first call that pays for
+    loading the kernel"""
+    acc.qualities(a.hamming)
+    q, t_q = clock(lambda: acc.qualities(a.hamming))
+    acc.mismatches(a.hamming)
+    m, t_m = clock(lambda: acc.mismatches(a.hamming))
+    row = q[0]
+    assert (row[[0, 1, 3]] == m[0][:3]).all() and q[3].sum() == row[2] == row[1] * a.cycles and q[4].sum() == row[3], \
+        "the quality rows do not add up"
+    print("%s: qualities, max_d %d: %d pairs, %d profiled, %d observations in %d cells of Obs (the fullest holds %.4f), "
+          "%d mismatches in %d cells of Mis; %d quality values seen"
+          % (what, a.hamming, row[0], row[1], row[2], int((q[3] > 0).sum()), q[3].max() / max(1, row[2]), row[3],
+             int((q[4] > 0).sum()), int((q[2] > 0).sum())))
+    print("  %-22s %9.3f ms  (%.4f ms per tile; add: %.4f; qual_add / add = %.2f)"
+          % ("lane qual_add", t_qual_add, t_qual_add / tiles_n, t_plain_add / tiles_n, t_qual_add / t_plain_add))
+    print("  %-22s %9.3f ms  (%.4f ms per tile; mismatches(%d): %.4f; qualities / mismatches = %.2f; the equality finish: "
+          "%.4f)" % ("lane qualities", t_q, t_q / tiles_n, a.hamming, t_m / tiles_n, t_q / t_m, t_finish / tiles_n))
+
+
 if a.distance:
     time_distances(ld, max(1, a.tiles), t_fin, "the planted lane")
 ld.close()
@@ -172,6 +213,8 @@ if a.hamming:
         ldn.mismatches(a.hamming)                    # (the first call of a kernel pays for loading it)
         mm, t_mm = clock(lambda: ldn.mismatches(a.hamming))
         assert mm[0][0] == near[3][3] and mm[0][4:].sum() == mm[0][0], "Pairs is not the near finish's Redundant"
+    if a.quality:
+        time_qualities(ldn, max(1, a.tiles), t_fin, t_qadd, t_add, "the planted lane")
     ldn.close()
     assert (near[0] == lane).all() and (near[1] == trow).all(), "the near finish delivers other classes"
 for tb in tbs:
@@ -276,7 +319,11 @@ if a.equal:
     for s in range(3):
         three.upload_tile(s, [np.full(n, 0x42 + (c % 4), dtype=np.uint8) for c in range(a.cycles)], np.ones(n, dtype=np.uint8))
     eq = LaneDups(sc, n, 3, a.cycles)
+    if a.quality:
+        eq.qual_begin(QUALITY_BINS)
     _, e_add = clock(lambda: eq.add(three, [0, 1, 2]))
+    if a.quality:
+        _, e_qadd = clock(lambda: eq.qual_add(three, [0, 1, 2]))
     (lane, trow, _), e_fin = clock(lambda: eq.finish())
     assert lane[:6].tolist() == [3 * n, 1, 3 * n, 3 * n - 1, 1, 3]
     print("every read equal, three tiles: add %.3f ms, finish %.3f ms" % (e_add, e_fin))
@@ -288,6 +335,22 @@ if a.equal:
     if a.distance:
         row = time_distances(eq, 3, e_fin, "every read equal, three tiles")
         assert row[:2].tolist() == [3 * n - 1, n - 1], "the equal lane's pairs are not all on well 0 of tile 0"
+    if a.quality:
+        time_qualities(eq, 3, e_fin, e_qadd, e_add, "every read equal, one quality value, three tiles")
+        # the same bases under random qualities 1..63: eight random planes take turns
+        rng = np.random.default_rng(13)
+        pool = [rng.integers(1, 64, n).astype(np.uint8) << 2 for _ in range(8)]
+        for s in range(3):
+            for c in range(a.cycles):
+                sc.h2d(three.plane_ptr(s, c), pool[(3 * s + c) % 8] | np.uint8((0x42 + c % 4) & 3))
+        sc.synchronize()
+        rq = LaneDups(sc, n, 3, a.cycles)
+        rq.qual_begin(QUALITY_BINS)
+        _, r_add = clock(lambda: rq.add(three, [0, 1, 2]))
+        _, r_qadd = clock(lambda: rq.qual_add(three, [0, 1, 2]))
+        _, r_fin = clock(lambda: rq.finish())
+        time_qualities(rq, 3, r_fin, r_qadd, r_add, "every read equal, random qualities, three tiles")
+        rq.close()
     eq.close()
     three.free()
 

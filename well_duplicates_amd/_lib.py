@@ -171,6 +171,20 @@ LANEDISTANCE_MAX_COORD = (1 << 24) - 1
 LANEDISTANCE_MAX_RADIUS = 1 << 25
 LANEDISTANCE_MATRIX_MAX_TILES = 4096
 
+# name -> (restype, argtypes); every symbol include/welldup_lanequality.h declares beyond the nine above
+LANEQUALITY_PROTOTYPES = {
+    "wd_lane_qual_workspace": (_i, [_i64, _i, _i, ctypes.POINTER(_sz)]),
+    "wd_lane_qual_begin": (_i, [_vp, _i, ctypes.POINTER(_i), _vp, _sz]),
+    "wd_lane_qual_add": (_i, [_vp, _i, ctypes.POINTER(_i), _pp, _pp]),
+    "wd_lane_qual_scratch": (_i, [_i, ctypes.POINTER(_sz)]),
+    "wd_lane_qualities": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+}
+LANEQUALITY_MAX_BINS = 8
+LANEQUALITY_VALUES = 64
+LANEQUALITY_MAX_D = LANEMISMATCH_MAX_D
+LANEQUALITY_LANE_COLS = 4
+LANEQUALITY_TILE_COLS = 4
+
 _lib = None
 
 
@@ -257,7 +271,7 @@ def unit_of_kernel(kernel: str) -> str:
         return "ingest"
     if kernel.startswith("k_sets"):
         return "sets"
-    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_")):
+    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_")):
         return "tiledups"
     return "scan"
 
@@ -319,7 +333,7 @@ def load():
     for name, (res, args) in list(PROTOTYPES.items()) + list(SETS_PROTOTYPES.items()) + list(TILEDUPS_PROTOTYPES.items()) + \
             list(TILENEAR_PROTOTYPES.items()) + list(LANEDUPS_PROTOTYPES.items()) + list(LANENEAR_PROTOTYPES.items()) + \
             list(LANEINDEX_PROTOTYPES.items()) + list(LANEMISMATCH_PROTOTYPES.items()) + \
-            list(LANEDISTANCE_PROTOTYPES.items()):
+            list(LANEDISTANCE_PROTOTYPES.items()) + list(LANEQUALITY_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -23,7 +23,7 @@ Differences from the reference, all deliberate:
   * extra flags: --device, --dist-backend, --tile-batch, --threads, --strict, -o/--output,
     --all-wells, --slocs, --layout, --serial-ingest, --dup-sets, --dup-sets-out, --tile-dups, --tile-dups-out,
     --tile-dups-hamming, --tile-dups-pair-budget, --lane-dups, --lane-dups-out,
-    --lane-dups-hamming, --lane-dups-index, --lane-dups-mismatches, --lane-dups-distance;
+    --lane-dups-hamming, --lane-dups-index, --lane-dups-mismatches, --lane-dups-distance, --lane-dups-quality;
   * --all-wells --dup-sets groups every tile's wells into duplicate sets and follows each lane's report
     with their counts and the exact duplication (report.write_dup_sets);
   * --all-wells --tile-dups groups every tile's PF wells into classes of equal reads, wherever on the tile they
@@ -40,7 +40,10 @@ Differences from the reference, all deliberate:
     and says how far apart the copies lie and at which cycles they differ (report.write_lane_mismatches);
     --lane-dups-distance holds every redundant well against the first of its class or cluster by where the two sit:
     on the same tile or not, how far apart, and how many closer than --lane-dups-distance-radius, the local copies
-    that the library size should not count (report.write_lane_distances);
+    that the library size should not count (report.write_lane_distances); --lane-dups-quality keeps the reported
+    quality of every base beside the reads and counts the (copy, cycle) observations by the quality bins of the two
+    wells, all of them and those where the bases differ: the error rate among copies per reported quality
+    (report.write_lane_qualities);
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
@@ -231,7 +234,40 @@ def parse_args(argv=None):
                         "is a local copy (0..%d).  R is in the units of the FASTQ header's coordinates, "
                         "int(10 x the s.locs position + 1000.5), the units of Picard's OPTICAL_DUPLICATE_PIXEL_DISTANCE, "
                         "whose documentation gives 2500 for patterned flowcells" % _lib.LANEDISTANCE_MAX_RADIUS)
+    p.add_argument("--lane-dups-quality", action="store_true",
+                   help="with --lane-dups: keep the reported quality (byte >> 2) of every base of a lane beside its "
+                        "reads, hold every redundant well against the first well of its class (of its cluster with "
+                        "--lane-dups-hamming K) cycle by cycle, and print, after every other block of the lane, a line per "
+                        "quality bin: the raw values seen in it, its share of the lane's bases, of the first wells' and "
+                        "of the copies', and the error rate observed among copies reported in that bin beside the "
+                        "quality it amounts to - an empirical quality table of the run without an alignment.  The rates "
+                        "are truncated from above (the clusters only link within K) and distinct molecules within K "
+                        "inflate them; without --lane-dups-hamming every copy is identical and only the reported "
+                        "qualities of the copies against the lane's are shown.  Doubles the device memory of a lane's "
+                        "packed reads")
+    p.add_argument("--lane-dups-quality-bins", default=None, metavar="E0,E1,..",
+                   help="with --lane-dups-quality: the lower edges of 1..%d quality bins, ascending from 0, at most 63 "
+                        "(default %s: no-call, then the ranges of the instruments' 8-level quality binning).  For an "
+                        "instrument that reports a few quality levels give its levels: the bins are then exact - the "
+                        "block prints the raw values seen in every bin, so a wrong choice shows"
+                        % (_lib.LANEQUALITY_MAX_BINS, ",".join(str(e) for e in DEFAULT_QUALITY_BINS)))
+    p.add_argument("--lane-dups-quality-max-d", type=int, default=None, metavar="D",
+                   help="with --lane-dups-quality: only pairs at most D cycles apart enter the table (0..%d; default "
+                        "--lane-dups-mismatches-max-d where --lane-dups-mismatches is given, else K)"
+                        % _lib.LANEQUALITY_MAX_D)
     args = p.parse_args(argv)
+    if args.lane_dups_quality and not args.lane_dups:
+        p.error("--lane-dups-quality needs --lane-dups")
+    if args.lane_dups_quality_bins is not None and not args.lane_dups_quality:
+        p.error("--lane-dups-quality-bins needs --lane-dups-quality")
+    if args.lane_dups_quality_max_d is not None and not args.lane_dups_quality:
+        p.error("--lane-dups-quality-max-d needs --lane-dups-quality")
+    if args.lane_dups_quality_max_d is not None and not 0 <= args.lane_dups_quality_max_d <= _lib.LANEQUALITY_MAX_D:
+        p.error("--lane-dups-quality-max-d takes 0..%d, not %d" % (_lib.LANEQUALITY_MAX_D, args.lane_dups_quality_max_d))
+    try:
+        args.lane_dups_quality_edges = parse_quality_bins(args.lane_dups_quality_bins)
+    except ValueError as e:
+        p.error("--lane-dups-quality-bins: %s" % e)
     if not args.coord_file and not args.all_wells:
         p.error("the following arguments are required: -f/--coord_file (or --all-wells)")
     if args.layout == "interleaved" and (args.all_wells or (args.edit_distance > 3 and not args.hamming)):
@@ -299,6 +335,28 @@ def parse_args(argv=None):
         p.error("--lane-dups runs in a single process only: under WORLD_SIZE > 1 a lane's tiles are spread over the "
                 "ranks, and the classes of a lane need all of them in one GPU's table")
     return args
+
+
+DEFAULT_QUALITY_BINS = [0, 2, 10, 20, 25, 30, 35, 40]
+
+
+def parse_quality_bins(text):
+    """--lane-dups-quality-bins E0,E1,.. -> the edges (None: the default); ValueError says what is wrong with them."""
+    if text is None:
+        return list(DEFAULT_QUALITY_BINS)
+    try:
+        edges = [int(e) for e in text.split(",")]
+    except ValueError:
+        raise ValueError("a comma-separated list of integers, not %r" % text)
+    if not 1 <= len(edges) <= _lib.LANEQUALITY_MAX_BINS:
+        raise ValueError("1..%d lower edges, not %d" % (_lib.LANEQUALITY_MAX_BINS, len(edges)))
+    if edges[0] != 0:
+        raise ValueError("the first edge is 0 (every quality has a bin), not %d" % edges[0])
+    if any(b < a for a, b in zip(edges, edges[1:])):
+        raise ValueError("the edges ascend")
+    if edges[-1] >= _lib.LANEQUALITY_VALUES:
+        raise ValueError("a quality is at most %d, not %d" % (_lib.LANEQUALITY_VALUES - 1, edges[-1]))
+    return edges
 
 
 _T0 = [0.0]
@@ -404,19 +462,20 @@ def lane_cluster_members(class_labels: np.ndarray, cluster_labels: np.ndarray):
 
 
 def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0, index: int = 0,
-                         mismatch: int = 0, distance: int = 0):
+                         mismatch: int = 0, distance: int = 0, quality: int = 0):
     """--lane-dups: the accumulator's workspace - with --lane-dups-hamming plus the scratch of the near finish, with
     --lane-dups-index plus the index workspace, with --lane-dups-mismatches or --lane-dups-distance plus that pass's
-    scratch - against the free device memory, before anything is loaded."""
-    need += scratch + index + mismatch + distance
+    scratch, with --lane-dups-quality plus the quality workspace and that pass's scratch - against the free device memory, before anything is loaded."""
+    need += scratch + index + mismatch + distance + quality
     if need > free:
         raise MemoryError("--lane-dups needs %.2f GB of device memory for a lane of %d tiles x %d wells x %d cycles "
-                          "(%d bytes%s%s%s%s), and %.2f GB (%d bytes) are free" % (
+                          "(%d bytes%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
                               need / 1e9, tiles, wells, cycles, need,
                               ", %d of them for --lane-dups-hamming" % scratch if scratch else "",
                               ", %d of them for --lane-dups-index" % index if index else "",
                               ", %d of them for --lane-dups-mismatches" % mismatch if mismatch else "",
-                              ", %d of them for --lane-dups-distance" % distance if distance else "", free / 1e9, free))
+                              ", %d of them for --lane-dups-distance" % distance if distance else "",
+                              ", %d of them for --lane-dups-quality" % quality if quality else "", free / 1e9, free))
 
 
 def index_listing(min_share: float, pf: int):
@@ -428,7 +487,7 @@ def index_listing(min_share: float, pf: int):
 def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells, tile_batch,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
                dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0, lane_near=0, lane_pair_budget=0,
-               lane_index=None, lane_mismatch=None, lane_distance=None):
+               lane_index=None, lane_mismatch=None, lane_distance=None, lane_quality=None):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
@@ -454,6 +513,9 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     lane_distance = (x, y, radius) (with lane_dups; x, y: the coordinates of a tile's wells): after everything else
     of the lane LaneDups.distances(x, y, radius), with TilePairs up to 4096 tiles: into["ldistance"][lane] =
     LaneDistanceCounts, on the labels the lane was left with.
+    lane_quality = (edges, D) (with lane_dups): the accumulator gets a quality part with these bins, every batch is
+    fed to LaneDups.qual_add beside add, and after everything else of the lane LaneDups.qualities(D):
+    into["lquality"][lane] = LaneQualityCounts, on the labels the lane was left with.
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -649,8 +711,12 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                         ld = lane_acc["ld"] = LaneDups(sc, n_clusters, len(names), len(cycle_list))
                         if index_cycles:
                             ld.index_begin(len(index_cycles))
+                        if lane_quality is not None:
+                            ld.qual_begin(lane_quality[0])
                     lane_acc["lane"] = lane
                 ld.add(tb, [names.index(t) for t in chunk])
+                if lane_quality is not None:
+                    ld.qual_add(tb, [names.index(t) for t in chunk])
                 if index_cycles:
                     ld.index_add(index_tb[id(tb)], [names.index(t) for t in chunk])
                 if last_batch_of[lane] == bi:
@@ -679,6 +745,9 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                         into["ldistance"][lane] = report.LaneDistanceCounts.from_rows(
                             *ld.distances(lx, ly, radius, matrix=len(names) <= _lib.LANEDISTANCE_MATRIX_MAX_TILES), names,
                             radius, into["lnear"][lane] if lane_near else into["ldups"][lane], area)
+                    if lane_quality is not None:
+                        into["lquality"][lane] = report.LaneQualityCounts.from_rows(
+                            *ld.qualities(lane_quality[1]), names, lane_near, lane_quality[1], lane_quality[0])
                     del lane_labels, got
                 _lap("batch %d: lane classes" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
@@ -917,6 +986,10 @@ def _main(args, log, wdist, rank, world, device, opener, early):
             mismatch_d = None
             if args.lane_dups_mismatches:
                 mismatch_d = lane_near_k if args.lane_dups_mismatches_max_d is None else args.lane_dups_mismatches_max_d
+            quality_d = None
+            if args.lane_dups_quality:
+                quality_d = args.lane_dups_quality_max_d if args.lane_dups_quality_max_d is not None else \
+                    mismatch_d if mismatch_d is not None else lane_near_k
             ntn = 5 + 2 * levels + len(report.CLASS_BIN_NAMES) if near_k else 0
             rows = np.zeros((len(mine), ncnt + nsets + ntd + ntn), dtype=np.int64)
             logs = {}
@@ -956,6 +1029,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                     report.write_lane_mismatches(lane, results["lmismatch"][lane], verbose=not args.summary_only, out=out_fh)
                 if args.lane_dups_distance:
                     report.write_lane_distances(lane, results["ldistance"][lane], verbose=not args.summary_only, out=out_fh)
+                if args.lane_dups_quality:
+                    report.write_lane_qualities(lane, results["lquality"][lane], verbose=not args.summary_only, out=out_fh)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
@@ -963,7 +1038,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 # scan_lanes fills these, lane_done reads them
                 results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
                            "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}, "lnear": {}, "lindex": {},
-                           "lmindex": {}, "lmismatch": {}, "ldistance": {}}
+                           "lmindex": {}, "lmismatch": {}, "ldistance": {}, "lquality": {}}
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
@@ -994,7 +1069,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                          if mismatch_d is not None else 0,
                                          distance=sc.lane_distance_scratch_bytes(
                                              n_targets, len(tiles), len(tiles) <= _lib.LANEDISTANCE_MATRIX_MAX_TILES)
-                                         if args.lane_dups_distance else 0)
+                                         if args.lane_dups_distance else 0,
+                                         quality=sc.lane_qual_workspace_bytes(n_targets, len(tiles), len(cycle_list)) +
+                                         sc.lane_qual_scratch_bytes(len(tiles)) if quality_d is not None else 0)
                 if err is None:             # (a rank whose setup failed has nothing to scan: it goes to the flag)
                     scan_lanes(sc, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                                max(0, args.tile_batch), args.threads,
@@ -1011,7 +1088,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                            args.lane_dups_index_min_share) if index_cycles else None,
                                lane_mismatch=mismatch_d,
                                lane_distance=(xy[0], xy[1], args.lane_dups_distance_radius)
-                               if args.lane_dups_distance else None)
+                               if args.lane_dups_distance else None,
+                               lane_quality=(args.lane_dups_quality_edges, quality_d) if quality_d is not None else None)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
                     if args.tile_dups_out and near_k:

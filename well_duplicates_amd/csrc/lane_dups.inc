@@ -103,6 +103,24 @@ __device__ inline void ld_pack_well(const uint8_t *const *pl, int L, int words, 
     members[g] = 0;
 }
 
+// The kc words staged word-major in s_words, written out as words k .. k + kc - 1 of the wave's first n_quad rows
+// (k_lq_pack, lane_quality.inc, stores its quality rows the same way).
+__device__ inline void ld_store_staged(const uint32_t *s_words, uint32_t *__restrict__ out, int words, int k, int kc,
+                                       int n_quad, int lane)
+{
+    if (kc == kLdChunk) {
+        for (int e = lane; e < n_quad * kLdChunk; e += kWave) {
+            const int well = e / kLdChunk, j = e % kLdChunk;
+            out[(size_t)well * words + k + j] = s_words[j * kLdStride + well];
+        }
+    } else {                                                               // the last words of a row
+        for (int e = lane; e < n_quad * kc; e += kWave) {
+            const int well = e / kc, j = e - well * kc;
+            out[(size_t)well * words + k + j] = s_words[j * kLdStride + well];
+        }
+    }
+}
+
 // VEC4 (every plane 4-byte aligned): grid (ceil(N / 256), n_tiles of the batch), 64 threads, a lane folds wells
 // 4 i .. 4 i + 3.  Else: grid (ceil(N / 256), n_tiles), 256 threads, a lane one well.
 template <bool VEC4>
@@ -145,17 +163,7 @@ __global__ void __launch_bounds__(VEC4 ? kWave : kTdBlock) k_ld_pack(const uint8
             }
         }
         __syncthreads();
-        if (kc == kLdChunk) {
-            for (int e = lane; e < n_quad * kLdChunk; e += kWave) {
-                const int well = e / kLdChunk, j = e % kLdChunk;
-                out[(size_t)well * words + k + j] = s_words[j * kLdStride + well];
-            }
-        } else {                                                           // the last words of a row
-            for (int e = lane; e < n_quad * kc; e += kWave) {
-                const int well = e / kc, j = e - well * kc;
-                out[(size_t)well * words + k + j] = s_words[j * kLdStride + well];
-            }
-        }
+        ld_store_staged(s_words, out, words, k, kc, n_quad, lane);
         k += kc;
         __syncthreads();
     }
@@ -387,6 +395,7 @@ __global__ void __launch_bounds__(kTdBlock) k_ld_span_sum(const int *__restrict_
 }  // namespace
 
 struct wd_lane_index;                              // lane_index.inc: the index part of an accumulator
+struct wd_lane_quality;                            // lane_quality.inc: the quality part of an accumulator
 
 // the host side of an accumulator (the device side is the caller's workspace)
 struct wd_lane_dups {
@@ -402,6 +411,7 @@ struct wd_lane_dups {
     bool resolved;
     std::vector<int64_t> eq_lane, eq_tiles;
     std::shared_ptr<wd_lane_index> index;          // null unless wd_lane_index_begin has been called
+    std::shared_ptr<wd_lane_quality> qual;         // null unless wd_lane_qual_begin has been called
 };
 
 namespace {

@@ -27,6 +27,7 @@ constexpr int kLmLaneCnt = 16;                     // per copy: Dist
 static_assert(kLmBins == kLmMaxD + 2 && kLmBins <= kLmLaneCnt, "Dist has a bin per distance up to max_d and an open one");
 static_assert(kLmRun % kTdBlock == 0, "a run is whole trips of the workgroup");
 static_assert(kLmWindow % kFpCycles == 0 && kLmWindow * kLmCell * 4 <= 16384, "the window: whole words, 16 KB of LDS");
+constexpr uint32_t kLmLow = 0x09249249u;             // the lowest bit of each of a word's ten codes
 static_assert(kMaxCycles <= 1024, "a noted mismatch keeps its cycle in ten bits");
 
 // the scratch (include/welldup_lanemismatch.h states the arithmetic)
@@ -65,14 +66,21 @@ struct LmNotes {
     }
 };
 
+// The codes of two words that differ, one bit each at the code's lowest bit (ln_diff's fold); k_lq_tally
+// (lane_quality.inc) holds the same mask against the qualities.
+__device__ inline uint32_t lm_fold(uint32_t x, uint32_t y)
+{
+    const uint32_t z = x ^ y;
+    return (z | (z >> 1) | (z >> 2)) & kLmLow;
+}
+
 // Word k of the root's row (x) and of the member's (y): the differing codes, one bit each at the code's lowest bit
-// (ln_diff's fold), counted into d; while fewer than kLmMaxD are noted, each is noted.  The row format is
+// (lm_fold), counted into d; while fewer than kLmMaxD are noted, each is noted.  The row format is
 // k_ld_pack's: cycle 10 k + j at bits 3 j .. 3 j + 2 of word k, the unused codes of the last word zero in both
 // rows - they never differ.
 __device__ inline void lm_word(int k, uint32_t x, uint32_t y, int &d, LmNotes &notes)
 {
-    const uint32_t z = x ^ y;
-    uint32_t m = (z | (z >> 1) | (z >> 2)) & 0x09249249u;
+    uint32_t m = lm_fold(x, y);
     if (!m)
         return;
     int n = d;

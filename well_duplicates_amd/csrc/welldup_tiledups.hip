@@ -15,7 +15,9 @@
 // tiles of a lane of welldup_lanedups.h, lane_near.inc (after it) the near-duplicate clusters of a lane of
 // welldup_lanenear.h, lane_index.inc (after it) a lane's duplication per index read of welldup_laneindex.h,
 // lane_mismatch.inc (after it) where a lane's duplicate copies differ of welldup_lanemismatch.h, lane_distance.inc
-// (last) how far apart they lie of welldup_lanedistance.h.
+// (last) how far apart they lie of welldup_lanedistance.h: all of these work on the accumulator as lane_dups.inc laid
+// it out.  lane_quality.inc, behind them, gives it a second packed array - the reported base qualities - and holds
+// them against the copies: welldup_lanequality.h.
 #include <memory>
 
 #include "wd_ctx.h"
@@ -499,3 +501,4 @@ try {
 #include "lane_index.inc"     // a lane's classes split by index read (include/welldup_laneindex.h)
 #include "lane_mismatch.inc"  // where a lane's duplicate copies differ (include/welldup_lanemismatch.h)
 #include "lane_distance.inc"  // how far apart a lane's duplicate copies lie (include/welldup_lanedistance.h)
+#include "lane_quality.inc"   // reported base quality against a lane's duplicate copies (include/welldup_lanequality.h)

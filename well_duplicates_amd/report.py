@@ -899,3 +899,138 @@ def write_lane_distances(lane, counts: LaneDistanceCounts, verbose: bool = False
     size = c.library_size_without_local()
     print("Estimated library size without local copies (R = %i; distinct/X = 1 - exp(-(PF - Local)/X)): %s" % (
         c.radius, "n/a" if size is None else "%.0f" % size), file=out)
+
+
+LANE_QUALITY_MAX_D = 7
+LANE_QUALITY_MAX_BINS = 8
+LANE_QUALITY_VALUES = 64
+LANE_QUALITY_COLS = 4
+
+
+@dataclass
+class LaneQualityCounts:
+    """A lane's reported base quality against its duplicate copies (include/welldup_lanequality.h,
+    LaneDups.qualities): the bins' lower edges, the lane row's columns, per tile (by the tile's name) [Pairs,
+    Profiled, Observations, Mismatches], QHist by raw quality, and Obs and Mis by [root's bin][member's bin] over the
+    pairs with d <= max_d.  k = 0: the labels are classes, every copy is identical."""
+    k: int = 0
+    max_d: int = 0
+    edges: List[int] = field(default_factory=lambda: [0])
+    pairs: int = 0
+    profiled: int = 0
+    observations: int = 0
+    mismatches: int = 0
+    tiles: Dict[str, List[int]] = field(default_factory=dict)
+    qhist: List[int] = field(default_factory=lambda: [0] * LANE_QUALITY_VALUES)
+    obs: List[List[int]] = field(default_factory=lambda: [[0] * LANE_QUALITY_MAX_BINS for _ in range(LANE_QUALITY_MAX_BINS)])
+    mis: List[List[int]] = field(default_factory=lambda: [[0] * LANE_QUALITY_MAX_BINS for _ in range(LANE_QUALITY_MAX_BINS)])
+
+    @classmethod
+    def from_rows(cls, lane_row: Sequence[int], tile_rows: Sequence[Sequence[int]], qhist, obs, mis, tile_names: Sequence,
+                  k: int, max_d: int, edges: Sequence[int]) -> "LaneQualityCounts":
+        """The five results of LaneDups.qualities(max_d); tile_names as LaneDupCounts.from_rows takes them; edges: what
+        LaneDups.qual_begin got."""
+        b = [int(v) for v in lane_row]
+        edges = [int(e) for e in edges]
+        assert len(b) == LANE_QUALITY_COLS and 0 <= max_d <= LANE_QUALITY_MAX_D
+        assert 1 <= len(edges) <= LANE_QUALITY_MAX_BINS and edges[0] == 0 and edges == sorted(edges) and edges[-1] < LANE_QUALITY_VALUES
+        tiles = {}
+        for name, row in zip(tile_names, tile_rows):
+            assert len(row) == LANE_QUALITY_COLS
+            if name is not None:
+                tiles[name] = [int(v) for v in row]
+        qhist = [int(v) for v in qhist]
+        obs, mis = ([[int(v) for v in row] for row in m] for m in (obs, mis))
+        assert len(qhist) == LANE_QUALITY_VALUES
+        assert all(len(m) == LANE_QUALITY_MAX_BINS and all(len(row) == LANE_QUALITY_MAX_BINS for row in m) for m in (obs, mis))
+        return cls(int(k), int(max_d), edges, b[0], b[1], b[2], b[3], tiles, qhist, obs, mis)
+
+    def bin_range(self, b: int):
+        """-> (lowest, highest quality of bin b); highest < lowest for a bin that an equal edge leaves empty"""
+        return self.edges[b], (self.edges[b + 1] if b + 1 < len(self.edges) else LANE_QUALITY_VALUES) - 1
+
+    def values(self, b: int) -> List[int]:
+        """the raw qualities seen in bin b"""
+        lo, hi = self.bin_range(b)
+        return [q for q in range(lo, hi + 1) if self.qhist[q]]
+
+    def seen(self, b: int) -> int:
+        """the PF observations of the lane in bin b"""
+        lo, hi = self.bin_range(b)
+        return sum(self.qhist[lo:hi + 1])
+
+    def roots(self, b: int) -> int:
+        return sum(self.obs[b])
+
+    def members(self, b: int) -> int:
+        return sum(row[b] for row in self.obs)
+
+    def occupied(self) -> List[int]:
+        return [b for b in range(len(self.edges)) if self.seen(b) or self.roots(b) or self.members(b)]
+
+    def mean_quality(self, b: int) -> Optional[float]:
+        lo, hi = self.bin_range(b)
+        n = self.seen(b)
+        return sum(q * self.qhist[q] for q in range(lo, hi + 1)) / n if n else None
+
+    def error_rate(self, b: int) -> Optional[float]:
+        """Mis[b][b] / (2 x Obs[b][b]): the two bases of such an observation were reported alike, so either is as
+        likely to be the wrong one.  None without an observation."""
+        return self.mis[b][b] / (2 * self.obs[b][b]) if self.obs[b][b] else None
+
+    def error_rate_against_top(self, b: int) -> Optional[float]:
+        """(Mis[b][t] + Mis[t][b]) / (Obs[b][t] + Obs[t][b]) - error_rate(t), not below 0, t the highest occupied bin:
+        what is left for the base of bin b once the other's share is taken off.  None for t itself and without an
+        observation on either side."""
+        occ = self.occupied()
+        t = occ[-1] if occ else None
+        if t is None or b == t or self.error_rate(t) is None:
+            return None
+        den = self.obs[b][t] + self.obs[t][b]
+        return max(0.0, (self.mis[b][t] + self.mis[t][b]) / den - self.error_rate(t)) if den else None
+
+
+def phred(rate: Optional[float]) -> str:
+    """-10 log10 of an error rate as text: "-" for None, "inf" for 0"""
+    if rate is None:
+        return "-"
+    return "inf" if rate <= 0 else "%.1f" % (-10.0 * math.log10(rate) + 0.0)      # (+ 0.0: a rate of 1 is Q 0.0, not -0.0)
+
+
+def write_lane_qualities(lane, counts: LaneQualityCounts, verbose: bool = False, out=None) -> None:
+    """The block that closes a lane's output under --lane-dups-quality: per-tile lines (verbose, in sorted tile order
+    as write_report), the summary line with the caveats, a line per occupied quality bin - its range, the raw values
+    seen in it, its share of the lane's PF observations, of the roots' and of the members' observations, the mean
+    reported quality, the error rate and empirical quality among pairs of that bin, and the error rate against the
+    highest occupied bin - and (verbose) Obs and Mis row by row."""
+    out = out or sys.stdout
+    c = counts
+    share = lambda v, of: v / of if of else 0.0
+    rate = lambda r: "-" if r is None else "%.3e" % r
+    print(file=out)
+    if verbose:
+        for tile in sorted(c.tiles):
+            t = c.tiles[tile]
+            print("LaneQualities: %s\tTile: %s\tPairs: %i\tProfiled: %i\tObservations: %i\tMismatches: %i" % (
+                lane, tile, t[0], t[1], t[2], t[3]), file=out)
+    caveat = ("rates are truncated from above: clusters only link within %i; distinct molecules within %i inflate them"
+              % (c.k, c.k)) if c.k else \
+        "under equality every copy is identical: only the reported qualities of copies against the lane's are shown"
+    print("LaneQualitiesSummary: %s\tTiles: %i\tHamming: %i\tMaxD: %i\tPairs: %i\tProfiled: %i (%.5f)\tObservations: %i\t"
+          "Mismatches: %i\t(%s)" % (lane, len(c.tiles), c.k, c.max_d, c.pairs, c.profiled, share(c.profiled, c.pairs),
+                                    c.observations, c.mismatches, caveat), file=out)
+    total = sum(c.qhist)
+    for b in c.occupied():
+        lo, hi = c.bin_range(b)
+        mean = c.mean_quality(b)
+        e, top = c.error_rate(b), c.error_rate_against_top(b)
+        print("LaneQualities: %s\tBin: %i-%i\tValues: %s\tPF share: %.5f\tRoots: %.5f\tMembers: %.5f\tMean Q: %s\t"
+              "Error rate: %s (Q %s)\tAgainst top bin: %s (Q %s)" % (
+                  lane, lo, hi, ",".join(str(q) for q in c.values(b)) or "-", share(c.seen(b), total),
+                  share(c.roots(b), c.observations), share(c.members(b), c.observations),
+                  "-" if mean is None else "%.2f" % mean, rate(e), phred(e), rate(top), phred(top)), file=out)
+    if verbose:
+        for name, m in (("Obs", c.obs), ("Mis", c.mis)):
+            for a in range(len(c.edges)):
+                print("LaneQualities: %s\t%s root bin %i-%i:\t%s" % ((lane, name) + c.bin_range(a) + (
+                    "\t".join(str(v) for v in m[a][:len(c.edges)]),)), file=out)

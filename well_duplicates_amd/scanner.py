@@ -331,6 +331,16 @@ class Scanner:
         matrix raise RuntimeError)."""
         return self._workspace_bytes(self._lib.wd_lane_distance_scratch, n_clusters, max_tiles, int(bool(matrix)))
 
+    def lane_qual_workspace_bytes(self, n_clusters: int, max_tiles: int, L: int) -> int:
+        """Device bytes the quality part of a LaneDups accumulator needs (wd_lane_qual_workspace: a second packed
+        array of the packed rows' size, and the QHist counters)."""
+        return self._workspace_bytes(self._lib.wd_lane_qual_workspace, n_clusters, max_tiles, L)
+
+    def lane_qual_scratch_bytes(self, max_tiles: int) -> int:
+        """Device bytes LaneDups.qualities needs beside the accumulator's workspaces (wd_lane_qual_scratch; it
+        depends on neither the wells of a tile nor the cycles)."""
+        return self._workspace_bytes(self._lib.wd_lane_qual_scratch, max_tiles)
+
     def scan_async(self, tables, n_tiles: int, L: int, n_clusters: int, mode: int, k: int,
                    out_tile_dev: int, out_per_target_dev: Optional[int] = None):
         pt, ft = tables
@@ -526,6 +536,7 @@ class LaneDups:
         self.d_ws = scanner.malloc(self.ws_bytes)
         self.d_labels = self.d_near_labels = 0
         self.d_index, self.index_bytes, self.I, self.index_listed = 0, 0, 0, 0
+        self.d_qual, self.qual_bytes, self.qual_edges = 0, 0, None
         self.refused = None
         self._h = None
         try:
@@ -546,6 +557,79 @@ class LaneDups:
         self._begin(self.d_ws, self.ws_bytes)
         if self.I:
             self._index_begin()
+        if self.qual_edges is not None:
+            self._qual_begin()
+
+    # ---- the lane's reported base quality against its copies (include/welldup_lanequality.h)
+    def qual_begin(self, edges: Sequence[int]):
+        """Gives the lane a quality part before the first add: edges are the bins' lower edges (1..8 of them,
+        ascending from 0, at most 63).  The accumulator owns and frees its workspace."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        if self.qual_edges is not None:
+            raise ValueError("qual_begin is called once")
+        nbytes = self.sc.lane_qual_workspace_bytes(self.N, self.max_tiles, self.L)
+        self.d_qual, self.qual_bytes = self.sc.malloc(max(1, nbytes)), nbytes
+        try:
+            self.qual_edges = [int(e) for e in edges]
+            self._qual_begin()
+        except Exception:
+            self.sc.free(self.d_qual)
+            self.d_qual, self.qual_bytes, self.qual_edges = 0, 0, None
+            raise
+
+    def _qual_begin(self):
+        e = (ctypes.c_int * max(1, len(self.qual_edges)))(*self.qual_edges)
+        self.sc._ck(self.sc._lib.wd_lane_qual_begin(self._h, len(self.qual_edges), e, ctypes.c_void_p(self.d_qual),
+                                                    self.qual_bytes))
+
+    def qual_add(self, tables, tile_indices: Sequence[int], well_stride: int = 1):
+        """Packs the qualities of resident tiles and counts QHist over their PF wells.  tables: the TileBatch `add`
+        takes, or the ctypes pointer tables Scanner._tables makes (planes n x L, filters n); tile_indices as `add`
+        takes them.  Independent of `add` in order and batching."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        idx = [int(t) for t in tile_indices]
+        if isinstance(tables, TileBatch):
+            tb = tables
+            if len(idx) != tb.n_tiles or tb.L != self.L or tb.N != self.N:
+                raise ValueError("the batch has %d tiles of %d wells and %d cycles; %d indices for a lane of %d wells "
+                                 "and %d cycles" % (tb.n_tiles, tb.N, tb.L, len(idx), self.N, self.L))
+            tables, well_stride = tb.tables, tb.interleave
+        pt, ft = tables
+        ti = (ctypes.c_int * max(1, len(idx)))(*idx)
+        self.sc.set_option("well_stride", well_stride)
+        try:
+            self.sc._ck(self.sc._lib.wd_lane_qual_add(self._h, len(idx), ti, pt, ft))
+        finally:
+            self.sc.set_option("well_stride", 1)
+
+    def qualities(self, max_d: int):
+        """After finish(), any number of times, before or after index_finish, mismatches and distances
+        (wd_lane_qualities): every redundant well against its root under the labels the finish left, cycle by cycle,
+        by the quality bins of the two.
+        -> (lane row int64 [4]: [Pairs, Profiled, Observations, Mismatches], tile rows int64 [max_tiles, 4]: the same
+        by the member's tile, qhist int64 [64]: the PF observations of the lane by raw quality, obs and mis int64
+        [8, 8]: [root's bin][member's bin] over the pairs with d <= max_d, all cycles and those where the bases
+        differ).  The scratch is allocated for the call and released.  max_d outside 0..7, a call before a successful
+        finish or without qual_begin, or a tile that has reads but no qualities (or the reverse) raises ValueError."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        lane_row = np.zeros(_lib.LANEQUALITY_LANE_COLS, dtype=np.int64)
+        tile_rows = np.zeros((self.max_tiles, _lib.LANEQUALITY_TILE_COLS), dtype=np.int64)
+        qhist = np.zeros(_lib.LANEQUALITY_VALUES, dtype=np.int64)
+        obs = np.zeros((_lib.LANEQUALITY_MAX_BINS, _lib.LANEQUALITY_MAX_BINS), dtype=np.int64)
+        mis = np.zeros_like(obs)
+        sbytes = self.sc.lane_qual_scratch_bytes(self.max_tiles)
+        d_scratch = self.sc.malloc(sbytes)
+        try:
+            self.sc._ck(self.sc._lib.wd_lane_qualities(
+                self._h, int(max_d), ctypes.c_void_p(d_scratch), sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
+                tile_rows.ctypes.data_as(ctypes.c_void_p), qhist.ctypes.data_as(ctypes.c_void_p),
+                obs.ctypes.data_as(ctypes.c_void_p), mis.ctypes.data_as(ctypes.c_void_p)))
+        finally:
+            self.sc.free(d_scratch)
+        return lane_row, tile_rows, qhist, obs, mis
 
     # ---- the lane's duplication per index read (include/welldup_laneindex.h)
     def index_begin(self, I: int):
@@ -754,10 +838,10 @@ class LaneDups:
     def close(self):
         """Drops the lane, finished or not, and frees the workspace."""
         self._end()
-        for ptr in (self.d_ws, self.d_labels, self.d_near_labels, self.d_index):
+        for ptr in (self.d_ws, self.d_labels, self.d_near_labels, self.d_index, self.d_qual):
             if ptr:
                 self.sc.free(ptr)
-        self.d_ws = self.d_labels = self.d_near_labels = self.d_index = 0
+        self.d_ws = self.d_labels = self.d_near_labels = self.d_index = self.d_qual = 0
 
 
 class TileBatch:
