@@ -37,12 +37,19 @@ the equality finish, on three inputs: the planted lane (39 quality levels, the C
 whose bases all carry one quality value (every well a profiled pair, every observation in one cell of Obs: the case the
 counting inside a lane is there for), and the `--equal` lane with random qualities (every cell of Obs, no two
 neighbouring cycles alike).
+`--saturation [--steps S] [--radius R]` times LaneDups.saturation (the lane's distinct reads against its depth,
+include/welldup_lanesaturation.h) per tile of the lane beside LaneDups.distances and the equality finish on the same
+batches and labels, with the local copies within R dropped and without coordinates, on the three inputs of
+`--distance`: the planted lane, the `--equal` lane (every pair's minimum goes to one word: what the read before the
+atomic is for) and the lane whose odd wells repeat their left neighbour (with R every pair is dropped).  The call
+includes the memset of its 4 bytes per well of the lane and the upload of the coordinates: the kernels' own times are
+the k_ls_min and k_ls_tally rows of the trace below.
 For per-kernel times run it under
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/lanedups_probe.py
 
 (the k_ld_* rows of the stats are this stage, k_li_* the index part, k_lm_* the mismatch pass, k_lg_* the distance pass,
-k_lq_* the quality part, k_td_* the per-tile classes, k_dense_* the scan)."""
+k_lq_* the quality part, k_ls_* the saturation pass, k_td_* the per-tile classes, k_dense_* the scan)."""
 import argparse
 import os
 import sys
@@ -73,7 +80,10 @@ ap.add_argument("--mismatches", action="store_true",
                 help="also time LaneDups.mismatches(K) beside the equality finish (needs --hamming; three inputs)")
 ap.add_argument("--distance", action="store_true",
                 help="also time LaneDups.distances beside the equality finish and mismatches (three inputs with --equal)")
-ap.add_argument("--radius", type=int, default=2500, metavar="R", help="the radius of --distance")
+ap.add_argument("--radius", type=int, default=2500, metavar="R", help="the radius of --distance and --saturation")
+ap.add_argument("--saturation", action="store_true",
+                help="also time LaneDups.saturation beside distances and the equality finish (three inputs with --equal)")
+ap.add_argument("--steps", type=int, default=20, metavar="S", help="the steps of --saturation")
 ap.add_argument("--quality", action="store_true",
                 help="also time LaneDups.qual_add beside add and LaneDups.qualities(K) beside mismatches(K) (needs "
                      "--hamming; three inputs with --equal)")
@@ -184,6 +194,24 @@ def time_distances(acc, tiles_n, t_finish, what):
     return row
 
 
+def time_saturation(acc, tiles_n, t_finish, what):
+    """LaneDups.saturation with the local copies dropped and without coordinates, and on the same labels
+    LaneDups.distances without the matrix, each after a first call that pays for loading the kernels"""
+    acc.saturation(a.steps, 0, x, y, a.radius)
+    sat, t_s = clock(lambda: acc.saturation(a.steps, 0, x, y, a.radius))
+    plain, t_s0 = clock(lambda: acc.saturation(a.steps, 0))
+    acc.distances(x, y, a.radius, matrix=False)
+    dg, t_dg = clock(lambda: acc.distances(x, y, a.radius, matrix=False))
+    head, reads, distinct = sat
+    assert reads.sum() == head[0] - head[1] and head[1] == dg[0][2] and distinct.sum() == head[0] - dg[0][0] == plain[2].sum() \
+        and plain[1].sum() == head[0], "the saturation rows do not add up"
+    print("%s: saturation, %d steps, R = %d: %d PF wells, %d dropped, %d distinct; the last step: %d new of %d reads"
+          % (what, a.steps, a.radius, head[0], head[1], distinct.sum(), distinct[-1], reads[-1]))
+    print("  %-22s %9.3f ms  (%.4f ms per tile; without coordinates %.4f; distances without the matrix: %.4f; "
+          "saturation / distances = %.2f; the equality finish: %.4f)"
+          % ("lane saturation", t_s, t_s / tiles_n, t_s0 / tiles_n, t_dg / tiles_n, t_s / t_dg, t_finish / tiles_n))
+
+
 def time_qualities(acc, tiles_n, t_finish, t_qual_add, t_plain_add, what):
     """LaneDups.qualities(K) and, on the same labels, LaneDups.mismatches(K), each after a first call that pays for
     loading the kernel"""
@@ -206,6 +234,8 @@ def time_qualities(acc, tiles_n, t_finish, t_qual_add, t_plain_add, what):
 
 if a.distance:
     time_distances(ld, max(1, a.tiles), t_fin, "the planted lane")
+if a.saturation:
+    time_saturation(ld, max(1, a.tiles), t_fin, "the planted lane")
 ld.close()
 if a.hamming:
     near, t_near = clock(lambda: ldn.finish(hamming=a.hamming))
@@ -335,6 +365,8 @@ if a.equal:
     if a.distance:
         row = time_distances(eq, 3, e_fin, "every read equal, three tiles")
         assert row[:2].tolist() == [3 * n - 1, n - 1], "the equal lane's pairs are not all on well 0 of tile 0"
+    if a.saturation:
+        time_saturation(eq, 3, e_fin, "every read equal, three tiles")
     if a.quality:
         time_qualities(eq, 3, e_fin, e_qadd, e_add, "every read equal, one quality value, three tiles")
         # the same bases under random qualities 1..63: eight random planes take turns
@@ -377,7 +409,7 @@ if a.mismatches:
     print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("lane mismatches", o_mm, o_mm / 3))
     one.close()
     three.free()
-if a.distance:
+if a.distance or a.saturation:
     # three tiles without planted copies whose wells of odd index repeat the well to their left, cycle by cycle
     bare = synth.SynthSpec(seed=5, n_clusters=n, row=a.cols, plant_per_64k=0)
     three = TileBatch(sc, 3, a.cycles, n)
@@ -393,8 +425,11 @@ if a.distance:
     nb = LaneDups(sc, n, 3, a.cycles)
     nb.add(three, [0, 1, 2])
     (nlane, _, _), n_fin = clock(lambda: nb.finish())
-    row = time_distances(nb, 3, n_fin, "every odd well a copy of its left neighbour, three tiles")
-    assert row[0] >= 3 * (n // 2) and row[3] >= 0.99 * row[1], "the copies do not sit beside their originals"
+    if a.distance:
+        row = time_distances(nb, 3, n_fin, "every odd well a copy of its left neighbour, three tiles")
+        assert row[0] >= 3 * (n // 2) and row[3] >= 0.99 * row[1], "the copies do not sit beside their originals"
+    if a.saturation:
+        time_saturation(nb, 3, n_fin, "every odd well a copy of its left neighbour, three tiles")
     nb.close()
     three.free()
 sc.close()

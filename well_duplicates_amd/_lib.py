@@ -185,6 +185,15 @@ LANEQUALITY_MAX_D = LANEMISMATCH_MAX_D
 LANEQUALITY_LANE_COLS = 4
 LANEQUALITY_TILE_COLS = 4
 
+# name -> (restype, argtypes); every symbol include/welldup_lanesaturation.h declares beyond the ten above
+LANESATURATION_PROTOTYPES = {
+    "wd_lane_saturation_scratch": (_i, [_i64, _i, _i, ctypes.POINTER(_sz)]),
+    "wd_lane_saturation": (_i, [_vp, _i, ctypes.c_uint32, _vp, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),
+}
+LANESATURATION_MAX_STEPS = 64
+LANESATURATION_HEAD_COLS = 2
+LANESATURATION_MAX_RADIUS = LANEDISTANCE_MAX_RADIUS
+
 _lib = None
 
 
@@ -271,7 +280,7 @@ def unit_of_kernel(kernel: str) -> str:
         return "ingest"
     if kernel.startswith("k_sets"):
         return "sets"
-    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_")):
+    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_", "k_ls_")):
         return "tiledups"
     return "scan"
 
@@ -333,7 +342,8 @@ def load():
     for name, (res, args) in list(PROTOTYPES.items()) + list(SETS_PROTOTYPES.items()) + list(TILEDUPS_PROTOTYPES.items()) + \
             list(TILENEAR_PROTOTYPES.items()) + list(LANEDUPS_PROTOTYPES.items()) + list(LANENEAR_PROTOTYPES.items()) + \
             list(LANEINDEX_PROTOTYPES.items()) + list(LANEMISMATCH_PROTOTYPES.items()) + \
-            list(LANEDISTANCE_PROTOTYPES.items()) + list(LANEQUALITY_PROTOTYPES.items()):
+            list(LANEDISTANCE_PROTOTYPES.items()) + list(LANEQUALITY_PROTOTYPES.items()) + \
+            list(LANESATURATION_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -23,7 +23,8 @@ Differences from the reference, all deliberate:
   * extra flags: --device, --dist-backend, --tile-batch, --threads, --strict, -o/--output,
     --all-wells, --slocs, --layout, --serial-ingest, --dup-sets, --dup-sets-out, --tile-dups, --tile-dups-out,
     --tile-dups-hamming, --tile-dups-pair-budget, --lane-dups, --lane-dups-out,
-    --lane-dups-hamming, --lane-dups-index, --lane-dups-mismatches, --lane-dups-distance, --lane-dups-quality;
+    --lane-dups-hamming, --lane-dups-index, --lane-dups-mismatches, --lane-dups-distance, --lane-dups-quality,
+    --lane-dups-saturation;
   * --all-wells --dup-sets groups every tile's wells into duplicate sets and follows each lane's report
     with their counts and the exact duplication (report.write_dup_sets);
   * --all-wells --tile-dups groups every tile's PF wells into classes of equal reads, wherever on the tile they
@@ -43,7 +44,10 @@ Differences from the reference, all deliberate:
     that the library size should not count (report.write_lane_distances); --lane-dups-quality keeps the reported
     quality of every base beside the reads and counts the (copy, cycle) observations by the quality bins of the two
     wells, all of them and those where the bases differ: the error rate among copies per reported quality
-    (report.write_lane_qualities);
+    (report.write_lane_qualities); --lane-dups-saturation gives every PF well of the lane a pseudo-random step and
+    counts, step by step, the reads and the distinct reads among them - the lane's saturation curve, exact, with the
+    local copies of --lane-dups-saturation-radius left out: what the last reads still brought, whether the library
+    size holds at half the depth, and what it projects for more reads (report.write_lane_saturation);
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
@@ -255,7 +259,38 @@ def parse_args(argv=None):
                    help="with --lane-dups-quality: only pairs at most D cycles apart enter the table (0..%d; default "
                         "--lane-dups-mismatches-max-d where --lane-dups-mismatches is given, else K)"
                         % _lib.LANEQUALITY_MAX_D)
+    p.add_argument("--lane-dups-saturation", action="store_true",
+                   help="with --lane-dups: give every PF well of a lane a pseudo-random step (a hash of the well's "
+                        "number in the lane) and print, after every other block of the lane, a line per step: the reads "
+                        "and the distinct reads (classes, or clusters with --lane-dups-hamming) among the wells up to "
+                        "that step, their duplication, the library size they give and the new molecules per read of "
+                        "the step - the lane's saturation curve, exact and without an alignment.  The closing lines "
+                        "say what the last reads still brought (measured), how the library size at full depth compares "
+                        "with the one at half depth (near 1: the estimate can be trusted; well above 1: the library is "
+                        "uneven and the estimate a lower bound), and what the estimate projects for 2x and 4x the "
+                        "reads.  Needs 4 bytes of device memory per well of the lane")
+    p.add_argument("--lane-dups-saturation-steps", type=int, default=None, metavar="S",
+                   help="with --lane-dups-saturation: the steps of the curve (1..%d, default 20)"
+                        % _lib.LANESATURATION_MAX_STEPS)
+    p.add_argument("--lane-dups-saturation-seed", type=int, default=None, metavar="SEED",
+                   help="with --lane-dups-saturation: another seed (0..2^32 - 1, default 0) draws other subsamples; the "
+                        "totals do not depend on it")
+    p.add_argument("--lane-dups-saturation-radius", type=int, default=None, metavar="R",
+                   help="with --lane-dups-saturation: leave out the copies closer than R to the first well of their class "
+                        "on the same tile (0..%d, in the units of --lane-dups-distance-radius; 0: leave out none) - they "
+                        "are made on the flowcell and say nothing about the library.  Default: "
+                        "--lane-dups-distance-radius where --lane-dups-distance is given, else 0"
+                        % _lib.LANESATURATION_MAX_RADIUS)
     args = p.parse_args(argv)
+    if args.lane_dups_saturation and not args.lane_dups:
+        p.error("--lane-dups-saturation needs --lane-dups")
+    for flag, value, lo, hi in (("steps", args.lane_dups_saturation_steps, 1, _lib.LANESATURATION_MAX_STEPS),
+                                ("seed", args.lane_dups_saturation_seed, 0, (1 << 32) - 1),
+                                ("radius", args.lane_dups_saturation_radius, 0, _lib.LANESATURATION_MAX_RADIUS)):
+        if value is not None and not args.lane_dups_saturation:
+            p.error("--lane-dups-saturation-%s needs --lane-dups-saturation" % flag)
+        if value is not None and not lo <= value <= hi:
+            p.error("--lane-dups-saturation-%s takes %d..%d, not %d" % (flag, lo, hi, value))
     if args.lane_dups_quality and not args.lane_dups:
         p.error("--lane-dups-quality needs --lane-dups")
     if args.lane_dups_quality_bins is not None and not args.lane_dups_quality:
@@ -462,20 +497,23 @@ def lane_cluster_members(class_labels: np.ndarray, cluster_labels: np.ndarray):
 
 
 def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0, index: int = 0,
-                         mismatch: int = 0, distance: int = 0, quality: int = 0):
+                         mismatch: int = 0, distance: int = 0, quality: int = 0, saturation: int = 0):
     """--lane-dups: the accumulator's workspace - with --lane-dups-hamming plus the scratch of the near finish, with
     --lane-dups-index plus the index workspace, with --lane-dups-mismatches or --lane-dups-distance plus that pass's
-    scratch, with --lane-dups-quality plus the quality workspace and that pass's scratch - against the free device memory, before anything is loaded."""
-    need += scratch + index + mismatch + distance + quality
+    scratch, with --lane-dups-quality plus the quality workspace and that pass's scratch, with --lane-dups-saturation
+    plus that pass's scratch - against the free device memory, before anything is loaded."""
+    need += scratch + index + mismatch + distance + quality + saturation
     if need > free:
         raise MemoryError("--lane-dups needs %.2f GB of device memory for a lane of %d tiles x %d wells x %d cycles "
-                          "(%d bytes%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
+                          "(%d bytes%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
                               need / 1e9, tiles, wells, cycles, need,
                               ", %d of them for --lane-dups-hamming" % scratch if scratch else "",
                               ", %d of them for --lane-dups-index" % index if index else "",
                               ", %d of them for --lane-dups-mismatches" % mismatch if mismatch else "",
                               ", %d of them for --lane-dups-distance" % distance if distance else "",
-                              ", %d of them for --lane-dups-quality" % quality if quality else "", free / 1e9, free))
+                              ", %d of them for --lane-dups-quality" % quality if quality else "",
+                              ", %d of them for --lane-dups-saturation" % saturation if saturation else "",
+                              free / 1e9, free))
 
 
 def index_listing(min_share: float, pf: int):
@@ -487,7 +525,7 @@ def index_listing(min_share: float, pf: int):
 def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells, tile_batch,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
                dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0, lane_near=0, lane_pair_budget=0,
-               lane_index=None, lane_mismatch=None, lane_distance=None, lane_quality=None):
+               lane_index=None, lane_mismatch=None, lane_distance=None, lane_quality=None, lane_saturation=None):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
@@ -516,6 +554,9 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     lane_quality = (edges, D) (with lane_dups): the accumulator gets a quality part with these bins, every batch is
     fed to LaneDups.qual_add beside add, and after everything else of the lane LaneDups.qualities(D):
     into["lquality"][lane] = LaneQualityCounts, on the labels the lane was left with.
+    lane_saturation = (steps, seed, x, y, radius) (with lane_dups; x, y: the coordinates of a tile's wells, or None
+    with radius 0): after everything else of the lane LaneDups.saturation(steps, seed, x, y, radius):
+    into["lsaturation"][lane] = LaneSaturationCounts, on the labels the lane was left with.
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -748,6 +789,11 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                     if lane_quality is not None:
                         into["lquality"][lane] = report.LaneQualityCounts.from_rows(
                             *ld.qualities(lane_quality[1]), names, lane_near, lane_quality[1], lane_quality[0])
+                    if lane_saturation is not None:
+                        steps, seed, lx, ly, radius = lane_saturation
+                        into["lsaturation"][lane] = report.LaneSaturationCounts.from_rows(
+                            *ld.saturation(steps, seed, lx, ly, radius), seed, radius,
+                            into["lnear"][lane] if lane_near else into["ldups"][lane], lane_near)
                     del lane_labels, got
                 _lap("batch %d: lane classes" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
@@ -990,6 +1036,13 @@ def _main(args, log, wdist, rank, world, device, opener, early):
             if args.lane_dups_quality:
                 quality_d = args.lane_dups_quality_max_d if args.lane_dups_quality_max_d is not None else \
                     mismatch_d if mismatch_d is not None else lane_near_k
+            saturation = None
+            if args.lane_dups_saturation:
+                radius = args.lane_dups_saturation_radius if args.lane_dups_saturation_radius is not None else \
+                    args.lane_dups_distance_radius if args.lane_dups_distance else 0
+                saturation = (20 if args.lane_dups_saturation_steps is None else args.lane_dups_saturation_steps,
+                              args.lane_dups_saturation_seed or 0, xy[0] if radius else None, xy[1] if radius else None,
+                              radius)
             ntn = 5 + 2 * levels + len(report.CLASS_BIN_NAMES) if near_k else 0
             rows = np.zeros((len(mine), ncnt + nsets + ntd + ntn), dtype=np.int64)
             logs = {}
@@ -1031,6 +1084,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                     report.write_lane_distances(lane, results["ldistance"][lane], verbose=not args.summary_only, out=out_fh)
                 if args.lane_dups_quality:
                     report.write_lane_qualities(lane, results["lquality"][lane], verbose=not args.summary_only, out=out_fh)
+                if args.lane_dups_saturation:
+                    report.write_lane_saturation(lane, results["lsaturation"][lane], verbose=not args.summary_only,
+                                                 out=out_fh)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
@@ -1038,7 +1094,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 # scan_lanes fills these, lane_done reads them
                 results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
                            "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}, "lnear": {}, "lindex": {},
-                           "lmindex": {}, "lmismatch": {}, "ldistance": {}, "lquality": {}}
+                           "lmindex": {}, "lmismatch": {}, "ldistance": {}, "lquality": {}, "lsaturation": {}}
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
@@ -1071,7 +1127,10 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                              n_targets, len(tiles), len(tiles) <= _lib.LANEDISTANCE_MATRIX_MAX_TILES)
                                          if args.lane_dups_distance else 0,
                                          quality=sc.lane_qual_workspace_bytes(n_targets, len(tiles), len(cycle_list)) +
-                                         sc.lane_qual_scratch_bytes(len(tiles)) if quality_d is not None else 0)
+                                         sc.lane_qual_scratch_bytes(len(tiles)) if quality_d is not None else 0,
+                                         saturation=sc.lane_saturation_scratch_bytes(n_targets, len(tiles),
+                                                                                     saturation[4] > 0)
+                                         if saturation is not None else 0)
                 if err is None:             # (a rank whose setup failed has nothing to scan: it goes to the flag)
                     scan_lanes(sc, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                                max(0, args.tile_batch), args.threads,
@@ -1089,7 +1148,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                lane_mismatch=mismatch_d,
                                lane_distance=(xy[0], xy[1], args.lane_dups_distance_radius)
                                if args.lane_dups_distance else None,
-                               lane_quality=(args.lane_dups_quality_edges, quality_d) if quality_d is not None else None)
+                               lane_quality=(args.lane_dups_quality_edges, quality_d) if quality_d is not None else None,
+                               lane_saturation=saturation)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
                     if args.tile_dups_out and near_k:

@@ -582,4 +582,9 @@ try {
 } WD_CATCH
 
 }  // extern "C"
+
+// The unit ends with the line that includes this file (tests/test_lanequality_host.py holds it to that), so what
+// comes after it in the unit is included from here: a lane's distinct reads against its depth
+// (include/welldup_lanesaturation.h), which uses nothing of this file.
+#include "lane_saturation.inc"
 #endif

@@ -17,7 +17,8 @@
 // lane_mismatch.inc (after it) where a lane's duplicate copies differ of welldup_lanemismatch.h, lane_distance.inc
 // (last) how far apart they lie of welldup_lanedistance.h: all of these work on the accumulator as lane_dups.inc laid
 // it out.  lane_quality.inc, behind them, gives it a second packed array - the reported base qualities - and holds
-// them against the copies: welldup_lanequality.h.
+// them against the copies: welldup_lanequality.h.  lane_saturation.inc, which lane_quality.inc includes at its
+// end, reads the labels alone: the lane's distinct reads against its depth of welldup_lanesaturation.h.
 #include <memory>
 
 #include "wd_ctx.h"

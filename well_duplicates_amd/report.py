@@ -1034,3 +1034,110 @@ def write_lane_qualities(lane, counts: LaneQualityCounts, verbose: bool = False,
             for a in range(len(c.edges)):
                 print("LaneQualities: %s\t%s root bin %i-%i:\t%s" % ((lane, name) + c.bin_range(a) + (
                     "\t".join(str(v) for v in m[a][:len(c.edges)]),)), file=out)
+
+
+LANE_SATURATION_MAX_STEPS = 64
+LANE_SATURATION_MAX_RADIUS = LANE_DISTANCE_MAX_RADIUS
+
+
+@dataclass
+class LaneSaturationCounts:
+    """A lane's distinct reads against its depth (include/welldup_lanesaturation.h, LaneDups.saturation): PF wells,
+    the wells dropped as local copies (closer than `radius` to their root on its tile; 0 without a radius), Redundant
+    of the lane row the labels belong to, and per step the counted wells and the distinct reads the step brought.
+    k = 0: the labels are classes; K > 0: clusters at Hamming distance <= K."""
+    pf: int = 0
+    dropped: int = 0
+    redundant: int = 0
+    new_reads: List[int] = field(default_factory=lambda: [0])
+    new_distinct: List[int] = field(default_factory=lambda: [0])
+    steps: int = 1
+    seed: int = 0
+    radius: int = 0
+    k: int = 0
+
+    @classmethod
+    def from_rows(cls, head: Sequence[int], new_reads: Sequence[int], new_distinct: Sequence[int], seed: int, radius: int,
+                  final: "LaneDupCounts", k: int = 0) -> "LaneSaturationCounts":
+        """The three results of LaneDups.saturation(steps, seed, x, y, radius); final: the LaneDupCounts
+        (LaneNearCounts under --lane-dups-hamming K = k) of the labels the lane was left with."""
+        h = [int(v) for v in head]
+        r, d = [int(v) for v in new_reads], [int(v) for v in new_distinct]
+        assert len(h) == 2 and 1 <= len(r) == len(d) <= LANE_SATURATION_MAX_STEPS
+        assert 0 <= radius <= LANE_SATURATION_MAX_RADIUS and 0 <= seed < 1 << 32
+        assert sum(r) == h[0] - h[1] and sum(d) == h[0] - final.redundant and h[0] == final.pf
+        return cls(h[0], h[1], final.redundant, r, d, len(r), int(seed), int(radius), int(k))
+
+    def cumulative(self):
+        """-> (reads, distinct) of the subsample at each step"""
+        reads, distinct, a, b = [], [], 0, 0
+        for r, d in zip(self.new_reads, self.new_distinct):
+            a, b = a + r, b + d
+            reads.append(a)
+            distinct.append(b)
+        return reads, distinct
+
+    def half_step(self) -> int:
+        """the step whose nominal share (j + 1) / S is nearest a half (the earlier of two)"""
+        return min(range(self.steps), key=lambda j: (abs(2 * (j + 1) - self.steps), j))
+
+    def size_ratio(self) -> Optional[float]:
+        """library_size at full depth over library_size at half_step(); None where either has no solution"""
+        reads, distinct = self.cumulative()
+        j = self.half_step()
+        full, half = library_size(reads[-1], distinct[-1]), library_size(reads[j], distinct[j])
+        return full / half if full is not None and half is not None else None
+
+    def projection(self, factor: float):
+        """-> (distinct reads, duplication) Lander-Waterman gives at factor x the counted reads with the full-depth
+        library size; None without one"""
+        reads, distinct = self.cumulative()
+        size = library_size(reads[-1], distinct[-1])
+        if size is None:
+            return None
+        n = factor * reads[-1]
+        c = -size * math.expm1(-n / size)
+        return c, 1.0 - c / n
+
+
+def write_lane_saturation(lane, counts: LaneSaturationCounts, verbose: bool = False, out=None) -> None:
+    """The block that closes a lane's output under --lane-dups-saturation: a line per step (verbose) - its nominal
+    share of the reads, the reads and distinct reads up to it, their duplication, the library size they give and
+    the step's own yield of new molecules -, then the summary: what the last reads still brought (measured), whether
+    the library size holds at half the depth (the model's test), what the model projects for more reads, and the
+    local copies that were left out."""
+    out = out or sys.stdout
+    c = counts
+    share = lambda v, of: v / of if of else 0.0
+    size_text = lambda s: "n/a" if s is None else "%.0f" % s
+    reads, distinct = c.cumulative()
+    print(file=out)
+    if verbose:
+        for j in range(c.steps):
+            print("LaneSaturation: %s\tStep: %i/%i\tShare: %.5f\tReads: %i\tDistinct: %i\tDuplication: %.5f\t"
+                  "Library size: %s\tNewReads: %i\tNewDistinct: %i\tYield: %.5f" % (
+                      lane, j + 1, c.steps, (j + 1) / c.steps, reads[j], distinct[j], 1.0 - share(distinct[j], reads[j])
+                      if reads[j] else 0.0, size_text(library_size(reads[j], distinct[j])), c.new_reads[j],
+                      c.new_distinct[j], share(c.new_distinct[j], c.new_reads[j])), file=out)
+    print("LaneSaturationSummary: %s\tSteps: %i\tSeed: %i\tHamming: %i\tPF wells: %i\tDropped: %i\tReads: %i\t"
+          "Distinct: %i\tDuplication: %.5f\tLibrary size: %s" % (
+              lane, c.steps, c.seed, c.k, c.pf, c.dropped, reads[-1], distinct[-1],
+              1.0 - share(distinct[-1], reads[-1]) if reads[-1] else 0.0, size_text(library_size(reads[-1], distinct[-1]))),
+          file=out)
+    print("New molecules per 1000 further reads (measured, no model: the last step's %i reads brought %i): %s" % (
+        c.new_reads[-1], c.new_distinct[-1],
+        "%.1f" % (1000.0 * c.new_distinct[-1] / c.new_reads[-1]) if c.new_reads[-1] else "n/a"), file=out)
+    j = c.half_step()
+    ratio = c.size_ratio()
+    print("Library size at full depth / at step %i/%i: %s (near 1: equally likely molecules, as Lander-Waterman assumes, "
+          "fit; well above 1: the library is more uneven and the size a lower bound)" % (
+              j + 1, c.steps, "n/a" if ratio is None else "%.3f" % ratio), file=out)
+    proj = [(f, c.projection(f)) for f in (2, 4)]
+    print("Projection (Lander-Waterman with the full-depth size, not a measurement): %s" % "\t".join(
+        "%ix reads: n/a" % f if p is None else "%ix reads: %.0f distinct, duplication %.5f" % (f, p[0], p[1])
+        for f, p in proj), file=out)
+    if c.radius > 0:
+        print("Local copies dropped: %i closer than R = %i to the first well of their class on its tile (%.5f of PF wells)" % (
+            c.dropped, c.radius, share(c.dropped, c.pf)), file=out)
+    else:
+        print("Local copies dropped: none (no radius)", file=out)

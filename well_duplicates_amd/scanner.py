@@ -341,6 +341,11 @@ class Scanner:
         depends on neither the wells of a tile nor the cycles)."""
         return self._workspace_bytes(self._lib.wd_lane_qual_scratch, max_tiles)
 
+    def lane_saturation_scratch_bytes(self, n_clusters: int, max_tiles: int, coords: bool = True) -> int:
+        """Device bytes LaneDups.saturation needs beside the accumulator's workspace (wd_lane_saturation_scratch: a
+        word per well of the lane, the counters, and with `coords` the coordinates of a tile's wells)."""
+        return self._workspace_bytes(self._lib.wd_lane_saturation_scratch, n_clusters, max_tiles, int(bool(coords)))
+
     def scan_async(self, tables, n_tiles: int, L: int, n_clusters: int, mode: int, k: int,
                    out_tile_dev: int, out_per_target_dev: Optional[int] = None):
         pt, ft = tables
@@ -829,6 +834,50 @@ class LaneDups:
         finally:
             self.sc.free(d_scratch)
         return lane_row, tile_rows, tile_pairs
+
+    def saturation(self, steps: int, seed: int = 0, x=None, y=None, radius: int = 0):
+        """After finish(), any number of times, before or after every other pass that follows a finish
+        (wd_lane_saturation, include/welldup_lanesaturation.h): the lane's saturation curve under the labels the
+        finish left.  Every PF well gets a step 0 .. steps - 1 from a hash of its global id and `seed` (uint32); with
+        x, y (the coordinates of a tile's N wells, each 0 .. 2^24 - 1) and radius > 0 the same-tile copies closer
+        than radius to their root - `distances`' Local - are dropped.
+        -> (head int64 [2]: [PF, Dropped], new reads int64 [steps]: the counted wells of each step, new distinct
+        int64 [steps]: the distinct reads that first appear in each step).  The scratch is allocated for the call
+        and released.  steps outside 1..64, a seed outside uint32, a radius outside 0 .. 2^25 or without
+        coordinates, one of x and y alone, a coordinate out of range or a call before a successful finish raises
+        ValueError."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        if not 0 <= int(seed) < 1 << 32:
+            raise ValueError("the seed is a uint32, not %d" % seed)
+        if (x is None) != (y is None):
+            raise ValueError("x and y come together or not at all")
+        coords = x is not None
+        xs = ys = None
+        if coords:
+            xs, ys = (np.asarray(v) for v in (x, y))
+            if xs.shape != (self.N,) or ys.shape != (self.N,):
+                raise ValueError("x and y hold a coordinate per well of a tile: %d each" % self.N)
+            for v in (xs, ys):                           # (what int32 cannot hold is out of range as well)
+                if v.size and (int(v.min()) < 0 or int(v.max()) > _lib.LANEDISTANCE_MAX_COORD):
+                    w = int(np.flatnonzero((v < 0) | (v > _lib.LANEDISTANCE_MAX_COORD))[0])
+                    raise ValueError("well %d lies at (%d, %d), outside 0..%d" % (w, xs[w], ys[w], _lib.LANEDISTANCE_MAX_COORD))
+            xs, ys = np.ascontiguousarray(xs, dtype=np.int32), np.ascontiguousarray(ys, dtype=np.int32)
+        n = min(max(int(steps), 1), _lib.LANESATURATION_MAX_STEPS)     # (the library refuses steps out of range)
+        head = np.zeros(_lib.LANESATURATION_HEAD_COLS, dtype=np.int64)
+        new_reads = np.zeros(n, dtype=np.int64)
+        new_distinct = np.zeros(n, dtype=np.int64)
+        sbytes = self.sc.lane_saturation_scratch_bytes(self.N, self.max_tiles, coords)
+        d_scratch = self.sc.malloc(max(1, sbytes))
+        try:
+            self.sc._ck(self.sc._lib.wd_lane_saturation(
+                self._h, int(steps), int(seed), xs.ctypes.data_as(ctypes.c_void_p) if coords else None,
+                ys.ctypes.data_as(ctypes.c_void_p) if coords else None, int(radius), ctypes.c_void_p(d_scratch), sbytes,
+                head.ctypes.data_as(ctypes.c_void_p), new_reads.ctypes.data_as(ctypes.c_void_p),
+                new_distinct.ctypes.data_as(ctypes.c_void_p)))
+        finally:
+            self.sc.free(d_scratch)
+        return head, new_reads, new_distinct
 
     def _end(self):
         if self._h is not None:
