@@ -14,14 +14,16 @@ from well_duplicates_amd.scanner import INVALID_TARGET, Scanner, TileBatch
 
 pytestmark = pytest.mark.gpu
 
-DEFAULT_OPTIONS = (("early_exit", 1), ("batch_first", 4), ("batch_next", 4), ("targets_per_block", 32),
-                   ("queue_kernel", 1), ("queue_first", 0), ("dense_kernel", -1), ("dense_pack", -1),
-                   ("dense_queue_cap", 0), ("dense_sym", 1), ("line_walk", -1), ("line_pairs", 0))
+OPTION_NAMES = ("early_exit", "batch_first", "batch_next", "targets_per_block", "queue_kernel", "queue_first",
+                "dense_kernel", "dense_pack", "dense_queue_cap", "dense_sym", "line_walk", "line_pairs")
+DEFAULT_OPTIONS = []      # (name, value) as a fresh context reports them - the library's defaults, not a copy of them
+                          # that can go stale: filled in by the `sc` fixture, restored by the tests that change options
 
 
 @pytest.fixture(scope="module")
 def sc():
     s = Scanner(0)
+    DEFAULT_OPTIONS[:] = [(name, s.get_option(name)) for name in OPTION_NAMES]
     yield s
     s.close()
 
@@ -1018,6 +1020,7 @@ def test_fresh_context_requires_targets():
 def test_production_shape_properties(sc):
     """BASELINE config 1/2 shape (HiSeq-4000 tile geometry, 2500 targets, 5 levels, 50 bp)
     on a few tiles: size-independent properties + one tile against the oracle."""
+    assert sc.get_option("targets_per_block") == 64      # the shipped workgroup shape (csrc/wd_ctx.h), not one a test left behind
     rows, cols = 2743, 1571
     n = rows * cols
     spec = synth.SynthSpec(seed=2, n_clusters=n, row=cols)

@@ -29,6 +29,8 @@ constexpr int kLwPairs = 12288;       // pairs per block, by default (the first 
 constexpr int kLwStep = 2 * kWave;    // pairs per wave and step
 constexpr int kLwQCap = 128;          // survivor queue entries per wave (>= kLwStep: after a drain one step's survivors always fit)
 constexpr int kLwInPlace = 43;        // survivors of a step's first round (of its 128 pairs) from which the step is finished where it stands
+static_assert(kLwQCap >= kLwStep && kLwQCap >= kFinishAllMax,
+              "after a drain one step must fit the queue, and q_finish_all adds up its pieces in the idle queue buffer");
 
 // (ScanArgs first: the survivor queue's rare paths fetch `rare`, `perm` and `log_hits` from the kernel
 // argument segment at ScanArgs' offsets - late_arg, scan_queue.inc)

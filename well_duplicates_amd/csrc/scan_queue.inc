@@ -36,6 +36,8 @@ constexpr int kQCap = WD_QCAP;      // >= kPass: after a drain one pass always f
 constexpr int kQDepth = WD_Q_DEPTH; // steps between the issue of an item's plane-byte gather and its use (k_scan_q, phase 1)
 constexpr int kFinishInPlace = 40;  // survivors of a pass's first round from which the pass is finished where it stands
                                     // (low-diversity reads: amplicons, failed cycles), not through the queue
+static_assert(kQCap >= kPass && kQCap >= kFinishAllMax,
+              "after a drain one pass must fit the queue, and q_finish_all adds up its pieces in the idle queue buffer");
 
 // A field of k_scan_q's kernel argument (ScanArgs is its only one), loaded WHERE IT IS USED.  Left to
 // the compiler every field is fetched at the top of the kernel and then occupies scalar registers to
