@@ -115,7 +115,9 @@ int wd_synchronize(wd_ctx *ctx);
  * offsets), "dense_window_groups" (those scanned through signature windows in LDS),
  * "dense_window_dwords" (LDS dwords per wave of the largest window), "dense_sym_on" (1: the tables
  * built last are those of the one-ended compare), "line_walk_blocks" (workgroups per tile of the line
- * walk's tables: -1 not built, 0 = the walk does not apply to these targets).
+ * walk's tables: -1 not built, 0 = the walk does not apply to these targets), "lane_top_passes" (histogram passes
+ * the last wd_lane_top took, -1 before the first) and "lane_top_max_passes" (the most it takes whatever the data:
+ * welldup_lanetop.h).
  * Unknown names return WD_ERR_ARG. */
 int wd_set_option(wd_ctx *ctx, const char *name, int64_t value);
 int wd_get_option(wd_ctx *ctx, const char *name, int64_t *value);

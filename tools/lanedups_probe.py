@@ -44,12 +44,19 @@ batches and labels, with the local copies within R dropped and without coordinat
 atomic is for) and the lane whose odd wells repeat their left neighbour (with R every pair is dropped).  The call
 includes the memset of its 4 bytes per well of the lane and the upload of the coordinates: the kernels' own times are
 the k_ls_min and k_ls_tally rows of the trace below.
+`--top N [--capacity C]` times LaneDups.top(N, C) (the lane's most frequent reads and their spread,
+include/welldup_lanetop.h) per tile of the lane beside the equality finish and LaneDups.saturation (without coordinates)
+on the same batches and labels, on three inputs: the planted lane, the `--equal` lane (one group holds every well: one
+rank takes every add of k_lt_spread) and the lane whose odd wells repeat their left neighbour - classes of size 2 only,
+the tie worst case; with `--capacity N` the selection there has to refine the root ids to the end, the longest it can
+be.  The histogram passes taken are printed, and the bytes a pass streams (8 per well) over the time of a pass against
+the pure read.
 For per-kernel times run it under
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/lanedups_probe.py
 
 (the k_ld_* rows of the stats are this stage, k_li_* the index part, k_lm_* the mismatch pass, k_lg_* the distance pass,
-k_lq_* the quality part, k_ls_* the saturation pass, k_td_* the per-tile classes, k_dense_* the scan)."""
+k_lq_* the quality part, k_ls_* the saturation pass, k_lt_* the top pass, k_td_* the per-tile classes, k_dense_* the scan)."""
 import argparse
 import os
 import sys
@@ -84,6 +91,9 @@ ap.add_argument("--radius", type=int, default=2500, metavar="R", help="the radiu
 ap.add_argument("--saturation", action="store_true",
                 help="also time LaneDups.saturation beside distances and the equality finish (three inputs with --equal)")
 ap.add_argument("--steps", type=int, default=20, metavar="S", help="the steps of --saturation")
+ap.add_argument("--top", type=int, default=0, metavar="N",
+                help="also time LaneDups.top(N) beside the equality finish and saturation (three inputs with --equal)")
+ap.add_argument("--capacity", type=int, default=0, metavar="C", help="the candidate capacity of --top (0: the default)")
 ap.add_argument("--quality", action="store_true",
                 help="also time LaneDups.qual_add beside add and LaneDups.qualities(K) beside mismatches(K) (needs "
                      "--hamming; three inputs with --equal)")
@@ -212,6 +222,36 @@ def time_saturation(acc, tiles_n, t_finish, what):
           % ("lane saturation", t_s, t_s / tiles_n, t_s0 / tiles_n, t_dg / tiles_n, t_s / t_dg, t_finish / tiles_n))
 
 
+def time_top(acc, tiles_n, t_finish, what):
+    """LaneDups.top(N, C) and, on the same labels, LaneDups.saturation without coordinates, each after a first call
+    that pays for loading the kernels; the time of a histogram pass is taken from the call with capacity N less the
+    call with the default capacity, over the passes they differ by"""
+    acc.top(a.top, a.capacity)
+    top, t_t = clock(lambda: acc.top(a.top, a.capacity))
+    passes = sc.get_option("lane_top_passes")
+    full, t_full = clock(lambda: acc.top(a.top, a.top))
+    full_passes = sc.get_option("lane_top_passes")
+    one, t_one = clock(lambda: acc.top(a.top, 0))
+    one_passes = sc.get_option("lane_top_passes")
+    acc.saturation(a.steps, 0)
+    sat, t_s = clock(lambda: acc.saturation(a.steps, 0))
+    head, levels, root, size, exact, tile_count, reads = top
+    assert levels[1].sum() == head[0] == sat[0][0] and levels[0].sum() == sat[2].sum() and (size == exact).all() \
+        and (tile_count.sum(axis=1) == size).all() and all((f == t).all() for f, t in zip(full[:6], top[:6])) \
+        and all((f == t).all() for f, t in zip(one[:6], top[:6])), "the top rows do not add up"
+    print("%s: top %d, capacity %d: %d PF wells, %d groups, %d listed covering %d wells; sizes %s ...; levels %s"
+          % (what, a.top, a.capacity, head[0], head[1], head[2], head[3], " ".join(str(v) for v in size[:5]),
+             " ".join(str(v) for v in levels[0])))
+    print("  %-22s %9.3f ms  (%.4f ms per tile, %d histogram passes of at most %d; capacity N: %.4f in %d passes; default: "
+          "%.4f in %d; saturation without coordinates: %.4f; the equality finish: %.4f)"
+          % ("lane top", t_t, t_t / tiles_n, passes, sc.get_option("lane_top_max_passes"), t_full / tiles_n, full_passes,
+             t_one / tiles_n, one_passes, t_s / tiles_n, t_finish / tiles_n))
+    if full_passes > one_passes:
+        per_pass = (t_full - t_one) / (full_passes - one_passes)
+        print("  a histogram pass: %.4f ms, %.1f us per tile: 8 bytes per well at %.0f GB/s (pure read: %.0f GB/s)"
+              % (per_pass, 1e3 * per_pass / tiles_n, 8.0 * n * tiles_n / per_pass / 1e6, float(np.mean(read_gbs))))
+
+
 def time_qualities(acc, tiles_n, t_finish, t_qual_add, t_plain_add, what):
     """LaneDups.qualities(K) and, on the same labels, LaneDups.mismatches(K), each after a first call that pays for
     loading the kernel"""
@@ -236,6 +276,8 @@ if a.distance:
     time_distances(ld, max(1, a.tiles), t_fin, "the planted lane")
 if a.saturation:
     time_saturation(ld, max(1, a.tiles), t_fin, "the planted lane")
+if a.top:
+    time_top(ld, max(1, a.tiles), t_fin, "the planted lane")
 ld.close()
 if a.hamming:
     near, t_near = clock(lambda: ldn.finish(hamming=a.hamming))
@@ -367,6 +409,8 @@ if a.equal:
         assert row[:2].tolist() == [3 * n - 1, n - 1], "the equal lane's pairs are not all on well 0 of tile 0"
     if a.saturation:
         time_saturation(eq, 3, e_fin, "every read equal, three tiles")
+    if a.top:
+        time_top(eq, 3, e_fin, "every read equal, three tiles")
     if a.quality:
         time_qualities(eq, 3, e_fin, e_qadd, e_add, "every read equal, one quality value, three tiles")
         # the same bases under random qualities 1..63: eight random planes take turns
@@ -409,7 +453,7 @@ if a.mismatches:
     print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("lane mismatches", o_mm, o_mm / 3))
     one.close()
     three.free()
-if a.distance or a.saturation:
+if a.distance or a.saturation or a.top:
     # three tiles without planted copies whose wells of odd index repeat the well to their left, cycle by cycle
     bare = synth.SynthSpec(seed=5, n_clusters=n, row=a.cols, plant_per_64k=0)
     three = TileBatch(sc, 3, a.cycles, n)
@@ -430,6 +474,8 @@ if a.distance or a.saturation:
         assert row[0] >= 3 * (n // 2) and row[3] >= 0.99 * row[1], "the copies do not sit beside their originals"
     if a.saturation:
         time_saturation(nb, 3, n_fin, "every odd well a copy of its left neighbour, three tiles")
+    if a.top:
+        time_top(nb, 3, n_fin, "every odd well a copy of its left neighbour, three tiles")
     nb.close()
     three.free()
 sc.close()

@@ -1,5 +1,5 @@
 // wave_emu.h - what a kernel's source needs to run on the CPU as it stands (tools/lane_mismatch_emu.cpp,
-// tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp): the 256 lanes of a
+// tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp): the 256 lanes of a
 // workgroup are fibers (ucontext) that a round-robin scheduler switches at the collectives - __syncthreads is a
 // rendezvous of the workgroup, __ballot and __shfl of a wave -, LDS is the kernel's static storage, an atomic add or
 // minimum is a plain one (one fiber runs at a time), and the qualifiers are empty.  Include it, then the kernel's
@@ -16,6 +16,8 @@
 using std::min; using std::max;
 struct uint4 { uint32_t x, y, z, w; };
 struct int2 { int x, y; };
+struct uint2 { uint32_t x, y; };
+static uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{x, y}; }
 struct D3 { unsigned x, y, z; };
 constexpr int kTdBlock = 256, kWave = 64, kSpread = 64, kFpCycles = 10, kLdCmpWords = 8;
 constexpr uint32_t kInvalid = 0xFFFFFFFFu;
@@ -53,7 +55,11 @@ static int __shfl(int v, int src) {
 template <class T, class U> static T atomicAdd(T *p, U v) { T o = *p; *p += (T)v; return o; }
 template <class T, class U> static T atomicMin(T *p, U v) { T o = *p; if ((T)v < o) *p = (T)v; return o; }
 static unsigned long long *spread_row(unsigned long long *cnt, size_t row, int width) { return cnt + (row * kSpread + blockIdx.x % kSpread) * width; }
+// the lanes of the wave below this one whose bit is set in the mask's low (high) half, added to a
+#define __builtin_amdgcn_mbcnt_lo(m, a) ((a) + (uint32_t)__builtin_popcount((uint32_t)(m) & (uint32_t)((1ull << std::min(cur % kWave, 32)) - 1)))
+#define __builtin_amdgcn_mbcnt_hi(m, a) ((a) + (uint32_t)__builtin_popcount((uint32_t)(m) & (uint32_t)((1ull << std::max(cur % kWave - 32, 0)) - 1)))
 #define __device__
+#define __host__
 #define __global__
 #define __shared__ static
 #define __launch_bounds__(x)

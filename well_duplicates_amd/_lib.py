@@ -194,6 +194,18 @@ LANESATURATION_MAX_STEPS = 64
 LANESATURATION_HEAD_COLS = 2
 LANESATURATION_MAX_RADIUS = LANEDISTANCE_MAX_RADIUS
 
+# name -> (restype, argtypes); every symbol include/welldup_lanetop.h declares beyond the eleven above
+LANETOP_PROTOTYPES = {
+    "wd_lane_top_scratch": (_i, [_i64, _i, _i, _i, _i64, ctypes.POINTER(_sz)]),
+    "wd_lane_top": (_i, [_vp, _i, _i64, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+LANETOP_MAX = 1024
+LANETOP_LEVELS = 16
+LANETOP_HEAD_COLS = 4
+LANETOP_EDGES = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 50, 100, 500, 1000, 5000, 10000)
+LANETOP_MAX_PASSES = 8
+LANETOP_DEFAULT_CAPACITY = 65536
+
 _lib = None
 
 
@@ -280,7 +292,7 @@ def unit_of_kernel(kernel: str) -> str:
         return "ingest"
     if kernel.startswith("k_sets"):
         return "sets"
-    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_", "k_ls_")):
+    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_", "k_ls_", "k_lt_")):
         return "tiledups"
     return "scan"
 
@@ -343,7 +355,7 @@ def load():
             list(TILENEAR_PROTOTYPES.items()) + list(LANEDUPS_PROTOTYPES.items()) + list(LANENEAR_PROTOTYPES.items()) + \
             list(LANEINDEX_PROTOTYPES.items()) + list(LANEMISMATCH_PROTOTYPES.items()) + \
             list(LANEDISTANCE_PROTOTYPES.items()) + list(LANEQUALITY_PROTOTYPES.items()) + \
-            list(LANESATURATION_PROTOTYPES.items()):
+            list(LANESATURATION_PROTOTYPES.items()) + list(LANETOP_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

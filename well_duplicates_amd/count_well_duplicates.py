@@ -24,7 +24,7 @@ Differences from the reference, all deliberate:
     --all-wells, --slocs, --layout, --serial-ingest, --dup-sets, --dup-sets-out, --tile-dups, --tile-dups-out,
     --tile-dups-hamming, --tile-dups-pair-budget, --lane-dups, --lane-dups-out,
     --lane-dups-hamming, --lane-dups-index, --lane-dups-mismatches, --lane-dups-distance, --lane-dups-quality,
-    --lane-dups-saturation;
+    --lane-dups-saturation, --lane-dups-top, --lane-dups-top-out;
   * --all-wells --dup-sets groups every tile's wells into duplicate sets and follows each lane's report
     with their counts and the exact duplication (report.write_dup_sets);
   * --all-wells --tile-dups groups every tile's PF wells into classes of equal reads, wherever on the tile they
@@ -48,6 +48,8 @@ Differences from the reference, all deliberate:
     counts, step by step, the reads and the distinct reads among them - the lane's saturation curve, exact, with the
     local copies of --lane-dups-saturation-radius left out: what the last reads still brought, whether the library
     size holds at half the depth, and what it projects for more reads (report.write_lane_saturation);
+    --lane-dups-top N names the duplicates: the lane's duplication levels and its N largest classes (clusters under
+    --lane-dups-hamming) with their spread over the tiles and the read itself (report.write_lane_top);
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
@@ -281,7 +283,23 @@ def parse_args(argv=None):
                         "are made on the flowcell and say nothing about the library.  Default: "
                         "--lane-dups-distance-radius where --lane-dups-distance is given, else 0"
                         % _lib.LANESATURATION_MAX_RADIUS)
+    p.add_argument("--lane-dups-top", type=int, default=None, metavar="N",
+                   help="with --lane-dups: print, after every other block of the lane, the lane's duplication levels (the "
+                        "groups and wells per class size: FastQC's two curves, exact and over every PF read) and its N "
+                        "(1..%d) largest classes (clusters with --lane-dups-hamming): size, share of the PF reads, "
+                        "where the first well lies, the tiles touched, the read itself and a note - poly-A/C/G/T, all "
+                        "N, N-rich, one tile - that tells a contaminant from a large PCR family"
+                        % _lib.LANETOP_MAX)
+    p.add_argument("--lane-dups-top-out", default=None, metavar="FILE",
+                   help="with --lane-dups-top: also write the listed groups to FILE, tab-separated: lane, rank, size, "
+                        "exact, tiles, root_tile, root_well, read, then a tile=count column per tile touched")
     args = p.parse_args(argv)
+    if args.lane_dups_top is not None and not args.lane_dups:
+        p.error("--lane-dups-top needs --lane-dups")
+    if args.lane_dups_top_out is not None and args.lane_dups_top is None:
+        p.error("--lane-dups-top-out needs --lane-dups-top")
+    if args.lane_dups_top is not None and not 1 <= args.lane_dups_top <= _lib.LANETOP_MAX:
+        p.error("--lane-dups-top takes 1..%d, not %d" % (_lib.LANETOP_MAX, args.lane_dups_top))
     if args.lane_dups_saturation and not args.lane_dups:
         p.error("--lane-dups-saturation needs --lane-dups")
     for flag, value, lo, hi in (("steps", args.lane_dups_saturation_steps, 1, _lib.LANESATURATION_MAX_STEPS),
@@ -497,15 +515,15 @@ def lane_cluster_members(class_labels: np.ndarray, cluster_labels: np.ndarray):
 
 
 def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0, index: int = 0,
-                         mismatch: int = 0, distance: int = 0, quality: int = 0, saturation: int = 0):
+                         mismatch: int = 0, distance: int = 0, quality: int = 0, saturation: int = 0, top: int = 0):
     """--lane-dups: the accumulator's workspace - with --lane-dups-hamming plus the scratch of the near finish, with
     --lane-dups-index plus the index workspace, with --lane-dups-mismatches or --lane-dups-distance plus that pass's
     scratch, with --lane-dups-quality plus the quality workspace and that pass's scratch, with --lane-dups-saturation
-    plus that pass's scratch - against the free device memory, before anything is loaded."""
-    need += scratch + index + mismatch + distance + quality + saturation
+    or --lane-dups-top plus that pass's scratch - against the free device memory, before anything is loaded."""
+    need += scratch + index + mismatch + distance + quality + saturation + top
     if need > free:
         raise MemoryError("--lane-dups needs %.2f GB of device memory for a lane of %d tiles x %d wells x %d cycles "
-                          "(%d bytes%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
+                          "(%d bytes%s%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
                               need / 1e9, tiles, wells, cycles, need,
                               ", %d of them for --lane-dups-hamming" % scratch if scratch else "",
                               ", %d of them for --lane-dups-index" % index if index else "",
@@ -513,6 +531,7 @@ def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: i
                               ", %d of them for --lane-dups-distance" % distance if distance else "",
                               ", %d of them for --lane-dups-quality" % quality if quality else "",
                               ", %d of them for --lane-dups-saturation" % saturation if saturation else "",
+                              ", %d of them for --lane-dups-top" % top if top else "",
                               free / 1e9, free))
 
 
@@ -525,7 +544,8 @@ def index_listing(min_share: float, pf: int):
 def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells, tile_batch,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
                dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0, lane_near=0, lane_pair_budget=0,
-               lane_index=None, lane_mismatch=None, lane_distance=None, lane_quality=None, lane_saturation=None):
+               lane_index=None, lane_mismatch=None, lane_distance=None, lane_quality=None, lane_saturation=None,
+               lane_top=0):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
@@ -557,6 +577,8 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     lane_saturation = (steps, seed, x, y, radius) (with lane_dups; x, y: the coordinates of a tile's wells, or None
     with radius 0): after everything else of the lane LaneDups.saturation(steps, seed, x, y, radius):
     into["lsaturation"][lane] = LaneSaturationCounts, on the labels the lane was left with.
+    lane_top = N > 0 (with lane_dups): after every other pass of the lane LaneDups.top(N): into["ltop"][lane] =
+    LaneTopCounts, on the labels the lane was left with.
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -793,6 +815,10 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                         steps, seed, lx, ly, radius = lane_saturation
                         into["lsaturation"][lane] = report.LaneSaturationCounts.from_rows(
                             *ld.saturation(steps, seed, lx, ly, radius), seed, radius,
+                            into["lnear"][lane] if lane_near else into["ldups"][lane], lane_near)
+                    if lane_top:
+                        into["ltop"][lane] = report.LaneTopCounts.from_rows(
+                            *ld.top(lane_top), lane_top, n_clusters, names,
                             into["lnear"][lane] if lane_near else into["ldups"][lane], lane_near)
                     del lane_labels, got
                 _lap("batch %d: lane classes" % bi)
@@ -1087,6 +1113,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 if args.lane_dups_saturation:
                     report.write_lane_saturation(lane, results["lsaturation"][lane], verbose=not args.summary_only,
                                                  out=out_fh)
+                if args.lane_dups_top is not None:
+                    report.write_lane_top(lane, results["ltop"][lane], verbose=not args.summary_only, out=out_fh)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
@@ -1094,7 +1122,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 # scan_lanes fills these, lane_done reads them
                 results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
                            "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}, "lnear": {}, "lindex": {},
-                           "lmindex": {}, "lmismatch": {}, "ldistance": {}, "lquality": {}, "lsaturation": {}}
+                           "lmindex": {}, "lmismatch": {}, "ldistance": {}, "lquality": {}, "lsaturation": {}, "ltop": {}}
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
@@ -1130,7 +1158,10 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                          sc.lane_qual_scratch_bytes(len(tiles)) if quality_d is not None else 0,
                                          saturation=sc.lane_saturation_scratch_bytes(n_targets, len(tiles),
                                                                                      saturation[4] > 0)
-                                         if saturation is not None else 0)
+                                         if saturation is not None else 0,
+                                         top=sc.lane_top_scratch_bytes(n_targets, len(tiles), len(cycle_list),
+                                                                       args.lane_dups_top)
+                                         if args.lane_dups_top is not None else 0)
                 if err is None:             # (a rank whose setup failed has nothing to scan: it goes to the flag)
                     scan_lanes(sc, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                                max(0, args.tile_batch), args.threads,
@@ -1149,13 +1180,17 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                lane_distance=(xy[0], xy[1], args.lane_dups_distance_radius)
                                if args.lane_dups_distance else None,
                                lane_quality=(args.lane_dups_quality_edges, quality_d) if quality_d is not None else None,
-                               lane_saturation=saturation)
+                               lane_saturation=saturation, lane_top=args.lane_dups_top or 0)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
                     if args.tile_dups_out and near_k:
                         write_cluster_members(args.tile_dups_out, results["tnmembers"])
                     elif args.tile_dups_out:
                         write_set_members(args.tile_dups_out, results["tmembers"], column="class")
+                    if args.lane_dups_top_out:
+                        with open(args.lane_dups_top_out, "w") as fh:
+                            for i, lane in enumerate(sorted(results["ltop"], key=lanes.index)):
+                                report.write_lane_top_tsv(lane, results["ltop"][lane], fh, header=i == 0)
                     if args.lane_dups_out:
                         write_lane_members(args.lane_dups_out, results["lmembers"],
                                            index=([e - s for s, e in index_ranges], results["lmindex"])

@@ -302,4 +302,8 @@ try {
 } WD_CATCH
 
 }  // extern "C"
+
+// What comes after this file in the unit is included from here, as lane_quality.inc includes this file: a lane's
+// most frequent reads and their spread (include/welldup_lanetop.h), which uses nothing of this file.
+#include "lane_top.inc"
 #endif

@@ -7,6 +7,8 @@
 // -------------------------------------------------------------------------------------
 // Context
 // -------------------------------------------------------------------------------------
+constexpr int kLaneTopMaxPasses = 8;                  // lane_top.inc derives and asserts it; wd_get_option reports it
+
 struct wd_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -176,6 +178,7 @@ struct wd_ctx {
     int lw_blocks = -1;                                // -1: not built for the current targets; 0: does not apply to them
     int lw_tmax = 0;                                   // most targets of any block
     int line_pairs = 0;                                // option: pairs per block of the line walk (0 = kLwPairs)
+    int lane_top_passes = -1;                          // read-only: histogram passes of the last wd_lane_top (lane_top.inc)
     int sort_targets = 1;                              // option: use it (0: file order, as rounds 1 and 2)
     int sort_strip = 256;                              // option: width of the column strips of that order (0: plain well order)
     int lev2_closed = 1;                               // option: Levenshtein <= 2 by the closed form (0: banded DP)

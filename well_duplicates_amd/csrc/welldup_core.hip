@@ -493,6 +493,9 @@ try {
     else if (n == "dense_uniform_groups") *value = ctx->n_uniform_groups;
     else if (n == "dense_window_groups") *value = ctx->n_window_groups;
     else if (n == "dense_window_dwords") *value = ctx->win_dwords;
+    // read-only: histogram passes the last wd_lane_top took (-1 before the first), and the most it can take
+    else if (n == "lane_top_passes") *value = ctx->lane_top_passes;
+    else if (n == "lane_top_max_passes") *value = kLaneTopMaxPasses;
     else return fail(ctx, WD_ERR_ARG, "unknown option " + n);
     return WD_OK;
 } WD_CATCH

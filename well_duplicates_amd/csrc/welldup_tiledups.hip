@@ -19,6 +19,8 @@
 // it out.  lane_quality.inc, behind them, gives it a second packed array - the reported base qualities - and holds
 // them against the copies: welldup_lanequality.h.  lane_saturation.inc, which lane_quality.inc includes at its
 // end, reads the labels alone: the lane's distinct reads against its depth of welldup_lanesaturation.h.
+// lane_top.inc, which lane_saturation.inc includes at its end, reads the labels, the members and the rows: the lane's
+// most frequent reads and their spread of welldup_lanetop.h.
 #include <memory>
 
 #include "wd_ctx.h"

@@ -1141,3 +1141,116 @@ def write_lane_saturation(lane, counts: LaneSaturationCounts, verbose: bool = Fa
             c.dropped, c.radius, share(c.dropped, c.pf)), file=out)
     else:
         print("Local copies dropped: none (no radius)", file=out)
+
+
+LANE_TOP_MAX = 1024
+LANE_TOP_EDGES = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 50, 100, 500, 1000, 5000, 10000)
+
+
+def lane_top_note(read: str, size: int, tiles_touched: int) -> str:
+    """What a listed read looks like, from the read alone: 'all N'; 'poly-A/C/G/T' when at least 90 % of the called
+    bases are one base; 'N-rich' at 20 % N or more; 'one tile' when the whole group lies on one tile and has at least
+    ten wells; else empty.  The first that applies."""
+    called = [b for b in read if b != "N"]
+    if read and not called:
+        return "all N"
+    for base in "ACGT":
+        if called and 10 * called.count(base) >= 9 * len(called):
+            return "poly-" + base
+    if read and 5 * (len(read) - len(called)) >= len(read):
+        return "N-rich"
+    if tiles_touched == 1 and size >= 10:
+        return "one tile"
+    return ""
+
+
+@dataclass
+class LaneTopCounts:
+    """A lane's most frequent reads and their spread (include/welldup_lanetop.h, LaneDups.top): PF wells, the groups
+    of at least two wells, per duplication level the groups and their wells, and the listed groups - root, size, the
+    wells whose read equals the root's, the wells per tile, the root's read.  redundant: Redundant of the lane row
+    the labels belong to.  k = 0: the groups are classes; K > 0: clusters at Hamming distance <= K."""
+    pf: int = 0
+    groups2: int = 0
+    covered: int = 0
+    redundant: int = 0
+    groups: List[int] = field(default_factory=lambda: [0] * len(LANE_TOP_EDGES))
+    wells: List[int] = field(default_factory=lambda: [0] * len(LANE_TOP_EDGES))
+    root: List[int] = field(default_factory=list)
+    size: List[int] = field(default_factory=list)
+    exact: List[int] = field(default_factory=list)
+    tile_count: List[List[int]] = field(default_factory=list)
+    reads: List[str] = field(default_factory=list)
+    tiles: List[str] = field(default_factory=list)
+    n_wells: int = 1
+    n_top: int = 1
+    k: int = 0
+
+    @classmethod
+    def from_rows(cls, head: Sequence[int], levels, root, size, exact, tile_count, reads: Sequence[str], n_top: int,
+                  n_wells: int, tiles: Sequence[str], final: "LaneDupCounts", k: int = 0) -> "LaneTopCounts":
+        """The seven results of LaneDups.top(n_top); n_wells: the wells of a tile; tiles: the tiles' names by tile
+        index; final: the LaneDupCounts (LaneNearCounts under --lane-dups-hamming K = k) of the labels the lane was
+        left with."""
+        h = [int(v) for v in head]
+        g, w = ([int(v) for v in row] for row in levels)
+        counts = [[int(v) for v in row] for row in tile_count]
+        assert len(h) == 4 and len(g) == len(w) == len(LANE_TOP_EDGES) and 1 <= n_top <= LANE_TOP_MAX
+        assert h[2] == min(n_top, h[1]) == len(root) == len(size) == len(exact) == len(counts) == len(reads)
+        assert sum(w) == h[0] == final.pf and sum(g[1:]) == h[1] and sum(w[1:]) - h[1] == final.redundant
+        assert all(len(row) == len(tiles) and sum(row) == s for row, s in zip(counts, size))
+        return cls(h[0], h[1], h[3], final.redundant, g, w, [int(v) for v in root], [int(v) for v in size],
+                   [int(v) for v in exact], counts, list(reads), [str(t) for t in tiles], int(n_wells), int(n_top), int(k))
+
+    def listed_redundancy(self) -> int:
+        """the redundant wells that lie in the listed groups: sum(size - 1)"""
+        return sum(s - 1 for s in self.size)
+
+
+def write_lane_top(lane, counts: LaneTopCounts, verbose: bool = False, out=None) -> None:
+    """The block that closes a lane's output under --lane-dups-top: (a) a line per non-empty duplication level - its
+    groups, its wells, their share of the distinct reads and of the PF reads -, (b) the listed groups - rank, size,
+    share of PF, the root's tile and well, the tiles touched, the largest share of the group on one tile, the wells
+    that equal the root's read (clusters only), the read and a note (lane_top_note) -, (c) the share of the lane's
+    redundancy that lies in the listed groups.  Not verbose: (c), the top level line and the first five entries."""
+    out = out or sys.stdout
+    c = counts
+    share = lambda v, of: v / of if of else 0.0
+    distinct = sum(c.groups)
+    print(file=out)
+    occupied = [i for i in range(len(LANE_TOP_EDGES)) if c.groups[i]]
+    for i in occupied if verbose else occupied[-1:]:
+        last = i + 1 == len(LANE_TOP_EDGES)
+        hi = None if last else LANE_TOP_EDGES[i + 1] - 1
+        name = ">=%i" % LANE_TOP_EDGES[i] if last else str(hi) if hi == LANE_TOP_EDGES[i] else "%i-%i" % (LANE_TOP_EDGES[i], hi)
+        print("LaneTopLevel: %s\tSize: %s\tGroups: %i\tWells: %i\tOf distinct: %.5f\tOf PF: %.5f" % (
+            lane, name, c.groups[i], c.wells[i], share(c.groups[i], distinct), share(c.wells[i], c.pf)), file=out)
+    if c.k and c.root:
+        print("LaneTop: %s\tthe read shown is that of the cluster's first well (Hamming <= %i), not a consensus" % (lane, c.k),
+              file=out)
+    for r in range(len(c.root) if verbose else min(5, len(c.root))):
+        row = c.tile_count[r]
+        touched = sum(1 for v in row if v)
+        t, w = divmod(c.root[r], c.n_wells)
+        exact = "\tExact: %i/%i" % (c.exact[r], c.size[r]) if c.k else ""
+        print("LaneTop: %s\tRank: %i\tSize: %i\tOf PF: %.5f\tRoot: %s:%i\tTiles: %i\tLargest tile share: %.5f%s\tRead: %s\t"
+              "Note: %s" % (lane, r + 1, c.size[r], share(c.size[r], c.pf), c.tiles[t], w, touched,
+                            share(max(row), c.size[r]), exact, c.reads[r], lane_top_note(c.reads[r], c.size[r], touched) or "-"),
+              file=out)
+    print("LaneTopSummary: %s\tAsked: %i\tListed: %i\tHamming: %i\tPF wells: %i\tGroups: %i\tCovered: %i (%.5f of PF)\t"
+          "Redundant in listed: %i of %i (%.5f)" % (
+              lane, c.n_top, len(c.root), c.k, c.pf, c.groups2, c.covered, share(c.covered, c.pf), c.listed_redundancy(),
+              c.redundant, share(c.listed_redundancy(), c.redundant)), file=out)
+
+
+def write_lane_top_tsv(lane, counts: LaneTopCounts, out, header: bool = True) -> None:
+    """--lane-dups-top-out: a line per listed group - lane, rank, size, exact, tiles, root_tile, root_well, read - and
+    then a tile=count column per tile the group touches."""
+    c = counts
+    if header:
+        print("lane\trank\tsize\texact\ttiles\troot_tile\troot_well\tread", file=out)
+    for r in range(len(c.root)):
+        t, w = divmod(c.root[r], c.n_wells)
+        cols = ["%s=%i" % (c.tiles[i], v) for i, v in enumerate(c.tile_count[r]) if v]
+        print("\t".join([str(lane), str(r + 1), str(c.size[r]), str(c.exact[r]), str(len(cols)), c.tiles[t], str(w),
+                         c.reads[r]] + cols), file=out)

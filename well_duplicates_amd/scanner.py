@@ -341,6 +341,12 @@ class Scanner:
         depends on neither the wells of a tile nor the cycles)."""
         return self._workspace_bytes(self._lib.wd_lane_qual_scratch, max_tiles)
 
+    def lane_top_scratch_bytes(self, n_clusters: int, max_tiles: int, L: int, n_top: int, cand_capacity: int = 0) -> int:
+        """Device bytes LaneDups.top needs beside the accumulator's workspace (wd_lane_top_scratch: the histograms,
+        cand_capacity candidate roots - 0: 65536, raised to n_top -, and per listed group a row of tile counts and its
+        packed read; the wells of a tile take no part)."""
+        return self._workspace_bytes(self._lib.wd_lane_top_scratch, n_clusters, max_tiles, L, n_top, cand_capacity)
+
     def lane_saturation_scratch_bytes(self, n_clusters: int, max_tiles: int, coords: bool = True) -> int:
         """Device bytes LaneDups.saturation needs beside the accumulator's workspace (wd_lane_saturation_scratch: a
         word per well of the lane, the counters, and with `coords` the coordinates of a tile's wells)."""
@@ -878,6 +884,40 @@ class LaneDups:
         finally:
             self.sc.free(d_scratch)
         return head, new_reads, new_distinct
+
+    def top(self, n_top: int, cand_capacity: int = 0):
+        """After finish(), any number of times, before or after every other pass that follows a finish (wd_lane_top,
+        include/welldup_lanetop.h): the lane's duplication levels and its n_top largest groups under the labels the
+        finish left - classes, or clusters after a near finish -, ordered by size descending, then root ascending.
+        -> (head int64 [4]: [PF, Groups2, Listed, Covered], levels int64 [2, 16]: Groups and Wells per level, root
+        uint32 [n], size uint32 [n], exact uint32 [n]: the group's wells whose read equals the root's, tile_count uint32
+        [n, max_tiles], reads: list of n str, the roots' reads), cut to n = Listed.  cand_capacity: how many candidate
+        roots the selection may gather (0: 65536, raised to n_top); the result does not depend on it.  The scratch is
+        allocated for the call and released.  n_top outside 1..1024, a capacity that is negative or positive and
+        below n_top, or a call before a successful finish raises ValueError."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        n = min(max(int(n_top), 1), _lib.LANETOP_MAX)                  # (the library refuses what is out of range)
+        cap = int(cand_capacity)
+        head = np.zeros(_lib.LANETOP_HEAD_COLS, dtype=np.int64)
+        levels = np.zeros((2, _lib.LANETOP_LEVELS), dtype=np.int64)
+        root, size, exact = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+        tile_count = np.zeros((n, self.max_tiles), dtype=np.uint32)
+        reads = np.zeros((n, self.L), dtype=np.uint8)
+        ok = 1 <= int(n_top) <= _lib.LANETOP_MAX and (cap == 0 or n <= cap < 1 << 32)
+        sbytes = self.sc.lane_top_scratch_bytes(self.N, self.max_tiles, self.L, n, cap if ok else 0)
+        d_scratch = self.sc.malloc(max(1, sbytes))
+        try:
+            self.sc._ck(self.sc._lib.wd_lane_top(
+                self._h, int(n_top), cap, ctypes.c_void_p(d_scratch), sbytes, head.ctypes.data_as(ctypes.c_void_p),
+                levels.ctypes.data_as(ctypes.c_void_p), root.ctypes.data_as(ctypes.c_void_p),
+                size.ctypes.data_as(ctypes.c_void_p), exact.ctypes.data_as(ctypes.c_void_p),
+                tile_count.ctypes.data_as(ctypes.c_void_p), reads.ctypes.data_as(ctypes.c_void_p)))
+        finally:
+            self.sc.free(d_scratch)
+        k = int(head[2])
+        return (head, levels, root[:k], size[:k], exact[:k], tile_count[:k],
+                [reads[i].tobytes().decode("ascii") for i in range(k)])
 
     def _end(self):
         if self._h is not None:
