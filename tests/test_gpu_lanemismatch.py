@@ -33,6 +33,8 @@ BYTE = {0: 0x40, 1: 0x81, 2: 0xC2, 3: 0x23, 4: 0x00}                  # a byte o
 
 with open(os.path.join(_lib.CSRC, "lane_mismatch.inc")) as _fh:
     WINDOW = int(re.search(r"constexpr int kLmWindow = (\d+);", _fh.read()).group(1))      # cycles counted in LDS
+with open(os.path.join(_lib.CSRC, "lane_pass.inc")) as _fh:
+    RUN = int(re.search(r"constexpr int kLaneRun = (\d+);", _fh.read()).group(1))         # wells a workgroup takes
 
 
 @pytest.fixture(scope="module")
@@ -150,6 +152,51 @@ def test_lane_mismatches_match_reference_however_the_tiles_are_fed(sc, k, cycles
                 finally:
                     ld.close()
     finally:
+        tb.free()
+
+
+# ---- 1b: pairs across runs and tiles -----------------------------------------------------------------
+def test_pairs_that_cross_a_run_or_a_tile(sc):
+    """2 tiles of 90 x 100 wells - a run of kLaneRun and a bit -, 20 cycles, random reads, K = 2, max_d = 2.  300
+    originals in the first run of tile 0, each copied once at 0, 1 or 2 mismatches: 100 copies into the second,
+    partial run of tile 0, 100 into the first run of tile 1 and 100 into its second.  So a root sits in the first run
+    of tile 0 and its member in one of the other three places - at least one pair in each, held to below on the
+    reference's labels -: every pair crosses a run or a tile, and k_lm_tally takes a second run."""
+    n, cycles, k = 90 * 100, 20, 2
+    assert RUN < n < 2 * RUN
+    rng = np.random.default_rng(9000)
+    reads = [rng.integers(1, 256, (n, cycles)).astype(np.uint8) for _ in range(2)]
+    for r in reads:
+        r[rng.random(r.shape) < 0.005] = 0
+    filts = [(rng.random(n) < 0.95).astype(np.uint8) for _ in range(2)]
+    src = rng.choice(RUN, 300, replace=False)
+    places = [(0, RUN, n), (1, 0, RUN), (1, RUN, n)]                   # (tile, first well, one past the last)
+    for p, (t, lo, hi) in enumerate(places):
+        dst = lo + rng.choice(hi - lo, 100, replace=False)
+        for i, (a, b) in enumerate(zip(src[100 * p:100 * p + 100].tolist(), dst.tolist())):
+            reads[t][b] = reads[0][a]
+            for c in rng.choice(cycles, i % 3, replace=False).tolist():
+                reads[t][b, c] = _other_base(reads[t][b, c])
+            filts[0][a] = filts[t][b] = 1
+    tiles = _host_tiles(reads, filts, [0, 1])
+    near_lane, near_tiles, labels = lane_near_dups(tiles, n, 2, k)
+    want = lane_mismatches(tiles, n, 2, labels, k)
+    flat = labels.reshape(-1)
+    member = np.flatnonzero((flat != 0xFFFFFFFF) & (flat != np.arange(flat.size)))
+    assert member.size >= 300 and (flat[member] < RUN).all()           # every root in the first run of tile 0
+    for t, lo, hi in places:                                           # and members in each of the other three places
+        assert int(((member >= t * n + lo) & (member < t * n + hi)).sum()) >= 100, (t, lo)
+    assert (want[0][4:7] >= 90).all() and want[0][0] == member.size
+    check_mismatch_identities(*want, k, near_lane, near_tiles)
+    tb = _upload(sc, reads, filts)
+    ld = _lane(sc, tb, [0, 1], 2, [[0, 1]])
+    try:
+        rows = _finish(ld, k)
+        got = ld.mismatches(k)
+        _same(got, want)
+        check_mismatch_identities(*got, k, *rows)
+    finally:
+        ld.close()
         tb.free()
 
 

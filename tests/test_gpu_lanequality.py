@@ -5,6 +5,7 @@ the tiles are fed and whatever hash_bits, and against the identities the header 
 import ctypes
 import io
 import os
+import re
 import shutil
 from contextlib import redirect_stdout
 
@@ -33,6 +34,9 @@ QUAL_WAYS = {"one call": "2 + 3", "a tile per call": "one call", "2 + 3": "desce
              "descending indices": "a tile per call"}                 # the qualities come batched otherwise than the reads
 EDGES = [0, 2, 8, 14, 20, 26, 32, 38]                                 # the synthetic planes hold 0 and 2..40: every bin occurs
 NAMES = ("lane row", "tile rows", "qhist", "obs", "mis")
+
+with open(os.path.join(_lib.CSRC, "lane_pass.inc")) as _fh:
+    RUN = int(re.search(r"constexpr int kLaneRun = (\d+);", _fh.read()).group(1))         # wells a workgroup takes
 
 
 @pytest.fixture(scope="module")
@@ -168,6 +172,53 @@ def test_lane_qualities_match_reference_however_the_tiles_are_fed(sc, k, cycles)
                 finally:
                     ld.close()
     finally:
+        tb.free()
+
+
+# ---- 1b: pairs across runs and tiles -----------------------------------------------------------------
+def test_pairs_that_cross_a_run_or_a_tile(sc):
+    """The lane of test_gpu_lanemismatch.py's test of this name, the copies with qualities of their own: 2 tiles of
+    90 x 100 wells - a run of kLaneRun and a bit -, 20 cycles, random reads, K = 2, max_d = 2.  300 originals in the
+    first run of tile 0, each copied once at 0, 1 or 2 mismatches: 100 copies into the second, partial run of tile 0,
+    100 into the first run of tile 1 and 100 into its second.  So a root sits in the first run of tile 0 and its member
+    in one of the other three places - at least one pair in each, held to below on the reference's labels -: every
+    pair crosses a run or a tile, and k_lq_tally takes a second run."""
+    n, cycles, k = 90 * 100, 20, 2
+    assert RUN < n < 2 * RUN
+    rng = np.random.default_rng(9001)
+    reads = [rng.integers(1, 256, (n, cycles)).astype(np.uint8) for _ in range(2)]
+    for r in reads:
+        r[rng.random(r.shape) < 0.005] = 0
+    filts = [(rng.random(n) < 0.95).astype(np.uint8) for _ in range(2)]
+    src = rng.choice(RUN, 300, replace=False)
+    places = [(0, RUN, n), (1, 0, RUN), (1, RUN, n)]                   # (tile, first well, one past the last)
+    for p, (t, lo, hi) in enumerate(places):
+        dst = lo + rng.choice(hi - lo, 100, replace=False)
+        for i, (a, b) in enumerate(zip(src[100 * p:100 * p + 100].tolist(), dst.tolist())):
+            reads[t][b] = _requalify(reads[0][a], rng.integers(2, 41, cycles).astype(np.uint8) << 2)
+            for c in rng.choice(cycles, i % 3, replace=False).tolist():
+                reads[t][b, c] = _other_base(reads[t][b, c])
+            filts[0][a] = filts[t][b] = 1
+    tiles = _host_tiles(reads, filts, [0, 1])
+    labels = lane_near_dups(tiles, n, 2, k)[2]
+    want = lane_qualities(tiles, n, 2, labels, k, EDGES)
+    mism = lane_mismatches(tiles, n, 2, labels, k)
+    flat = labels.reshape(-1)
+    member = np.flatnonzero((flat != 0xFFFFFFFF) & (flat != np.arange(flat.size)))
+    assert member.size >= 300 and (flat[member] < RUN).all()           # every root in the first run of tile 0
+    for t, lo, hi in places:                                           # and members in each of the other three places
+        assert int(((member >= t * n + lo) & (member < t * n + hi)).sum()) >= 100, (t, lo)
+    assert want[0][1] >= 300 and want[0][3] >= 250 and (want[3] > 0).sum() > 32 and (mism[0][4:7] >= 90).all()
+    check_quality_identities(*want, k, cycles, 8, mismatch=mism, pf_wells=_pf(filts))
+    tb = _upload(sc, reads, filts)
+    ld = _lane(sc, tb, [0, 1], 2, [[0, 1]], EDGES)
+    try:
+        _finish(ld, k)
+        got = ld.qualities(k)
+        _same(got, want)
+        check_quality_identities(*got, k, cycles, 8, mismatch=ld.mismatches(k), pf_wells=_pf(filts))
+    finally:
+        ld.close()
         tb.free()
 
 

@@ -44,7 +44,7 @@ int main() {
         for (size_t g = 0; g < W; g++) if (label[g] != kInvalid && label[g] != g && label[label[g]] != label[g]) label[g] = (uint32_t)g;
         std::vector<unsigned long long> cnt_t((size_t)T * kSpread * kLgTileCnt, 0), cnt_l(kSpread * kLgLaneCnt, 0), pairs((size_t)T * T, 0);
         A = Args{tiles, N, label.data(), xy.data(), (unsigned long long)radius * (unsigned long long)radius, matrix ? T : 0, cnt_t.data(), cnt_l.data(), pairs.data()};
-        for (unsigned by = 0; by < 2; by++) for (unsigned bx = 0; bx < (unsigned)((N + kLgRun - 1) / kLgRun); bx++) run_block(bx, by, entry);
+        for (unsigned by = 0; by < 2; by++) for (unsigned bx = 0; bx < (unsigned)((N + kLaneRun - 1) / kLaneRun); bx++) run_block(bx, by, entry);
         // the definitions, directly
         std::vector<long long> wt((size_t)T * 3, 0), wd(11, 0), wp((size_t)T * T, 0);
         for (int ti : tiles) for (int64_t w = 0; w < N; w++) {

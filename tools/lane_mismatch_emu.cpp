@@ -46,7 +46,7 @@ int main() {
         for (size_t g = 0; g < W; g++) if (!code[g].empty()) for (int c = 0; c < L; c++) rows[g * words + c / 10] |= (uint32_t)code[g][c] << (3 * (c % 10));
         std::vector<unsigned long long> cnt_t((size_t)T * kSpread * kLmTileCnt, 0), cnt_l(kSpread * kLmLaneCnt, 0), sub((size_t)L * 25, 0);
         A = Args{tiles, N, label.data(), rows.data(), words, L, max_d, cnt_t.data(), cnt_l.data(), sub.data()};
-        for (unsigned by = 0; by < 2; by++) for (unsigned bx = 0; bx < (unsigned)((N + kLmRun - 1) / kLmRun); bx++) run_block(bx, by, entry);
+        for (unsigned by = 0; by < 2; by++) for (unsigned bx = 0; bx < (unsigned)((N + kLaneRun - 1) / kLaneRun); bx++) run_block(bx, by, entry);
         // the definitions, directly
         std::vector<long long> wt((size_t)T * 4, 0), wd(9, 0), wsub((size_t)L * 25, 0);
         for (int ti : tiles) for (int64_t w = 0; w < N; w++) {

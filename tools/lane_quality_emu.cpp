@@ -54,7 +54,7 @@ int main() {
             rows[g * words + c / 10] |= (uint32_t)code[g][c] << (3 * (c % 10)); qrows[g * words + c / 10] |= (uint32_t)qbin[g][c] << (3 * (c % 10)); }
         std::vector<unsigned long long> cnt_t((size_t)T * kSpread * kLqTileCnt, 0), cells((size_t)kSpread * 2 * kLqCells, 0);
         A = Args{tiles, N, label.data(), rows.data(), qrows.data(), words, L, max_d, cnt_t.data(), cells.data()};
-        for (unsigned by = 0; by < 2; by++) for (unsigned bx = 0; bx < (unsigned)((N + kLqRun - 1) / kLqRun); bx++) run_block(bx, by, entry);
+        for (unsigned by = 0; by < 2; by++) for (unsigned bx = 0; bx < (unsigned)((N + kLaneRun - 1) / kLaneRun); bx++) run_block(bx, by, entry);
         // the definitions, directly
         std::vector<long long> wt((size_t)T * 4, 0), wobs(64, 0), wmis(64, 0);
         for (int ti : tiles) for (int64_t w = 0; w < N; w++) {

@@ -55,7 +55,7 @@ int main() {
         std::vector<uint32_t> cls(W, 0xFFFFFFFFu);
         std::vector<unsigned long long> cnt((size_t)kSpread * 2 * kLsSteps, 0), head((size_t)kSpread * kLsHead, 0);
         A = Args{tiles, N, label.data(), radius2 ? xy.data() : nullptr, radius2, (uint32_t)S, seed * 0x9E3779B9u, cls.data(), cnt.data(), head.data()};
-        const unsigned nbx = (unsigned)((N + kLsRun - 1) / kLsRun);
+        const unsigned nbx = (unsigned)((N + kLaneRun - 1) / kLaneRun);
         for (unsigned by = 0; by < 2; by++) for (unsigned bx = 0; bx < nbx; bx++) run_block(bx, by, entry_min);
         for (unsigned by = 0; by < 2; by++) for (unsigned bx = 0; bx < nbx; bx++) run_block(bx, by, entry_tally);
         // the definitions, directly

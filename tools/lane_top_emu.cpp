@@ -50,7 +50,7 @@ int main() {
         for (size_t g : pf) if (label[g] != g && rand() % 3) memcpy(&rows[g * words], &rows[(size_t)label[g] * words], 4 * words);   // two of three copies exact
         // ---- the first pass
         std::vector<unsigned long long> hist((size_t)kSpread * kLtRow, 0);
-        const unsigned nbx = (unsigned)((N + kLtRun - 1) / kLtRun);
+        const unsigned nbx = (unsigned)((N + kLaneRun - 1) / kLaneRun);
         A = Args{}; A.tile_idx = tiles; A.N = N; A.T = T; A.label = label.data(); A.members = members.data(); A.rows = rows.data(); A.words = words;
         A.first = 1; A.nb = kLtFirstBins; A.hist = hist.data();
         for (unsigned by = 0; by < 2; by++) for (unsigned bx = 0; bx < nbx; bx++) run_block(bx, by, entry_hist);

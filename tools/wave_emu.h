@@ -3,7 +3,8 @@
 // workgroup are fibers (ucontext) that a round-robin scheduler switches at the collectives - __syncthreads is a
 // rendezvous of the workgroup, __ballot and __shfl of a wave -, LDS is the kernel's static storage, an atomic add or
 // minimum is a plain one (one fiber runs at a time), and the qualifiers are empty.  Include it, then the kernel's
-// .inc file, then call run_block(block x, block y, kernel call) per workgroup.
+// .inc file, then call run_block(block x, block y, kernel call) per workgroup.  The device half of csrc/lane_pass.inc -
+// the run (kLaneRun, LaneRun) and wave_by_key - comes with it, included at the end: the kernels' own, not a copy.
 // Nothing here says anything about time.
 #pragma once
 #include <ucontext.h>
@@ -78,3 +79,5 @@ static void run_block(unsigned bx, unsigned by, void (*kernel)()) {
     int left = kTdBlock;
     while (left) for (int t = 0; t < kTdBlock; t++) if (!fib[t].done) { cur = t; swapcontext(&sched, &fib[t].ctx); if (fib[t].done) left--; }
 }
+#define WD_LANE_PASS_EMU
+#include "../well_duplicates_amd/csrc/lane_pass.inc"

@@ -1,8 +1,8 @@
 // lane_distance.inc - how far apart a lane's duplicate copies lie (include/welldup_lanedistance.h): every redundant
 // well of a lane against its root, by where the two sit - same tile or not, and for the same tile the squared
 // distance of their coordinates binned by powers of four and held against the caller's radius.  Included at the end
-// of welldup_tiledups.hip, after lane_mismatch.inc: it uses read_classes.inc (the spread counters) and lane_dups.inc
-// (the accumulator, its label array, ld_tiles_added).
+// of welldup_tiledups.hip, after lane_mismatch.inc: it uses read_classes.inc (the spread counters), lane_dups.inc
+// (the accumulator, its label array) and lane_pass.inc as lane_mismatch.inc does, with its coordinate check.
 //
 // wd_lane_distances, over the tiles that were added (grid y = tile): one kernel, k_lg_tally, and nothing else.  It
 // reads label and writes the caller's scratch only.  Who writes label, and that nobody does after a successful
@@ -12,14 +12,12 @@
 
 namespace {
 
-constexpr int kLgRun = 8192;                       // consecutive wells of a tile a workgroup takes (k_lm_tally's run)
 constexpr int kLgBins = WD_LANEDISTANCE_DIST_BINS;
 constexpr int kLgTileCnt = WD_LANEDISTANCE_TILE_COLS;      // per tile and copy: Pairs, SameTile, Local
 constexpr int kLgLaneCnt = 16;                     // per copy: Dist
 constexpr int kLgHist = WD_LANEDISTANCE_MATRIX_MAX_TILES;  // root tiles a workgroup counts in LDS
 constexpr int kLgCrossKey = 16;                    // grouping key of a cross-tile pair: kLgCrossKey + its root's tile
 static_assert(kLgBins <= kLgLaneCnt && kLgBins <= kLgCrossKey, "a bin is a key below the cross-tile keys");
-static_assert(kLgRun % kTdBlock == 0, "a run is whole trips of the workgroup");
 static_assert(kLgHist * 4 <= 16384, "the root-tile histogram: 16 KB of LDS, k_lm_tally's budget");
 
 // the scratch (include/welldup_lanedistance.h states the arithmetic)
@@ -50,21 +48,18 @@ __device__ inline int lg_bin(unsigned long long q)
 }
 
 // ---- tally --------------------------------------------------------------------------------------
-// grid (ceil(N / kLgRun), tiles added), tile_idx = their tile indices.  A workgroup takes a run of kLgRun
-// consecutive wells of a tile, a lane one well per trip.  A well that is PF (it has a label) and not its own root is
-// a pair.  Its root lies on the same tile when label - base < N (the root is the smaller id, so it is never beyond
-// the tile): no division.  A same-tile pair loads its own (x, y) - coalesced - and its root's - anywhere in the 8 N
-// bytes of the table -, forms q in 64 bits and takes its bin from q's highest bit.  Only a cross-tile pair divides,
-// for its root's tile, and only when the matrix is wanted (n_hist > 0).
+// LaneRun's grid and walk (lane_pass.inc).  A well that is PF (it has a label) and not its own root is a pair.  Its
+// root lies on the same tile when label - base < N (the root is the smaller id, so it is never beyond the tile): no
+// division.  A same-tile pair loads its own (x, y) - coalesced - and its root's - anywhere in the 8 N bytes of the
+// table -, forms q in 64 bits and takes its bin from q's highest bit.  Only a cross-tile pair divides, for its root's
+// tile, and only when the matrix is wanted (n_hist > 0).
 //   - Pairs, SameTile and Local are three ballots per trip, the same in every lane of the wave: summed in registers
 //     over the run, added to LDS once by the wave's first lane.
 //   - Dist and the root tiles.  A lane of equal reads puts every pair on one root - one bin, or one root tile -, a
-//     lane of copies beside their originals puts every pair into Dist[0]: one add per pair would queue them on one
-//     word, in LDS as in memory.  So the pairs of a wave are grouped by key (the bin, or kLgCrossKey + the root's
-//     tile) with ballots as k_lm_tally groups its bins - a trip per key that occurs in the wave, none in a wave
-//     without a pair - and the first lane of a group adds the group's size to the workgroup's Dist or to its
-//     histogram of root tiles [kLgHist] in LDS (32-bit: a run adds at most kLgRun).  SameTile goes to the tile's own
-//     entry of the histogram - the diagonal of TilePairs.
+//     lane of copies beside their originals puts every pair into Dist[0].  So the pairs of a wave are grouped by key
+//     (wave_by_key: the bin, or kLgCrossKey + the root's tile), and the first lane of a group adds the group's size to
+//     the workgroup's Dist or to its histogram of root tiles [kLgHist] in LDS (32-bit: a run adds at most kLaneRun).
+//     SameTile goes to the tile's own entry of the histogram - the diagonal of TilePairs.
 // At the end the workgroup adds what is not zero: the counters to its copy of the spread rows, the histogram to
 // column tile of TilePairs with one 64-bit atomic per root tile it met.
 // Why the result is exact and does not depend on the order of execution: every output is a sum of ones over wells,
@@ -85,21 +80,17 @@ __global__ void __launch_bounds__(kTdBlock) k_lg_tally(const int *__restrict__ t
     if (threadIdx.x < kLgTileCnt + kLgBins)
         s_cnt[threadIdx.x] = 0;
     __syncthreads();
-    const int ti = tile_idx[blockIdx.y];
-    const size_t base = (size_t)ti * (size_t)N;
-    const int64_t run0 = (int64_t)blockIdx.x * kLgRun, run1 = min(run0 + kLgRun, N);
-    const int lane = threadIdx.x & (kWave - 1);
+    const LaneRun run(tile_idx, N);
+    const int ti = run.ti, lane = threadIdx.x & (kWave - 1);
     uint32_t n_pairs = 0, n_same = 0, n_local = 0;                   // the same in every lane of a wave
-    for (int64_t w0 = run0; w0 < run1; w0 += kTdBlock) {              // (the same trips for every lane of the block)
-        const int64_t w = w0 + threadIdx.x;
+    run.walk([&](bool has, int64_t w, size_t g64) {
         bool pair = false, same = false, local = false;
         int key = -1;                                                  // (-1: nothing to group)
-        if (w < run1) {
-            const size_t g64 = base + (size_t)w;
+        if (has) {
             const uint32_t lab = label[g64];
             if (lab != kInvalid && lab != (uint32_t)g64) {
                 pair = true;
-                const int64_t off = (int64_t)lab - (int64_t)base;
+                const int64_t off = (int64_t)lab - (int64_t)run.base;
                 same = off >= 0 && off < N;
                 if (same) {
                     const int2 a = xy[w], b = xy[off];
@@ -115,21 +106,16 @@ __global__ void __launch_bounds__(kTdBlock) k_lg_tally(const int *__restrict__ t
         n_pairs += (uint32_t)__popcll(__ballot(pair));
         n_same += (uint32_t)__popcll(__ballot(same));
         n_local += (uint32_t)__popcll(__ballot(local));
-        unsigned long long rest = __ballot(key >= 0);
-        while (rest) {                                                 // (the same for the wave: a trip per key in it)
-            const int leader = __ffsll((long long)rest) - 1;
-            const int k0 = __shfl(key, leader);
-            const unsigned long long group = __ballot(key == k0);
-            if (lane == leader) {
+        wave_by_key(key >= 0, (uint32_t)key, [&](uint32_t k0, unsigned long long group, bool first) {
+            if (first) {
                 const uint32_t n = (uint32_t)__popcll(group);
-                if (k0 < kLgCrossKey)
+                if (k0 < (uint32_t)kLgCrossKey)
                     atomicAdd(&s_cnt[kLgTileCnt + k0], n);
                 else
                     atomicAdd(&s_hist[k0 - kLgCrossKey], n);
             }
-            rest &= ~group;
-        }
-    }
+        });
+    });
     if (lane == 0) {
         if (n_pairs)
             atomicAdd(&s_cnt[0], n_pairs);
@@ -178,35 +164,26 @@ try {
     const int64_t N = ld->N;
     const int T = ld->max_tiles;
     const bool matrix = tile_pairs != nullptr;
-    if (!ld->finished)
-        return fail(ctx, WD_ERR_ARG, "lane distances come after a successful finish of the lane");
-    if (radius < 0 || radius > WD_LANEDISTANCE_MAX_RADIUS)
-        return fail(ctx, WD_ERR_ARG, "lane distances: the radius is 0.." + std::to_string(WD_LANEDISTANCE_MAX_RADIUS) +
-                                         ", not " + std::to_string(radius));
+    LanePass p(ld);
+    if (const int rc = p.finished("lane distances come after a successful finish of the lane"))
+        return rc;
+    if (const int rc = lane_pass_radius(ctx, "lane distances", radius))
+        return rc;
     if (matrix && T > kLgHist)
         return fail(ctx, WD_ERR_UNSUPPORTED, "lane distances: TilePairs takes at most " + std::to_string(kLgHist) + " tiles");
     const LgLayout lay = lg_layout_of(N, T, matrix);
-    if (!scratch_dev || scratch_bytes < lay.bytes)
-        return fail(ctx, WD_ERR_ARG, "scratch smaller than wd_lane_distance_scratch");
-    if (!on_device(scratch_dev))
-        return fail(ctx, WD_ERR_ARG, "lane distances: the scratch must be in device memory");
-    std::vector<int2> h_xy((size_t)N);
-    for (int64_t w = 0; w < N; w++) {
-        if (((uint32_t)x[w] | (uint32_t)y[w]) > (uint32_t)WD_LANEDISTANCE_MAX_COORD)
-            return fail(ctx, WD_ERR_ARG, "lane distances: well " + std::to_string(w) + " lies at (" + std::to_string(x[w]) +
-                                             ", " + std::to_string(y[w]) + "), outside 0.." +
-                                             std::to_string(WD_LANEDISTANCE_MAX_COORD));
-        h_xy[(size_t)w] = make_int2(x[w], y[w]);
-    }
+    if (const int rc = p.scratch(scratch_dev, scratch_bytes, lay.bytes, "scratch smaller than wd_lane_distance_scratch",
+                                 "lane distances: the scratch must be in device memory"))
+        return rc;
+    std::vector<int2> h_xy;
+    if (const int rc = lane_pass_coords(ctx, "lane distances", x, y, N, h_xy))
+        return rc;
     memset(lane_row, 0, WD_LANEDISTANCE_LANE_COLS * sizeof(int64_t));
     memset(tile_rows, 0, (size_t)T * kLgTileCnt * sizeof(int64_t));
     if (matrix)
         memset(tile_pairs, 0, (size_t)T * T * sizeof(int64_t));
-    const std::vector<int> tiles = ld_tiles_added(ld);
-    if (N == 0 || tiles.empty())
-        return WD_OK;
-    if (bind_device(ctx))
-        return WD_ERR_HIP;
+    if (!p.start())
+        return p.rc;
     uint8_t *sc = (uint8_t *)scratch_dev;
     unsigned long long *cnt_t = (unsigned long long *)(sc + lay.cnt_t);
     unsigned long long *cnt_l = (unsigned long long *)(sc + lay.cnt_l);
@@ -214,29 +191,18 @@ try {
     unsigned long long *d_pairs = (unsigned long long *)(sc + lay.pairs);
     WD_HIP(ctx, hipMemcpyAsync(sc + lay.xy, h_xy.data(), (size_t)N * 8, hipMemcpyHostToDevice, ctx->stream));
     WD_HIP(ctx, hipMemsetAsync(sc + lay.cnt_t, 0, lay.bytes - lay.cnt_t, ctx->stream));
-    WD_HIP(ctx, hipMemcpyAsync(d_tidx, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_lg_tally, dim3((unsigned)((N + kLgRun - 1) / kLgRun), (unsigned)tiles.size()), dim3(kTdBlock), 0,
-                       ctx->stream, d_tidx, N, (const uint32_t *)(ld->ws + ld->lay.label), (const int2 *)(sc + lay.xy),
+    if (const int rc = p.upload(d_tidx))
+        return rc;
+    hipLaunchKernelGGL(k_lg_tally, p.grid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N,
+                       (const uint32_t *)(ld->ws + ld->lay.label), (const int2 *)(sc + lay.xy),
                        (unsigned long long)radius * (unsigned long long)radius, matrix ? T : 0, cnt_t, cnt_l, d_pairs);
     WD_HIP(ctx, hipGetLastError());
-    std::vector<unsigned long long> h_t((size_t)T * kSpread * kLgTileCnt), h_l((size_t)kSpread * kLgLaneCnt);
-    WD_HIP(ctx, hipMemcpyAsync(h_t.data(), cnt_t, h_t.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    WD_HIP(ctx, hipMemcpyAsync(h_l.data(), cnt_l, h_l.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SpreadFetch f_t(cnt_t, (size_t)T, kLgTileCnt), f_l(cnt_l, 1, kLgLaneCnt);
     if (matrix)
         WD_HIP(ctx, hipMemcpyAsync(tile_pairs, d_pairs, (size_t)T * T * 8, hipMemcpyDeviceToHost, ctx->stream));
-    WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int t = 0; t < T; t++) {
-        unsigned long long c[kLgTileCnt];
-        sum_spread(h_t.data(), (size_t)t, kLgTileCnt, c);
-        for (int f = 0; f < kLgTileCnt; f++) {
-            tile_rows[(size_t)t * kLgTileCnt + f] = (int64_t)c[f];
-            lane_row[f] += (int64_t)c[f];
-        }
-    }
-    unsigned long long c[kLgLaneCnt];
-    sum_spread(h_l.data(), 0, kLgLaneCnt, c);
-    for (int b = 0; b < kLgBins; b++)
-        lane_row[kLgTileCnt + b] = (int64_t)c[b];
+    if (const int rc = spread_fetch(ctx, {&f_t, &f_l}))
+        return rc;
+    lane_pass_rows(f_t, T, tile_rows, lane_row, &f_l, kLgBins);
     return WD_OK;
 } WD_CATCH
 

@@ -1,7 +1,8 @@
 // lane_index.inc - a lane's classes split by index read (include/welldup_laneindex.h): the wells of a lane grouped
 // by the bases of their index cycles, and what the last finish found counted per group.  Included at the end of
 // welldup_tiledups.hip: it uses read_classes.inc (plane_pass, mix64, claim_or_join, the spread counters) and
-// lane_dups.inc (the accumulator, its label and member arrays, k_ld_span_count).
+// lane_dups.inc (the accumulator, its label and member arrays, k_ld_span_count); k_li_tally walks LaneRun's runs and
+// the counters come back through spread_fetch (lane_pass.inc).
 //
 // In the caller's index workspace, for W = max_tiles * N wells of capacity: key [W] uint2 (the index read, two words
 // of ten 3-bit codes), glabel [W] (the smallest global id of the well's group), cnt [W][5] uint32 (a group's row, at
@@ -191,8 +192,8 @@ __global__ void __launch_bounds__(kTdBlock) k_li_sub(const int *__restrict__ til
 // ---- tally --------------------------------------------------------------------------------------
 // Every PF well adds up to five ones to the row of its group, and a lane of 96 libraries has 5 M wells for each of
 // ~100 rows (a single-index lane 480 M for one): added to memory one by one they would queue on a handful of
-// addresses (4.3 M adds to one word: 49 ms, read_classes.inc).  So a workgroup takes a run of kLiRun consecutive
-// wells of a tile and adds them up in LDS first:
+// addresses (4.3 M adds to one word: 49 ms, read_classes.inc).  So a workgroup takes a run of kLaneRun consecutive
+// wells of a tile (LaneRun, lane_pass.inc) and adds them up in LDS first:
 //   - within a wave the lanes of the first active lane's group are counted by ballots and added once, by that
 //     lane (the wave-grouped add, for five columns at a time): a single-index lane costs a wave one LDS add per
 //     column, not 64 on one LDS word;
@@ -200,15 +201,14 @@ __global__ void __launch_bounds__(kTdBlock) k_li_sub(const int *__restrict__ til
 //     columns as 16-bit fields of one uint64}: 16 bytes an entry, 8 KB, so that eight workgroups - all 2048 lanes -
 //     fit the 160 KB of a CU with room to spare, and 512 entries hold the few hundred libraries of a pool plus the
 //     keys with a sequencing error that a run of 8192 wells brings (a few per cent of it);
-//   - a field counts at most kLiRun = 8192 < 2^16 wells, so no field carries into the next;
+//   - a field counts at most kLaneRun = 8192 < 2^16 wells, so no field carries into the next;
 //   - an add that finds kLiProbe entries in a row taken by other groups goes to the group's row in memory at once
 //     (it is already wave-grouped), so the result is exact whatever the number of groups;
 //   - at the end an occupied entry is flushed with one global atomic per column that is not zero.
 // The lane index row goes through registers, LDS and the kSpread copies.
-constexpr int kLiRun = 8192;
 constexpr int kLiSlots = 512;
 constexpr int kLiProbe = 8;
-static_assert(kLiRun < 65536 && kLiRun % kTdBlock == 0, "a 16-bit field must hold a run's wells");
+static_assert(kLaneRun < 65536, "a 16-bit field must hold a run's wells");
 static_assert((kLiSlots & (kLiSlots - 1)) == 0, "the LDS table is a power of two");
 
 __device__ inline void li_add_row(uint32_t *row, uint32_t pf, unsigned long long cls)
@@ -223,7 +223,7 @@ __device__ inline void li_add_row(uint32_t *row, uint32_t pf, unsigned long long
     }
 }
 
-// grid (ceil(N / kLiRun), tiles added)
+// LaneRun's grid and walk
 __global__ void __launch_bounds__(kTdBlock) k_li_tally(const int *__restrict__ tile_idx, int64_t N,
                                                         const uint32_t *__restrict__ label,
                                                         const uint32_t *__restrict__ members,
@@ -243,16 +243,12 @@ __global__ void __launch_bounds__(kTdBlock) k_li_tally(const int *__restrict__ t
     if (threadIdx.x < 3)
         s_lane[threadIdx.x] = 0;
     __syncthreads();
-    const size_t base = (size_t)tile_idx[blockIdx.y] * (size_t)N;
-    const int64_t run0 = (int64_t)blockIdx.x * kLiRun, run1 = min(run0 + kLiRun, N);
     const int lane = threadIdx.x & (kWave - 1);
     uint32_t groups = 0, spans = 0, mixed_classes = 0;
-    for (int64_t w0 = run0; w0 < run1; w0 += kTdBlock) {              // (the same trips for every lane of the block)
-        const int64_t w = w0 + threadIdx.x;
+    LaneRun(tile_idx, N).walk([&](bool has, int64_t, size_t g64) {
         bool pf = false, in_lane = false, in_group = false, redundant = false, mixed = false;
         uint32_t gl = kInvalid;
-        if (w < run1) {
-            const size_t g64 = base + (size_t)w;
+        if (has) {
             const uint32_t g = (uint32_t)g64, lab = label[g64];
             if (lab != kInvalid) {
                 pf = true;
@@ -307,7 +303,7 @@ __global__ void __launch_bounds__(kTdBlock) k_li_tally(const int *__restrict__ t
                 li_add_row(cnt + (size_t)gl * kLiCols, add_pf, add_cls);
             }
         }
-    }
+    });
     if (groups)
         atomicAdd(&s_lane[0], groups);
     if (spans)
@@ -412,7 +408,7 @@ int li_tally(wd_lane_dups *ld, const std::vector<int> &tiles)
     unsigned long long *cnt_l = (unsigned long long *)(iws + li->lay.cnt_l);
     const unsigned long long slot_mask = lay.slots - 1;
     const dim3 wgrid((unsigned)((N + kTdBlock - 1) / kTdBlock), (unsigned)tiles.size()), blk(kTdBlock);
-    const dim3 rgrid((unsigned)((N + kLiRun - 1) / kLiRun), (unsigned)tiles.size());
+    const dim3 rgrid((unsigned)((N + kLaneRun - 1) / kLaneRun), (unsigned)tiles.size());
 
     WD_HIP(ctx, hipMemcpyAsync(d_tidx, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     WD_HIP(ctx, hipMemsetAsync(cnt_l, 0, (size_t)kSpread * kLiLaneCnt * 8, ctx->stream));
@@ -424,10 +420,11 @@ int li_tally(wd_lane_dups *ld, const std::vector<int> &tiles)
     hipLaunchKernelGGL(k_ld_span_count, wgrid, blk, 0, ctx->stream, d_tidx, N, aux, table);
     hipLaunchKernelGGL(k_li_tally, rgrid, blk, 0, ctx->stream, d_tidx, N, label, members, glabel, aux, table, cnt, cnt_l);
     WD_HIP(ctx, hipGetLastError());
-    unsigned long long h_l[kSpread * kLiLaneCnt], c[kLiLaneCnt];
-    WD_HIP(ctx, hipMemcpyAsync(h_l, cnt_l, sizeof(h_l), hipMemcpyDeviceToHost, ctx->stream));
-    WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    sum_spread(h_l, 0, kLiLaneCnt, c);
+    SpreadFetch f_l(cnt_l, 1, kLiLaneCnt);
+    unsigned long long c[kLiLaneCnt];
+    if (const int rc = spread_fetch(ctx, {&f_l}))
+        return rc;
+    f_l.sum(0, c);
     li->groups = (int64_t)c[kLiGroups];
     li->spans = (int64_t)c[kLiSpans];
     li->mixed_classes = (int64_t)c[kLiMixedClasses];
@@ -585,11 +582,11 @@ try {
         hipLaunchKernelGGL(k_li_emit, wgrid, blk, 0, ctx->stream, d_tidx, N, glabel, cnt,
                            (unsigned long long)std::max<int64_t>(min_pf, 0), list, d_listed, other);
         WD_HIP(ctx, hipGetLastError());
-        unsigned long long h_o[kSpread * kLiOtherCnt];
-        WD_HIP(ctx, hipMemcpyAsync(h_o, other, sizeof(h_o), hipMemcpyDeviceToHost, ctx->stream));
+        SpreadFetch f_o(other, 1, kLiOtherCnt);
         WD_HIP(ctx, hipMemcpyAsync(&listed, d_listed, 8, hipMemcpyDeviceToHost, ctx->stream));
-        WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        sum_spread(h_o, 0, kLiOtherCnt, h_other);
+        if (const int rc = spread_fetch(ctx, {&f_o}))
+            return rc;
+        f_o.sum(0, h_other);
         if (listed <= (unsigned long long)cap) {
             h_stage.resize((size_t)listed * kLiStage);
             for (size_t off = 0; off < listed; off += chunk) {

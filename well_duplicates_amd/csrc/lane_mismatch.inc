@@ -1,8 +1,8 @@
 // lane_mismatch.inc - where a lane's duplicate copies differ (include/welldup_lanemismatch.h): every redundant well
 // of a lane compared with its root, the distances binned and the differing cycles of the near pairs counted by
 // cycle and by (root's code, member's code).  Included at the end of welldup_tiledups.hip: it uses read_classes.inc
-// (the spread counters), lane_dups.inc (the accumulator, its packed rows and label array, ld_tiles_added) and
-// lane_near.inc's way of loading two rows.
+// (the spread counters), lane_dups.inc (the accumulator, its packed rows and label array), lane_near.inc's way of
+// loading two rows and lane_pass.inc (the run, the grouping by key, the start of a pass and the counters' way back).
 //
 // wd_lane_mismatches, over the tiles that were added (grid y = tile): one kernel, k_lm_tally, and nothing else.
 // It reads rows and label and writes the caller's scratch only.  That neither array changes once a finish has
@@ -17,7 +17,6 @@
 
 namespace {
 
-constexpr int kLmRun = 8192;                       // consecutive wells of a tile a workgroup takes (k_li_tally's run)
 constexpr int kLmWindow = 160;                     // cycles whose substitutions a workgroup counts in LDS
 constexpr int kLmCodes = 5;
 constexpr int kLmCell = kLmCodes * kLmCodes;       // entries of Sub per cycle
@@ -26,7 +25,6 @@ constexpr int kLmBins = WD_LANEMISMATCH_DIST_BINS;
 constexpr int kLmTileCnt = WD_LANEMISMATCH_TILE_COLS;      // per tile and copy: Pairs, Profiled, Mismatches, WithN
 constexpr int kLmLaneCnt = 16;                     // per copy: Dist
 static_assert(kLmBins == kLmMaxD + 2 && kLmBins <= kLmLaneCnt, "Dist has a bin per distance up to max_d and an open one");
-static_assert(kLmRun % kTdBlock == 0, "a run is whole trips of the workgroup");
 static_assert(kLmWindow % kFpCycles == 0 && kLmWindow * kLmCell * 4 <= 16384, "the window: whole words, 16 KB of LDS");
 constexpr uint32_t kLmLow = 0x09249249u;             // the lowest bit of each of a word's ten codes
 static_assert(kMaxCycles <= 1024, "a noted mismatch keeps its cycle in ten bits");
@@ -142,25 +140,23 @@ __device__ inline int lm_compare(const uint32_t *__restrict__ rows, int words, u
 }
 
 // ---- tally --------------------------------------------------------------------------------------
-// grid (ceil(N / kLmRun), tiles added), tile_idx = their tile indices.  A workgroup takes a run of kLmRun
-// consecutive wells of a tile, a lane one well per trip.  A well that is PF (it has a label) and not its own root
-// is a pair: it loads its row and its root's, and d is the popcount of their folded XOR.
+// LaneRun's grid and walk (lane_pass.inc).  A well that is PF (it has a label) and not its own root is a pair: it
+// loads its row and its root's, and d is the popcount of their folded XOR.
 //   - Dist and the tile's four counters.  A lane of equal reads puts every pair into Dist[0], a lane of copies with
-//     one error into Dist[1]: one add per pair would queue millions of them on one word.  So the pairs of a wave
-//     are grouped by bin with ballots - one trip per bin that occurs in the wave, and a wave without a pair, the
-//     common one at 2 % redundancy, pays one ballot - and the first lane of a group adds the group's size to the
-//     workgroup's Dist in LDS.  Pairs, Profiled and Mismatches (d x the group's size for a bin <= max_d) are the
-//     same for every lane of the wave: they are summed in registers over the run, and the wave's first lane adds
-//     them to LDS once.  At the end the workgroup adds what is not zero to its copy of the spread counters.
+//     one error into Dist[1]: the pairs of a wave are grouped by bin (wave_by_key), and the first lane of a group adds
+//     the group's size to the workgroup's Dist in LDS.  Pairs, Profiled and Mismatches (d x the group's size for a
+//     bin <= max_d) are the same for every lane of the wave: they are summed in registers over the run, and the
+//     wave's first lane adds them to LDS once.  At the end the workgroup adds what is not zero to its copy of the
+//     spread counters.
 //   - Sub.  A profiled pair pops its d <= 7 notes: one add each to the LDS histogram [cycle][a][b] of 32-bit
-//     counters (a run adds at most 7 x 8192 to an entry), flushed with one 64-bit atomic per entry that is not
+//     counters (a run adds at most 7 x kLaneRun to an entry), flushed with one 64-bit atomic per entry that is not
 //     zero.  The histogram holds the first kLmWindow cycles - 16 000 bytes, so that eight workgroups, all 2048
 //     lanes of a CU, keep within its 160 KB and occupancy is not what bounds the pass; a mismatch at a later cycle
 //     is added to Sub in memory at once, so the result is exact for every L the accumulator takes.  WithN is
 //     counted where the notes are popped.
 // Why the result is exact and does not depend on the order of execution: every output is a sum of ones (or of d)
 // over wells, each well is visited by exactly one lane of one workgroup, integer adds commute and none can
-// overflow (a 32-bit LDS counter takes at most 7 x kLmRun, the memory counters are 64-bit); what a lane reads -
+// overflow (a 32-bit LDS counter takes at most 7 x kLaneRun, the memory counters are 64-bit); what a lane reads -
 // label and rows - was written by launches that ended before this one began, and nothing writes them after a
 // successful finish (the head of this file says where that was checked); a root's label is a global id of a PF
 // well of an added tile, whose row k_ld_pack wrote.
@@ -178,39 +174,30 @@ __global__ void __launch_bounds__(kTdBlock) k_lm_tally(const int *__restrict__ t
     if (threadIdx.x < kLmTileCnt + kLmBins)
         s_cnt[threadIdx.x] = 0;
     __syncthreads();
-    const int ti = tile_idx[blockIdx.y];
-    const size_t base = (size_t)ti * (size_t)N;
-    const int64_t run0 = (int64_t)blockIdx.x * kLmRun, run1 = min(run0 + kLmRun, N);
-    const int lane = threadIdx.x & (kWave - 1);
+    const LaneRun run(tile_idx, N);
+    const int ti = run.ti, lane = threadIdx.x & (kWave - 1);
     uint32_t n_pairs = 0, n_prof = 0, n_mis = 0, with_n = 0;         // the first three: the same in every lane of a wave
-    for (int64_t w0 = run0; w0 < run1; w0 += kTdBlock) {              // (the same trips for every lane of the block)
-        const int64_t w = w0 + threadIdx.x;
+    run.walk([&](bool has, int64_t, size_t g64) {
         bool pair = false;
         int d = 0;
         LmNotes notes;
-        if (w < run1) {
-            const size_t g64 = base + (size_t)w;
+        if (has) {
             const uint32_t lab = label[g64];
             if (lab != kInvalid && lab != (uint32_t)g64) {
                 pair = true;
                 d = min(lm_compare(rows, words, lab, (uint32_t)g64, notes), kLmBins - 1);
             }
         }
-        unsigned long long rest = __ballot(pair);
-        n_pairs += (uint32_t)__popcll(rest);
-        while (rest) {                                                 // (the same for the wave: a trip per bin in it)
-            const int leader = __ffsll((long long)rest) - 1;
-            const int d0 = __shfl(d, leader);
-            const unsigned long long group = __ballot(pair && d == d0);
+        wave_by_key(pair, (uint32_t)d, [&](uint32_t d0, unsigned long long group, bool first) {
             const uint32_t n = (uint32_t)__popcll(group);
-            if (lane == leader)
+            if (first)
                 atomicAdd(&s_cnt[kLmTileCnt + d0], n);
-            if (d0 <= max_d) {
+            n_pairs += n;
+            if (d0 <= (uint32_t)max_d) {
                 n_prof += n;
-                n_mis += n * (uint32_t)d0;
+                n_mis += n * d0;
             }
-            rest &= ~group;
-        }
+        });
         if (pair && d <= max_d)
             for (int i = 0; i < d; i++) {
                 const uint32_t e = notes.pop();
@@ -221,7 +208,7 @@ __global__ void __launch_bounds__(kTdBlock) k_lm_tally(const int *__restrict__ t
                 else
                     atomicAdd(sub + cell, 1ull);
             }
-    }
+    });
     if (lane == 0) {
         if (n_pairs)
             atomicAdd(&s_cnt[0], n_pairs);
@@ -268,54 +255,40 @@ try {
     wd_ctx *ctx = ld->ctx;
     const int64_t N = ld->N;
     const int T = ld->max_tiles, L = ld->L;
-    if (!ld->finished)
-        return fail(ctx, WD_ERR_ARG, "lane mismatches come after a successful finish of the lane");
+    LanePass p(ld);
+    if (const int rc = p.finished("lane mismatches come after a successful finish of the lane"))
+        return rc;
     if (max_d < 0 || max_d > kLmMaxD)
         return fail(ctx, WD_ERR_ARG, "lane mismatches: max_d is 0.." + std::to_string(kLmMaxD) + ", not " +
                                          std::to_string(max_d));
     const LmLayout lay = lm_layout_of(T, L);
-    if (!scratch_dev || scratch_bytes < lay.bytes)
-        return fail(ctx, WD_ERR_ARG, "scratch smaller than wd_lane_mismatch_scratch");
-    if (!on_device(scratch_dev))
-        return fail(ctx, WD_ERR_ARG, "lane mismatches: the scratch must be in device memory");
+    if (const int rc = p.scratch(scratch_dev, scratch_bytes, lay.bytes, "scratch smaller than wd_lane_mismatch_scratch",
+                                 "lane mismatches: the scratch must be in device memory"))
+        return rc;
     const size_t n_sub = (size_t)L * kLmCell;
     memset(lane_row, 0, WD_LANEMISMATCH_LANE_COLS * sizeof(int64_t));
     memset(tile_rows, 0, (size_t)T * kLmTileCnt * sizeof(int64_t));
     memset(sub, 0, n_sub * sizeof(int64_t));
-    const std::vector<int> tiles = ld_tiles_added(ld);
-    if (N == 0 || tiles.empty())
-        return WD_OK;
-    if (bind_device(ctx))
-        return WD_ERR_HIP;
+    if (!p.start())
+        return p.rc;
     uint8_t *sc = (uint8_t *)scratch_dev;
     unsigned long long *cnt_t = (unsigned long long *)(sc + lay.cnt_t);
     unsigned long long *cnt_l = (unsigned long long *)(sc + lay.cnt_l);
     int *d_tidx = (int *)(sc + lay.tidx);
     unsigned long long *d_sub = (unsigned long long *)(sc + lay.sub);
     WD_HIP(ctx, hipMemsetAsync(sc, 0, lay.bytes, ctx->stream));
-    WD_HIP(ctx, hipMemcpyAsync(d_tidx, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_lm_tally, dim3((unsigned)((N + kLmRun - 1) / kLmRun), (unsigned)tiles.size()), dim3(kTdBlock), 0,
-                       ctx->stream, d_tidx, N, (const uint32_t *)(ld->ws + ld->lay.label),
-                       (const uint32_t *)(ld->ws + ld->lay.rows), ld->lay.words, L, max_d, cnt_t, cnt_l, d_sub);
+    if (const int rc = p.upload(d_tidx))
+        return rc;
+    hipLaunchKernelGGL(k_lm_tally, p.grid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N,
+                       (const uint32_t *)(ld->ws + ld->lay.label), (const uint32_t *)(ld->ws + ld->lay.rows), ld->lay.words, L,
+                       max_d, cnt_t, cnt_l, d_sub);
     WD_HIP(ctx, hipGetLastError());
-    std::vector<unsigned long long> h_t((size_t)T * kSpread * kLmTileCnt), h_l((size_t)kSpread * kLmLaneCnt);
-    WD_HIP(ctx, hipMemcpyAsync(h_t.data(), cnt_t, h_t.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    WD_HIP(ctx, hipMemcpyAsync(h_l.data(), cnt_l, h_l.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SpreadFetch f_t(cnt_t, (size_t)T, kLmTileCnt), f_l(cnt_l, 1, kLmLaneCnt);
     if (n_sub)
         WD_HIP(ctx, hipMemcpyAsync(sub, d_sub, n_sub * 8, hipMemcpyDeviceToHost, ctx->stream));
-    WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int t = 0; t < T; t++) {
-        unsigned long long c[kLmTileCnt];
-        sum_spread(h_t.data(), (size_t)t, kLmTileCnt, c);
-        for (int f = 0; f < kLmTileCnt; f++) {
-            tile_rows[(size_t)t * kLmTileCnt + f] = (int64_t)c[f];
-            lane_row[f] += (int64_t)c[f];
-        }
-    }
-    unsigned long long c[kLmLaneCnt];
-    sum_spread(h_l.data(), 0, kLmLaneCnt, c);
-    for (int b = 0; b < kLmBins; b++)
-        lane_row[kLmTileCnt + b] = (int64_t)c[b];
+    if (const int rc = spread_fetch(ctx, {&f_t, &f_l}))
+        return rc;
+    lane_pass_rows(f_t, T, tile_rows, lane_row, &f_l, kLmBins);
     return WD_OK;
 } WD_CATCH
 

@@ -3,7 +3,8 @@
 // the caller's bins, and after a finish the (pair, cycle) observations counted by the bins of root and member, all of
 // them and those at which the bases differ.  Included at the end of welldup_tiledups.hip, after lane_distance.inc: it
 // uses read_classes.inc (the plane loads, the spread counters), lane_dups.inc (the accumulator, its packed rows and
-// label array, the staged store of k_ld_pack, ld_tiles_added) and lane_mismatch.inc (lm_compare, lm_fold).
+// label array, the staged store of k_ld_pack, ld_tiles_added), lane_mismatch.inc (lm_compare, lm_fold) and, for
+// wd_lane_qualities, lane_pass.inc as lane_mismatch.inc does.
 //
 // wd_lane_qual_add, per batch of tiles (grid y = tile of the batch):
 //   k_lq_pack        the pass of k_ld_pack over the same planes; of every byte it keeps the bin of byte >> 2 where
@@ -16,15 +17,13 @@
 
 namespace {
 
-constexpr int kLqRun = 8192;                       // consecutive wells of a tile a workgroup takes (k_lm_tally's run)
 constexpr int kLqBins = WD_LANEQUALITY_MAX_BINS;
 constexpr int kLqCells = kLqBins * kLqBins;        // entries of Obs, and of Mis
 constexpr int kLqValues = WD_LANEQUALITY_VALUES;
 constexpr int kLqTileCnt = WD_LANEQUALITY_TILE_COLS;       // per tile and copy: Pairs, Profiled, Observations, Mismatches
 static_assert(kLqBins == 8, "a bin is a 3-bit code of a packed row");
 static_assert(WD_LANEQUALITY_MAX_D == kLmMaxD, "a profiled pair is lane_mismatch.inc's");
-static_assert(kLqRun % kTdBlock == 0, "a run is whole trips of the workgroup");
-static_assert((unsigned long long)kLqRun * kMaxCycles < (1ull << 32), "a 32-bit LDS counter must hold a run's observations");
+static_assert((unsigned long long)kLaneRun * kMaxCycles < (1ull << 32), "a 32-bit LDS counter must hold a run's observations");
 
 // the scratch of wd_lane_qualities (include/welldup_lanequality.h states the arithmetic)
 struct LqScratch {
@@ -125,14 +124,14 @@ __device__ inline void lq_pair(const uint32_t *__restrict__ rows, const uint32_t
 }
 
 // ---- tally --------------------------------------------------------------------------------------
-// grid (ceil(N / kLqRun), tiles added), tile_idx = their tile indices: k_lm_tally's grid and pair walk.  A well
-// that is PF (it has a label) and not its own root is a pair; d is lm_compare's.
-//   - Pairs, Profiled, Observations and Mismatches.  The pairs of a wave are grouped by d with ballots, as k_lm_tally
-//     groups them: Profiled and Mismatches (d x the group's size for d <= max_d) are the same for every lane of the
-//     wave, are summed in registers over the run and added to LDS once by the wave's first lane.  Observations is
-//     Profiled x L; what lq_pair counted cell by cell must add up to it, which the tests hold it to.
+// LaneRun's grid and walk (lane_pass.inc), k_lm_tally's pairs: a well that is PF (it has a label) and not its own
+// root; d is lm_compare's.
+//   - Pairs, Profiled, Observations and Mismatches.  The pairs of a wave are grouped by d (wave_by_key): Profiled and
+//     Mismatches (d x the group's size for d <= max_d) are the same for every lane of the wave, are summed in
+//     registers over the run and added to LDS once by the wave's first lane.  Observations is Profiled x L; what
+//     lq_pair counted cell by cell must add up to it, which the tests hold it to.
 //   - Obs and Mis.  A profiled pair walks its four rows (lq_pair) and counts into an LDS histogram of 2 x 64 32-bit
-//     counters (a run adds at most kLqRun x 1024 to one).  The worst lane is one of equal reads with one quality
+//     counters (a run adds at most kLaneRun x 1024 to one).  The worst lane is one of equal reads with one quality
 //     value: every well is a profiled pair and every observation lands in one cell.  An LDS add per observation
 //     would put 64 lanes on one word L times per pair; counted as lq_word counts, such a pair costs one add, and a
 //     pair of binned real qualities a handful.
@@ -155,18 +154,14 @@ __global__ void __launch_bounds__(kTdBlock) k_lq_tally(const int *__restrict__ t
     if (threadIdx.x < kLqTileCnt)
         s_cnt[threadIdx.x] = 0;
     __syncthreads();
-    const int ti = tile_idx[blockIdx.y];
-    const size_t base = (size_t)ti * (size_t)N;
-    const int64_t run0 = (int64_t)blockIdx.x * kLqRun, run1 = min(run0 + kLqRun, N);
-    const int lane = threadIdx.x & (kWave - 1);
+    const LaneRun run(tile_idx, N);
+    const int ti = run.ti, lane = threadIdx.x & (kWave - 1);
     uint32_t n_pairs = 0, n_prof = 0, n_mis = 0;                     // the same in every lane of a wave
-    for (int64_t w0 = run0; w0 < run1; w0 += kTdBlock) {              // (the same trips for every lane of the block)
-        const int64_t w = w0 + threadIdx.x;
+    run.walk([&](bool has, int64_t, size_t g64) {
         bool pair = false;
         int d = 0;
         uint32_t lab = kInvalid;
-        if (w < run1) {
-            const size_t g64 = base + (size_t)w;
+        if (has) {
             lab = label[g64];
             if (lab != kInvalid && lab != (uint32_t)g64) {
                 LmNotes notes;
@@ -174,22 +169,17 @@ __global__ void __launch_bounds__(kTdBlock) k_lq_tally(const int *__restrict__ t
                 d = min(lm_compare(rows, words, lab, (uint32_t)g64, notes), kLmBins - 1);
             }
         }
-        unsigned long long rest = __ballot(pair);
-        n_pairs += (uint32_t)__popcll(rest);
-        while (rest) {                                                 // (the same for the wave: a trip per d in it)
-            const int leader = __ffsll((long long)rest) - 1;
-            const int d0 = __shfl(d, leader);
-            const unsigned long long group = __ballot(pair && d == d0);
-            if (d0 <= max_d) {
-                const uint32_t n = (uint32_t)__popcll(group);
+        wave_by_key(pair, (uint32_t)d, [&](uint32_t d0, unsigned long long group, bool) {
+            const uint32_t n = (uint32_t)__popcll(group);
+            n_pairs += n;
+            if (d0 <= (uint32_t)max_d) {
                 n_prof += n;
-                n_mis += n * (uint32_t)d0;
+                n_mis += n * d0;
             }
-            rest &= ~group;
-        }
+        });
         if (pair && d <= max_d)
-            lq_pair(rows, qrows, words, L, lab, (uint32_t)(base + (size_t)w), s_hist);
-    }
+            lq_pair(rows, qrows, words, L, lab, (uint32_t)g64, s_hist);
+    });
     if (lane == 0) {
         if (n_pairs)
             atomicAdd(&s_cnt[0], n_pairs);
@@ -520,16 +510,16 @@ try {
     const int T = ld->max_tiles, L = ld->L;
     if (!lq)
         return fail(ctx, WD_ERR_ARG, "lane qualities come after wd_lane_qual_begin");
-    if (!ld->finished)
-        return fail(ctx, WD_ERR_ARG, "lane qualities come after a successful finish of the lane");
+    LanePass p(ld);
+    if (const int rc = p.finished("lane qualities come after a successful finish of the lane"))
+        return rc;
     if (max_d < 0 || max_d > kLmMaxD)
         return fail(ctx, WD_ERR_ARG, "lane qualities: max_d is 0.." + std::to_string(kLmMaxD) + ", not " +
                                          std::to_string(max_d));
     const LqScratch lay = lq_scratch_of(T);
-    if (!scratch_dev || scratch_bytes < lay.bytes)
-        return fail(ctx, WD_ERR_ARG, "scratch smaller than wd_lane_qual_scratch");
-    if (!on_device(scratch_dev))
-        return fail(ctx, WD_ERR_ARG, "lane qualities: the scratch must be in device memory");
+    if (const int rc = p.scratch(scratch_dev, scratch_bytes, lay.bytes, "scratch smaller than wd_lane_qual_scratch",
+                                 "lane qualities: the scratch must be in device memory"))
+        return rc;
     for (int t = 0; t < T; t++)
         if (lq->added[t] != ld->added[t])
             return fail(ctx, WD_ERR_ARG, "lane qualities: tile index " + std::to_string(t) +
@@ -539,39 +529,26 @@ try {
     memset(qhist, 0, kLqValues * sizeof(int64_t));
     memset(obs, 0, kLqCells * sizeof(int64_t));
     memset(mis, 0, kLqCells * sizeof(int64_t));
-    const std::vector<int> tiles = ld_tiles_added(ld);
-    if (N == 0 || tiles.empty())
-        return WD_OK;
-    if (bind_device(ctx))
-        return WD_ERR_HIP;
+    if (!p.start())
+        return p.rc;
     uint8_t *sc = (uint8_t *)scratch_dev;
     unsigned long long *cnt_t = (unsigned long long *)(sc + lay.cnt_t);
     unsigned long long *cells = (unsigned long long *)(sc + lay.cells);
     int *d_tidx = (int *)(sc + lay.tidx);
     WD_HIP(ctx, hipMemsetAsync(sc, 0, lay.bytes, ctx->stream));
-    WD_HIP(ctx, hipMemcpyAsync(d_tidx, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_lq_tally, dim3((unsigned)((N + kLqRun - 1) / kLqRun), (unsigned)tiles.size()), dim3(kTdBlock), 0,
-                       ctx->stream, d_tidx, N, (const uint32_t *)(ld->ws + ld->lay.label),
-                       (const uint32_t *)(ld->ws + ld->lay.rows), (const uint32_t *)(lq->ws + lq->lay.qrows), ld->lay.words, L,
-                       max_d, cnt_t, cells);
+    if (const int rc = p.upload(d_tidx))
+        return rc;
+    hipLaunchKernelGGL(k_lq_tally, p.grid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N,
+                       (const uint32_t *)(ld->ws + ld->lay.label), (const uint32_t *)(ld->ws + ld->lay.rows),
+                       (const uint32_t *)(lq->ws + lq->lay.qrows), ld->lay.words, L, max_d, cnt_t, cells);
     WD_HIP(ctx, hipGetLastError());
-    std::vector<unsigned long long> h_t((size_t)T * kSpread * kLqTileCnt), h_c((size_t)kSpread * 2 * kLqCells),
-        h_q((size_t)kSpread * kLqValues);
-    WD_HIP(ctx, hipMemcpyAsync(h_t.data(), cnt_t, h_t.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    WD_HIP(ctx, hipMemcpyAsync(h_c.data(), cells, h_c.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    WD_HIP(ctx, hipMemcpyAsync(h_q.data(), lq->ws + lq->lay.qhist, h_q.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int t = 0; t < T; t++) {
-        unsigned long long c[kLqTileCnt];
-        sum_spread(h_t.data(), (size_t)t, kLqTileCnt, c);
-        for (int f = 0; f < kLqTileCnt; f++) {
-            tile_rows[(size_t)t * kLqTileCnt + f] = (int64_t)c[f];
-            lane_row[f] += (int64_t)c[f];
-        }
-    }
+    SpreadFetch f_t(cnt_t, (size_t)T, kLqTileCnt), f_c(cells, 1, 2 * kLqCells), f_q(lq->ws + lq->lay.qhist, 1, kLqValues);
+    if (const int rc = spread_fetch(ctx, {&f_t, &f_c, &f_q}))
+        return rc;
+    lane_pass_rows(f_t, T, tile_rows, lane_row);
     unsigned long long c[2 * kLqCells], q[kLqValues];
-    sum_spread(h_c.data(), 0, 2 * kLqCells, c);
-    sum_spread(h_q.data(), 0, kLqValues, q);
+    f_c.sum(0, c);
+    f_q.sum(0, q);
     for (int e = 0; e < kLqCells; e++) {
         obs[e] = (int64_t)c[e];
         mis[e] = (int64_t)c[kLqCells + e];

@@ -2,8 +2,8 @@
 // of a lane gets a pseudo-random step from its global id, and per step the wells and the distinct reads that the
 // step brings are counted - the lane's saturation curve, exact, optionally without the local copies
 // lane_distance.inc counts.  Included at the end of welldup_tiledups.hip, after everything of lane_quality.inc (from
-// that file's last lines: the unit's own last line is pinned): it uses read_classes.inc (the spread counters) and
-// lane_dups.inc (the accumulator, its label array, ld_tiles_added).
+// that file's last lines: the unit's own last line is pinned): it uses read_classes.inc (the spread counters),
+// lane_dups.inc (the accumulator, its label array) and lane_pass.inc as lane_distance.inc does.
 //
 // wd_lane_saturation, over the tiles that were added (grid y = tile): a memset and two kernels, k_ls_min and
 // k_ls_tally.  They read label and write the caller's scratch only.  Who writes label, and that nobody does after a
@@ -13,12 +13,10 @@
 
 namespace {
 
-constexpr int kLsRun = 8192;                       // consecutive wells of a tile a workgroup takes (k_lg_tally's run)
 constexpr int kLsSteps = WD_LANESATURATION_MAX_STEPS;
 constexpr int kLsHead = WD_LANESATURATION_HEAD_COLS;       // per copy: PF, Dropped
 constexpr int kLsStepBits = 6;                     // a step is below 2^6
 static_assert(kLsSteps <= 1 << kLsStepBits, "the smallest step of a wave's group is found bit by bit");
-static_assert(kLsRun % kTdBlock == 0, "a run is whole trips of the workgroup");
 static_assert(2 * kLsSteps <= kTdBlock, "a lane per bin when the workgroup adds its histogram");
 
 // the scratch (include/welldup_lanesaturation.h states the arithmetic)
@@ -69,15 +67,13 @@ __device__ inline bool ls_dropped(int64_t w, uint32_t lab, size_t base, int64_t 
 }
 
 // ---- the class steps ------------------------------------------------------------------------------
-// grid (ceil(N / kLsRun), tiles added), tile_idx = their tile indices.  cls: a word per well of the lane, all
-// 0xFFFFFFFF when the kernel starts (a memset on the same stream).  A workgroup takes a run of kLsRun consecutive
-// wells of a tile, a lane one well per trip.  A counted well that is a pair (PF, not its own root, not dropped) forms
-// its step and reads its root's word - every lane of the wave at once -; it is a candidate only where its step is
-// smaller.  Roots and wells in no class write nothing: k_ls_tally takes the minimum with their own step.  A dropped
-// well takes no part.
-//   - The candidates of a wave are grouped by root with ballots as k_lg_tally groups its keys - a trip per root that
-//     occurs among them, none in a wave without a candidate -, and the group's first lane issues one atomicMin of the
-//     group's smallest step; nobody waits for it.  A group of one lane - the usual case: a class has few members
+// LaneRun's grid and walk (lane_pass.inc).  cls: a word per well of the lane, all 0xFFFFFFFF when the kernel starts
+// (a memset on the same stream).  A counted well that is a pair (PF, not its own root, not dropped) forms its step and
+// reads its root's word - every lane of the wave at once -; it is a candidate only where its step is smaller.  Roots
+// and wells in no class write nothing: k_ls_tally takes the minimum with their own step.  A dropped well takes no
+// part.
+//   - The candidates of a wave are grouped by root (wave_by_key), and the group's first lane issues one atomicMin of
+//     the group's smallest step; nobody waits for it.  A group of one lane - the usual case: a class has few members
 //     and they lie anywhere - has its step at hand; of a larger group the smallest step is found bit by bit from the
 //     top with six ballots (a step is below 64).  A lane of equal reads puts every pair on one root: with one
 //     atomicMin per candidate k_ls_min took 3.4 ms on three such tiles, 40 times the planted lane's time per tile
@@ -97,29 +93,21 @@ __global__ void __launch_bounds__(kTdBlock) k_ls_min(const int *__restrict__ til
                                                       const int2 *__restrict__ xy, unsigned long long radius2,
                                                       uint32_t steps, uint32_t salt, uint32_t *cls)
 {
-    const size_t base = (size_t)tile_idx[blockIdx.y] * (size_t)N;
-    const int64_t run0 = (int64_t)blockIdx.x * kLsRun, run1 = min(run0 + kLsRun, N);
-    const int lane = threadIdx.x & (kWave - 1);
+    const LaneRun run(tile_idx, N);
     uint32_t last_root = kInvalid, last_step = 0;                     // the same in every lane of a wave
-    for (int64_t w0 = run0; w0 < run1; w0 += kTdBlock) {              // (the same trips for every lane of the block)
-        const int64_t w = w0 + threadIdx.x;
+    run.walk([&](bool has, int64_t w, size_t g64) {
         bool cand = false;
         uint32_t lab = kInvalid, s = 0;
-        if (w < run1) {
-            const size_t g64 = base + (size_t)w;
+        if (has) {
             lab = label[g64];
-            if (lab != kInvalid && lab != (uint32_t)g64 && !ls_dropped(w, lab, base, N, xy, radius2)) {
+            if (lab != kInvalid && lab != (uint32_t)g64 && !ls_dropped(w, lab, run.base, N, xy, radius2)) {
                 s = ls_step((uint32_t)g64, salt, steps);
                 cand = s < cls[lab];
             }
         }
-        unsigned long long rest = __ballot(cand);
-        while (rest) {                                                 // (the same for the wave: a trip per root in it)
-            const int leader = __ffsll((long long)rest) - 1;
-            const uint32_t r0 = (uint32_t)__shfl((int)lab, leader);
-            const unsigned long long group = __ballot(cand && lab == r0);
-            uint32_t m = (uint32_t)__shfl((int)s, leader);
-            if (group & (group - 1)) {                                 // more lanes than the leader
+        wave_by_key(cand, lab, [&](uint32_t r0, unsigned long long group, bool first) {
+            uint32_t m = (uint32_t)__shfl((int)s, __ffsll((long long)group) - 1);
+            if (group & (group - 1)) {                                 // more lanes than the first
                 unsigned long long low = group;                        // the lanes of the group that hold its smallest step
                 m = 0;
                 for (int bit = kLsStepBits - 1; bit >= 0; bit--) {
@@ -131,24 +119,23 @@ __global__ void __launch_bounds__(kTdBlock) k_ls_min(const int *__restrict__ til
                 }
             }
             if (r0 != last_root || m < last_step) {
-                if (lane == leader)
+                if (first)
                     atomicMin(&cls[r0], m);
                 last_root = r0;
                 last_step = m;
             }
-            rest &= ~group;
-        }
-    }
+        });
+    });
 }
 
 // ---- tally ----------------------------------------------------------------------------------------
 // The same grid, after k_ls_min on the same stream: every word of cls is final.  A counted well adds one to
 // NewReads[its step]; a well with label = own id (a root, or a PF well in no class - never dropped) also adds one to
 // NewDistinct[min(its word, its own step)].  Both are counted in the workgroup's LDS histogram [2][kLsSteps] (32-bit:
-// a run adds at most kLsRun to a bin); PF and Dropped are two ballots per trip, the same in every lane of the wave,
+// a run adds at most kLaneRun to a bin); PF and Dropped are two ballots per trip, the same in every lane of the wave,
 // summed in registers over the run as k_lg_tally sums Pairs.  At the end the workgroup adds what is not zero to its
 // copy of the spread counters.
-// No grouping by key as k_lg_tally has it: there the keys follow the data - a lane of equal reads puts every pair
+// No wave_by_key as in k_lg_tally: there the keys follow the data - a lane of equal reads puts every pair
 // into one bin -, here the key is a hash of the well's id, whatever the reads are, and spreads a wave's 64 wells
 // evenly over the S steps, so no bin is hot beyond what a small S makes of it (S = 1: the 64 adds of a wave queue on
 // one LDS word; a lane's worth of that is still LDS traffic only).
@@ -168,20 +155,17 @@ __global__ void __launch_bounds__(kTdBlock) k_ls_tally(const int *__restrict__ t
     if (threadIdx.x < kLsHead)
         s_head[threadIdx.x] = 0;
     __syncthreads();
-    const size_t base = (size_t)tile_idx[blockIdx.y] * (size_t)N;
-    const int64_t run0 = (int64_t)blockIdx.x * kLsRun, run1 = min(run0 + kLsRun, N);
+    const LaneRun run(tile_idx, N);
     const int lane = threadIdx.x & (kWave - 1);
     uint32_t n_pf = 0, n_dropped = 0;                                 // the same in every lane of a wave
-    for (int64_t w0 = run0; w0 < run1; w0 += kTdBlock) {              // (the same trips for every lane of the block)
-        const int64_t w = w0 + threadIdx.x;
+    run.walk([&](bool has, int64_t w, size_t g64) {
         bool pf = false, dropped = false;
-        if (w < run1) {
-            const size_t g64 = base + (size_t)w;
+        if (has) {
             const uint32_t lab = label[g64];
             if (lab != kInvalid) {
                 pf = true;
                 const bool own = lab == (uint32_t)g64;
-                dropped = !own && ls_dropped(w, lab, base, N, xy, radius2);
+                dropped = !own && ls_dropped(w, lab, run.base, N, xy, radius2);
                 if (!dropped) {
                     const uint32_t s = ls_step((uint32_t)g64, salt, steps);
                     atomicAdd(&s_hist[s], 1u);
@@ -192,7 +176,7 @@ __global__ void __launch_bounds__(kTdBlock) k_ls_tally(const int *__restrict__ t
         }
         n_pf += (uint32_t)__popcll(__ballot(pf));
         n_dropped += (uint32_t)__popcll(__ballot(dropped));
-    }
+    });
     if (lane == 0) {
         if (n_pf)
             atomicAdd(&s_head[0], n_pf);
@@ -231,38 +215,30 @@ try {
     const int64_t N = ld->N;
     const int T = ld->max_tiles;
     const bool coords = x != nullptr;
-    if (!ld->finished)
-        return fail(ctx, WD_ERR_ARG, "lane saturation comes after a successful finish of the lane");
+    LanePass p(ld);
+    if (const int rc = p.finished("lane saturation comes after a successful finish of the lane"))
+        return rc;
     if (steps < 1 || steps > kLsSteps)
         return fail(ctx, WD_ERR_ARG, "lane saturation: 1.." + std::to_string(kLsSteps) + " steps, not " + std::to_string(steps));
-    if (radius < 0 || radius > WD_LANEDISTANCE_MAX_RADIUS)
-        return fail(ctx, WD_ERR_ARG, "lane saturation: the radius is 0.." + std::to_string(WD_LANEDISTANCE_MAX_RADIUS) +
-                                         ", not " + std::to_string(radius));
+    if (const int rc = lane_pass_radius(ctx, "lane saturation", radius))
+        return rc;
     if ((x == nullptr) != (y == nullptr))
         return fail(ctx, WD_ERR_ARG, "lane saturation: x and y come together or not at all");
     if (radius > 0 && !coords)
         return fail(ctx, WD_ERR_ARG, "lane saturation: a radius needs the coordinates");
     const LsLayout lay = ls_layout_of(N, T, coords);
-    if (!scratch_dev || scratch_bytes < lay.bytes)
-        return fail(ctx, WD_ERR_ARG, "scratch smaller than wd_lane_saturation_scratch");
-    if (!on_device(scratch_dev))
-        return fail(ctx, WD_ERR_ARG, "lane saturation: the scratch must be in device memory");
-    std::vector<int2> h_xy(coords ? (size_t)N : 0);
-    for (int64_t w = 0; coords && w < N; w++) {
-        if (((uint32_t)x[w] | (uint32_t)y[w]) > (uint32_t)WD_LANEDISTANCE_MAX_COORD)
-            return fail(ctx, WD_ERR_ARG, "lane saturation: well " + std::to_string(w) + " lies at (" + std::to_string(x[w]) +
-                                             ", " + std::to_string(y[w]) + "), outside 0.." +
-                                             std::to_string(WD_LANEDISTANCE_MAX_COORD));
-        h_xy[(size_t)w] = make_int2(x[w], y[w]);
-    }
+    if (const int rc = p.scratch(scratch_dev, scratch_bytes, lay.bytes, "scratch smaller than wd_lane_saturation_scratch",
+                                 "lane saturation: the scratch must be in device memory"))
+        return rc;
+    std::vector<int2> h_xy;
+    if (coords)
+        if (const int rc = lane_pass_coords(ctx, "lane saturation", x, y, N, h_xy))
+            return rc;
     memset(head_row, 0, kLsHead * sizeof(int64_t));
     memset(new_reads, 0, (size_t)steps * sizeof(int64_t));
     memset(new_distinct, 0, (size_t)steps * sizeof(int64_t));
-    const std::vector<int> tiles = ld_tiles_added(ld);
-    if (N == 0 || tiles.empty())
-        return WD_OK;
-    if (bind_device(ctx))
-        return WD_ERR_HIP;
+    if (!p.start())
+        return p.rc;
     uint8_t *sc = (uint8_t *)scratch_dev;
     uint32_t *cls = (uint32_t *)(sc + lay.cls);
     unsigned long long *cnt = (unsigned long long *)(sc + lay.cnt);
@@ -277,21 +253,20 @@ try {
     if (drop)
         WD_HIP(ctx, hipMemcpyAsync(sc + lay.xy, h_xy.data(), (size_t)N * 8, hipMemcpyHostToDevice, ctx->stream));
     WD_HIP(ctx, hipMemsetAsync(sc + lay.cnt, 0, lay.tidx - lay.cnt, ctx->stream));
-    WD_HIP(ctx, hipMemcpyAsync(d_tidx, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    const dim3 grid((unsigned)((N + kLsRun - 1) / kLsRun), (unsigned)tiles.size());
-    hipLaunchKernelGGL(k_ls_min, grid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, label, d_xy, radius2, (uint32_t)steps, salt,
+    if (const int rc = p.upload(d_tidx))
+        return rc;
+    hipLaunchKernelGGL(k_ls_min, p.grid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, label, d_xy, radius2, (uint32_t)steps, salt,
                        cls);
     WD_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_ls_tally, grid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, label, d_xy, radius2, (uint32_t)steps,
+    hipLaunchKernelGGL(k_ls_tally, p.grid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, label, d_xy, radius2, (uint32_t)steps,
                        salt, (const uint32_t *)cls, cnt, head);
     WD_HIP(ctx, hipGetLastError());
-    std::vector<unsigned long long> h_c((size_t)kSpread * 2 * kLsSteps), h_h((size_t)kSpread * kLsHead);
-    WD_HIP(ctx, hipMemcpyAsync(h_c.data(), cnt, h_c.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    WD_HIP(ctx, hipMemcpyAsync(h_h.data(), head, h_h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SpreadFetch f_c(cnt, 1, 2 * kLsSteps), f_h(head, 1, kLsHead);
+    if (const int rc = spread_fetch(ctx, {&f_c, &f_h}))
+        return rc;
     unsigned long long c[2 * kLsSteps], h[kLsHead];
-    sum_spread(h_c.data(), 0, 2 * kLsSteps, c);
-    sum_spread(h_h.data(), 0, kLsHead, h);
+    f_c.sum(0, c);
+    f_h.sum(0, h);
     for (int j = 0; j < steps; j++) {
         new_reads[j] = (int64_t)c[j];
         new_distinct[j] = (int64_t)c[kLsSteps + j];

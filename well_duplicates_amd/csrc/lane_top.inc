@@ -1,7 +1,7 @@
 // lane_top.inc - a lane's most frequent reads and their spread (include/welldup_lanetop.h): the duplication levels of
 // the whole lane, and the n_top largest groups with their wells per tile, their wells of exactly the root's read, and
 // the read.  Included at the end of lane_saturation.inc, after everything of it: it uses read_classes.inc (the spread
-// counters) and lane_dups.inc (the accumulator, its label, members and rows, ld_tiles_added).
+// counters), lane_dups.inc (the accumulator, its label, members and rows) and lane_pass.inc as lane_mismatch.inc does.
 //
 // wd_lane_top, over the tiles that were added (grid y = tile): k_lt_hist once or a few times, k_lt_collect, a sort on
 // the host, k_lt_spread and k_lt_rows.  They read label, members and the rows and write the caller's scratch only
@@ -28,7 +28,6 @@
 
 namespace {
 
-constexpr int kLtRun = 8192;                       // consecutive wells of a tile a workgroup takes (k_ls_tally's run)
 constexpr int kLtBins = 2048;                      // bins of a linear pass
 constexpr int kLtBinBits = 11;
 constexpr int kLtLevels = WD_LANETOP_LEVELS;
@@ -42,7 +41,7 @@ constexpr int kLtFirstWidthBits = 30 + 32;         // its widest bin, in keys
 static_assert(1 << kLtBinBits == kLtBins, "a linear pass takes kLtBinBits bits off the range");
 static_assert(1 + (kLtFirstWidthBits + kLtBinBits - 1) / kLtBinBits <= kLaneTopMaxPasses, "the bound on the passes");
 static_assert(kLaneTopMaxPasses == WD_LANETOP_MAX_PASSES, "the header states the bound");
-static_assert(kLtFirstBins <= kLtBins && kLtRun % kTdBlock == 0 && kLtSlots % kTdBlock == 0, "");
+static_assert(kLtFirstBins <= kLtBins && kLtSlots % kTdBlock == 0, "");
 static_assert((kLtSlots & (kLtSlots - 1)) == 0 && kLtSlots >= 2 * WD_LANETOP_MAX, "half of the table stays free");
 
 // the scratch (include/welldup_lanetop.h states the arithmetic)
@@ -102,13 +101,12 @@ __device__ inline unsigned long long lt_key(uint32_t size, uint32_t root)
 }
 
 // ---- the histograms -------------------------------------------------------------------------------
-// grid (ceil(N / kLtRun), tiles added), tile_idx = their tile indices.  A workgroup takes a run of kLtRun consecutive
-// wells of a tile, a lane one well per trip: label, and - of a well that is its own label, a root or a PF well in no
-// group - members: 8 bytes a well, both coalesced.
+// LaneRun's grid and walk (lane_pass.inc).  A lane loads label, and - of a well that is its own label, a root or a PF
+// well in no group - members: 8 bytes a well, both coalesced.
 //   first pass (first != 0): wells in no group are counted by ballot into level 0; a root adds one to the bin of its
 //     size, one to Groups and its size to Wells of its level.
 //   later passes: a root of key >= lo adds one to bin (key - lo) >> shift, or to `above` when that is >= nb.
-// The adds go to the workgroup's LDS words (32-bit: a run adds at most kLtRun ones to a word, and sizes that are
+// The adds go to the workgroup's LDS words (32-bit: a run adds at most kLaneRun ones to a word, and sizes that are
 // summed anywhere sum to at most the lane's wells, < 2^32); the lanes of a wave that carry the same size (first
 // pass) or name the same word (later) as the wave's first root add once - a lane of pairs has every root in one bin,
 // and 32 LDS atomics on one word per trip would queue.  At the end the workgroup adds what is not zero to its copy of
@@ -125,30 +123,24 @@ __global__ void __launch_bounds__(kTdBlock) k_lt_hist(const int *__restrict__ ti
     for (int i = threadIdx.x; i < kLtRow; i += kTdBlock)
         s_cnt[i] = 0;
     __syncthreads();
-    const size_t base = (size_t)tile_idx[blockIdx.y] * (size_t)N;
-    const int64_t run0 = (int64_t)blockIdx.x * kLtRun, run1 = min(run0 + kLtRun, N);
     const int lane = threadIdx.x & (kWave - 1);
     uint32_t n_single = 0;                                             // the same in every lane of a wave
-    for (int64_t w0 = run0; w0 < run1; w0 += kTdBlock) {              // (the same trips for every lane of the block)
-        const int64_t w = w0 + threadIdx.x;
+    LaneRun(tile_idx, N).walk([&](bool has, int64_t, size_t g64) {
         bool single = false, root = false;
         uint32_t size = 0, word = 0;
-        if (w < run1) {
-            const size_t g64 = base + (size_t)w;
-            if (label[g64] == (uint32_t)g64) {
-                size = members[g64] + 1u;
-                single = size == 1u;
-                if (!single) {
-                    if (first) {
+        if (has && label[g64] == (uint32_t)g64) {
+            size = members[g64] + 1u;
+            single = size == 1u;
+            if (!single) {
+                if (first) {
+                    root = true;
+                    word = lt_first_bin(size);
+                } else {
+                    const unsigned long long key = lt_key(size, (uint32_t)g64);
+                    if (key >= lo) {
+                        const unsigned long long b = (key - lo) >> shift;
                         root = true;
-                        word = lt_first_bin(size);
-                    } else {
-                        const unsigned long long key = lt_key(size, (uint32_t)g64);
-                        if (key >= lo) {
-                            const unsigned long long b = (key - lo) >> shift;
-                            root = true;
-                            word = b < nb ? (uint32_t)b : (uint32_t)kLtAbove;
-                        }
+                        word = b < nb ? (uint32_t)b : (uint32_t)kLtAbove;
                     }
                 }
             }
@@ -172,7 +164,7 @@ __global__ void __launch_bounds__(kTdBlock) k_lt_hist(const int *__restrict__ ti
                 }
             }
         }
-    }
+    });
     if (first && lane == 0 && n_single) {
         atomicAdd(&s_cnt[kLtLev], n_single);
         atomicAdd(&s_cnt[kLtLev + kLtLevels], n_single);
@@ -194,21 +186,17 @@ __global__ void __launch_bounds__(kTdBlock) k_lt_collect(const int *__restrict__
                                                           const uint32_t *__restrict__ members, unsigned long long thr,
                                                           uint2 *__restrict__ cand, uint32_t capacity, uint32_t *count)
 {
-    const size_t base = (size_t)tile_idx[blockIdx.y] * (size_t)N;
-    const int64_t run0 = (int64_t)blockIdx.x * kLtRun, run1 = min(run0 + kLtRun, N);
     const int lane = threadIdx.x & (kWave - 1);
-    for (int64_t w0 = run0; w0 < run1; w0 += kTdBlock) {              // (the same trips for every lane of the block)
-        const int64_t w = w0 + threadIdx.x;
+    LaneRun(tile_idx, N).walk([&](bool has, int64_t, size_t g64) {
         bool take = false;
         uint32_t size = 0;
-        const size_t g64 = base + (size_t)w;
-        if (w < run1 && label[g64] == (uint32_t)g64) {
+        if (has && label[g64] == (uint32_t)g64) {
             size = members[g64] + 1u;
             take = size >= 2u && lt_key(size, (uint32_t)g64) >= thr;
         }
         const unsigned long long m = __ballot(take);
         if (!m)                                                        // (the same for the wave)
-            continue;
+            return;
         const int leader = __ffsll((long long)m) - 1;
         uint32_t at = 0;
         if (lane == leader)
@@ -217,7 +205,7 @@ __global__ void __launch_bounds__(kTdBlock) k_lt_collect(const int *__restrict__
         const uint32_t pos = at + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
         if (take && pos >= at && pos < capacity)                       // (pos >= at: the count has not wrapped)
             cand[pos] = make_uint2((uint32_t)g64, size);
-    }
+    });
 }
 
 // ---- spread and exactness -------------------------------------------------------------------------
@@ -229,8 +217,8 @@ __global__ void __launch_bounds__(kTdBlock) k_lt_collect(const int *__restrict__
 // itself and cheaper, so members is not read here.)  A well whose label is listed counts itself in the workgroup's
 // row s_cnt [n] - a workgroup lies in one tile, so the row is part of the tile's column - and, when its packed row
 // equals the root's (all `words` words; the root's own trivially), in s_eq.  The lanes of a wave that name the same
-// rank add once, a trip per rank among them as k_ls_min has it: a lane of equal reads puts 256 wells a trip on one
-// word.  What is not zero is flushed with global atomics: tile_count[rank][tile], exact[rank].
+// rank add once (wave_by_key): a lane of equal reads puts 256 wells a trip on one word.  What is not zero is
+// flushed with global atomics: tile_count[rank][tile], exact[rank].
 // Exact: sums of ones over wells as in k_lt_hist; the rows were written before the finish and nobody writes them.
 __device__ inline uint32_t lt_slot(uint32_t root) { return (root * 0x9E3779B1u) >> (32 - kLtBinBits); }
 static_assert(1 << kLtBinBits == kLtSlots, "lt_slot keeps the top bits of the product");
@@ -250,16 +238,12 @@ __global__ void __launch_bounds__(kTdBlock) k_lt_spread(const int *__restrict__ 
         s_eq[i] = 0;
     }
     __syncthreads();
-    const int ti = tile_idx[blockIdx.y];
-    const size_t base = (size_t)ti * (size_t)N;
-    const int64_t run0 = (int64_t)blockIdx.x * kLtRun, run1 = min(run0 + kLtRun, N);
-    const int lane = threadIdx.x & (kWave - 1);
-    for (int64_t w0 = run0; w0 < run1; w0 += kTdBlock) {              // (the same trips for every lane of the block)
-        const int64_t w = w0 + threadIdx.x;
+    const LaneRun run(tile_idx, N);
+    const int ti = run.ti;
+    run.walk([&](bool has, int64_t, size_t g64) {
         bool listed = false, equal = false;
         uint32_t rank = 0;
-        if (w < run1) {
-            const size_t g64 = base + (size_t)w;
+        if (has) {
             const uint32_t lab = label[g64];
             if (lab != kInvalid) {
                 uint32_t h = lt_slot(lab);
@@ -282,20 +266,15 @@ __global__ void __launch_bounds__(kTdBlock) k_lt_spread(const int *__restrict__ 
                 }
             }
         }
-        unsigned long long rest = __ballot(listed);
-        while (rest) {                                                 // (the same for the wave: a trip per rank in it)
-            const int leader = __ffsll((long long)rest) - 1;
-            const uint32_t r0 = (uint32_t)__shfl((int)rank, leader);
-            const unsigned long long group = __ballot(listed && rank == r0);
+        wave_by_key(listed, rank, [&](uint32_t r0, unsigned long long group, bool first) {
             const unsigned long long eq = __ballot(listed && rank == r0 && equal);
-            if (lane == leader) {
+            if (first) {
                 atomicAdd(&s_cnt[r0], (uint32_t)__popcll(group));
                 if (eq)
                     atomicAdd(&s_eq[r0], (uint32_t)__popcll(eq));
             }
-            rest &= ~group;
-        }
-    }
+        });
+    });
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += kTdBlock) {
         if (s_cnt[i])
@@ -326,15 +305,15 @@ struct LtCand {
 // one histogram pass; h: the summed row
 int lt_hist_pass(wd_ctx *ctx, const dim3 &grid, const int *d_tidx, int64_t N, const uint32_t *label,
                  const uint32_t *members, bool first, unsigned long long lo, int shift, uint32_t nb,
-                 unsigned long long *d_hist, std::vector<unsigned long long> &h_copies, unsigned long long *h)
+                 unsigned long long *d_hist, SpreadFetch &copies, unsigned long long *h)
 {
     WD_HIP(ctx, hipMemsetAsync(d_hist, 0, (size_t)kSpread * kLtRow * 8, ctx->stream));
     hipLaunchKernelGGL(k_lt_hist, grid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, label, members, first ? 1 : 0, lo, shift,
                        nb, d_hist);
     WD_HIP(ctx, hipGetLastError());
-    WD_HIP(ctx, hipMemcpyAsync(h_copies.data(), d_hist, h_copies.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    sum_spread(h_copies.data(), 0, kLtRow, h);
+    if (const int rc = spread_fetch(ctx, {&copies}))
+        return rc;
+    copies.sum(0, h);
     return WD_OK;
 }
 
@@ -362,8 +341,9 @@ try {
     wd_ctx *ctx = ld->ctx;
     const int64_t N = ld->N;
     const int T = ld->max_tiles, L = ld->L;
-    if (!ld->finished)
-        return fail(ctx, WD_ERR_ARG, "lane top comes after a successful finish of the lane");
+    LanePass p(ld);
+    if (const int rc = p.finished("lane top comes after a successful finish of the lane"))
+        return rc;
     if (n_top < 1 || n_top > WD_LANETOP_MAX)
         return fail(ctx, WD_ERR_ARG, "lane top: 1.." + std::to_string(WD_LANETOP_MAX) + " groups, not " + std::to_string(n_top));
     if (cand_capacity < 0 || (cand_capacity > 0 && cand_capacity < n_top))
@@ -372,10 +352,9 @@ try {
     const LtLayout lay = lt_layout_of(T, L, n_top, cand_capacity);
     if (lay.cap > 0xFFFFFFFFll)
         return fail(ctx, WD_ERR_ARG, "lane top: the candidate capacity is below 2^32");
-    if (!scratch_dev || scratch_bytes < lay.bytes)
-        return fail(ctx, WD_ERR_ARG, "scratch smaller than wd_lane_top_scratch");
-    if (!on_device(scratch_dev))
-        return fail(ctx, WD_ERR_ARG, "lane top: the scratch must be in device memory");
+    if (const int rc = p.scratch(scratch_dev, scratch_bytes, lay.bytes, "scratch smaller than wd_lane_top_scratch",
+                                 "lane top: the scratch must be in device memory"))
+        return rc;
     const size_t n = (size_t)n_top;
     memset(head_row, 0, kLtHead * sizeof(int64_t));
     memset(levels, 0, 2 * kLtLevels * sizeof(int64_t));
@@ -385,11 +364,8 @@ try {
     memset(tile_count, 0, n * (size_t)T * 4);
     memset(reads, 0, n * (size_t)L);
     ctx->lane_top_passes = 0;
-    const std::vector<int> tiles = ld_tiles_added(ld);
-    if (N == 0 || tiles.empty())
-        return WD_OK;
-    if (bind_device(ctx))
-        return WD_ERR_HIP;
+    if (!p.start())
+        return p.rc;
     uint8_t *sc = (uint8_t *)scratch_dev;
     unsigned long long *d_hist = (unsigned long long *)(sc + lay.hist);
     uint2 *d_cand = (uint2 *)(sc + lay.cand);
@@ -404,13 +380,14 @@ try {
     const uint32_t *members = (const uint32_t *)(ld->ws + ld->lay.members);
     const uint32_t *rows = (const uint32_t *)(ld->ws + ld->lay.rows);
     const int words = lay.words;
-    WD_HIP(ctx, hipMemcpyAsync(d_tidx, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    const dim3 grid((unsigned)((N + kLtRun - 1) / kLtRun), (unsigned)tiles.size());
+    if (const int rc = p.upload(d_tidx))
+        return rc;
+    const dim3 &grid = p.grid;
 
     // the first pass: the levels, and the sizes on the log-linear scale
-    std::vector<unsigned long long> h_copies((size_t)kSpread * kLtRow);
+    SpreadFetch copies(d_hist, 1, kLtRow);
     unsigned long long h[kLtRow];
-    if (const int rc = lt_hist_pass(ctx, grid, d_tidx, N, label, members, true, 0, 0, kLtFirstBins, d_hist, h_copies, h))
+    if (const int rc = lt_hist_pass(ctx, grid, d_tidx, N, label, members, true, 0, 0, kLtFirstBins, d_hist, copies, h))
         return rc;
     int passes = 1;
     ctx->lane_top_passes = passes;
@@ -461,7 +438,7 @@ try {
             while (((width - 1) >> shift) + 1 > (unsigned long long)kLtBins)
                 shift++;
             nb = (uint32_t)(((width - 1) >> shift) + 1);
-            if (const int rc = lt_hist_pass(ctx, grid, d_tidx, N, label, members, false, lo, shift, nb, d_hist, h_copies, h))
+            if (const int rc = lt_hist_pass(ctx, grid, d_tidx, N, label, members, false, lo, shift, nb, d_hist, copies, h))
                 return rc;
             ctx->lane_top_passes = ++passes;
         }

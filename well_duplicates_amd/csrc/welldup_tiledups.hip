@@ -13,7 +13,9 @@
 // tile_near.inc (included at the end, after the near_core.inc it shares with lane_near.inc) builds the
 // near-duplicate clusters of welldup_tilenear.h on these parts, lane_dups.inc (after it) the classes across all
 // tiles of a lane of welldup_lanedups.h, lane_near.inc (after it) the near-duplicate clusters of a lane of
-// welldup_lanenear.h, lane_index.inc (after it) a lane's duplication per index read of welldup_laneindex.h,
+// welldup_lanenear.h, lane_pass.inc (after it) what the passes that follow a lane's finish share - the walk over a run
+// of wells, the grouping of a wave by key, the start of a pass and the counters' way back -, lane_index.inc (after
+// it) a lane's duplication per index read of welldup_laneindex.h,
 // lane_mismatch.inc (after it) where a lane's duplicate copies differ of welldup_lanemismatch.h, lane_distance.inc
 // (last) how far apart they lie of welldup_lanedistance.h: all of these work on the accumulator as lane_dups.inc laid
 // it out.  lane_quality.inc, behind them, gives it a second packed array - the reported base qualities - and holds
@@ -501,6 +503,7 @@ try {
 #include "tile_near.inc"      // near-duplicate clusters (include/welldup_tilenear.h) on the parts above
 #include "lane_dups.inc"      // read classes across the tiles of a lane (include/welldup_lanedups.h)
 #include "lane_near.inc"      // near-duplicate clusters of a lane (include/welldup_lanenear.h) on all of the above
+#include "lane_pass.inc"      // what the passes after a lane's finish share: the walk, the grouping, the host's steps
 #include "lane_index.inc"     // a lane's classes split by index read (include/welldup_laneindex.h)
 #include "lane_mismatch.inc"  // where a lane's duplicate copies differ (include/welldup_lanemismatch.h)
 #include "lane_distance.inc"  // how far apart a lane's duplicate copies lie (include/welldup_lanedistance.h)

@@ -571,6 +571,26 @@ class LaneDups:
         if self.qual_edges is not None:
             self._qual_begin()
 
+    def _with_scratch(self, nbytes: int, call):
+        """call(scratch pointer, nbytes) -> a return code, checked; the scratch lives for the call."""
+        d_scratch = self.sc.malloc(max(1, nbytes))
+        try:
+            self.sc._ck(call(ctypes.c_void_p(d_scratch), nbytes))
+        finally:
+            self.sc.free(d_scratch)
+
+    def _coords(self, x, y):
+        """x, y of a tile's N wells, each 0 .. 2^24 - 1 -> contiguous int32 arrays; ValueError names the first
+        well that is out of range."""
+        xs, ys = (np.asarray(v) for v in (x, y))
+        if xs.shape != (self.N,) or ys.shape != (self.N,):
+            raise ValueError("x and y hold a coordinate per well of a tile: %d each" % self.N)
+        for v in (xs, ys):                               # (what int32 cannot hold is out of range as well)
+            if v.size and (int(v.min()) < 0 or int(v.max()) > _lib.LANEDISTANCE_MAX_COORD):
+                w = int(np.flatnonzero((v < 0) | (v > _lib.LANEDISTANCE_MAX_COORD))[0])
+                raise ValueError("well %d lies at (%d, %d), outside 0..%d" % (w, xs[w], ys[w], _lib.LANEDISTANCE_MAX_COORD))
+        return np.ascontiguousarray(xs, dtype=np.int32), np.ascontiguousarray(ys, dtype=np.int32)
+
     # ---- the lane's reported base quality against its copies (include/welldup_lanequality.h)
     def qual_begin(self, edges: Sequence[int]):
         """Gives the lane a quality part before the first add: edges are the bins' lower edges (1..8 of them,
@@ -631,15 +651,11 @@ class LaneDups:
         qhist = np.zeros(_lib.LANEQUALITY_VALUES, dtype=np.int64)
         obs = np.zeros((_lib.LANEQUALITY_MAX_BINS, _lib.LANEQUALITY_MAX_BINS), dtype=np.int64)
         mis = np.zeros_like(obs)
-        sbytes = self.sc.lane_qual_scratch_bytes(self.max_tiles)
-        d_scratch = self.sc.malloc(sbytes)
-        try:
-            self.sc._ck(self.sc._lib.wd_lane_qualities(
-                self._h, int(max_d), ctypes.c_void_p(d_scratch), sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
-                tile_rows.ctypes.data_as(ctypes.c_void_p), qhist.ctypes.data_as(ctypes.c_void_p),
-                obs.ctypes.data_as(ctypes.c_void_p), mis.ctypes.data_as(ctypes.c_void_p)))
-        finally:
-            self.sc.free(d_scratch)
+        self._with_scratch(self.sc.lane_qual_scratch_bytes(self.max_tiles),
+                           lambda d_scratch, sbytes: self.sc._lib.wd_lane_qualities(
+                               self._h, int(max_d), d_scratch, sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
+                               tile_rows.ctypes.data_as(ctypes.c_void_p), qhist.ctypes.data_as(ctypes.c_void_p),
+                               obs.ctypes.data_as(ctypes.c_void_p), mis.ctypes.data_as(ctypes.c_void_p)))
         return lane_row, tile_rows, qhist, obs, mis
 
     # ---- the lane's duplication per index read (include/welldup_laneindex.h)
@@ -798,14 +814,10 @@ class LaneDups:
         lane_row = np.zeros(_lib.LANEMISMATCH_LANE_COLS, dtype=np.int64)
         tile_rows = np.zeros((self.max_tiles, _lib.LANEMISMATCH_TILE_COLS), dtype=np.int64)
         sub = np.zeros((self.L, 5, 5), dtype=np.int64)
-        sbytes = self.sc.lane_mismatch_scratch_bytes(self.max_tiles, self.L)
-        d_scratch = self.sc.malloc(sbytes)
-        try:
-            self.sc._ck(self.sc._lib.wd_lane_mismatches(
-                self._h, int(max_d), ctypes.c_void_p(d_scratch), sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
-                tile_rows.ctypes.data_as(ctypes.c_void_p), sub.ctypes.data_as(ctypes.c_void_p)))
-        finally:
-            self.sc.free(d_scratch)
+        self._with_scratch(self.sc.lane_mismatch_scratch_bytes(self.max_tiles, self.L),
+                           lambda d_scratch, sbytes: self.sc._lib.wd_lane_mismatches(
+                               self._h, int(max_d), d_scratch, sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
+                               tile_rows.ctypes.data_as(ctypes.c_void_p), sub.ctypes.data_as(ctypes.c_void_p)))
         return lane_row, tile_rows, sub
 
     def distances(self, x, y, radius: int, matrix: bool = True):
@@ -818,27 +830,16 @@ class LaneDups:
         a coordinate out of range or a call before a successful finish raises ValueError."""
         if self._h is None:
             raise ValueError("the accumulator is closed")
-        xs, ys = (np.asarray(v) for v in (x, y))
-        if xs.shape != (self.N,) or ys.shape != (self.N,):
-            raise ValueError("x and y hold a coordinate per well of a tile: %d each" % self.N)
-        for v in (xs, ys):                               # (what int32 cannot hold is out of range as well)
-            if v.size and (int(v.min()) < 0 or int(v.max()) > _lib.LANEDISTANCE_MAX_COORD):
-                w = int(np.flatnonzero((v < 0) | (v > _lib.LANEDISTANCE_MAX_COORD))[0])
-                raise ValueError("well %d lies at (%d, %d), outside 0..%d" % (w, xs[w], ys[w], _lib.LANEDISTANCE_MAX_COORD))
-        xs, ys = np.ascontiguousarray(xs, dtype=np.int32), np.ascontiguousarray(ys, dtype=np.int32)
+        xs, ys = self._coords(x, y)
         lane_row = np.zeros(_lib.LANEDISTANCE_LANE_COLS, dtype=np.int64)
         tile_rows = np.zeros((self.max_tiles, _lib.LANEDISTANCE_TILE_COLS), dtype=np.int64)
         tile_pairs = np.zeros((self.max_tiles, self.max_tiles), dtype=np.int64) if matrix else None
-        sbytes = self.sc.lane_distance_scratch_bytes(self.N, self.max_tiles, matrix)
-        d_scratch = self.sc.malloc(max(1, sbytes))
-        try:
-            self.sc._ck(self.sc._lib.wd_lane_distances(
-                self._h, xs.ctypes.data_as(ctypes.c_void_p), ys.ctypes.data_as(ctypes.c_void_p), int(radius),
-                ctypes.c_void_p(d_scratch), sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
-                tile_rows.ctypes.data_as(ctypes.c_void_p),
-                tile_pairs.ctypes.data_as(ctypes.c_void_p) if matrix else None))
-        finally:
-            self.sc.free(d_scratch)
+        self._with_scratch(self.sc.lane_distance_scratch_bytes(self.N, self.max_tiles, matrix),
+                           lambda d_scratch, sbytes: self.sc._lib.wd_lane_distances(
+                               self._h, xs.ctypes.data_as(ctypes.c_void_p), ys.ctypes.data_as(ctypes.c_void_p), int(radius),
+                               d_scratch, sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
+                               tile_rows.ctypes.data_as(ctypes.c_void_p),
+                               tile_pairs.ctypes.data_as(ctypes.c_void_p) if matrix else None))
         return lane_row, tile_rows, tile_pairs
 
     def saturation(self, steps: int, seed: int = 0, x=None, y=None, radius: int = 0):
@@ -861,28 +862,17 @@ class LaneDups:
         coords = x is not None
         xs = ys = None
         if coords:
-            xs, ys = (np.asarray(v) for v in (x, y))
-            if xs.shape != (self.N,) or ys.shape != (self.N,):
-                raise ValueError("x and y hold a coordinate per well of a tile: %d each" % self.N)
-            for v in (xs, ys):                           # (what int32 cannot hold is out of range as well)
-                if v.size and (int(v.min()) < 0 or int(v.max()) > _lib.LANEDISTANCE_MAX_COORD):
-                    w = int(np.flatnonzero((v < 0) | (v > _lib.LANEDISTANCE_MAX_COORD))[0])
-                    raise ValueError("well %d lies at (%d, %d), outside 0..%d" % (w, xs[w], ys[w], _lib.LANEDISTANCE_MAX_COORD))
-            xs, ys = np.ascontiguousarray(xs, dtype=np.int32), np.ascontiguousarray(ys, dtype=np.int32)
+            xs, ys = self._coords(x, y)
         n = min(max(int(steps), 1), _lib.LANESATURATION_MAX_STEPS)     # (the library refuses steps out of range)
         head = np.zeros(_lib.LANESATURATION_HEAD_COLS, dtype=np.int64)
         new_reads = np.zeros(n, dtype=np.int64)
         new_distinct = np.zeros(n, dtype=np.int64)
-        sbytes = self.sc.lane_saturation_scratch_bytes(self.N, self.max_tiles, coords)
-        d_scratch = self.sc.malloc(max(1, sbytes))
-        try:
-            self.sc._ck(self.sc._lib.wd_lane_saturation(
-                self._h, int(steps), int(seed), xs.ctypes.data_as(ctypes.c_void_p) if coords else None,
-                ys.ctypes.data_as(ctypes.c_void_p) if coords else None, int(radius), ctypes.c_void_p(d_scratch), sbytes,
-                head.ctypes.data_as(ctypes.c_void_p), new_reads.ctypes.data_as(ctypes.c_void_p),
-                new_distinct.ctypes.data_as(ctypes.c_void_p)))
-        finally:
-            self.sc.free(d_scratch)
+        self._with_scratch(self.sc.lane_saturation_scratch_bytes(self.N, self.max_tiles, coords),
+                           lambda d_scratch, sbytes: self.sc._lib.wd_lane_saturation(
+                               self._h, int(steps), int(seed), xs.ctypes.data_as(ctypes.c_void_p) if coords else None,
+                               ys.ctypes.data_as(ctypes.c_void_p) if coords else None, int(radius), d_scratch, sbytes,
+                               head.ctypes.data_as(ctypes.c_void_p), new_reads.ctypes.data_as(ctypes.c_void_p),
+                               new_distinct.ctypes.data_as(ctypes.c_void_p)))
         return head, new_reads, new_distinct
 
     def top(self, n_top: int, cand_capacity: int = 0):
@@ -905,16 +895,12 @@ class LaneDups:
         tile_count = np.zeros((n, self.max_tiles), dtype=np.uint32)
         reads = np.zeros((n, self.L), dtype=np.uint8)
         ok = 1 <= int(n_top) <= _lib.LANETOP_MAX and (cap == 0 or n <= cap < 1 << 32)
-        sbytes = self.sc.lane_top_scratch_bytes(self.N, self.max_tiles, self.L, n, cap if ok else 0)
-        d_scratch = self.sc.malloc(max(1, sbytes))
-        try:
-            self.sc._ck(self.sc._lib.wd_lane_top(
-                self._h, int(n_top), cap, ctypes.c_void_p(d_scratch), sbytes, head.ctypes.data_as(ctypes.c_void_p),
-                levels.ctypes.data_as(ctypes.c_void_p), root.ctypes.data_as(ctypes.c_void_p),
-                size.ctypes.data_as(ctypes.c_void_p), exact.ctypes.data_as(ctypes.c_void_p),
-                tile_count.ctypes.data_as(ctypes.c_void_p), reads.ctypes.data_as(ctypes.c_void_p)))
-        finally:
-            self.sc.free(d_scratch)
+        self._with_scratch(self.sc.lane_top_scratch_bytes(self.N, self.max_tiles, self.L, n, cap if ok else 0),
+                           lambda d_scratch, sbytes: self.sc._lib.wd_lane_top(
+                               self._h, int(n_top), cap, d_scratch, sbytes, head.ctypes.data_as(ctypes.c_void_p),
+                               levels.ctypes.data_as(ctypes.c_void_p), root.ctypes.data_as(ctypes.c_void_p),
+                               size.ctypes.data_as(ctypes.c_void_p), exact.ctypes.data_as(ctypes.c_void_p),
+                               tile_count.ctypes.data_as(ctypes.c_void_p), reads.ctypes.data_as(ctypes.c_void_p)))
         k = int(head[2])
         return (head, levels, root[:k], size[:k], exact[:k], tile_count[:k],
                 [reads[i].tobytes().decode("ascii") for i in range(k)])
