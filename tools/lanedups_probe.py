@@ -18,7 +18,11 @@ less tile_dups.  `--heavy M` adds a lane of four tiles with M distinct reads in 
 streamed again into an accumulator with an index part of I cycles, once per case - M libraries of equal size, one
 library (every counter on one row: the hottest case), and uniform random index reads (the most groups) - and
 LaneDups.index_add per tile and LaneDups.index_finish are printed beside the equality add and finish on the same
-batches.
+batches.  With `--hops` LaneDups.hops (which libraries the lane's duplicate copies join, include/welldup_lanehops.h)
+is timed per tile on each of the three, in the same process and on the same labels, beside index_finish, the equality
+finish and LaneDups.mismatches(0): split I / 2 (a single index for I = 1), E = 1, the listing index_finish's first
+1024 groups - on the lane of random index reads, where no group is large enough to be listed, 1024 keys that no well
+carries, so that every pair searches the whole listing twice and lands in the one cell Other x Other.
 `--hamming K --mismatches` times LaneDups.mismatches(K) (where the lane's duplicate copies differ,
 include/welldup_lanemismatch.h) per tile of the lane beside the equality finish on the same batches, on three
 inputs: the planted lane (after the near finish), the `--equal` lane (every well a pair of one root, every pair in
@@ -56,7 +60,7 @@ For per-kernel times run it under
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/lanedups_probe.py
 
 (the k_ld_* rows of the stats are this stage, k_li_* the index part, k_lm_* the mismatch pass, k_lg_* the distance pass,
-k_lq_* the quality part, k_ls_* the saturation pass, k_lt_* the top pass, k_td_* the per-tile classes, k_dense_* the scan)."""
+k_lq_* the quality part, k_ls_* the saturation pass, k_lt_* the top pass, k_lh_* the hops pass, k_td_* the per-tile classes, k_dense_* the scan)."""
 import argparse
 import os
 import sys
@@ -83,6 +87,8 @@ ap.add_argument("--heavy", type=int, default=0, metavar="M",
                 help="also time a lane of M distinct reads that share their first segment (needs --hamming)")
 ap.add_argument("--index", type=int, default=0, metavar="I", help="also time the index part with I index cycles (1..20)")
 ap.add_argument("--libraries", type=int, default=96, metavar="M", help="libraries of the pooled lane (with --index)")
+ap.add_argument("--hops", action="store_true",
+                help="also time LaneDups.hops beside index_finish, the equality finish and mismatches(0) (needs --index)")
 ap.add_argument("--mismatches", action="store_true",
                 help="also time LaneDups.mismatches(K) beside the equality finish (needs --hamming; three inputs)")
 ap.add_argument("--distance", action="store_true",
@@ -102,6 +108,8 @@ if a.mismatches and not a.hamming:
     ap.error("--mismatches needs --hamming K")
 if a.quality and not a.hamming:
     ap.error("--quality needs --hamming K")
+if a.hops and not a.index:
+    ap.error("--hops needs --index I")
 QUALITY_BINS = [0, 2, 10, 20, 25, 30, 35, 40]         # the CLI's default
 
 n = a.rows * a.cols
@@ -372,8 +380,25 @@ if a.index:
             i_iadd += dt
         (ilane, _, _), i_fin = clock(lambda: li.finish())
         pf = int(ilane[0])
-        (irow, other, rows, _), i_ifin = clock(lambda: li.index_finish(max(1, -(-pf // 1000)), 1001))
+        (irow, other, rows, ikeys), i_ifin = clock(lambda: li.index_finish(max(1, -(-pf // 1000)), 1001))
         _, i_again = clock(lambda: li.index_finish(max(1, -(-pf // 1000)), 1001))
+        if a.hops:
+            listed = ikeys[:1024]
+            if listed.size == 0:                     # keys that begin with N, which no generated index read does
+                digits = min(I - 1, 5)
+                listed = np.array([4 | sum(((i >> (2 * d)) & 3) << (3 * (d + 1)) for d in range(digits))
+                                   for i in range(4 ** digits)], dtype=np.uint64)
+            split = max(1, I // 2)
+            li.hops(split, 1, listed)                # (the first call of a kernel pays for loading it)
+            hp, t_hp = clock(lambda: li.hops(split, 1, listed))
+            li.mismatches(0)
+            hm, t_hm = clock(lambda: li.mismatches(0))
+            assert hp[0][0] == hm[0][0] == ilane[3] and hp[0][4:].sum() == hp[0][0] == hp[2].sum(), "the hops rows do not add up"
+            print("  %-22s %9.3f ms  (%.4f ms per tile; mismatches(0): %.4f; hops / mismatches = %.2f; index_finish: %.4f; "
+                  "the equality finish: %.4f)" % ("lane hops", t_hp, t_hp / k, t_hm / k, t_hp / t_hm, i_ifin / k, i_fin / k))
+            print("    split %d, E 1, %d listed: %d pairs, %d on the root's tile, one index read swapped %d, both %d; State %s; "
+                  "%d cells of the matrix occupied" % (split, listed.size, hp[0][0], hp[0][1], hp[0][2], hp[0][3],
+                                                       " ".join(str(v) for v in hp[0][4:]), int((hp[2] > 0).sum())))
         li.close()
         assert rows[:, 0].sum() + other[0] == pf and (ilane[:4] == lane[:4]).all(), "the index rows do not add up"
         print("%s: %d groups, %d listed, %d mixed classes of %d" % (name, irow[0], irow[1], irow[3], ilane[1]))

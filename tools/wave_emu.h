@@ -1,8 +1,8 @@
 // wave_emu.h - what a kernel's source needs to run on the CPU as it stands (tools/lane_mismatch_emu.cpp,
-// tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp): the 256 lanes of a
+// tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp, tools/lane_hops_emu.cpp): the 256 lanes of a
 // workgroup are fibers (ucontext) that a round-robin scheduler switches at the collectives - __syncthreads is a
 // rendezvous of the workgroup, __ballot and __shfl of a wave -, LDS is the kernel's static storage, an atomic add or
-// minimum is a plain one (one fiber runs at a time), and the qualifiers are empty.  Include it, then the kernel's
+// minimum or a compare-and-swap is a plain one (one fiber runs at a time), and the qualifiers are empty.  Include it, then the kernel's
 // .inc file, then call run_block(block x, block y, kernel call) per workgroup.  The device half of csrc/lane_pass.inc -
 // the run (kLaneRun, LaneRun) and wave_by_key - comes with it, included at the end: the kernels' own, not a copy.
 // Nothing here says anything about time.
@@ -54,6 +54,7 @@ static int __shfl(int v, int src) {
 #define __popc __builtin_popcount
 #define __ffs __builtin_ffs
 template <class T, class U> static T atomicAdd(T *p, U v) { T o = *p; *p += (T)v; return o; }
+template <class T> static T atomicCAS(T *p, T expect, T v) { T o = *p; if (o == expect) *p = v; return o; }
 template <class T, class U> static T atomicMin(T *p, U v) { T o = *p; if ((T)v < o) *p = (T)v; return o; }
 static unsigned long long *spread_row(unsigned long long *cnt, size_t row, int width) { return cnt + (row * kSpread + blockIdx.x % kSpread) * width; }
 // the lanes of the wave below this one whose bit is set in the mask's low (high) half, added to a

@@ -206,6 +206,17 @@ LANETOP_EDGES = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 50, 100, 500, 1000, 5000, 10000)
 LANETOP_MAX_PASSES = 8
 LANETOP_DEFAULT_CAPACITY = 65536
 
+# name -> (restype, argtypes); every symbol include/welldup_lanehops.h declares beyond the twelve above
+LANEHOPS_PROTOTYPES = {
+    "wd_lane_hops_scratch": (_i, [_i, _i, ctypes.POINTER(_sz)]),
+    "wd_lane_hops": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
+}
+LANEHOPS_MAX_E = 3
+LANEHOPS_STATES = 9
+LANEHOPS_TILE_COLS = 4
+LANEHOPS_LANE_COLS = LANEHOPS_TILE_COLS + LANEHOPS_STATES
+LANEHOPS_MAX_LISTED = 1024
+
 _lib = None
 
 
@@ -292,7 +303,7 @@ def unit_of_kernel(kernel: str) -> str:
         return "ingest"
     if kernel.startswith("k_sets"):
         return "sets"
-    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_", "k_ls_", "k_lt_")):
+    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_", "k_ls_", "k_lt_", "k_lh_")):
         return "tiledups"
     return "scan"
 
@@ -355,7 +366,8 @@ def load():
             list(TILENEAR_PROTOTYPES.items()) + list(LANEDUPS_PROTOTYPES.items()) + list(LANENEAR_PROTOTYPES.items()) + \
             list(LANEINDEX_PROTOTYPES.items()) + list(LANEMISMATCH_PROTOTYPES.items()) + \
             list(LANEDISTANCE_PROTOTYPES.items()) + list(LANEQUALITY_PROTOTYPES.items()) + \
-            list(LANESATURATION_PROTOTYPES.items()) + list(LANETOP_PROTOTYPES.items()):
+            list(LANESATURATION_PROTOTYPES.items()) + list(LANETOP_PROTOTYPES.items()) + \
+            list(LANEHOPS_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -24,7 +24,8 @@ Differences from the reference, all deliberate:
     --all-wells, --slocs, --layout, --serial-ingest, --dup-sets, --dup-sets-out, --tile-dups, --tile-dups-out,
     --tile-dups-hamming, --tile-dups-pair-budget, --lane-dups, --lane-dups-out,
     --lane-dups-hamming, --lane-dups-index, --lane-dups-mismatches, --lane-dups-distance, --lane-dups-quality,
-    --lane-dups-saturation, --lane-dups-top, --lane-dups-top-out;
+    --lane-dups-saturation, --lane-dups-top, --lane-dups-top-out, --lane-dups-hops, --lane-dups-hops-mismatches,
+    --lane-dups-hops-out;
   * --all-wells --dup-sets groups every tile's wells into duplicate sets and follows each lane's report
     with their counts and the exact duplication (report.write_dup_sets);
   * --all-wells --tile-dups groups every tile's PF wells into classes of equal reads, wherever on the tile they
@@ -50,6 +51,9 @@ Differences from the reference, all deliberate:
     size holds at half the depth, and what it projects for more reads (report.write_lane_saturation);
     --lane-dups-top N names the duplicates: the lane's duplication levels and its N largest classes (clusters under
     --lane-dups-hamming) with their spread over the tiles and the read itself (report.write_lane_top);
+    --lane-dups-hops (with --lane-dups-index) holds the index read of every redundant well against that of the first
+    of its class or cluster: read error or another index, in which index read, between which libraries, and into a
+    listed library or an index combination nobody used (report.write_lane_hops);
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
@@ -293,7 +297,35 @@ def parse_args(argv=None):
     p.add_argument("--lane-dups-top-out", default=None, metavar="FILE",
                    help="with --lane-dups-top: also write the listed groups to FILE, tab-separated: lane, rank, size, "
                         "exact, tiles, root_tile, root_well, read, then a tile=count column per tile touched")
+    p.add_argument("--lane-dups-hops", type=int, nargs="?", const=10, default=None, metavar="N",
+                   help="with --lane-dups-index: hold the index read of every redundant well of a lane against that of "
+                        "the first well of its class (of its cluster with --lane-dups-hamming) and print, after every "
+                        "other block of the lane: the pairs by what became of each of the two index reads - the same, "
+                        "a read error (at most --lane-dups-hops-mismatches cycles differ: what a demultiplexer forgives) "
+                        "or another index -, per listed library the pairs inside it and those it exchanged with "
+                        "another, the N (default 10) library pairs that exchanged most beside what random index hopping "
+                        "would give them, and how many swapped copies land in a listed library and how many in an "
+                        "index combination nobody used.  The first range of --lane-dups-index is the first index read "
+                        "(i7), the rest the second; one range is a single index.  The libraries are the first %d that "
+                        "--lane-dups-index lists" % _lib.LANEHOPS_MAX_LISTED)
+    p.add_argument("--lane-dups-hops-mismatches", type=int, default=None, metavar="E",
+                   help="with --lane-dups-hops: an index read that differs from the first well's in at most E cycles "
+                        "(0..%d, default 1) is a read error, one that differs in more another index"
+                        % _lib.LANEHOPS_MAX_E)
+    p.add_argument("--lane-dups-hops-out", default=None, metavar="FILE",
+                   help="with --lane-dups-hops: also write every cell of the library matrix that is not zero to FILE, "
+                        "tab-separated: lane, index_a (the first well's), index_b (the copy's), pairs")
     args = p.parse_args(argv)
+    if args.lane_dups_hops is not None and args.lane_dups_index is None:
+        p.error("--lane-dups-hops needs --lane-dups-index")
+    if args.lane_dups_hops is not None and args.lane_dups_hops < 0:
+        p.error("--lane-dups-hops takes the number of library pairs to list, not %d" % args.lane_dups_hops)
+    if args.lane_dups_hops_mismatches is not None and args.lane_dups_hops is None:
+        p.error("--lane-dups-hops-mismatches needs --lane-dups-hops")
+    if args.lane_dups_hops_mismatches is not None and not 0 <= args.lane_dups_hops_mismatches <= _lib.LANEHOPS_MAX_E:
+        p.error("--lane-dups-hops-mismatches takes 0..%d, not %d" % (_lib.LANEHOPS_MAX_E, args.lane_dups_hops_mismatches))
+    if args.lane_dups_hops_out is not None and args.lane_dups_hops is None:
+        p.error("--lane-dups-hops-out needs --lane-dups-hops")
     if args.lane_dups_top is not None and not args.lane_dups:
         p.error("--lane-dups-top needs --lane-dups")
     if args.lane_dups_top_out is not None and args.lane_dups_top is None:
@@ -515,15 +547,17 @@ def lane_cluster_members(class_labels: np.ndarray, cluster_labels: np.ndarray):
 
 
 def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0, index: int = 0,
-                         mismatch: int = 0, distance: int = 0, quality: int = 0, saturation: int = 0, top: int = 0):
+                         mismatch: int = 0, distance: int = 0, quality: int = 0, saturation: int = 0, top: int = 0,
+                         hops: int = 0):
     """--lane-dups: the accumulator's workspace - with --lane-dups-hamming plus the scratch of the near finish, with
     --lane-dups-index plus the index workspace, with --lane-dups-mismatches or --lane-dups-distance plus that pass's
-    scratch, with --lane-dups-quality plus the quality workspace and that pass's scratch, with --lane-dups-saturation
-    or --lane-dups-top plus that pass's scratch - against the free device memory, before anything is loaded."""
-    need += scratch + index + mismatch + distance + quality + saturation + top
+    scratch, with --lane-dups-quality plus the quality workspace and that pass's scratch, with --lane-dups-saturation,
+    --lane-dups-top or --lane-dups-hops plus that pass's scratch - against the free device memory, before anything is
+    loaded."""
+    need += scratch + index + mismatch + distance + quality + saturation + top + hops
     if need > free:
         raise MemoryError("--lane-dups needs %.2f GB of device memory for a lane of %d tiles x %d wells x %d cycles "
-                          "(%d bytes%s%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
+                          "(%d bytes%s%s%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
                               need / 1e9, tiles, wells, cycles, need,
                               ", %d of them for --lane-dups-hamming" % scratch if scratch else "",
                               ", %d of them for --lane-dups-index" % index if index else "",
@@ -532,6 +566,7 @@ def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: i
                               ", %d of them for --lane-dups-quality" % quality if quality else "",
                               ", %d of them for --lane-dups-saturation" % saturation if saturation else "",
                               ", %d of them for --lane-dups-top" % top if top else "",
+                              ", %d of them for --lane-dups-hops" % hops if hops else "",
                               free / 1e9, free))
 
 
@@ -545,7 +580,7 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
                dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0, lane_near=0, lane_pair_budget=0,
                lane_index=None, lane_mismatch=None, lane_distance=None, lane_quality=None, lane_saturation=None,
-               lane_top=0):
+               lane_top=0, lane_hops=None):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
@@ -579,6 +614,9 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     into["lsaturation"][lane] = LaneSaturationCounts, on the labels the lane was left with.
     lane_top = N > 0 (with lane_dups): after every other pass of the lane LaneDups.top(N): into["ltop"][lane] =
     LaneTopCounts, on the labels the lane was left with.
+    lane_hops = (E, pairs to list) (with lane_index): after every other pass of the lane LaneDups.hops(cycles of the
+    first index range, E, the keys of the first 1024 groups the index finish listed): into["lhops"][lane] =
+    LaneHopCounts, on the labels the lane was left with.
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -794,8 +832,8 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                         into["lmembers"][lane] = (names,) + lane_members(lane_labels)
                     if index_cycles:
                         final = got[3] if lane_near else lane_row      # the row of the labels the lane was left with
-                        into["lindex"][lane] = report.LaneIndexCounts.from_rows(
-                            *ld.index_finish(*index_listing(index_share, int(final[0]))), index_lengths, final[0], final[1])
+                        listing = ld.index_finish(*index_listing(index_share, int(final[0])))
+                        into["lindex"][lane] = report.LaneIndexCounts.from_rows(*listing, index_lengths, final[0], final[1])
                         if lane_labels is not None:
                             m = into["lmembers"][lane]
                             into["lmindex"][lane] = ld.index_keys()[m[1] * n_clusters + m[2]]
@@ -820,6 +858,12 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                         into["ltop"][lane] = report.LaneTopCounts.from_rows(
                             *ld.top(lane_top), lane_top, n_clusters, names,
                             into["lnear"][lane] if lane_near else into["ldups"][lane], lane_near)
+                    if lane_hops is not None:
+                        keys = listing[3][:_lib.LANEHOPS_MAX_LISTED]
+                        pf = [int(v) for v in listing[2][:len(keys), 0]]
+                        into["lhops"][lane] = report.LaneHopCounts.from_rows(
+                            *ld.hops(index_lengths[0], lane_hops[0], keys), keys, pf + [int(final[0]) - sum(pf)],
+                            index_lengths, names, lane_hops[0], lane_near, lane_hops[1])
                     del lane_labels, got
                 _lap("batch %d: lane classes" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
@@ -1115,6 +1159,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                                  out=out_fh)
                 if args.lane_dups_top is not None:
                     report.write_lane_top(lane, results["ltop"][lane], verbose=not args.summary_only, out=out_fh)
+                if args.lane_dups_hops is not None:
+                    report.write_lane_hops(lane, results["lhops"][lane], verbose=not args.summary_only, out=out_fh)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
@@ -1122,7 +1168,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 # scan_lanes fills these, lane_done reads them
                 results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
                            "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}, "lnear": {}, "lindex": {},
-                           "lmindex": {}, "lmismatch": {}, "ldistance": {}, "lquality": {}, "lsaturation": {}, "ltop": {}}
+                           "lmindex": {}, "lmismatch": {}, "ldistance": {}, "lquality": {}, "lsaturation": {}, "ltop": {},
+                           "lhops": {}}
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
@@ -1161,7 +1208,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                          if saturation is not None else 0,
                                          top=sc.lane_top_scratch_bytes(n_targets, len(tiles), len(cycle_list),
                                                                        args.lane_dups_top)
-                                         if args.lane_dups_top is not None else 0)
+                                         if args.lane_dups_top is not None else 0,
+                                         hops=sc.lane_hops_scratch_bytes(len(tiles), _lib.LANEHOPS_MAX_LISTED)
+                                         if args.lane_dups_hops is not None else 0)
                 if err is None:             # (a rank whose setup failed has nothing to scan: it goes to the flag)
                     scan_lanes(sc, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                                max(0, args.tile_batch), args.threads,
@@ -1180,7 +1229,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                lane_distance=(xy[0], xy[1], args.lane_dups_distance_radius)
                                if args.lane_dups_distance else None,
                                lane_quality=(args.lane_dups_quality_edges, quality_d) if quality_d is not None else None,
-                               lane_saturation=saturation, lane_top=args.lane_dups_top or 0)
+                               lane_saturation=saturation, lane_top=args.lane_dups_top or 0,
+                               lane_hops=(1 if args.lane_dups_hops_mismatches is None else args.lane_dups_hops_mismatches,
+                                          args.lane_dups_hops) if args.lane_dups_hops is not None else None)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
                     if args.tile_dups_out and near_k:
@@ -1191,6 +1242,10 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                         with open(args.lane_dups_top_out, "w") as fh:
                             for i, lane in enumerate(sorted(results["ltop"], key=lanes.index)):
                                 report.write_lane_top_tsv(lane, results["ltop"][lane], fh, header=i == 0)
+                    if args.lane_dups_hops_out:
+                        with open(args.lane_dups_hops_out, "w") as fh:
+                            for i, lane in enumerate(sorted(results["lhops"], key=lanes.index)):
+                                report.write_lane_hops_tsv(lane, results["lhops"][lane], fh, header=i == 0)
                     if args.lane_dups_out:
                         write_lane_members(args.lane_dups_out, results["lmembers"],
                                            index=([e - s for s, e in index_ranges], results["lmindex"])

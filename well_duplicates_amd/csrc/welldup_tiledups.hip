@@ -16,7 +16,8 @@
 // welldup_lanenear.h, lane_pass.inc (after it) what the passes that follow a lane's finish share - the walk over a run
 // of wells, the grouping of a wave by key, the start of a pass and the counters' way back -, lane_index.inc (after
 // it) a lane's duplication per index read of welldup_laneindex.h,
-// lane_mismatch.inc (after it) where a lane's duplicate copies differ of welldup_lanemismatch.h, lane_distance.inc
+// lane_mismatch.inc (after it) where a lane's duplicate copies differ of welldup_lanemismatch.h, lane_hops.inc (after
+// it: it folds two keys with lane_mismatch.inc's lm_fold) which libraries they join of welldup_lanehops.h, lane_distance.inc
 // (last) how far apart they lie of welldup_lanedistance.h: all of these work on the accumulator as lane_dups.inc laid
 // it out.  lane_quality.inc, behind them, gives it a second packed array - the reported base qualities - and holds
 // them against the copies: welldup_lanequality.h.  lane_saturation.inc, which lane_quality.inc includes at its
@@ -506,5 +507,6 @@ try {
 #include "lane_pass.inc"      // what the passes after a lane's finish share: the walk, the grouping, the host's steps
 #include "lane_index.inc"     // a lane's classes split by index read (include/welldup_laneindex.h)
 #include "lane_mismatch.inc"  // where a lane's duplicate copies differ (include/welldup_lanemismatch.h)
+#include "lane_hops.inc"      // which libraries a lane's duplicate copies join (include/welldup_lanehops.h)
 #include "lane_distance.inc"  // how far apart a lane's duplicate copies lie (include/welldup_lanedistance.h)
 #include "lane_quality.inc"   // reported base quality against a lane's duplicate copies (include/welldup_lanequality.h)

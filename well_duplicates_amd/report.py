@@ -23,6 +23,7 @@ from __future__ import annotations
 import math
 import sys
 from dataclasses import dataclass, field
+from fractions import Fraction
 from typing import Dict, List, Optional, Sequence
 
 TALLY = 0    # count_well_duplicates.py:17
@@ -1254,3 +1255,159 @@ def write_lane_top_tsv(lane, counts: LaneTopCounts, out, header: bool = True) ->
         cols = ["%s=%i" % (c.tiles[i], v) for i, v in enumerate(c.tile_count[r]) if v]
         print("\t".join([str(lane), str(r + 1), str(c.size[r]), str(c.exact[r]), str(len(cols)), c.tiles[t], str(w),
                          c.reads[r]] + cols), file=out)
+
+
+LANE_HOPS_MAX_E = 3
+LANE_HOPS_MAX_LISTED = 1024
+LANE_HOPS_STATE_NAMES = ("Same", "Near", "Far")
+LANE_HOPS_TILE_COLS = 4
+LANE_HOPS_LANE_COLS = LANE_HOPS_TILE_COLS + 9
+
+
+@dataclass
+class LaneHopCounts:
+    """Which libraries a lane's duplicate copies join (include/welldup_lanehops.h, LaneDups.hops): the index read of
+    every redundant well against its root's.  The lane row's columns - state[3 s1 + s2] with s = 0 Same, 1 Near (at
+    most max_e cycles of the index read differ), 2 Far -, per tile (by the tile's name) [Pairs, SameTile, Hop1, Hop2],
+    the listed libraries' keys, names (bases; the last is Other) and PF wells (the last: every PF well of the lane
+    whose key is not listed), and matrix[root's library][copy's library]."""
+    k: int = 0
+    split: int = 1
+    single: bool = True
+    max_e: int = 0
+    n_pairs: int = 10
+    pairs: int = 0
+    same_tile: int = 0
+    hop1: int = 0
+    hop2: int = 0
+    state: List[int] = field(default_factory=lambda: [0] * 9)
+    tiles: Dict[str, List[int]] = field(default_factory=dict)
+    keys: List[int] = field(default_factory=list)
+    names: List[str] = field(default_factory=lambda: ["Other"])
+    pf: List[int] = field(default_factory=lambda: [0])
+    matrix: List[List[int]] = field(default_factory=lambda: [[0]])
+
+    @classmethod
+    def from_rows(cls, lane_row: Sequence[int], tile_rows: Sequence[Sequence[int]], matrix, keys: Sequence[int],
+                  pf: Sequence[int], lengths: Sequence[int], tile_names: Sequence, max_e: int, k: int = 0,
+                  n_pairs: int = 10) -> "LaneHopCounts":
+        """The three results of LaneDups.hops(lengths[0], max_e, keys); keys: the listed keys in the order given to
+        it; pf: the PF wells of each listed library and, last, of all the others; lengths: the cycles of every index
+        range (the first is the split; one range is a single index); tile_names as LaneDupCounts.from_rows takes
+        them; k: the K of --lane-dups-hamming; n_pairs: the library pairs write_lane_hops lists."""
+        b = [int(v) for v in lane_row]
+        m = len(keys)
+        assert len(b) == LANE_HOPS_LANE_COLS and 0 <= max_e <= LANE_HOPS_MAX_E and m <= LANE_HOPS_MAX_LISTED
+        assert len(pf) == m + 1 and len(matrix) == m + 1 and all(len(row) == m + 1 for row in matrix)
+        tiles = {}
+        for name, row in zip(tile_names, tile_rows):
+            assert len(row) == LANE_HOPS_TILE_COLS
+            if name is not None:
+                tiles[name] = [int(v) for v in row]
+        names = [index_bases(key, lengths) for key in keys] + ["Other"]
+        return cls(int(k), int(lengths[0]), len(lengths) == 1 or lengths[0] == sum(lengths), int(max_e), int(n_pairs),
+                   b[0], b[1], b[2], b[3], b[4:], tiles, [int(key) for key in keys], names, [int(v) for v in pf],
+                   [[int(v) for v in row] for row in matrix])
+
+    @property
+    def errors_only(self) -> int:
+        """The pairs with an index-read error and no other index: no part Far, not both Same."""
+        return sum(self.state[s] for s in (1, 3, 4))
+
+    @property
+    def off_diagonal(self) -> int:
+        """H: the pairs whose root and copy lie in different libraries (Other being one)."""
+        return sum(map(sum, self.matrix)) - sum(self.matrix[i][i] for i in range(len(self.matrix)))
+
+    def within(self, a: int) -> int:
+        return self.matrix[a][a]
+
+    def exchanged(self, a: int) -> int:
+        """The pairs with exactly one end in library a: its row and its column without the diagonal."""
+        return sum(self.matrix[a]) + sum(row[a] for row in self.matrix) - 2 * self.matrix[a][a]
+
+    def into_listed(self) -> int:
+        """The off-diagonal pairs whose copy carries a listed key - a matrix count, not a state count (see
+        write_lane_hops)."""
+        m = len(self.keys)
+        return sum(self.matrix[a][b] for a in range(m + 1) for b in range(m) if a != b)
+
+    def into_unlisted(self) -> int:
+        """The pairs of a listed root whose copy carries no listed key: column Other without its diagonal."""
+        m = len(self.keys)
+        return sum(self.matrix[a][m] for a in range(m))
+
+    def expected(self, a: int, b: int) -> Optional[Fraction]:
+        """What random exchange between libraries a and b would give: H x 2 p_a p_b / (1 - sum p_i^2), p the PF
+        shares over the listed libraries and Other - an exact fraction; None where the denominator is 0 (no PF well,
+        or one library holds them all)."""
+        total = sum(self.pf)
+        den = total * total - sum(v * v for v in self.pf)
+        return Fraction(self.off_diagonal * 2 * self.pf[a] * self.pf[b], den) if den else None
+
+    def top_pairs(self):
+        """-> [(a, b, count)], a < b: the unordered library pairs with a pair between them, [a][b] + [b][a], by
+        count (largest first), then by the two keys (Other last)."""
+        m = len(self.keys)
+        key = lambda i: self.keys[i] if i < m else 1 << 64
+        got = [(a, b, self.matrix[a][b] + self.matrix[b][a]) for a in range(m + 1) for b in range(a + 1, m + 1)
+               if self.matrix[a][b] + self.matrix[b][a]]
+        return sorted(got, key=lambda t: (-t[2], ) + tuple(sorted((key(t[0]), key(t[1])))))
+
+
+def write_lane_hops(lane, counts: LaneHopCounts, verbose: bool = False, out=None) -> None:
+    """The block that follows every other block of a lane under --lane-dups-hops: (a) a line per state that can
+    occur - nine, or three for a single index -: the states of the two index reads, the pairs and their share;
+    (b) verbose: a line per tile; (c) a line per listed library and one for Other: the index read, its PF wells, the
+    pairs inside it, the pairs with one end in it and their share of its PF wells; (d) the n_pairs largest unordered
+    library pairs: count, share of all pairs between libraries, what random exchange would give and the ratio to it
+    (n/a where that is 0 or undefined); (e) the summary.
+    Its last two counts before SameTile are matrix counts, not state counts: "into a listed library" is every pair
+    whose copy carries a listed key other than its root's, "into an unlisted combination" every pair of a listed
+    root whose copy's key is not listed.  With max_e = 0 every pair off the diagonal has a Far part and they split
+    Hop1 + Hop2 (less the pairs between two unlisted keys, which lie in the one cell Other x Other).  With max_e >= 1
+    a Near pair is off the diagonal too - its key differs from its root's, and is rarely listed -, so "into an
+    unlisted combination" then holds the index-read errors as well and the two can exceed Hop1 + Hop2."""
+    out = out or sys.stdout
+    c = counts
+    ham = "\tHamming: %i" % c.k if c.k else ""
+    share = lambda v, of: v / of if of else 0.0
+    print(file=out)
+    for s in range(9):
+        if c.single and s % 3:
+            continue
+        print("LaneHops: %s%s\tIndex1: %s\tIndex2: %s\tPairs: %i (%.5f)" % (
+            lane, ham, LANE_HOPS_STATE_NAMES[s // 3], "-" if c.single else LANE_HOPS_STATE_NAMES[s % 3], c.state[s],
+            share(c.state[s], c.pairs)), file=out)
+    if verbose:
+        for tile in sorted(c.tiles):
+            t = c.tiles[tile]
+            print("LaneHopsTile: %s\tTile: %s\tPairs: %i\tSameTile: %i\tHop1: %i\tHop2: %i" % (
+                lane, tile, t[0], t[1], t[2], t[3]), file=out)
+    for a, name in enumerate(c.names):
+        print("LaneHopLibrary: %s%s\tIndex: %s\tPF wells: %i\tWithin: %i\tExchanged: %i (%.6f of PF)" % (
+            lane, ham, name, c.pf[a], c.within(a), c.exchanged(a), share(c.exchanged(a), c.pf[a])), file=out)
+    h = c.off_diagonal
+    for a, b, n in c.top_pairs()[:max(0, c.n_pairs)]:
+        e = c.expected(a, b)
+        print("LaneHopPair: %s%s\tIndex: %s\tIndex: %s\tPairs: %i (%.5f)\tExpected: %s\tRatio: %s" % (
+            lane, ham, c.names[a], c.names[b], n, share(n, h), "n/a" if e is None else "%.2f" % float(e),
+            "%.3f" % float(n / e) if e else "n/a"), file=out)
+    print("LaneHopsSummary: %s%s\tSplit: %s\tMaxE: %i\tListed: %i\tPairs: %i\tSame index: %i (%.5f)\t"
+          "Index-read errors only: %i (%.5f)\tOne index read swapped: %i (%.6f per pair)\tBoth: %i\t"
+          "Into a listed library: %i\tInto an unlisted combination: %i\tSameTile: %i" % (
+              lane, ham, "single" if c.single else str(c.split), c.max_e, len(c.keys), c.pairs, c.state[0],
+              share(c.state[0], c.pairs), c.errors_only, share(c.errors_only, c.pairs), c.hop1, share(c.hop1, c.pairs),
+              c.hop2, c.into_listed(), c.into_unlisted(), c.same_tile), file=out)
+
+
+def write_lane_hops_tsv(lane, counts: LaneHopCounts, out, header: bool = True) -> None:
+    """--lane-dups-hops-out: a line per cell of the matrix that is not zero - lane, the root's index read, the
+    copy's, the pairs -, row by row."""
+    c = counts
+    if header:
+        print("lane\tindex_a\tindex_b\tpairs", file=out)
+    for a, row in enumerate(c.matrix):
+        for b, n in enumerate(row):
+            if n:
+                print("%s\t%s\t%s\t%i" % (lane, c.names[a], c.names[b], n), file=out)

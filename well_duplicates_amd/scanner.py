@@ -325,6 +325,12 @@ class Scanner:
         it does not depend on the wells of a tile)."""
         return self._workspace_bytes(self._lib.wd_lane_mismatch_scratch, max_tiles, L)
 
+    def lane_hops_scratch_bytes(self, max_tiles: int, M: int) -> int:
+        """Device bytes LaneDups.hops needs beside the accumulator's workspaces for M listed keys
+        (wd_lane_hops_scratch: the counters, the listing and the (M + 1)^2 cells of the matrix; it does not depend on
+        the wells of a tile; M outside 0..1024 raises ValueError)."""
+        return self._workspace_bytes(self._lib.wd_lane_hops_scratch, max_tiles, M)
+
     def lane_distance_scratch_bytes(self, n_clusters: int, max_tiles: int, matrix: bool = True) -> int:
         """Device bytes LaneDups.distances needs beside the accumulator's workspace (wd_lane_distance_scratch: the
         coordinates of a tile's wells, the counters, and with `matrix` TilePairs; more than 4096 tiles with the
@@ -819,6 +825,31 @@ class LaneDups:
                                self._h, int(max_d), d_scratch, sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
                                tile_rows.ctypes.data_as(ctypes.c_void_p), sub.ctypes.data_as(ctypes.c_void_p)))
         return lane_row, tile_rows, sub
+
+    def hops(self, split: int, max_e: int, keys):
+        """After finish() of a lane with an index part, any number of times, before or after index_finish and every
+        other pass (wd_lane_hops, include/welldup_lanehops.h): the index key of every redundant well against its
+        root's under the labels the finish left.  split: the cycles of the first index read, 1..I (I: a single
+        index); max_e: the differing cycles an index read may have and still count as a read error, 0..3; keys: up
+        to 1024 distinct index keys (uint64), the listed libraries.
+        -> (lane row int64 [13]: [Pairs, SameTile, Hop1, Hop2, State[0..8]] with State[3 s1 + s2], s = 0 Same, 1 Near,
+        2 Far, tile rows int64 [max_tiles, 4]: [Pairs, SameTile, Hop1, Hop2] by the copy's tile, matrix int64
+        [M + 1, M + 1]: [root's rank][copy's rank], rank M = a key that is not listed).  The scratch is allocated for
+        the call and released.  A bad split, max_e or list of keys, a lane without an index part, a tile that has
+        reads but no index planes (or the reverse) or a call before a successful finish raises ValueError."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        listed = np.ascontiguousarray(np.asarray(keys, dtype=np.uint64).reshape(-1))
+        M = int(listed.size)
+        lane_row = np.zeros(_lib.LANEHOPS_LANE_COLS, dtype=np.int64)
+        tile_rows = np.zeros((self.max_tiles, _lib.LANEHOPS_TILE_COLS), dtype=np.int64)
+        matrix = np.zeros((min(M, _lib.LANEHOPS_MAX_LISTED) + 1,) * 2, dtype=np.int64)
+        self._with_scratch(self.sc.lane_hops_scratch_bytes(self.max_tiles, M),      # (M > 1024 raises here)
+                           lambda d_scratch, sbytes: self.sc._lib.wd_lane_hops(
+                               self._h, int(split), int(max_e), M, listed.ctypes.data_as(ctypes.c_void_p) if M else None,
+                               d_scratch, sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
+                               tile_rows.ctypes.data_as(ctypes.c_void_p), matrix.ctypes.data_as(ctypes.c_void_p)))
+        return lane_row, tile_rows, matrix
 
     def distances(self, x, y, radius: int, matrix: bool = True):
         """After finish(), any number of times, before or after index_finish and mismatches (wd_lane_distances,
