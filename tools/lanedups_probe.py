@@ -55,12 +55,18 @@ rank takes every add of k_lt_spread) and the lane whose odd wells repeat their l
 the tie worst case; with `--capacity N` the selection there has to refine the root ids to the end, the longest it can
 be.  The histogram passes taken are printed, and the bytes a pass streams (8 per well) over the time of a pass against
 the pure read.
+`--gc` times LaneDups.gc(0) (the lane's duplication against its reads' GC content, include/welldup_lanegc.h) per tile
+of the lane beside the equality finish, LaneDups.mismatches(0) and LaneDups.top(100) on the same batches and labels,
+and beside Scanner.stream_read_gbs over as many bytes as the pass reads - every packed row of the lane, label and
+members: 4 ceil(cycles / 10) + 8 bytes per well -, on three inputs: the planted lane, the `--equal` lane (every well
+of a wave on one bin of the histogram) and the lane whose odd wells repeat their left neighbour (pairs only: every
+second well a root that adds its family's size).
 For per-kernel times run it under
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/lanedups_probe.py
 
 (the k_ld_* rows of the stats are this stage, k_li_* the index part, k_lm_* the mismatch pass, k_lg_* the distance pass,
-k_lq_* the quality part, k_ls_* the saturation pass, k_lt_* the top pass, k_lh_* the hops pass, k_td_* the per-tile classes, k_dense_* the scan)."""
+k_lq_* the quality part, k_ls_* the saturation pass, k_lt_* the top pass, k_lh_* the hops pass, k_lgc_* the GC pass, k_td_* the per-tile classes, k_dense_* the scan)."""
 import argparse
 import os
 import sys
@@ -100,6 +106,9 @@ ap.add_argument("--steps", type=int, default=20, metavar="S", help="the steps of
 ap.add_argument("--top", type=int, default=0, metavar="N",
                 help="also time LaneDups.top(N) beside the equality finish and saturation (three inputs with --equal)")
 ap.add_argument("--capacity", type=int, default=0, metavar="C", help="the candidate capacity of --top (0: the default)")
+ap.add_argument("--gc", action="store_true",
+                help="also time LaneDups.gc(0) beside the equality finish, mismatches(0), top(100) and a pure read of as "
+                     "many bytes (three inputs with --equal)")
 ap.add_argument("--quality", action="store_true",
                 help="also time LaneDups.qual_add beside add and LaneDups.qualities(K) beside mismatches(K) (needs "
                      "--hamming; three inputs with --equal)")
@@ -260,6 +269,35 @@ def time_top(acc, tiles_n, t_finish, what):
               % (per_pass, 1e3 * per_pass / tiles_n, 8.0 * n * tiles_n / per_pass / 1e6, float(np.mean(read_gbs))))
 
 
+def time_gc(acc, tiles_n, t_finish, what):
+    """LaneDups.gc(0) and, on the same labels, LaneDups.mismatches(0) and LaneDups.top(100), each after a first call
+    that pays for loading the kernels; and a pure read of as many bytes as the pass reads, from the accumulator's own
+    workspace"""
+    acc.gc(0)
+    (grow, gtiles, ghist), t_g = clock(lambda: acc.gc(0))
+    _, t_g2 = clock(lambda: acc.gc(a.cycles))
+    acc.mismatches(0)
+    mm, t_m = clock(lambda: acc.mismatches(0))
+    acc.top(100)
+    top, t_t = clock(lambda: acc.top(100))
+    nbytes = tiles_n * n * (4 * ((a.cycles + 9) // 10) + 8)
+    gbs = sc.stream_read_gbs(acc.d_ws, min(nbytes, acc.ws_bytes))
+    t_read = nbytes / gbs / 1e6
+    assert grow[0] == grow[1:4].sum() == top[0][0] and grow[3] == mm[0][0] and \
+        ghist[:, 3].sum() + grow[7] == grow[2] + grow[3] and (ghist[:, :3].sum(axis=0) == grow[1:4] - grow[4:7]).all() and \
+        gtiles[:, 0].sum() == grow[0], "the gc rows do not add up"
+    g = np.arange(ghist.shape[0])
+    print("%s: gc, max_n 0: %d PF wells, %d single, %d roots, %d copies, %d skipped; %d values of g taken, mean GC of the "
+          "distinct molecules %.4f, of the copies %.4f"
+          % (what, grow[0], grow[1], grow[2], grow[3], grow[4:7].sum(), int((ghist[:, :3].sum(axis=1) > 0).sum()),
+             (g * (ghist[:, 0] + ghist[:, 1])).sum() / max(1, (ghist[:, 0] + ghist[:, 1]).sum()) / a.cycles,
+             (g * ghist[:, 2]).sum() / max(1, ghist[:, 2].sum()) / a.cycles))
+    print("  %-22s %9.3f ms  (%.4f ms per tile; max_n = L: %.4f; %.1f MB per tile at %.0f GB/s; a pure read of as many bytes: "
+          "%.4f ms per tile at %.0f GB/s; gc / read = %.2f; mismatches(0): %.4f; top(100): %.4f; the equality finish: %.4f)"
+          % ("lane gc", t_g, t_g / tiles_n, t_g2 / tiles_n, nbytes / tiles_n / 1e6, nbytes / t_g / 1e6, t_read / tiles_n, gbs,
+             t_g / t_read, t_m / tiles_n, t_t / tiles_n, t_finish / tiles_n))
+
+
 def time_qualities(acc, tiles_n, t_finish, t_qual_add, t_plain_add, what):
     """LaneDups.qualities(K) and, on the same labels, LaneDups.mismatches(K), each after a first call that pays for
     loading the kernel"""
@@ -286,6 +324,8 @@ if a.saturation:
     time_saturation(ld, max(1, a.tiles), t_fin, "the planted lane")
 if a.top:
     time_top(ld, max(1, a.tiles), t_fin, "the planted lane")
+if a.gc:
+    time_gc(ld, max(1, a.tiles), t_fin, "the planted lane")
 ld.close()
 if a.hamming:
     near, t_near = clock(lambda: ldn.finish(hamming=a.hamming))
@@ -436,6 +476,8 @@ if a.equal:
         time_saturation(eq, 3, e_fin, "every read equal, three tiles")
     if a.top:
         time_top(eq, 3, e_fin, "every read equal, three tiles")
+    if a.gc:
+        time_gc(eq, 3, e_fin, "every read equal, three tiles")
     if a.quality:
         time_qualities(eq, 3, e_fin, e_qadd, e_add, "every read equal, one quality value, three tiles")
         # the same bases under random qualities 1..63: eight random planes take turns
@@ -478,7 +520,7 @@ if a.mismatches:
     print("  %-22s %9.3f ms  (%.4f ms per tile)" % ("lane mismatches", o_mm, o_mm / 3))
     one.close()
     three.free()
-if a.distance or a.saturation or a.top:
+if a.distance or a.saturation or a.top or a.gc:
     # three tiles without planted copies whose wells of odd index repeat the well to their left, cycle by cycle
     bare = synth.SynthSpec(seed=5, n_clusters=n, row=a.cols, plant_per_64k=0)
     three = TileBatch(sc, 3, a.cycles, n)
@@ -501,6 +543,8 @@ if a.distance or a.saturation or a.top:
         time_saturation(nb, 3, n_fin, "every odd well a copy of its left neighbour, three tiles")
     if a.top:
         time_top(nb, 3, n_fin, "every odd well a copy of its left neighbour, three tiles")
+    if a.gc:
+        time_gc(nb, 3, n_fin, "every odd well a copy of its left neighbour, three tiles")
     nb.close()
     three.free()
 sc.close()

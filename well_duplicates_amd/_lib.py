@@ -217,6 +217,15 @@ LANEHOPS_TILE_COLS = 4
 LANEHOPS_LANE_COLS = LANEHOPS_TILE_COLS + LANEHOPS_STATES
 LANEHOPS_MAX_LISTED = 1024
 
+# name -> (restype, argtypes); every symbol include/welldup_lanegc.h declares beyond those above
+LANEGC_PROTOTYPES = {
+    "wd_lane_gc_scratch": (_i, [_i, _i, ctypes.POINTER(_sz)]),
+    "wd_lane_gc": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp]),
+}
+LANEGC_HIST_COLS = 4
+LANEGC_LANE_COLS = 8
+LANEGC_TILE_COLS = 5
+
 _lib = None
 
 
@@ -303,7 +312,7 @@ def unit_of_kernel(kernel: str) -> str:
         return "ingest"
     if kernel.startswith("k_sets"):
         return "sets"
-    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_", "k_ls_", "k_lt_", "k_lh_")):
+    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_", "k_ls_", "k_lt_", "k_lh_", "k_lgc_")):
         return "tiledups"
     return "scan"
 
@@ -367,7 +376,7 @@ def load():
             list(LANEINDEX_PROTOTYPES.items()) + list(LANEMISMATCH_PROTOTYPES.items()) + \
             list(LANEDISTANCE_PROTOTYPES.items()) + list(LANEQUALITY_PROTOTYPES.items()) + \
             list(LANESATURATION_PROTOTYPES.items()) + list(LANETOP_PROTOTYPES.items()) + \
-            list(LANEHOPS_PROTOTYPES.items()):
+            list(LANEHOPS_PROTOTYPES.items()) + list(LANEGC_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -25,7 +25,7 @@ Differences from the reference, all deliberate:
     --tile-dups-hamming, --tile-dups-pair-budget, --lane-dups, --lane-dups-out,
     --lane-dups-hamming, --lane-dups-index, --lane-dups-mismatches, --lane-dups-distance, --lane-dups-quality,
     --lane-dups-saturation, --lane-dups-top, --lane-dups-top-out, --lane-dups-hops, --lane-dups-hops-mismatches,
-    --lane-dups-hops-out;
+    --lane-dups-hops-out, --lane-dups-gc, --lane-dups-gc-bins, --lane-dups-gc-max-n, --lane-dups-gc-out;
   * --all-wells --dup-sets groups every tile's wells into duplicate sets and follows each lane's report
     with their counts and the exact duplication (report.write_dup_sets);
   * --all-wells --tile-dups groups every tile's PF wells into classes of equal reads, wherever on the tile they
@@ -54,6 +54,9 @@ Differences from the reference, all deliberate:
     --lane-dups-hops (with --lane-dups-index) holds the index read of every redundant well against that of the first
     of its class or cluster: read error or another index, in which index read, between which libraries, and into a
     listed library or an index combination nobody used (report.write_lane_hops);
+    --lane-dups-gc holds the duplication against the molecule: every PF read by its GC content and by what it is in
+    its class or cluster - the distinct molecules, the duplication, the mean family size and the library size per GC
+    bin, over every PF read and without an alignment (report.write_lane_gc);
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
@@ -315,7 +318,35 @@ def parse_args(argv=None):
     p.add_argument("--lane-dups-hops-out", default=None, metavar="FILE",
                    help="with --lane-dups-hops: also write every cell of the library matrix that is not zero to FILE, "
                         "tab-separated: lane, index_a (the first well's), index_b (the copy's), pairs")
+    p.add_argument("--lane-dups-gc", action="store_true",
+                   help="with --lane-dups: count every PF read of a lane by its GC content - the cycles that read C or "
+                        "G - and by what it is in its class (its cluster with --lane-dups-hamming): a lone read, the "
+                        "first well or a copy, and print, after every other block of the lane, per GC bin the distinct "
+                        "molecules, the reads and the redundant wells by the molecule's GC, the duplication in the bin "
+                        "and against the lane's, the mean family size, the copies by their own read and the library "
+                        "size; then the mean GC of the distinct molecules and of the redundant wells and the "
+                        "duplication below, between and above the quartiles of GC: whether GC-poor or GC-rich "
+                        "fragments were over-amplified")
+    p.add_argument("--lane-dups-gc-bins", type=int, default=None, metavar="B",
+                   help="with --lane-dups-gc: the GC bins printed, %d..%d (default 20); the bin of a read with g cycles "
+                        "of C or G among L is min(B - 1, g * B // L)" % (report.LANE_GC_MIN_BINS, report.LANE_GC_MAX_BINS))
+    p.add_argument("--lane-dups-gc-max-n", type=int, default=None, metavar="M",
+                   help="with --lane-dups-gc: a read with more than M no-calls (0..the scanned cycles, default 0, so "
+                        "that a read's GC fraction is exactly g / L) is counted by what it is but kept out of the bins")
+    p.add_argument("--lane-dups-gc-out", default=None, metavar="FILE",
+                   help="with --lane-dups-gc: also write a line per g to FILE, tab-separated: lane, gc, single, roots, "
+                        "copies, family_wells")
     args = p.parse_args(argv)
+    if args.lane_dups_gc and not args.lane_dups:
+        p.error("--lane-dups-gc needs --lane-dups")
+    for flag, value in (("bins", args.lane_dups_gc_bins), ("max-n", args.lane_dups_gc_max_n), ("out", args.lane_dups_gc_out)):
+        if value is not None and not args.lane_dups_gc:
+            p.error("--lane-dups-gc-%s needs --lane-dups-gc" % flag)
+    if args.lane_dups_gc_bins is not None and not report.LANE_GC_MIN_BINS <= args.lane_dups_gc_bins <= report.LANE_GC_MAX_BINS:
+        p.error("--lane-dups-gc-bins takes %d..%d, not %d" % (report.LANE_GC_MIN_BINS, report.LANE_GC_MAX_BINS,
+                                                              args.lane_dups_gc_bins))
+    if args.lane_dups_gc_max_n is not None and args.lane_dups_gc_max_n < 0:
+        p.error("--lane-dups-gc-max-n takes 0..the number of scanned cycles, not %d" % args.lane_dups_gc_max_n)
     if args.lane_dups_hops is not None and args.lane_dups_index is None:
         p.error("--lane-dups-hops needs --lane-dups-index")
     if args.lane_dups_hops is not None and args.lane_dups_hops < 0:
@@ -548,16 +579,16 @@ def lane_cluster_members(class_labels: np.ndarray, cluster_labels: np.ndarray):
 
 def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0, index: int = 0,
                          mismatch: int = 0, distance: int = 0, quality: int = 0, saturation: int = 0, top: int = 0,
-                         hops: int = 0):
+                         hops: int = 0, gc: int = 0):
     """--lane-dups: the accumulator's workspace - with --lane-dups-hamming plus the scratch of the near finish, with
     --lane-dups-index plus the index workspace, with --lane-dups-mismatches or --lane-dups-distance plus that pass's
     scratch, with --lane-dups-quality plus the quality workspace and that pass's scratch, with --lane-dups-saturation,
-    --lane-dups-top or --lane-dups-hops plus that pass's scratch - against the free device memory, before anything is
-    loaded."""
-    need += scratch + index + mismatch + distance + quality + saturation + top + hops
+    --lane-dups-top, --lane-dups-hops or --lane-dups-gc plus that pass's scratch - against the free device memory,
+    before anything is loaded."""
+    need += scratch + index + mismatch + distance + quality + saturation + top + hops + gc
     if need > free:
         raise MemoryError("--lane-dups needs %.2f GB of device memory for a lane of %d tiles x %d wells x %d cycles "
-                          "(%d bytes%s%s%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
+                          "(%d bytes%s%s%s%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
                               need / 1e9, tiles, wells, cycles, need,
                               ", %d of them for --lane-dups-hamming" % scratch if scratch else "",
                               ", %d of them for --lane-dups-index" % index if index else "",
@@ -567,6 +598,7 @@ def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: i
                               ", %d of them for --lane-dups-saturation" % saturation if saturation else "",
                               ", %d of them for --lane-dups-top" % top if top else "",
                               ", %d of them for --lane-dups-hops" % hops if hops else "",
+                              ", %d of them for --lane-dups-gc" % gc if gc else "",
                               free / 1e9, free))
 
 
@@ -580,7 +612,7 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
                dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0, lane_near=0, lane_pair_budget=0,
                lane_index=None, lane_mismatch=None, lane_distance=None, lane_quality=None, lane_saturation=None,
-               lane_top=0, lane_hops=None):
+               lane_top=0, lane_hops=None, lane_gc=None):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
@@ -617,6 +649,8 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     lane_hops = (E, pairs to list) (with lane_index): after every other pass of the lane LaneDups.hops(cycles of the
     first index range, E, the keys of the first 1024 groups the index finish listed): into["lhops"][lane] =
     LaneHopCounts, on the labels the lane was left with.
+    lane_gc = (max_n, bins) (with lane_dups): after every other pass of the lane LaneDups.gc(max_n): into["lgc"][lane] =
+    LaneGCCounts, on the labels the lane was left with.
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -864,6 +898,9 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                         into["lhops"][lane] = report.LaneHopCounts.from_rows(
                             *ld.hops(index_lengths[0], lane_hops[0], keys), keys, pf + [int(final[0]) - sum(pf)],
                             index_lengths, names, lane_hops[0], lane_near, lane_hops[1])
+                    if lane_gc is not None:
+                        into["lgc"][lane] = report.LaneGCCounts.from_rows(*ld.gc(lane_gc[0]), names, lane_gc[0], lane_gc[1],
+                                                                          lane_near)
                     del lane_labels, got
                 _lap("batch %d: lane classes" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
@@ -1113,6 +1150,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 saturation = (20 if args.lane_dups_saturation_steps is None else args.lane_dups_saturation_steps,
                               args.lane_dups_saturation_seed or 0, xy[0] if radius else None, xy[1] if radius else None,
                               radius)
+            gc_max_n = args.lane_dups_gc_max_n or 0
+            if args.lane_dups_gc and gc_max_n > len(cycle_list):
+                raise ValueError("--lane-dups-gc-max-n takes 0..%d, the scanned cycles, not %d" % (len(cycle_list), gc_max_n))
             ntn = 5 + 2 * levels + len(report.CLASS_BIN_NAMES) if near_k else 0
             rows = np.zeros((len(mine), ncnt + nsets + ntd + ntn), dtype=np.int64)
             logs = {}
@@ -1161,6 +1201,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                     report.write_lane_top(lane, results["ltop"][lane], verbose=not args.summary_only, out=out_fh)
                 if args.lane_dups_hops is not None:
                     report.write_lane_hops(lane, results["lhops"][lane], verbose=not args.summary_only, out=out_fh)
+                if args.lane_dups_gc:
+                    report.write_lane_gc(lane, results["lgc"][lane], verbose=not args.summary_only, out=out_fh)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
@@ -1169,7 +1211,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
                            "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}, "lnear": {}, "lindex": {},
                            "lmindex": {}, "lmismatch": {}, "ldistance": {}, "lquality": {}, "lsaturation": {}, "ltop": {},
-                           "lhops": {}}
+                           "lhops": {}, "lgc": {}}
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
@@ -1210,7 +1252,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                                                        args.lane_dups_top)
                                          if args.lane_dups_top is not None else 0,
                                          hops=sc.lane_hops_scratch_bytes(len(tiles), _lib.LANEHOPS_MAX_LISTED)
-                                         if args.lane_dups_hops is not None else 0)
+                                         if args.lane_dups_hops is not None else 0,
+                                         gc=sc.lane_gc_scratch_bytes(len(tiles), len(cycle_list))
+                                         if args.lane_dups_gc else 0)
                 if err is None:             # (a rank whose setup failed has nothing to scan: it goes to the flag)
                     scan_lanes(sc, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                                max(0, args.tile_batch), args.threads,
@@ -1231,7 +1275,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                lane_quality=(args.lane_dups_quality_edges, quality_d) if quality_d is not None else None,
                                lane_saturation=saturation, lane_top=args.lane_dups_top or 0,
                                lane_hops=(1 if args.lane_dups_hops_mismatches is None else args.lane_dups_hops_mismatches,
-                                          args.lane_dups_hops) if args.lane_dups_hops is not None else None)
+                                          args.lane_dups_hops) if args.lane_dups_hops is not None else None,
+                               lane_gc=(gc_max_n, args.lane_dups_gc_bins or 20) if args.lane_dups_gc else None)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
                     if args.tile_dups_out and near_k:
@@ -1246,6 +1291,10 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                         with open(args.lane_dups_hops_out, "w") as fh:
                             for i, lane in enumerate(sorted(results["lhops"], key=lanes.index)):
                                 report.write_lane_hops_tsv(lane, results["lhops"][lane], fh, header=i == 0)
+                    if args.lane_dups_gc_out:
+                        with open(args.lane_dups_gc_out, "w") as fh:
+                            for i, lane in enumerate(sorted(results["lgc"], key=lanes.index)):
+                                report.write_lane_gc_tsv(lane, results["lgc"][lane], fh, header=i == 0)
                     if args.lane_dups_out:
                         write_lane_members(args.lane_dups_out, results["lmembers"],
                                            index=([e - s for s, e in index_ranges], results["lmindex"])

@@ -1411,3 +1411,164 @@ def write_lane_hops_tsv(lane, counts: LaneHopCounts, out, header: bool = True) -
         for b, n in enumerate(row):
             if n:
                 print("%s\t%s\t%s\t%i" % (lane, c.names[a], c.names[b], n), file=out)
+
+
+# ---- --lane-dups-gc: a lane's duplication against its reads' GC content (include/welldup_lanegc.h) ----
+LANE_GC_HIST_COLS = 4
+LANE_GC_LANE_COLS = 8
+LANE_GC_TILE_COLS = 5
+LANE_GC_MIN_BINS, LANE_GC_MAX_BINS = 2, 100
+
+
+def gc_quartiles(distinct: Sequence[int]):
+    """distinct[g]: the distinct molecules with GC g -> (q1, q3), the quartiles of g over them cut at whole g: q1 is
+    the smallest g with 4 x (molecules at or below g) >= the molecules, q3 the smallest with 4 x (molecules at or
+    below g) >= 3 x the molecules.  Every molecule of one g lies on the same side of a cut: "at or below the first
+    quartile" is g <= q1 (it holds at least a quarter of the molecules, more when q1 is a tie), "above the third"
+    g > q3 (at most a quarter), and the rest, q1 < g <= q3, lies between.  (0, 0) without a molecule."""
+    total, below, q1, q3 = sum(distinct), 0, None, None
+    if total == 0:
+        return 0, 0
+    for g, n in enumerate(distinct):
+        below += n
+        if q1 is None and 4 * below >= total:
+            q1 = g
+        if q3 is None and 4 * below >= 3 * total:
+            q3 = g
+    return q1, q3
+
+
+@dataclass
+class LaneGCCounts:
+    """A lane's duplication against its reads' GC content (include/welldup_lanegc.h, LaneDups.gc): the lane row's
+    columns, per tile (by the tile's name) [PF, Counted, GC, CopiesCounted, CopiesGC], and hist[g] = [Single, Roots,
+    Copies, FamilyWells] for g = 0 .. L over the wells with at most max_n no-calls."""
+    k: int = 0
+    max_n: int = 0
+    bins: int = 20
+    pf: int = 0
+    single: int = 0
+    roots: int = 0
+    copies: int = 0
+    skip_single: int = 0
+    skip_roots: int = 0
+    skip_copies: int = 0
+    skip_family_wells: int = 0
+    tiles: Dict[str, List[int]] = field(default_factory=dict)
+    hist: List[List[int]] = field(default_factory=lambda: [[0] * LANE_GC_HIST_COLS])
+
+    @classmethod
+    def from_rows(cls, lane_row: Sequence[int], tile_rows: Sequence[Sequence[int]], hist, tile_names: Sequence,
+                  max_n: int, bins: int = 20, k: int = 0) -> "LaneGCCounts":
+        """The three results of LaneDups.gc(max_n); tile_names as LaneDupCounts.from_rows takes them; bins: the lines
+        write_lane_gc prints; k: the K of --lane-dups-hamming."""
+        b = [int(v) for v in lane_row]
+        h = [[int(v) for v in row] for row in hist]
+        assert len(b) == LANE_GC_LANE_COLS and len(h) >= 1 and all(len(row) == LANE_GC_HIST_COLS for row in h)
+        assert LANE_GC_MIN_BINS <= bins <= LANE_GC_MAX_BINS and 0 <= max_n <= len(h) - 1
+        tiles = {}
+        for name, row in zip(tile_names, tile_rows):
+            assert len(row) == LANE_GC_TILE_COLS
+            if name is not None:
+                tiles[name] = [int(v) for v in row]
+        return cls(int(k), int(max_n), int(bins), *b, tiles, h)
+
+    @property
+    def cycles(self) -> int:
+        return len(self.hist) - 1
+
+    @property
+    def skipped(self) -> int:
+        return self.skip_single + self.skip_roots + self.skip_copies
+
+    @property
+    def counted(self) -> int:
+        return self.pf - self.skipped
+
+    def bin_of(self, g: int) -> int:
+        """min(B - 1, g * B // L), in integers: g = L alone would open a bin of its own."""
+        return min(self.bins - 1, g * self.bins // self.cycles) if self.cycles else 0
+
+    def over(self, gs) -> List[int]:
+        """[distinct molecules, reads by the molecule's GC, redundant wells, Roots, FamilyWells, Copies by their own
+        read] summed over the g of gs."""
+        rows = [self.hist[g] for g in gs]
+        s, r, c, f = (sum(row[i] for row in rows) for i in range(LANE_GC_HIST_COLS))
+        return [s + r, s + f, f - r, r, f, c]
+
+    def mean_gc(self, col) -> Optional[float]:
+        """The mean of g / L over the wells of col(row) per g; None without a well."""
+        n = sum(col(row) for row in self.hist)
+        return sum(g * col(row) for g, row in enumerate(self.hist)) / (n * self.cycles) if n and self.cycles else None
+
+    def tile_means(self):
+        """tile -> (mean GC of its counted reads, of its counted copies), None for none."""
+        per = lambda gc, n: gc / (n * self.cycles) if n and self.cycles else None
+        return {t: (per(r[2], r[1]), per(r[4], r[3])) for t, r in self.tiles.items()}
+
+
+def write_lane_gc(lane, counts: LaneGCCounts, verbose: bool = False, out=None) -> None:
+    """The block that follows every other block of a lane under --lane-dups-gc: a line per GC bin - the range of g
+    it takes, the distinct molecules (Single + Roots) and their share, the reads by the molecule's GC (Single +
+    FamilyWells), the redundant wells among them (FamilyWells - Roots), the duplication in the bin and against the
+    lane's, the mean family size (FamilyWells / Roots), the copies by their own read, library_size of the bin -, with
+    verbose a line per tile and the tile whose mean lies furthest from the lane's (the first in sorted order on a tie),
+    then the summary: mean GC of the distinct
+    molecules and of the redundant wells (the copies, each by its own read) and the shift between them, the
+    duplication among the molecules at or below the first quartile of GC, between the quartiles and above the third
+    (gc_quartiles), and the bin with the highest duplication among those that hold at least 1 % of the distinct
+    molecules (the lowest such bin on a tie)."""
+    out = out or sys.stdout
+    c = counts
+    ham = "\tHamming: %i" % c.k if c.k else ""
+    share = lambda v, of: v / of if of else 0.0
+    num = lambda v, fmt="%.5f": "n/a" if v is None else fmt % v
+    L = c.cycles
+    every = c.over(range(L + 1))
+    lane_dup = share(every[2], every[1])
+    print(file=out)
+    best = None
+    for b in range(c.bins):
+        gs = [g for g in range(L + 1) if c.bin_of(g) == b]
+        distinct, reads, redundant, roots, family, copies = c.over(gs)
+        dup = share(redundant, reads)
+        if distinct and 100 * distinct >= every[0] and (best is None or dup > best[1]):
+            best = (b, dup, gs)
+        size = library_size(reads, distinct)
+        print("LaneGC: %s%s\tBin: %i\tGC: %s\tDistinct: %i (%.5f)\tReads: %i\tRedundant: %i\tDuplication: %.5f\t"
+              "Relative: %s\tMeanFamily: %s\tCopies: %i\tLibrarySize: %s" % (
+                  lane, ham, b, "%i-%i" % (gs[0], gs[-1]) if gs else "-", distinct, share(distinct, every[0]), reads,
+                  redundant, dup, num(dup / lane_dup if lane_dup else None, "%.3f"),
+                  num(family / roots if roots else None, "%.3f"), copies, num(size, "%.0f")), file=out)
+    lane_mean = share(sum(t[2] for t in c.tiles.values()), sum(t[1] for t in c.tiles.values()) * L)
+    if verbose:
+        means = c.tile_means()
+        for tile in sorted(c.tiles):
+            t = c.tiles[tile]
+            print("LaneGCTile: %s\tTile: %s\tPF: %i\tCounted: %i\tMeanGC: %s\tCopies: %i\tCopiesMeanGC: %s" % (
+                lane, tile, t[0], t[1], num(means[tile][0]), t[3], num(means[tile][1])), file=out)
+        gc, n = sum(t[2] for t in c.tiles.values()), sum(t[1] for t in c.tiles.values())
+        far = [(abs(Fraction(c.tiles[t][2], c.tiles[t][1]) - Fraction(gc, n)), t) for t in sorted(c.tiles) if c.tiles[t][1]]
+        if far:                                          # (in exact arithmetic: the first of the sorted tiles on a tie)
+            d, t = max(far, key=lambda e: e[0])
+            print("LaneGCTiles: %s\tLaneMeanGC: %.5f\tFurthest: %s (%.5f, %+.5f)" % (
+                lane, lane_mean, t, means[t][0], means[t][0] - lane_mean), file=out)
+    m_distinct = c.mean_gc(lambda row: row[0] + row[1])
+    m_copies = c.mean_gc(lambda row: row[2])
+    q1, q3 = gc_quartiles([row[0] + row[1] for row in c.hist])
+    parts = [c.over(range(0, q1 + 1)), c.over(range(q1 + 1, q3 + 1)), c.over(range(q3 + 1, L + 1))]
+    print("LaneGCSummary: %s%s\tMaxN: %i\tCycles: %i\tBins: %i\tCounted: %i\tSkipped: %i\tDistinct: %i\t"
+          "Duplication: %.5f\tMeanGC distinct: %s\tMeanGC redundant: %s\tShift: %s\tQ1: %i\tQ3: %i\t"
+          "Duplication at or below Q1: %.5f\tbetween: %.5f\tabove Q3: %.5f\tHighest: %s" % (
+              lane, ham, c.max_n, L, c.bins, c.counted, c.skipped, every[0], lane_dup, num(m_distinct), num(m_copies),
+              num(m_copies - m_distinct if m_distinct is not None and m_copies is not None else None, "%+.5f"), q1, q3,
+              share(parts[0][2], parts[0][1]), share(parts[1][2], parts[1][1]), share(parts[2][2], parts[2][1]),
+              "n/a" if best is None else "bin %i (GC %i-%i, %.5f)" % (best[0], best[2][0], best[2][-1], best[1])), file=out)
+
+
+def write_lane_gc_tsv(lane, counts: LaneGCCounts, out, header: bool = True) -> None:
+    """--lane-dups-gc-out: a line per g = 0 .. L - lane, gc, single, roots, copies, family_wells."""
+    if header:
+        print("lane\tgc\tsingle\troots\tcopies\tfamily_wells", file=out)
+    for g, row in enumerate(counts.hist):
+        print("%s\t%i\t%i\t%i\t%i\t%i" % (lane, g, row[0], row[1], row[2], row[3]), file=out)

@@ -325,6 +325,11 @@ class Scanner:
         it does not depend on the wells of a tile)."""
         return self._workspace_bytes(self._lib.wd_lane_mismatch_scratch, max_tiles, L)
 
+    def lane_gc_scratch_bytes(self, max_tiles: int, L: int) -> int:
+        """Device bytes LaneDups.gc needs beside the accumulator's workspace (wd_lane_gc_scratch: the counters per
+        tile and the histogram per g; it does not depend on the wells of a tile)."""
+        return self._workspace_bytes(self._lib.wd_lane_gc_scratch, max_tiles, L)
+
     def lane_hops_scratch_bytes(self, max_tiles: int, M: int) -> int:
         """Device bytes LaneDups.hops needs beside the accumulator's workspaces for M listed keys
         (wd_lane_hops_scratch: the counters, the listing and the (M + 1)^2 cells of the matrix; it does not depend on
@@ -825,6 +830,27 @@ class LaneDups:
                                self._h, int(max_d), d_scratch, sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
                                tile_rows.ctypes.data_as(ctypes.c_void_p), sub.ctypes.data_as(ctypes.c_void_p)))
         return lane_row, tile_rows, sub
+
+    def gc(self, max_n: int = 0):
+        """After finish(), any number of times, before or after every other pass (wd_lane_gc,
+        include/welldup_lanegc.h): every PF well by the GC of its own read - g, its cycles that read C or G - and by
+        what it is under the labels the finish left: a lone read, the first well of a group, or a copy.  A well with
+        more than max_n no-calls is counted by population only.
+        -> (lane row int64 [8]: [PF, Single, Roots, Copies, SkipSingle, SkipRoots, SkipCopies, SkipFamilyWells], tile
+        rows int64 [max_tiles, 5]: [PF, Counted, GC, CopiesCounted, CopiesGC] by the well's own tile, hist int64
+        [L + 1, 4]: [g][Single, Roots, Copies, FamilyWells], FamilyWells the groups' wells by the root's g).  The
+        scratch is allocated for the call and released.  max_n outside 0..L or a call before a successful finish
+        raises ValueError."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        lane_row = np.zeros(_lib.LANEGC_LANE_COLS, dtype=np.int64)
+        tile_rows = np.zeros((self.max_tiles, _lib.LANEGC_TILE_COLS), dtype=np.int64)
+        hist = np.zeros((self.L + 1, _lib.LANEGC_HIST_COLS), dtype=np.int64)
+        self._with_scratch(self.sc.lane_gc_scratch_bytes(self.max_tiles, self.L),
+                           lambda d_scratch, sbytes: self.sc._lib.wd_lane_gc(
+                               self._h, int(max_n), d_scratch, sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
+                               tile_rows.ctypes.data_as(ctypes.c_void_p), hist.ctypes.data_as(ctypes.c_void_p)))
+        return lane_row, tile_rows, hist
 
     def hops(self, split: int, max_e: int, keys):
         """After finish() of a lane with an index part, any number of times, before or after index_finish and every
