@@ -10,6 +10,8 @@
  *                metric and k); a pair in several rings has the smallest of them as its level;
  *   Sets[l]      connected components of at least two wells in the graph of the edges of level <= l
  *                (single linkage); InSets[l] = wells in them; Redundant[l] = InSets[l] - Sets[l];
+ *                A well that names itself in one of its rings (nbr[slot] == centre) is no pair: the scan counts
+ *                and logs that record as it does any duplicate (Dups, edges_out), the sets ignore it.
  *   label        of a well: the smallest well index of its outermost-level set; a PF well in no set is
  *                labelled with its own index, a non-PF well with WD_INVALID_TARGET.
  */

@@ -23,13 +23,13 @@ def levels_of_slots(lvl_off, targets, slots):
 
 def dup_sets(n, pf, a, b, lev, levels):
     """Single-linkage sets of the PF wells over edges (a[i], b[i]) of level lev[i]; an edge with an end that
-    fails the filter is dropped.  -> (row [PF, Sets[levels], InSets[levels], Redundant[levels], 8 size bins],
+    fails the filter, or from a well to itself, is dropped.  -> (row [PF, Sets[levels], InSets[levels], Redundant[levels], 8 size bins],
     labels uint32[n]: smallest well of the outermost-level set, own index in no set, INVALID if not PF)."""
     pf = np.asarray(pf).astype(bool)
     a = np.asarray(a, dtype=np.int64)
     b = np.asarray(b, dtype=np.int64)
     lev = np.asarray(lev, dtype=np.int64)
-    keep = pf[a] & pf[b]
+    keep = pf[a] & pf[b] & (a != b)               # (a well that names itself is no pair: a set has two wells)
     a, b, lev = a[keep], b[keep], lev[keep]
     parent = list(range(n))
 

@@ -7,7 +7,8 @@
 // wd_count_tiles); this unit reads the context (wd_ctx.h) and keeps no state of its own in it.  Per batch of
 // tiles, one launch each:
 //   k_sets_init      parent[w] = w for PF wells, INVALID for the rest; first level touched = none
-//   k_sets_edges     one lane per hit record: drop it unless both ends pass the filter, find its level from
+//   k_sets_edges     one lane per hit record: drop it unless both ends pass the filter and differ (a well that
+//                    names itself is no pair), find its level from
 //                    the target's lvl_off row, rewrite the record in place as {tile, a, b, level},
 //                    atomicMin both ends' first level
 //   k_sets_union     one launch per level, in increasing order: lock-free union-find over that level's edges
@@ -207,6 +208,11 @@ __global__ void __launch_bounds__(kSetsBlock) k_sets_edges(int4 *__restrict__ re
     const size_t base = (size_t)tile * N;
     // non-PF wells belong to no set (the scan records a duplicate for a PF centre whatever its neighbour's filter)
     if (parent[base + a] == kInvalid || parent[base + b] == kInvalid) {
+        rec[i] = make_int4(tile, a, b, -1);
+        return;
+    }
+    // a well that names itself is no pair: a set has at least two wells (the scan counts the record all the same)
+    if (a == b) {
         rec[i] = make_int4(tile, a, b, -1);
         return;
     }
