@@ -1,11 +1,27 @@
 // wave_emu.h - what a kernel's source needs to run on the CPU as it stands (tools/lane_mismatch_emu.cpp,
-// tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp, tools/lane_hops_emu.cpp, tools/lane_gc_emu.cpp): the 256 lanes of a
+// tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp, tools/lane_hops_emu.cpp, tools/lane_gc_emu.cpp,
+// tools/read_classes_emu.cpp, tools/near_emu.cpp): the 256 lanes of a
 // workgroup are fibers (ucontext) that a round-robin scheduler switches at the collectives - __syncthreads is a
 // rendezvous of the workgroup, __ballot and __shfl of a wave -, LDS is the kernel's static storage, an atomic add or
 // minimum or a compare-and-swap is a plain one (one fiber runs at a time), and the qualifiers are empty.  Include it, then the kernel's
 // .inc file, then call run_block(block x, block y, kernel call) per workgroup.  The device half of csrc/lane_pass.inc -
 // the run (kLaneRun, LaneRun) and wave_by_key - comes with it, included at the end: the kernels' own, not a copy.
 // Nothing here says anything about time.
+//
+// Schedules.  Every atomic - the atomicAdd family and the __hip_atomic_* builtins - is a scheduling point followed by
+// the plain operation: at a point the fiber may hand over to the next one, so that other lanes run between a lane's
+// load and its compare-and-swap, or between the two finds of a union.  emu_schedule(policy, seed) decides: never (the
+// default: fibers switch at the collectives alone, as they always did here), with probability 1/3, always; reverse
+// starts the fibers of a workgroup from lane 255 down; run_grid runs the workgroups of a launch one after the other
+// (a workgroup still runs to its end before the next begins), in a seeded permutation of (x, y) if asked.  emu_counts
+// holds the scheduling points passed and the compare-and-swaps that lost - found another value than expected - since
+// emu_counts_clear() (run_grid returns those of its launch), the latter by emu_cas_tag, which the emulator sets before a launch (kEmuTable, kEmuUnion).  The
+// emulation is sequentially consistent: every fiber sees every store at once.  With -DWAVE_EMU_TORN_CAS the
+// compare-and-swap is broken on purpose - a scheduling point between its load and its store - for the emulators' tests
+// to show that they notice (=2: in the compare-and-swaps tagged kEmuUnion alone); nothing else builds that way.
+// -DWAVE_EMU_UNIT_DEFS: the emulator includes csrc/read_classes.inc and csrc/tile_classes.inc (the head of the tiledups unit),
+// which define kTdBlock, kSpread, kFpCycles, kLdCmpWords, kInvalid, kMaxCycles, align256 and spread_row themselves:
+// this header then leaves them, and lane_pass.inc, out.
 #pragma once
 #include <ucontext.h>
 #include <cstdint>
@@ -21,32 +37,52 @@ struct int2 { int x, y; };
 struct uint2 { uint32_t x, y; };
 static uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{x, y}; }
 struct D3 { unsigned x, y, z; };
-constexpr int kTdBlock = 256, kWave = 64, kSpread = 64, kFpCycles = 10, kLdCmpWords = 8;
+constexpr int kEmuBlock = 256, kWave = 64;
+#ifndef WAVE_EMU_UNIT_DEFS
+constexpr int kTdBlock = kEmuBlock, kSpread = 64, kFpCycles = 10, kLdCmpWords = 8;
 constexpr uint32_t kInvalid = 0xFFFFFFFFu;
 constexpr int kMaxCycles = 1024;
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-// ---- fibers: one per lane of a workgroup, switched at collectives
-struct Fiber { ucontext_t ctx; bool done; char *stack; };
-static Fiber fib[kTdBlock]; static ucontext_t sched; static int cur;
+#endif
+// ---- fibers: one per lane of a workgroup, switched at collectives - and at atomics, if the schedule says so
+struct Fiber { ucontext_t ctx; void *sp; bool done; char *stack; const long *wait; long wait_at; };      // wait: the generation of the rendezvous it stands at
+static Fiber emu_fib[kEmuBlock]; static ucontext_t emu_sched; static void *emu_sched_sp; static int emu_lane;
+// A switch saves the registers a call preserves on the fiber's own stack and changes stacks: swapcontext does the same
+// and a system call for the signal mask on top, which at a switch per atomic was most of an emulator's run time (near_emu: 47 s against 6).
+// Elsewhere than on x86-64, or with -DWAVE_EMU_UCONTEXT, it is swapcontext.
+#if defined(__x86_64__) && !defined(WAVE_EMU_UCONTEXT)
+#define WAVE_EMU_FAST 1
+extern "C" void emu_switch(void **from_sp, void *to_sp);
+asm(".text\n.globl emu_switch\n.type emu_switch,@function\nemu_switch:\n"
+    "pushq %rbp\npushq %rbx\npushq %r12\npushq %r13\npushq %r14\npushq %r15\n"
+    "movq %rsp, (%rdi)\nmovq %rsi, %rsp\n"
+    "popq %r15\npopq %r14\npopq %r13\npopq %r12\npopq %rbx\npopq %rbp\nret\n");
+#endif
 static D3 g_block;
-#define threadIdx (D3{(unsigned)cur, 0, 0})
+#define threadIdx (D3{(unsigned)emu_lane, 0, 0})
 #define blockIdx g_block
-static void yield_() { swapcontext(&fib[cur].ctx, &sched); }
+#ifdef WAVE_EMU_FAST
+static void yield_() { emu_switch(&emu_fib[emu_lane].sp, emu_sched_sp); }
+#else
+static void yield_() { swapcontext(&emu_fib[emu_lane].ctx, &emu_sched); }
+#endif
+// at a rendezvous whose generation is g: not run again before the last lane has come (the scheduler passes it over)
+static void await_(const long &gen, long g) { Fiber &f = emu_fib[emu_lane]; f.wait = &gen; f.wait_at = g; while (gen == g) yield_(); f.wait = nullptr; }
 static int bar_count = 0; static long bar_gen = 0;
-static void __syncthreads() { long g = bar_gen; if (++bar_count == kTdBlock) { bar_count = 0; bar_gen++; } else while (bar_gen == g) yield_(); }
+static void __syncthreads() { long g = bar_gen; if (++bar_count == kEmuBlock) { bar_count = 0; bar_gen++; } else await_(bar_gen, g); }
 struct WaveSync { int count = 0; long gen = 0; unsigned long long pred[2] = {0, 0}; int val[2][kWave]; };
-static WaveSync ws[kTdBlock / kWave];
+static WaveSync emu_ws[kEmuBlock / kWave];
 static unsigned long long __ballot(bool p) {
-    WaveSync &w = ws[cur / kWave]; long g = w.gen; int par = g & 1, lane = cur % kWave;
+    WaveSync &w = emu_ws[emu_lane / kWave]; long g = w.gen; int par = g & 1, lane = emu_lane % kWave;
     if (w.count == 0) w.pred[par] = 0;
     if (p) w.pred[par] |= 1ull << lane;
-    if (++w.count == kWave) { w.count = 0; w.gen++; } else while (w.gen == g) yield_();
+    if (++w.count == kWave) { w.count = 0; w.gen++; } else await_(w.gen, g);
     return w.pred[par];
 }
 static int __shfl(int v, int src) {
-    WaveSync &w = ws[cur / kWave]; long g = w.gen; int par = g & 1, lane = cur % kWave;
+    WaveSync &w = emu_ws[emu_lane / kWave]; long g = w.gen; int par = g & 1, lane = emu_lane % kWave;
     w.val[par][lane] = v;
-    if (++w.count == kWave) { w.count = 0; w.gen++; } else while (w.gen == g) yield_();
+    if (++w.count == kWave) { w.count = 0; w.gen++; } else await_(w.gen, g);
     return w.val[par][src];
 }
 #define __popcll __builtin_popcountll
@@ -54,13 +90,49 @@ static int __shfl(int v, int src) {
 #define __clzll __builtin_clzll
 #define __popc __builtin_popcount
 #define __ffs __builtin_ffs
-template <class T, class U> static T atomicAdd(T *p, U v) { T o = *p; *p += (T)v; return o; }
-template <class T> static T atomicCAS(T *p, T expect, T v) { T o = *p; if (o == expect) *p = v; return o; }
-template <class T, class U> static T atomicMin(T *p, U v) { T o = *p; if ((T)v < o) *p = (T)v; return o; }
+// ---- the schedule: what happens at a scheduling point
+enum EmuPolicy { kEmuNever, kEmuThird, kEmuAlways };
+enum { kEmuTable = 0, kEmuUnion = 1 };
+struct EmuCounts { long points, lost[2]; };
+static EmuCounts emu_counts;
+static int emu_cas_tag = kEmuTable;
+static EmuPolicy emu_policy = kEmuNever; static bool emu_reverse = false; static uint64_t emu_rng = 1;
+static uint64_t emu_next() { emu_rng ^= emu_rng << 13; emu_rng ^= emu_rng >> 7; emu_rng ^= emu_rng << 17; return emu_rng; }      // (xorshift64: the inputs keep rand())
+static void emu_schedule(EmuPolicy policy, bool reverse, uint64_t seed) { emu_policy = policy; emu_reverse = reverse; emu_rng = seed * 0x9E3779B97F4A7C15ull | 1; }
+static void emu_counts_clear() { emu_counts = EmuCounts{0, {0, 0}}; }
+static void emu_point() {
+    emu_counts.points++;
+    if (emu_policy == kEmuAlways || (emu_policy == kEmuThird && emu_next() % 3 == 0)) yield_();
+}
+template <class T, class U> static T atomicAdd(T *p, U v) { emu_point(); T o = *p; *p += (T)v; return o; }
+template <class T> static T atomicCAS(T *p, T expect, T v) { emu_point(); T o = *p; if (o == expect) *p = v; return o; }
+template <class T, class U> static T atomicMin(T *p, U v) { emu_point(); T o = *p; if ((T)v < o) *p = (T)v; return o; }
+template <class T, class U> static T atomicOr(T *p, U v) { emu_point(); T o = *p; *p |= (T)v; return o; }
+// the clang builtins of the kernels that say their memory order and scope: the order and the scope mean nothing here
+#define __HIP_MEMORY_SCOPE_AGENT 4
+template <class T> static T __hip_atomic_load(const T *p, int, int) { emu_point(); return *p; }
+template <class T, class U> static void __hip_atomic_store(T *p, U v, int, int) { emu_point(); *p = (T)v; }
+template <class T, class U> static bool __hip_atomic_compare_exchange_strong(T *p, T *expect, U v, int, int, int) {
+    emu_point();
+    const T o = *p;
+    if (o != *expect) { emu_counts.lost[emu_cas_tag]++; *expect = o; return false; }
+#ifdef WAVE_EMU_TORN_CAS
+    if (WAVE_EMU_TORN_CAS != 2 || emu_cas_tag == kEmuUnion) emu_point();      // (the deliberate bug: another fiber may store between the load and the store)
+#endif
+    *p = (T)v;
+    return true;
+}
+template <class T, class U> static T __hip_atomic_fetch_min(T *p, U v, int, int) { emu_point(); T o = *p; if ((T)v < o) *p = (T)v; return o; }
+template <class T, class U> static T __hip_atomic_fetch_add(T *p, U v, int, int) { emu_point(); T o = *p; *p += (T)v; return o; }
+template <class T, class U> static T __hip_atomic_fetch_sub(T *p, U v, int, int) { emu_point(); T o = *p; *p -= (T)v; return o; }
+template <class T, class U> static T __hip_atomic_exchange(T *p, U v, int, int) { emu_point(); T o = *p; *p = (T)v; return o; }
+#define __builtin_nontemporal_load(p) (*(p))
+#ifndef WAVE_EMU_UNIT_DEFS
 static unsigned long long *spread_row(unsigned long long *cnt, size_t row, int width) { return cnt + (row * kSpread + blockIdx.x % kSpread) * width; }
+#endif
 // the lanes of the wave below this one whose bit is set in the mask's low (high) half, added to a
-#define __builtin_amdgcn_mbcnt_lo(m, a) ((a) + (uint32_t)__builtin_popcount((uint32_t)(m) & (uint32_t)((1ull << std::min(cur % kWave, 32)) - 1)))
-#define __builtin_amdgcn_mbcnt_hi(m, a) ((a) + (uint32_t)__builtin_popcount((uint32_t)(m) & (uint32_t)((1ull << std::max(cur % kWave - 32, 0)) - 1)))
+#define __builtin_amdgcn_mbcnt_lo(m, a) ((a) + (uint32_t)__builtin_popcount((uint32_t)(m) & (uint32_t)((1ull << std::min(emu_lane % kWave, 32)) - 1)))
+#define __builtin_amdgcn_mbcnt_hi(m, a) ((a) + (uint32_t)__builtin_popcount((uint32_t)(m) & (uint32_t)((1ull << std::max(emu_lane % kWave - 32, 0)) - 1)))
 #define __device__
 #define __host__
 #define __global__
@@ -69,17 +141,47 @@ static unsigned long long *spread_row(unsigned long long *cnt, size_t row, int w
 #define __restrict__
 // ---- a workgroup: every fiber runs `kernel` (the emulator's call of its kernel with its arguments) to the end
 static void (*g_kernel)();
-static void entry_() { g_kernel(); fib[cur].done = true; swapcontext(&fib[cur].ctx, &sched); }
+static void entry_() { g_kernel(); emu_fib[emu_lane].done = true; yield_(); }
 static void run_block(unsigned bx, unsigned by, void (*kernel)()) {
     g_block = D3{bx, by, 0};
     g_kernel = kernel;
-    for (int t = 0; t < kTdBlock; t++) {
-        if (!fib[t].stack) fib[t].stack = (char *)malloc(1 << 16);
-        getcontext(&fib[t].ctx); fib[t].ctx.uc_stack.ss_sp = fib[t].stack; fib[t].ctx.uc_stack.ss_size = 1 << 16; fib[t].ctx.uc_link = &sched;
-        fib[t].done = false; makecontext(&fib[t].ctx, entry_, 0);
+    for (int t = 0; t < kEmuBlock; t++) {
+        Fiber &f = emu_fib[t];
+        if (!f.stack) f.stack = (char *)malloc(1 << 16);
+        f.done = false; f.wait = nullptr;
+#ifdef WAVE_EMU_FAST
+        void **sp = (void **)(f.stack + (1 << 16));
+        *--sp = nullptr; *--sp = (void *)entry_;
+        for (int r = 0; r < 6; r++) *--sp = nullptr;
+        f.sp = sp;
+#else
+        getcontext(&f.ctx); f.ctx.uc_stack.ss_sp = f.stack; f.ctx.uc_stack.ss_size = 1 << 16; f.ctx.uc_link = &emu_sched;
+        makecontext(&f.ctx, entry_, 0);
+#endif
     }
-    int left = kTdBlock;
-    while (left) for (int t = 0; t < kTdBlock; t++) if (!fib[t].done) { cur = t; swapcontext(&sched, &fib[t].ctx); if (fib[t].done) left--; }
+    int left = kEmuBlock;
+    while (left) for (int i = 0; i < kEmuBlock; i++) {
+        const int t = emu_reverse ? kEmuBlock - 1 - i : i;
+        if (!emu_fib[t].done && !(emu_fib[t].wait && *emu_fib[t].wait == emu_fib[t].wait_at)) { emu_lane = t;
+#ifdef WAVE_EMU_FAST
+            emu_switch(&emu_sched_sp, emu_fib[t].sp);
+#else
+            swapcontext(&emu_sched, &emu_fib[t].ctx);
+#endif
+            if (emu_fib[t].done) left--; }
+    }
 }
+// a launch of gx * gy workgroups: in the order x fastest, or (permute) in a permutation drawn from the schedule's seed.
+// Returns the launch's own counts (emu_counts goes on adding up).
+static EmuCounts run_grid(unsigned gx, unsigned gy, void (*kernel)(), bool permute = false) {
+    const EmuCounts before = emu_counts;
+    std::vector<unsigned> order((size_t)gx * gy);
+    for (size_t i = 0; i < order.size(); i++) order[i] = (unsigned)i;
+    if (permute) for (size_t i = order.size(); i > 1; i--) std::swap(order[i - 1], order[emu_next() % i]);
+    for (unsigned b : order) run_block(b % gx, b / gx, kernel);
+    return EmuCounts{emu_counts.points - before.points, {emu_counts.lost[0] - before.lost[0], emu_counts.lost[1] - before.lost[1]}};
+}
+#ifndef WAVE_EMU_UNIT_DEFS
 #define WD_LANE_PASS_EMU
 #include "../well_duplicates_amd/csrc/lane_pass.inc"
+#endif

@@ -394,6 +394,7 @@ __global__ void __launch_bounds__(kTdBlock) k_ld_span_sum(const int *__restrict_
 
 }  // namespace
 
+#ifndef WD_TILEDUPS_EMU                            // (tools/read_classes_emu.cpp, tools/near_emu.cpp: the kernels above on the CPU, a fiber per lane)
 struct wd_lane_index;                              // lane_index.inc: the index part of an accumulator
 struct wd_lane_quality;                            // lane_quality.inc: the quality part of an accumulator
 
@@ -698,3 +699,4 @@ void wd_lane_dups_end(wd_lane_dups *ld)
 }
 
 }  // extern "C"
+#endif

@@ -200,6 +200,7 @@ __global__ void __launch_bounds__(kTdBlock) k_ln_members(const int *__restrict__
 
 }  // namespace
 
+#ifndef WD_TILEDUPS_EMU                            // (tools/read_classes_emu.cpp, tools/near_emu.cpp: the kernels above on the CPU, a fiber per lane)
 extern "C" {
 
 int wd_lane_near_dups_scratch(int64_t N, int max_tiles, int L, int k, size_t *bytes)
@@ -341,3 +342,4 @@ try {
 } WD_CATCH
 
 }  // extern "C"
+#endif

@@ -190,6 +190,7 @@ __global__ void __launch_bounds__(kTdBlock) k_tn_members(const uint32_t *__restr
 
 }  // namespace
 
+#ifndef WD_TILEDUPS_EMU                            // (tools/read_classes_emu.cpp, tools/near_emu.cpp: the kernels above on the CPU, a fiber per lane)
 extern "C" {
 
 int wd_tile_near_dups_workspace(int64_t N, int n_tiles, int k, size_t *bytes)
@@ -304,3 +305,4 @@ try {
 } WD_CATCH
 
 }  // extern "C"
+#endif
