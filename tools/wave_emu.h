@@ -1,6 +1,6 @@
 // wave_emu.h - what a kernel's source needs to run on the CPU as it stands (tools/lane_mismatch_emu.cpp,
 // tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp, tools/lane_hops_emu.cpp, tools/lane_gc_emu.cpp,
-// tools/read_classes_emu.cpp, tools/near_emu.cpp): the 256 lanes of a
+// tools/read_classes_emu.cpp, tools/near_emu.cpp, tools/dup_sets_emu.cpp): the 256 lanes of a
 // workgroup are fibers (ucontext) that a round-robin scheduler switches at the collectives - __syncthreads is a
 // rendezvous of the workgroup, __ballot and __shfl of a wave -, LDS is the kernel's static storage, an atomic add or
 // minimum or a compare-and-swap is a plain one (one fiber runs at a time), and the qualifiers are empty.  Include it, then the kernel's
@@ -21,7 +21,8 @@
 // to show that they notice (=2: in the compare-and-swaps tagged kEmuUnion alone); nothing else builds that way.
 // -DWAVE_EMU_UNIT_DEFS: the emulator includes csrc/read_classes.inc and csrc/tile_classes.inc (the head of the tiledups unit),
 // which define kTdBlock, kSpread, kFpCycles, kLdCmpWords, kInvalid, kMaxCycles, align256 and spread_row themselves:
-// this header then leaves them, and lane_pass.inc, out.
+// this header then leaves them, and lane_pass.inc, out.  tools/dup_sets_emu.cpp defines it too: csrc/dup_sets.inc
+// brings kSpread, kInvalid and align256 of its own.
 #pragma once
 #include <ucontext.h>
 #include <cstdint>
@@ -34,6 +35,8 @@ using std::min; using std::max;
 struct uint4 { uint32_t x, y, z, w; };
 static uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
 struct int2 { int x, y; };
+struct int4 { int x, y, z, w; };
+static int4 make_int4(int x, int y, int z, int w) { return int4{x, y, z, w}; }
 struct uint2 { uint32_t x, y; };
 static uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{x, y}; }
 struct D3 { unsigned x, y, z; };
@@ -68,21 +71,30 @@ static void yield_() { swapcontext(&emu_fib[emu_lane].ctx, &emu_sched); }
 #endif
 // at a rendezvous whose generation is g: not run again before the last lane has come (the scheduler passes it over)
 static void await_(const long &gen, long g) { Fiber &f = emu_fib[emu_lane]; f.wait = &gen; f.wait_at = g; while (gen == g) yield_(); f.wait = nullptr; }
-static int bar_count = 0; static long bar_gen = 0;
-static void __syncthreads() { long g = bar_gen; if (++bar_count == kEmuBlock) { bar_count = 0; bar_gen++; } else await_(bar_gen, g); }
-struct WaveSync { int count = 0; long gen = 0; unsigned long long pred[2] = {0, 0}; int val[2][kWave]; };
+// A ballot or a shuffle under a condition (if (w < N) { .. __ballot(pf) .. }) is one of the wave's lanes that take the
+// branch: it is complete when every lane of the wave stands at it, waits at the workgroup's barrier (away) or has ended
+// (gone) - the lanes that went round it - and a lane that is not there sets no bit.
+struct WaveSync { int count = 0, away = 0, gone = 0; long gen = 0; unsigned long long pred[2] = {0, 0}; int val[2][kWave]; };
 static WaveSync emu_ws[kEmuBlock / kWave];
+static bool wave_complete_(WaveSync &w) { if (w.count + w.away + w.gone < kWave) return false; w.count = 0; w.gen++; return true; }
+static int bar_count = 0; static long bar_gen = 0;
+static void __syncthreads() {
+    long g = bar_gen;
+    if (++bar_count == kEmuBlock) { bar_count = 0; bar_gen++; for (WaveSync &w : emu_ws) w.away = 0; return; }
+    WaveSync &w = emu_ws[emu_lane / kWave]; w.away++; if (w.count) wave_complete_(w);
+    await_(bar_gen, g);
+}
 static unsigned long long __ballot(bool p) {
     WaveSync &w = emu_ws[emu_lane / kWave]; long g = w.gen; int par = g & 1, lane = emu_lane % kWave;
     if (w.count == 0) w.pred[par] = 0;
     if (p) w.pred[par] |= 1ull << lane;
-    if (++w.count == kWave) { w.count = 0; w.gen++; } else await_(w.gen, g);
+    w.count++; if (!wave_complete_(w)) await_(w.gen, g);
     return w.pred[par];
 }
 static int __shfl(int v, int src) {
     WaveSync &w = emu_ws[emu_lane / kWave]; long g = w.gen; int par = g & 1, lane = emu_lane % kWave;
     w.val[par][lane] = v;
-    if (++w.count == kWave) { w.count = 0; w.gen++; } else await_(w.gen, g);
+    w.count++; if (!wave_complete_(w)) await_(w.gen, g);
     return w.val[par][src];
 }
 #define __popcll __builtin_popcountll
@@ -141,10 +153,11 @@ static unsigned long long *spread_row(unsigned long long *cnt, size_t row, int w
 #define __restrict__
 // ---- a workgroup: every fiber runs `kernel` (the emulator's call of its kernel with its arguments) to the end
 static void (*g_kernel)();
-static void entry_() { g_kernel(); emu_fib[emu_lane].done = true; yield_(); }
+static void entry_() { g_kernel(); emu_fib[emu_lane].done = true; WaveSync &w = emu_ws[emu_lane / kWave]; w.gone++; if (w.count) wave_complete_(w); yield_(); }
 static void run_block(unsigned bx, unsigned by, void (*kernel)()) {
     g_block = D3{bx, by, 0};
     g_kernel = kernel;
+    for (WaveSync &w : emu_ws) w.away = w.gone = 0;
     for (int t = 0; t < kEmuBlock; t++) {
         Fiber &f = emu_fib[t];
         if (!f.stack) f.stack = (char *)malloc(1 << 16);
@@ -172,13 +185,15 @@ static void run_block(unsigned bx, unsigned by, void (*kernel)()) {
     }
 }
 // a launch of gx * gy workgroups: in the order x fastest, or (permute) in a permutation drawn from the schedule's seed.
-// Returns the launch's own counts (emu_counts goes on adding up).
+// Returns the launch's own counts (emu_counts goes on adding up).  emu_after_block, if set, is called after every
+// workgroup of a launch with its (x, y): an emulator that wants to see what one workgroup changed.
+static void (*emu_after_block)(unsigned bx, unsigned by) = nullptr;
 static EmuCounts run_grid(unsigned gx, unsigned gy, void (*kernel)(), bool permute = false) {
     const EmuCounts before = emu_counts;
     std::vector<unsigned> order((size_t)gx * gy);
     for (size_t i = 0; i < order.size(); i++) order[i] = (unsigned)i;
     if (permute) for (size_t i = order.size(); i > 1; i--) std::swap(order[i - 1], order[emu_next() % i]);
-    for (unsigned b : order) run_block(b % gx, b / gx, kernel);
+    for (unsigned b : order) { run_block(b % gx, b / gx, kernel); if (emu_after_block) emu_after_block(b % gx, b / gx); }
     return EmuCounts{emu_counts.points - before.points, {emu_counts.lost[0] - before.lost[0], emu_counts.lost[1] - before.lost[1]}};
 }
 #ifndef WAVE_EMU_UNIT_DEFS
