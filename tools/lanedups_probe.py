@@ -61,12 +61,20 @@ and beside Scanner.stream_read_gbs over as many bytes as the pass reads - every 
 members: 4 ceil(cycles / 10) + 8 bytes per well -, on three inputs: the planted lane, the `--equal` lane (every well
 of a wave on one bin of the histogram) and the lane whose odd wells repeat their left neighbour (pairs only: every
 second well a root that adds its family's size).
+`--hamming K --consensus [--max-family M]` times LaneDups.consensus(K, M) (the lane's errors against its families' vote,
+include/welldup_laneconsensus.h) per tile of the lane beside LaneDups.mismatches(K) and the equality finish on the same
+batches and labels, and beside Scanner.stream_read_gbs over 8 bytes per well - label and members, all that the
+reservation and the scatter read of a lane without a voted family: their floor -, on three inputs: the planted lane
+(after the near finish; its copies are mostly pairs, which do not vote), the `--equal` lane (one Large family: no list,
+no vote) and a lane of three tiles whose wells repeat the first of every three (every well in a voted family of three:
+the longest list there is).
 For per-kernel times run it under
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/lanedups_probe.py
 
 (the k_ld_* rows of the stats are this stage, k_li_* the index part, k_lm_* the mismatch pass, k_lg_* the distance pass,
-k_lq_* the quality part, k_ls_* the saturation pass, k_lt_* the top pass, k_lh_* the hops pass, k_lgc_* the GC pass, k_td_* the per-tile classes, k_dense_* the scan)."""
+k_lq_* the quality part, k_ls_* the saturation pass, k_lt_* the top pass, k_lh_* the hops pass, k_lgc_* the GC pass,
+k_lc_* the consensus pass, k_td_* the per-tile classes, k_dense_* the scan)."""
 import argparse
 import os
 import sys
@@ -109,12 +117,18 @@ ap.add_argument("--capacity", type=int, default=0, metavar="C", help="the candid
 ap.add_argument("--gc", action="store_true",
                 help="also time LaneDups.gc(0) beside the equality finish, mismatches(0), top(100) and a pure read of as "
                      "many bytes (three inputs with --equal)")
+ap.add_argument("--consensus", action="store_true",
+                help="also time LaneDups.consensus(K, M) beside mismatches(K), the equality finish and a pure read of "
+                     "label and members (needs --hamming; three inputs with --equal)")
+ap.add_argument("--max-family", type=int, default=256, metavar="M", help="the largest family of --consensus that votes")
 ap.add_argument("--quality", action="store_true",
                 help="also time LaneDups.qual_add beside add and LaneDups.qualities(K) beside mismatches(K) (needs "
                      "--hamming; three inputs with --equal)")
 a = ap.parse_args()
 if a.mismatches and not a.hamming:
     ap.error("--mismatches needs --hamming K")
+if a.consensus and not a.hamming:
+    ap.error("--consensus needs --hamming K")
 if a.quality and not a.hamming:
     ap.error("--quality needs --hamming K")
 if a.hops and not a.index:
@@ -298,6 +312,31 @@ def time_gc(acc, tiles_n, t_finish, what):
              t_g / t_read, t_m / tiles_n, t_t / tiles_n, t_finish / tiles_n))
 
 
+def time_consensus(acc, tiles_n, t_finish, what):
+    """LaneDups.consensus(K, M) and, on the same labels, LaneDups.mismatches(K), each after a first call that pays for
+    loading the kernels; and a pure read of 8 bytes per well, from the accumulator's own workspace"""
+    acc.consensus(a.hamming, a.max_family)
+    (crow, ctiles, calls), t_c = clock(lambda: acc.consensus(a.hamming, a.max_family))
+    _, t_c0 = clock(lambda: acc.consensus(0, a.max_family))
+    acc.mismatches(a.hamming)
+    mm, t_m = clock(lambda: acc.mismatches(a.hamming))
+    nbytes = tiles_n * n * 8
+    gbs = sc.stream_read_gbs(acc.d_ws, min(nbytes, acc.ws_bytes))
+    t_read = nbytes / gbs / 1e6
+    assert crow[11:].sum() == crow[1] and calls.sum() == crow[2] * a.cycles - crow[6] and \
+        (ctiles.sum(axis=0) == crow[1:5]).all() and 2 * crow[8] + crow[1] + crow[10] == mm[0][0] + crow[8] + crow[0] + crow[9], \
+        "the consensus rows do not add up"
+    print("%s: consensus, max_d %d, max_family %d: %d families of %d wells, %d profiled, %d mismatches (%d with N), %d "
+          "undecided, %d first wells off; %d pairs and %d large families of %d wells left out; Dist %s"
+          % (what, a.hamming, a.max_family, crow[0], crow[1], crow[2], crow[3], crow[4], crow[5], crow[7], crow[8], crow[9],
+             crow[10], " ".join(str(v) for v in crow[11:])))
+    print("  %-22s %9.3f ms  (%.4f ms per tile; max_d 0: %.4f; a pure read of label and members, 8 bytes per well: %.4f ms "
+          "per tile at %.0f GB/s; consensus / read = %.2f; mismatches(%d): %.4f; consensus / mismatches = %.2f; the "
+          "equality finish: %.4f)"
+          % ("lane consensus", t_c, t_c / tiles_n, t_c0 / tiles_n, t_read / tiles_n, gbs, t_c / t_read, a.hamming,
+             t_m / tiles_n, t_c / t_m, t_finish / tiles_n))
+
+
 def time_qualities(acc, tiles_n, t_finish, t_qual_add, t_plain_add, what):
     """LaneDups.qualities(K) and, on the same labels, LaneDups.mismatches(K), each after a first call that pays for
     loading the kernel"""
@@ -335,6 +374,8 @@ if a.hamming:
         assert mm[0][0] == near[3][3] and mm[0][4:].sum() == mm[0][0], "Pairs is not the near finish's Redundant"
     if a.quality:
         time_qualities(ldn, max(1, a.tiles), t_fin, t_qadd, t_add, "the planted lane")
+    if a.consensus:
+        time_consensus(ldn, max(1, a.tiles), t_fin, "the planted lane")
     ldn.close()
     assert (near[0] == lane).all() and (near[1] == trow).all(), "the near finish delivers other classes"
 for tb in tbs:
@@ -478,6 +519,8 @@ if a.equal:
         time_top(eq, 3, e_fin, "every read equal, three tiles")
     if a.gc:
         time_gc(eq, 3, e_fin, "every read equal, three tiles")
+    if a.consensus:
+        time_consensus(eq, 3, e_fin, "every read equal, three tiles")
     if a.quality:
         time_qualities(eq, 3, e_fin, e_qadd, e_add, "every read equal, one quality value, three tiles")
         # the same bases under random qualities 1..63: eight random planes take turns
@@ -497,6 +540,28 @@ if a.equal:
     eq.close()
     three.free()
 
+if a.consensus:
+    # three tiles without planted copies whose wells 3 j + 1 and 3 j + 2 repeat well 3 j, cycle by cycle: triples only
+    bare = synth.SynthSpec(seed=5, n_clusters=n, row=a.cols, plant_per_64k=0)
+    three = TileBatch(sc, 3, a.cycles, n)
+    for s in range(3):
+        sc.h2d(three.filter_ptr(s), np.ones(n, dtype=np.uint8))
+        for c in range(a.cycles):
+            sc.synth_plane(three.plane_ptr(s, c), bare, 1, 1101 + s, c)
+            sc.synchronize()
+            plane = sc.d2h(three.plane_ptr(s, c), n, np.uint8).copy()
+            first = plane[0::3]
+            plane[1::3] = first[:plane[1::3].size]
+            plane[2::3] = first[:plane[2::3].size]
+            sc.h2d(three.plane_ptr(s, c), plane)
+    sc.synchronize()
+    tr = LaneDups(sc, n, 3, a.cycles)
+    tr.add(three, [0, 1, 2])
+    _, tr_fin = clock(lambda: tr.finish())
+    time_consensus(tr, 3, tr_fin, "every well one of three equal wells, three tiles")
+    assert tr.consensus(0, a.max_family)[0][0] >= 3 * (n // 3), "the wells are not triples"
+    tr.close()
+    three.free()
 if a.mismatches:
     # tile 0: the planted tile 1101 with G at cycle `at` of every well; tiles 1 and 2: the same with T there
     at = a.cycles // 2

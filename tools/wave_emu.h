@@ -1,5 +1,5 @@
 // wave_emu.h - what a kernel's source needs to run on the CPU as it stands (tools/lane_mismatch_emu.cpp,
-// tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp, tools/lane_hops_emu.cpp, tools/lane_gc_emu.cpp,
+// tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp, tools/lane_hops_emu.cpp, tools/lane_gc_emu.cpp, tools/lane_consensus_emu.cpp,
 // tools/read_classes_emu.cpp, tools/near_emu.cpp, tools/dup_sets_emu.cpp): the 256 lanes of a
 // workgroup are fibers (ucontext) that a round-robin scheduler switches at the collectives - __syncthreads is a
 // rendezvous of the workgroup, __ballot and __shfl of a wave -, LDS is the kernel's static storage, an atomic add or
@@ -19,6 +19,8 @@
 // emulation is sequentially consistent: every fiber sees every store at once.  With -DWAVE_EMU_TORN_CAS the
 // compare-and-swap is broken on purpose - a scheduling point between its load and its store - for the emulators' tests
 // to show that they notice (=2: in the compare-and-swaps tagged kEmuUnion alone); nothing else builds that way.
+// -DWAVE_EMU_TORN_ADD breaks atomicAdd the same way, for an emulator whose kernels take their places by adds
+// (tools/lane_consensus_emu.cpp).
 // -DWAVE_EMU_UNIT_DEFS: the emulator includes csrc/read_classes.inc and csrc/tile_classes.inc (the head of the tiledups unit),
 // which define kTdBlock, kSpread, kFpCycles, kLdCmpWords, kInvalid, kMaxCycles, align256 and spread_row themselves:
 // this header then leaves them, and lane_pass.inc, out.  tools/dup_sets_emu.cpp defines it too: csrc/dup_sets.inc
@@ -116,7 +118,11 @@ static void emu_point() {
     emu_counts.points++;
     if (emu_policy == kEmuAlways || (emu_policy == kEmuThird && emu_next() % 3 == 0)) yield_();
 }
+#ifdef WAVE_EMU_TORN_ADD                           // (the deliberate bug of an add: another fiber may add between its load and its store)
+template <class T, class U> static T atomicAdd(T *p, U v) { emu_point(); T o = *p; emu_point(); *p = o + (T)v; return o; }
+#else
 template <class T, class U> static T atomicAdd(T *p, U v) { emu_point(); T o = *p; *p += (T)v; return o; }
+#endif
 template <class T> static T atomicCAS(T *p, T expect, T v) { emu_point(); T o = *p; if (o == expect) *p = v; return o; }
 template <class T, class U> static T atomicMin(T *p, U v) { emu_point(); T o = *p; if ((T)v < o) *p = (T)v; return o; }
 template <class T, class U> static T atomicOr(T *p, U v) { emu_point(); T o = *p; *p |= (T)v; return o; }

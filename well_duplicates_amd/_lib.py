@@ -226,6 +226,17 @@ LANEGC_HIST_COLS = 4
 LANEGC_LANE_COLS = 8
 LANEGC_TILE_COLS = 5
 
+# name -> (restype, argtypes); every symbol include/welldup_laneconsensus.h declares beyond those above
+LANECONSENSUS_PROTOTYPES = {
+    "wd_lane_consensus_scratch": (_i, [_i, _i64, _i, ctypes.POINTER(_sz)]),
+    "wd_lane_consensus": (_i, [_vp, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+}
+LANECONSENSUS_MAX_D = 7
+LANECONSENSUS_DIST_BINS = 9
+LANECONSENSUS_MAX_FAMILY = 4096
+LANECONSENSUS_LANE_COLS = 20
+LANECONSENSUS_TILE_COLS = 4
+
 _lib = None
 
 
@@ -312,7 +323,7 @@ def unit_of_kernel(kernel: str) -> str:
         return "ingest"
     if kernel.startswith("k_sets"):
         return "sets"
-    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_", "k_ls_", "k_lt_", "k_lh_", "k_lgc_")):
+    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_", "k_ls_", "k_lt_", "k_lh_", "k_lgc_", "k_lc_")):
         return "tiledups"
     return "scan"
 
@@ -376,7 +387,7 @@ def load():
             list(LANEINDEX_PROTOTYPES.items()) + list(LANEMISMATCH_PROTOTYPES.items()) + \
             list(LANEDISTANCE_PROTOTYPES.items()) + list(LANEQUALITY_PROTOTYPES.items()) + \
             list(LANESATURATION_PROTOTYPES.items()) + list(LANETOP_PROTOTYPES.items()) + \
-            list(LANEHOPS_PROTOTYPES.items()) + list(LANEGC_PROTOTYPES.items()):
+            list(LANEHOPS_PROTOTYPES.items()) + list(LANEGC_PROTOTYPES.items()) + list(LANECONSENSUS_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

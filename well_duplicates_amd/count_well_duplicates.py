@@ -25,7 +25,8 @@ Differences from the reference, all deliberate:
     --tile-dups-hamming, --tile-dups-pair-budget, --lane-dups, --lane-dups-out,
     --lane-dups-hamming, --lane-dups-index, --lane-dups-mismatches, --lane-dups-distance, --lane-dups-quality,
     --lane-dups-saturation, --lane-dups-top, --lane-dups-top-out, --lane-dups-hops, --lane-dups-hops-mismatches,
-    --lane-dups-hops-out, --lane-dups-gc, --lane-dups-gc-bins, --lane-dups-gc-max-n, --lane-dups-gc-out;
+    --lane-dups-hops-out, --lane-dups-gc, --lane-dups-gc-bins, --lane-dups-gc-max-n, --lane-dups-gc-out,
+    --lane-dups-consensus, --lane-dups-consensus-max-d, --lane-dups-consensus-max-family, --lane-dups-consensus-out;
   * --all-wells --dup-sets groups every tile's wells into duplicate sets and follows each lane's report
     with their counts and the exact duplication (report.write_dup_sets);
   * --all-wells --tile-dups groups every tile's PF wells into classes of equal reads, wherever on the tile they
@@ -57,6 +58,9 @@ Differences from the reference, all deliberate:
     --lane-dups-gc holds the duplication against the molecule: every PF read by its GC content and by what it is in
     its class or cluster - the distinct molecules, the duplication, the mean family size and the library size per GC
     bin, over every PF read and without an alignment (report.write_lane_gc);
+    --lane-dups-consensus lets every family of three or more wells vote: the base most of its members call at a cycle
+    is the molecule's, a member that disagrees made the error - the lane's error profile by cycle and by direction,
+    G>T apart from T>G, which the comparison with a first well cannot give (report.write_lane_consensus);
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
@@ -336,7 +340,40 @@ def parse_args(argv=None):
     p.add_argument("--lane-dups-gc-out", default=None, metavar="FILE",
                    help="with --lane-dups-gc: also write a line per g to FILE, tab-separated: lane, gc, single, roots, "
                         "copies, family_wells")
+    p.add_argument("--lane-dups-consensus", action="store_true",
+                   help="with --lane-dups: gather the wells of every class (every cluster with --lane-dups-hamming K) of "
+                        "three or more wells, take the base that more than half of them call at a cycle for the "
+                        "molecule's, and print, after every other block of the lane: the families that voted, the "
+                        "errors per called base and the quality that amounts to, the families whose first well "
+                        "disagrees with the vote, the distances of the wells from their family's consensus and the "
+                        "twelve substitutions molecule>call with each direction's rate and its ratio to the reverse "
+                        "direction - which --lane-dups-mismatches, comparing with a first well, cannot tell apart.  "
+                        "Without --lane-dups-hamming every copy is identical: no well disagrees, and only the families "
+                        "and the calls per consensus base are shown.  Takes 8 bytes of device memory per well of the lane")
+    p.add_argument("--lane-dups-consensus-max-d", type=int, default=None, metavar="D",
+                   help="with --lane-dups-consensus: a well further than D (0..%d) from its family's consensus is "
+                        "counted by its distance but kept out of the substitutions (default: the D of "
+                        "--lane-dups-mismatches, else K)" % _lib.LANECONSENSUS_MAX_D)
+    p.add_argument("--lane-dups-consensus-max-family", type=int, default=None, metavar="M",
+                   help="with --lane-dups-consensus: a family of more than M wells (3..%d, default 256) is a contaminant "
+                        "- poly-G, an adapter dimer: what --lane-dups-top names -, not a molecule: it is counted and "
+                        "left out of the vote" % _lib.LANECONSENSUS_MAX_FAMILY)
+    p.add_argument("--lane-dups-consensus-out", default=None, metavar="FILE",
+                   help="with --lane-dups-consensus: also write every cell of the call matrix that is not zero to FILE, "
+                        "tab-separated: lane, cycle, consensus, call, count")
     args = p.parse_args(argv)
+    if args.lane_dups_consensus and not args.lane_dups:
+        p.error("--lane-dups-consensus needs --lane-dups")
+    for flag, value in (("max-d", args.lane_dups_consensus_max_d), ("max-family", args.lane_dups_consensus_max_family),
+                        ("out", args.lane_dups_consensus_out)):
+        if value is not None and not args.lane_dups_consensus:
+            p.error("--lane-dups-consensus-%s needs --lane-dups-consensus" % flag)
+    if args.lane_dups_consensus_max_d is not None and not 0 <= args.lane_dups_consensus_max_d <= _lib.LANECONSENSUS_MAX_D:
+        p.error("--lane-dups-consensus-max-d takes 0..%d, not %d" % (_lib.LANECONSENSUS_MAX_D, args.lane_dups_consensus_max_d))
+    if args.lane_dups_consensus_max_family is not None and \
+            not 3 <= args.lane_dups_consensus_max_family <= _lib.LANECONSENSUS_MAX_FAMILY:
+        p.error("--lane-dups-consensus-max-family takes 3..%d, not %d" % (_lib.LANECONSENSUS_MAX_FAMILY,
+                                                                          args.lane_dups_consensus_max_family))
     if args.lane_dups_gc and not args.lane_dups:
         p.error("--lane-dups-gc needs --lane-dups")
     for flag, value in (("bins", args.lane_dups_gc_bins), ("max-n", args.lane_dups_gc_max_n), ("out", args.lane_dups_gc_out)):
@@ -579,16 +616,17 @@ def lane_cluster_members(class_labels: np.ndarray, cluster_labels: np.ndarray):
 
 def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0, index: int = 0,
                          mismatch: int = 0, distance: int = 0, quality: int = 0, saturation: int = 0, top: int = 0,
-                         hops: int = 0, gc: int = 0):
+                         hops: int = 0, gc: int = 0, consensus: int = 0):
     """--lane-dups: the accumulator's workspace - with --lane-dups-hamming plus the scratch of the near finish, with
     --lane-dups-index plus the index workspace, with --lane-dups-mismatches or --lane-dups-distance plus that pass's
     scratch, with --lane-dups-quality plus the quality workspace and that pass's scratch, with --lane-dups-saturation,
-    --lane-dups-top, --lane-dups-hops or --lane-dups-gc plus that pass's scratch - against the free device memory,
+    --lane-dups-top, --lane-dups-hops, --lane-dups-gc or --lane-dups-consensus plus that pass's scratch - against the
+    free device memory,
     before anything is loaded."""
-    need += scratch + index + mismatch + distance + quality + saturation + top + hops + gc
+    need += scratch + index + mismatch + distance + quality + saturation + top + hops + gc + consensus
     if need > free:
         raise MemoryError("--lane-dups needs %.2f GB of device memory for a lane of %d tiles x %d wells x %d cycles "
-                          "(%d bytes%s%s%s%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
+                          "(%d bytes%s%s%s%s%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
                               need / 1e9, tiles, wells, cycles, need,
                               ", %d of them for --lane-dups-hamming" % scratch if scratch else "",
                               ", %d of them for --lane-dups-index" % index if index else "",
@@ -599,6 +637,7 @@ def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: i
                               ", %d of them for --lane-dups-top" % top if top else "",
                               ", %d of them for --lane-dups-hops" % hops if hops else "",
                               ", %d of them for --lane-dups-gc" % gc if gc else "",
+                              ", %d of them for --lane-dups-consensus" % consensus if consensus else "",
                               free / 1e9, free))
 
 
@@ -612,7 +651,7 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
                dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0, lane_near=0, lane_pair_budget=0,
                lane_index=None, lane_mismatch=None, lane_distance=None, lane_quality=None, lane_saturation=None,
-               lane_top=0, lane_hops=None, lane_gc=None):
+               lane_top=0, lane_hops=None, lane_gc=None, lane_consensus=None):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
@@ -651,6 +690,9 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     LaneHopCounts, on the labels the lane was left with.
     lane_gc = (max_n, bins) (with lane_dups): after every other pass of the lane LaneDups.gc(max_n): into["lgc"][lane] =
     LaneGCCounts, on the labels the lane was left with.
+    lane_consensus = (D, max family) (with lane_dups): after every other pass of the lane LaneDups.consensus(D, max
+    family): into["lconsensus"][lane] = LaneConsensusCounts, on the labels the lane was left with, its cycles numbered by
+    cycle_list.
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -901,6 +943,10 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                     if lane_gc is not None:
                         into["lgc"][lane] = report.LaneGCCounts.from_rows(*ld.gc(lane_gc[0]), names, lane_gc[0], lane_gc[1],
                                                                           lane_near)
+                    if lane_consensus is not None:
+                        into["lconsensus"][lane] = report.LaneConsensusCounts.from_rows(
+                            *ld.consensus(*lane_consensus), names, lane_near, lane_consensus[0], lane_consensus[1],
+                            (into["lnear"][lane] if lane_near else into["ldups"][lane]).pf, cycle_list)
                     del lane_labels, got
                 _lap("batch %d: lane classes" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
@@ -1153,6 +1199,11 @@ def _main(args, log, wdist, rank, world, device, opener, early):
             gc_max_n = args.lane_dups_gc_max_n or 0
             if args.lane_dups_gc and gc_max_n > len(cycle_list):
                 raise ValueError("--lane-dups-gc-max-n takes 0..%d, the scanned cycles, not %d" % (len(cycle_list), gc_max_n))
+            consensus = None
+            if args.lane_dups_consensus:
+                consensus = (args.lane_dups_consensus_max_d if args.lane_dups_consensus_max_d is not None else
+                             mismatch_d if mismatch_d is not None else lane_near_k,
+                             args.lane_dups_consensus_max_family or 256)
             ntn = 5 + 2 * levels + len(report.CLASS_BIN_NAMES) if near_k else 0
             rows = np.zeros((len(mine), ncnt + nsets + ntd + ntn), dtype=np.int64)
             logs = {}
@@ -1203,6 +1254,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                     report.write_lane_hops(lane, results["lhops"][lane], verbose=not args.summary_only, out=out_fh)
                 if args.lane_dups_gc:
                     report.write_lane_gc(lane, results["lgc"][lane], verbose=not args.summary_only, out=out_fh)
+                if args.lane_dups_consensus:
+                    report.write_lane_consensus(lane, results["lconsensus"][lane], verbose=not args.summary_only,
+                                                out=out_fh)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
@@ -1211,7 +1265,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
                            "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}, "lnear": {}, "lindex": {},
                            "lmindex": {}, "lmismatch": {}, "ldistance": {}, "lquality": {}, "lsaturation": {}, "ltop": {},
-                           "lhops": {}, "lgc": {}}
+                           "lhops": {}, "lgc": {}, "lconsensus": {}}
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
@@ -1254,7 +1308,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                          hops=sc.lane_hops_scratch_bytes(len(tiles), _lib.LANEHOPS_MAX_LISTED)
                                          if args.lane_dups_hops is not None else 0,
                                          gc=sc.lane_gc_scratch_bytes(len(tiles), len(cycle_list))
-                                         if args.lane_dups_gc else 0)
+                                         if args.lane_dups_gc else 0,
+                                         consensus=sc.lane_consensus_scratch_bytes(len(tiles), n_targets, len(cycle_list))
+                                         if consensus is not None else 0)
                 if err is None:             # (a rank whose setup failed has nothing to scan: it goes to the flag)
                     scan_lanes(sc, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                                max(0, args.tile_batch), args.threads,
@@ -1276,7 +1332,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                lane_saturation=saturation, lane_top=args.lane_dups_top or 0,
                                lane_hops=(1 if args.lane_dups_hops_mismatches is None else args.lane_dups_hops_mismatches,
                                           args.lane_dups_hops) if args.lane_dups_hops is not None else None,
-                               lane_gc=(gc_max_n, args.lane_dups_gc_bins or 20) if args.lane_dups_gc else None)
+                               lane_gc=(gc_max_n, args.lane_dups_gc_bins or 20) if args.lane_dups_gc else None,
+                               lane_consensus=consensus)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
                     if args.tile_dups_out and near_k:
@@ -1295,6 +1352,10 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                         with open(args.lane_dups_gc_out, "w") as fh:
                             for i, lane in enumerate(sorted(results["lgc"], key=lanes.index)):
                                 report.write_lane_gc_tsv(lane, results["lgc"][lane], fh, header=i == 0)
+                    if args.lane_dups_consensus_out:
+                        with open(args.lane_dups_consensus_out, "w") as fh:
+                            for i, lane in enumerate(sorted(results["lconsensus"], key=lanes.index)):
+                                report.write_lane_consensus_tsv(lane, results["lconsensus"][lane], fh, header=i == 0)
                     if args.lane_dups_out:
                         write_lane_members(args.lane_dups_out, results["lmembers"],
                                            index=([e - s for s, e in index_ranges], results["lmindex"])

@@ -1572,3 +1572,142 @@ def write_lane_gc_tsv(lane, counts: LaneGCCounts, out, header: bool = True) -> N
         print("lane\tgc\tsingle\troots\tcopies\tfamily_wells", file=out)
     for g, row in enumerate(counts.hist):
         print("%s\t%i\t%i\t%i\t%i\t%i" % (lane, g, row[0], row[1], row[2], row[3]), file=out)
+
+
+# ---- --lane-dups-consensus: a lane's errors against its families' vote (include/welldup_laneconsensus.h) ----
+LANE_CONSENSUS_MAX_D = 7
+LANE_CONSENSUS_MIN_FAMILY, LANE_CONSENSUS_MAX_FAMILY = 3, 4096
+LANE_CONSENSUS_DIST_NAMES = LANE_MISMATCH_DIST_NAMES
+LANE_CONSENSUS_LANE_COLS = 11 + len(LANE_CONSENSUS_DIST_NAMES)
+LANE_CONSENSUS_TILE_COLS = 4
+
+
+@dataclass
+class LaneConsensusCounts:
+    """A lane's errors against its families' vote (include/welldup_laneconsensus.h, LaneDups.consensus): the lane
+    row's columns, per tile (by the tile's name) [Wells, Profiled, Mismatches, WithN], calls[c][a][b] - consensus a,
+    own code b - over the wells with d <= max_d of the families of 3 .. max_family wells, the number of every scanned
+    cycle as --cycles counts them, and the lane's PF wells."""
+    k: int = 0
+    max_d: int = 0
+    max_family: int = 256
+    pf: int = 0
+    families: int = 0
+    wells: int = 0
+    profiled: int = 0
+    mismatches: int = 0
+    with_n: int = 0
+    undecided: int = 0
+    undecided_calls: int = 0
+    first_off: int = 0
+    pairs: int = 0
+    large: int = 0
+    large_wells: int = 0
+    dist: List[int] = field(default_factory=lambda: [0] * len(LANE_CONSENSUS_DIST_NAMES))
+    tiles: Dict[str, List[int]] = field(default_factory=dict)
+    calls: List = field(default_factory=list)
+    cycles: List[int] = field(default_factory=list)
+
+    @classmethod
+    def from_rows(cls, lane_row: Sequence[int], tile_rows: Sequence[Sequence[int]], calls, tile_names: Sequence, k: int,
+                  max_d: int, max_family: int, pf: int, cycles: Optional[Sequence[int]] = None) -> "LaneConsensusCounts":
+        """The three results of LaneDups.consensus(max_d, max_family); tile_names as LaneDupCounts.from_rows takes
+        them; pf: the lane's PF wells (the finish's lane row); cycles: the scanned cycles' numbers (default 0, 1, ..)."""
+        b = [int(v) for v in lane_row]
+        assert len(b) == LANE_CONSENSUS_LANE_COLS and 0 <= max_d <= LANE_CONSENSUS_MAX_D
+        assert LANE_CONSENSUS_MIN_FAMILY <= max_family <= LANE_CONSENSUS_MAX_FAMILY
+        tiles = {}
+        for name, row in zip(tile_names, tile_rows):
+            assert len(row) == LANE_CONSENSUS_TILE_COLS
+            if name is not None:
+                tiles[name] = [int(v) for v in row]
+        calls = [[[int(v) for v in row] for row in cell] for cell in calls]
+        assert all(len(cell) == 5 and all(len(row) == 5 for row in cell) for cell in calls)
+        cycles = list(range(len(calls))) if cycles is None else [int(c) for c in cycles]
+        assert len(cycles) == len(calls)
+        return cls(int(k), int(max_d), int(max_family), int(pf), *b[:11], b[11:], tiles, calls, cycles)
+
+    def called(self) -> int:
+        """Every call that was compared: the sum of calls."""
+        return sum(sum(map(sum, cell)) for cell in self.calls)
+
+    def error_rate(self) -> Optional[float]:
+        """Mismatches per called base; None without a call."""
+        n = self.called()
+        return self.mismatches / n if n else None
+
+    def count(self, a: int, b: int) -> int:
+        """The calls of b where the consensus is a, over the cycles."""
+        return sum(cell[a][b] for cell in self.calls)
+
+    def rate(self, a: int, b: int) -> Optional[float]:
+        """P(call b | molecule a) over the cycles; None where no consensus is a."""
+        n = sum(sum(cell[a]) for cell in self.calls)
+        return self.count(a, b) / n if n else None
+
+    def per_cycle(self):
+        """-> [(calls, errors, the most frequent substitution as (count, a, b) or None)] per scanned cycle; of equally
+        frequent substitutions the first in the order of the codes"""
+        rows = []
+        for cell in self.calls:
+            off = [(cell[a][b], -a, -b) for a in range(5) for b in range(5) if a != b and cell[a][b]]
+            top = max(off) if off else None
+            rows.append((sum(map(sum, cell)), sum(e[0] for e in off), None if top is None else (top[0], -top[1], -top[2])))
+        return rows
+
+
+def write_lane_consensus(lane, counts: LaneConsensusCounts, verbose: bool = False, out=None) -> None:
+    """The block that follows every other block of a lane under --lane-dups-consensus: per-tile and per-cycle lines
+    (verbose; tiles in sorted order as write_report, cycles numbered as --cycles: the calls compared, the errors
+    among them, their rate and the most frequent substitution), then the summary: the families that voted and their
+    wells, the errors per called base and the quality that amounts to, the (family, cycle) pairs without a majority,
+    the families whose first well disagrees with the vote - what wd_lane_mismatches counts once per copy and in the
+    wrong direction -, the distances of the wells from their family's consensus, and the twelve substitutions
+    molecule>call with each direction's rate and its ratio to the reverse direction."""
+    out = out or sys.stdout
+    c = counts
+    share = lambda v, of: v / of if of else 0.0
+    sci = lambda v: "n/a" if v is None else "%.3e" % v
+    name = lambda a, b: "%s>%s" % (CODE_NAMES[a], CODE_NAMES[b])
+    print(file=out)
+    if verbose:
+        for tile in sorted(c.tiles):
+            t = c.tiles[tile]
+            print("LaneConsensus: %s\tTile: %s\tWells: %i\tProfiled: %i\tMismatches: %i\tWithN: %i" % (
+                lane, tile, t[0], t[1], t[2], t[3]), file=out)
+        for cycle, (n, errors, top) in zip(c.cycles, c.per_cycle()):
+            print("LaneConsensus: %s\tCycle: %i\tCalls: %i\tErrors: %i\tRate: %s\tMost frequent: %s" % (
+                lane, cycle, n, errors, sci(errors / n if n else None),
+                "-" if top is None else "%s (%i)" % (name(top[1], top[2]), top[0])), file=out)
+    rate = c.error_rate()
+    print("LaneConsensusSummary: %s\tTiles: %i\tHamming: %i\tMaxD: %i\tMaxFamily: %i\tFamilies: %i\tWells: %i (%.5f of PF)\t"
+          "Profiled: %i (%.5f)\tMismatches: %i\tWithN: %i\tErrors per called base: %s (Q %s)\tUndecided: %i\t"
+          "FirstWellOff: %i (%.5f of Families)\tPairs left out: %i\tLarge left out: %i (%i wells)" % (
+              lane, len(c.tiles), c.k, c.max_d, c.max_family, c.families, c.wells, share(c.wells, c.pf), c.profiled,
+              share(c.profiled, c.wells), c.mismatches, c.with_n, sci(rate), phred(rate), c.undecided, c.first_off,
+              share(c.first_off, c.families), c.pairs, c.large, c.large_wells), file=out)
+    print("ConsensusDist: %s" % "\t".join("%s: %i (%.5f)" % (n, v, share(v, c.wells))
+                                          for n, v in zip(LANE_CONSENSUS_DIST_NAMES, c.dist)), file=out)
+    for a in range(4):
+        for b in range(4):
+            if a == b:
+                continue
+            fwd, rev = c.rate(a, b), c.rate(b, a)
+            ratio = "n/a" if fwd is None or rev is None or (fwd == 0 and rev == 0) else "inf" if rev == 0 else "%.3f" % (fwd / rev)
+            print("Consensus: %s\t%i (%.5f of Mismatches)\tRate: %s\tReverse %s: %i\tRatio: %s" % (
+                name(a, b), c.count(a, b), share(c.count(a, b), c.mismatches), sci(fwd), name(b, a), c.count(b, a), ratio),
+                  file=out)
+    to_n, from_n = sum(c.count(a, 4) for a in range(4)), sum(c.count(4, b) for b in range(4))
+    print("Consensus: N\tmolecule>N: %i\tN>call: %i\t(%.5f of Mismatches)" % (to_n, from_n, share(to_n + from_n, c.mismatches)),
+          file=out)
+
+
+def write_lane_consensus_tsv(lane, counts: LaneConsensusCounts, out, header: bool = True) -> None:
+    """--lane-dups-consensus-out: a line per cell of calls that is not zero - lane, cycle, consensus, call, count."""
+    if header:
+        print("lane\tcycle\tconsensus\tcall\tcount", file=out)
+    for cycle, cell in zip(counts.cycles, counts.calls):
+        for a in range(5):
+            for b in range(5):
+                if cell[a][b]:
+                    print("%s\t%i\t%s\t%s\t%i" % (lane, cycle, CODE_NAMES[a], CODE_NAMES[b], cell[a][b]), file=out)

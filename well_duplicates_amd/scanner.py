@@ -330,6 +330,12 @@ class Scanner:
         tile and the histogram per g; it does not depend on the wells of a tile)."""
         return self._workspace_bytes(self._lib.wd_lane_gc_scratch, max_tiles, L)
 
+    def lane_consensus_scratch_bytes(self, max_tiles: int, n_clusters: int, L: int) -> int:
+        """Device bytes LaneDups.consensus needs beside the accumulator's workspace (wd_lane_consensus_scratch: 8 bytes
+        per well of the lane - where a family's members begin, and the member list with the family table - and the
+        counters)."""
+        return self._workspace_bytes(self._lib.wd_lane_consensus_scratch, max_tiles, n_clusters, L)
+
     def lane_hops_scratch_bytes(self, max_tiles: int, M: int) -> int:
         """Device bytes LaneDups.hops needs beside the accumulator's workspaces for M listed keys
         (wd_lane_hops_scratch: the counters, the listing and the (M + 1)^2 cells of the matrix; it does not depend on
@@ -851,6 +857,29 @@ class LaneDups:
                                self._h, int(max_n), d_scratch, sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
                                tile_rows.ctypes.data_as(ctypes.c_void_p), hist.ctypes.data_as(ctypes.c_void_p)))
         return lane_row, tile_rows, hist
+
+    def consensus(self, max_d: int = 0, max_family: int = 256):
+        """After finish(), any number of times, before or after every other pass (wd_lane_consensus,
+        include/welldup_laneconsensus.h): the members of every family of 3 .. max_family wells under the labels the
+        finish left are gathered, the code that more than half of them call at a cycle is the family's consensus there,
+        and every member's calls are counted against it.
+        -> (lane row int64 [20]: [Families, Wells, Profiled, Mismatches, WithN, Undecided, UndecidedCalls, FirstWellOff,
+        PairFamilies, LargeFamilies, LargeWells, Dist d = 0..7 and >= 8], tile rows int64 [max_tiles, 4]: [Wells,
+        Profiled, Mismatches, WithN] by the well's own tile, calls int64 [L, 5, 5]: [cycle][consensus][own code] over
+        the wells with d <= max_d at the cycles their family decides).  The scratch is allocated for the call and
+        released.  max_d outside 0..7, max_family outside 3..4096 or a call before a successful finish raises
+        ValueError."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        lane_row = np.zeros(_lib.LANECONSENSUS_LANE_COLS, dtype=np.int64)
+        tile_rows = np.zeros((self.max_tiles, _lib.LANECONSENSUS_TILE_COLS), dtype=np.int64)
+        calls = np.zeros((self.L, 5, 5), dtype=np.int64)
+        self._with_scratch(self.sc.lane_consensus_scratch_bytes(self.max_tiles, self.N, self.L),
+                           lambda d_scratch, sbytes: self.sc._lib.wd_lane_consensus(
+                               self._h, int(max_d), int(max_family), d_scratch, sbytes,
+                               lane_row.ctypes.data_as(ctypes.c_void_p), tile_rows.ctypes.data_as(ctypes.c_void_p),
+                               calls.ctypes.data_as(ctypes.c_void_p)))
+        return lane_row, tile_rows, calls
 
     def hops(self, split: int, max_e: int, keys):
         """After finish() of a lane with an index part, any number of times, before or after index_finish and every
