@@ -1,10 +1,12 @@
 """What tests/contention_inputs.py promises of its reads, checked on the host with the references the GPU tests use:
 the families give hundreds of unions on a dozen roots and classes of many wells, the chains are chains - one cycle
-from step to step, one cluster at K = 1 - and descend where they are said to."""
+from step to step, one cluster at K = 1 - and descend where they are said to; the probe edge has the groups it says, at
+representatives that share an entry."""
 import numpy as np
 import pytest
 
-from contention_inputs import CENTRES, chain, families, filters, line_rings, split
+from contention_inputs import CENTRES, LANE_RUN, LI_PROBE, chain, families, filters, li_home, line_rings, probe_edge_index, split
+from laneindex_ref import index_keys
 from tiledups_ref import INVALID, codes_of
 from tilenear_ref import distinct_reads, edges_all_pairs, tile_near_dups
 
@@ -73,3 +75,24 @@ def test_split_and_rings():
     assert centre.tolist() == [0, 1, 2, 3, 4] and lvl_off.shape == (5, 3)
     assert nbr[lvl_off[2, 0]:lvl_off[2, 1]].tolist() == [1, 3] and nbr[lvl_off[2, 1]:lvl_off[2, 2]].tolist() == [0, 4]
     assert nbr[lvl_off[0, 0]:lvl_off[0, 2]].tolist() == [1, 2]
+
+
+@pytest.mark.parametrize("I", [8, 20])
+@pytest.mark.parametrize("extra", [0, 1, 4])
+def test_probe_edge_groups_share_an_entry(I, extra):
+    n, groups = 9000, LI_PROBE + extra
+    tiles, filts, reps, slot = probe_edge_index(300 + extra, n, I, groups)
+    assert len(tiles) == 2 and all(t.shape == (n, I) for t in tiles) and all(f.shape == (n,) for f in filts)
+    assert reps.size == groups and (np.diff(reps) > 0).all() and reps[-1] < LANE_RUN
+    assert (li_home(reps) == slot).all() and 0 <= slot < 512
+    keys, _ = index_keys([(t, [np.ascontiguousarray(x[:, c]) for c in range(I)]) for t, x in enumerate(tiles)], n, 2)
+    pf = (np.concatenate(filts) & 1).astype(bool)
+    assert not pf[:reps[0]].any() and pf[reps].all() and 0.85 * 2 * n < pf.sum() < 2 * n - reps[0]
+    ukeys, first = np.unique(keys[pf], return_index=True)
+    # exactly these groups, each with its representative where it was put, and wells enough behind each on both tiles
+    assert ukeys.size == groups and sorted(np.flatnonzero(pf)[first].tolist()) == reps.tolist()
+    for t in range(2):
+        here = keys[t * n:(t + 1) * n][pf[t * n:(t + 1) * n]]
+        assert np.unique(here).size == groups and np.unique(here, return_counts=True)[1].min() >= 100
+    assert I <= 10 or (np.unique(keys >> np.uint64(32)).size > 1 and np.unique(keys & np.uint64(0xFFFFFFFF)).size > 1)
+    assert (np.concatenate(filts) >> 1).any()                          # (only bit 0 counts)

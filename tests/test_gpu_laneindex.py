@@ -13,6 +13,7 @@ from contextlib import redirect_stdout
 import numpy as np
 import pytest
 
+from contention_inputs import LI_PROBE, li_home, probe_edge_index
 from laneindex_ref import check_index_identities, index_keys, key_of, lane_index
 from lanedups_ref import lane_dups
 from lanenear_ref import lane_near_dups
@@ -334,6 +335,64 @@ def test_more_groups_than_the_lds_table_holds(sc):
                                  finishes=((2, 0), (1, tiles * n)))
         _same(res, want)
         assert res1[0][1] == pf and (res1[2][:, 0] == 1).all() and np.unique(res1[3]).size == pf
+    finally:
+        tb.free()
+        itb.free()
+
+
+def _copied_reads(seed, n, cycles, tiles=2, copies=1500):
+    """random reads, `copies` of them copied to other wells of the lane: classes of two and a few larger ones"""
+    rng = np.random.default_rng(seed)
+    reads = rng.integers(1, 256, (tiles * n, cycles)).astype(np.uint8)
+    reads[rng.integers(0, tiles * n, copies)] = reads[rng.integers(0, tiles * n, copies)]
+    return [reads[t * n:(t + 1) * n] for t in range(tiles)]
+
+
+@pytest.mark.parametrize("I", [8, 20])
+def test_groups_that_share_a_home_entry_of_the_lds_table(sc, I):
+    """As many groups as a probe path of k_li_tally's table is long, one more and four more, their representatives all
+    beginning at one entry (tests/contention_inputs.py; tests/test_laneindex_emu.py holds its copy of the home entry
+    against the kernel's): the last group that comes finds the path's last entry, or none and adds to memory."""
+    n = 9000
+    reads = _copied_reads(50 + I, n, 12)
+    tb = _upload(sc, reads)                                            # (the filters come with each lane of index reads)
+    try:
+        for extra in (0, 1, 4):
+            idx, filts, reps, slot = probe_edge_index(300 + extra, n, I, LI_PROBE + extra)
+            assert (li_home(reps) == slot).all() and reps.size == LI_PROBE + extra
+            for s in range(2):
+                sc.h2d(tb.filter_ptr(s), filts[s])
+            itb = _upload(sc, idx)
+            try:
+                eq_lane, labels, itiles, want = _reference(tb, itb, [0, 1], 2)
+                check_index_identities(want, eq_lane)
+                assert want[0][0] == want[0][1] == LI_PROBE + extra and want[0][3] > 500 and (want[2][:, 0] > 500).all()
+                got, (res,) = _feed(sc, tb, itb, [0, 1], 2, [("add", [0, 1]), ("index", [0, 1])])
+                assert (got[0] == eq_lane).all() and (got[2] == labels).all()
+                _same(res, want)
+            finally:
+                itb.free()
+    finally:
+        tb.free()
+
+
+@pytest.mark.parametrize("n", [8192, 8193])
+def test_a_run_of_one_group_and_one_class_fills_the_fields(sc, n):
+    """One index read, every well PF, every read equal: a workgroup of k_li_tally adds a whole run of 8192 wells into
+    each 16-bit field of one entry.  After the equality finish and after the near finish at K = 1."""
+    equal = [np.tile(np.array([0x42 + (c % 4) for c in range(12)], dtype=np.uint8), (n, 1)) for _ in range(2)]
+    one = [np.tile(np.array([0x41 + 4 * (c % 5) for c in range(8)], dtype=np.uint8), (n, 1)) for _ in range(2)]
+    tb, itb = _upload(sc, equal), _upload(sc, one)
+    try:
+        total = 2 * n
+        for k in (0, 1):
+            lane_row, labels, _, want = _reference(tb, itb, [0, 1], 2, hamming=k)
+            assert (labels == 0).all()
+            assert want[0].tolist() == [1, 1, 1, 0, 0] and not want[1].any() and want[3].tolist() == [key_of("C" * 8)]
+            assert want[2].tolist() == [[total, total, total, total - 1, 0]]
+            got, (res,) = _feed(sc, tb, itb, [0, 1], 2, [("add", [0, 1]), ("index", [0, 1])], hamming=k)
+            assert (got[5 if k else 2] == labels).all()
+            _same(res, want)
     finally:
         tb.free()
         itb.free()

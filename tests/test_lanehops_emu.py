@@ -2,19 +2,21 @@
 plays the 256 lanes of a workgroup with fibers that meet at every __syncthreads, __ballot and __shfl, so the two
 wave-grouped adds, the binary search of the listing, the LDS table of matrix cells, its overflow into memory and its
 flush are checked against the header's definitions here, without a GPU (the GPU tests compare the kernel itself with
-tests/lanehops_ref.py: tests/test_gpu_lanehops.py)."""
+tests/lanehops_ref.py: tests/test_gpu_lanehops.py).  Every trial runs under the eleven schedules of tools/emu_reads.h - a
+lane may hand over at every atomic -, so the claims of the LDS table (a plain atomicCAS) meet on free entries; those
+that lose are counted, and a second build with that claim torn on purpose (-DWAVE_EMU_TORN_CAS=3) must end in MISMATCH."""
 import os
 import re
 import subprocess
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BUILD = ["g++", "-O1", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=undefined", "-std=c++17",
+         "-I" + os.path.join(REPO, "include"), os.path.join(REPO, "tools", "lane_hops_emu.cpp")]
 
 
 def test_emulated_kernel_gives_the_definitions_counts(tmp_path):
     exe = str(tmp_path / "lane_hops_emu")
-    subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=undefined", "-std=c++17",
-                           "-I" + os.path.join(REPO, "include"), os.path.join(REPO, "tools", "lane_hops_emu.cpp"),
-                           "-o", exe])
+    subprocess.check_call(BUILD + ["-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "MISMATCH" not in out.stdout, (out.stdout, out.stderr)
     ok = re.findall(r"trial (\d+) ok: I (\d+) split (\d+) E (\d+) N (\d+) M (\d+) mode (\d+) pairs (\d+) cells (\d+) slots (\d+)",
@@ -35,3 +37,18 @@ def test_emulated_kernel_gives_the_definitions_counts(tmp_path):
     assert all(r["cells"] == 1 for r in trials if r["mode"] in (1, 2))
     assert any(r["cells"] > 4 * slots for r in trials if r["mode"] == 3)
     assert any(r["N"] == 9000 and r["mode"] == 1 for r in trials)
+    # the eleven schedules: the one that never hands over loses nothing; the pooled trials and those with many cells
+    # lose claims of the LDS table, summed over the schedules at 1/3
+    sched = re.findall(r"trial (\d+) ok: .* mode (\d+) .* schedules (\d+) points (\d+) never_lost (\d+) lost_lds (\d+)$", out.stdout, re.M)
+    sched = [dict(zip(("trial", "mode", "schedules", "points", "never_lost", "lost_lds"), (int(v) for v in row))) for row in sched]
+    assert [r["trial"] for r in sched] == list(range(12)) and [r["mode"] for r in sched] == [r["mode"] for r in trials]
+    assert all(r["schedules"] == 11 and r["never_lost"] == 0 and r["points"] > 0 for r in sched)
+    assert all(r["lost_lds"] >= 1 for r in sched if r["mode"] in (0, 3))
+    assert sum(r["mode"] == 0 for r in sched) >= 5 and sum(r["mode"] == 3 for r in sched) == 2
+
+
+def test_a_torn_claim_of_the_lds_table_is_noticed(tmp_path):
+    exe = str(tmp_path / "lane_hops_emu_torn")
+    subprocess.check_call(BUILD + ["-DWAVE_EMU_TORN_CAS=3", "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 1 and "MISMATCH" in out.stdout, (out.returncode, out.stdout[-2000:], out.stderr[-2000:])

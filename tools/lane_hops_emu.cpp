@@ -4,13 +4,17 @@
 // key, a lane whose keys are all unlisted and a lane with more distinct (root, copy) cells in a run than the LDS table
 // has entries; tiles of less than a run and of a run and a bit; index reads of 8, 16 and 20 cycles split inside the
 // first word, at the word boundary, inside the second word and not at all; every max_e and M = 0, 3 and 1024: the
-// counters and the matrix are compared with the definitions of include/welldup_lanehops.h computed directly.  Prints
-// MISMATCH and exits 1 on a difference.  tests/test_lanehops_emu.py builds and runs it; no GPU is involved, and
-// nothing here says anything about time.
+// counters and the matrix are compared with the definitions of include/welldup_lanehops.h computed directly.  Every
+// trial runs under the eleven schedules of emu_reads.h - a lane may hand over at every atomic: never, lanes in reverse,
+// always, with probability 1/3 under eight seeds; workgroups permuted in all but the first - and each must give the
+// definitions: the claims of the LDS table (a plain atomicCAS) then meet on free entries, and those that lose are
+// counted (lost_lds, over the schedules at 1/3).  Prints MISMATCH and exits 1 on a difference.
+// tests/test_lanehops_emu.py builds and runs it, and once more with -DWAVE_EMU_TORN_CAS=3 (the LDS claim torn), which
+// must end in MISMATCH; no GPU is involved, and nothing here says anything about time.
 //
 //   g++ -O1 -g -std=c++17 -fsanitize=undefined -Iinclude tools/lane_hops_emu.cpp -o lane_hops_emu
 #include "wave_emu.h"
-#include <map>
+#include "emu_reads.h"
 #include <set>
 #define WD_LANE_MISMATCH_EMU                        // lm_fold is lane_mismatch.inc's
 #include "../well_duplicates_amd/csrc/lane_mismatch.inc"
@@ -88,7 +92,6 @@ int main() {
         const size_t cells = (size_t)(M + 1) * (M + 1);
         std::vector<unsigned long long> cnt_t((size_t)T * kSpread * kLhTileCnt, 0), cnt_l(kSpread * kLhLaneCnt, 0), matrix(cells, 0);
         A = Args{tiles, N, label.data(), key.data(), lh_mask(0, split), lh_mask(split, I), E, M, s_keys.data(), s_rank.data(), cnt_t.data(), cnt_l.data(), matrix.data()};
-        for (unsigned by = 0; by < 2; by++) for (unsigned bx = 0; bx < (unsigned)((N + kLaneRun - 1) / kLaneRun); bx++) run_block(bx, by, entry);
         // the definitions, directly
         std::vector<long long> wt((size_t)T * 4, 0), wst(9, 0), wm(cells, 0); size_t most_cells = 0;
         for (int ti : tiles) { std::set<size_t> in_run;
@@ -104,16 +107,26 @@ int main() {
                 size_t cell = (size_t)(a == rank_of.end() ? M : a->second) * (M + 1) + (b == rank_of.end() ? M : b->second);
                 wm[cell]++; in_run.insert(cell); most_cells = std::max(most_cells, in_run.size());
             } }
-        long long pairs = 0;
-        for (int tt = 0; tt < T; tt++) for (int f = 0; f < 4; f++) { unsigned long long s = 0; for (int r = 0; r < kSpread; r++) s += cnt_t[((size_t)tt * kSpread + r) * 4 + f];
-            if ((long long)s != wt[tt * 4 + f]) { printf("MISMATCH trial %d tile %d col %d: %llu want %lld\n", trial, tt, f, s, wt[tt * 4 + f]); return 1; } if (f == 0) pairs += s; }
-        for (int b = 0; b < 9; b++) { unsigned long long s = 0; for (int r = 0; r < kSpread; r++) s += cnt_l[r * kLhLaneCnt + b];
-            if ((long long)s != wst[b]) { printf("MISMATCH trial %d state %d: %llu want %lld\n", trial, b, s, wst[b]); return 1; } }
-        for (size_t e = 0; e < cells; e++) if ((long long)matrix[e] != wm[e]) { printf("MISMATCH trial %d cell %zu: %llu want %lld\n", trial, e, matrix[e], wm[e]); return 1; }
-        if (mode == 1 && (wm[0] != pairs || wst[0] != pairs)) { printf("MISMATCH trial %d: one key, but %lld of %lld pairs in cell 0\n", trial, wm[0], pairs); return 1; }
-        if (mode == 2 && wm[cells - 1] != pairs) { printf("MISMATCH trial %d: unlisted keys, but %lld of %lld pairs in Other\n", trial, wm[cells - 1], pairs); return 1; }
+        long long pairs = 0, points = 0, never_lost = 0, lost_lds = 0;
+        for (int sch = 0; sch < kSchedules; sch++) {
+            const bool permute = set_schedule(sch, 1000u * trial + 17);      // (the seed: one under which every trial loses a claim at 1/3)
+            std::fill(cnt_t.begin(), cnt_t.end(), 0ull); std::fill(cnt_l.begin(), cnt_l.end(), 0ull); std::fill(matrix.begin(), matrix.end(), 0ull);      // the host's memset of the scratch
+            run_grid((unsigned)((N + kLaneRun - 1) / kLaneRun), 2, entry, permute);
+            points += emu_counts.points;
+            if (sch == 0) never_lost = emu_counts.lost[kEmuTable] + emu_counts.lost[kEmuUnion] + emu_counts.lost[kEmuLds];
+            if (sch >= 3) lost_lds += emu_counts.lost[kEmuLds];
+            pairs = 0;
+            for (int tt = 0; tt < T; tt++) for (int f = 0; f < 4; f++) { unsigned long long s = 0; for (int r = 0; r < kSpread; r++) s += cnt_t[((size_t)tt * kSpread + r) * 4 + f];
+                if ((long long)s != wt[tt * 4 + f]) { printf("MISMATCH trial %d tile %d col %d: %llu want %lld\n", trial, tt, f, s, wt[tt * 4 + f]); printf("  (schedule %d %s)\n", sch, schedule_name(sch)); return 1; } if (f == 0) pairs += s; }
+            for (int b = 0; b < 9; b++) { unsigned long long s = 0; for (int r = 0; r < kSpread; r++) s += cnt_l[r * kLhLaneCnt + b];
+                if ((long long)s != wst[b]) { printf("MISMATCH trial %d state %d: %llu want %lld\n", trial, b, s, wst[b]); printf("  (schedule %d %s)\n", sch, schedule_name(sch)); return 1; } }
+            for (size_t e = 0; e < cells; e++) if ((long long)matrix[e] != wm[e]) { printf("MISMATCH trial %d cell %zu: %llu want %lld\n", trial, e, matrix[e], wm[e]); printf("  (schedule %d %s)\n", sch, schedule_name(sch)); return 1; }
+            if (mode == 1 && (wm[0] != pairs || wst[0] != pairs)) { printf("MISMATCH trial %d: one key, but %lld of %lld pairs in cell 0\n", trial, wm[0], pairs); printf("  (schedule %d %s)\n", sch, schedule_name(sch)); return 1; }
+            if (mode == 2 && wm[cells - 1] != pairs) { printf("MISMATCH trial %d: unlisted keys, but %lld of %lld pairs in Other\n", trial, wm[cells - 1], pairs); printf("  (schedule %d %s)\n", sch, schedule_name(sch)); return 1; }
+        }
         printf("trial %d ok: I %d split %d E %d N %ld M %d mode %d pairs %lld cells %zu slots %d state", trial, I, split, E, (long)N, M, mode, pairs, most_cells, kLhSlots);
-        for (int b = 0; b < 9; b++) printf(" %lld", wst[b]); printf("\n");
+        for (int b = 0; b < 9; b++) printf(" %lld", wst[b]);
+        printf(" schedules %d points %lld never_lost %lld lost_lds %lld\n", kSchedules, points, never_lost, lost_lds);
     }
     return 0;
 }

@@ -1,6 +1,6 @@
 // wave_emu.h - what a kernel's source needs to run on the CPU as it stands (tools/lane_mismatch_emu.cpp,
 // tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp, tools/lane_hops_emu.cpp, tools/lane_gc_emu.cpp, tools/lane_consensus_emu.cpp,
-// tools/read_classes_emu.cpp, tools/near_emu.cpp, tools/dup_sets_emu.cpp): the 256 lanes of a
+// tools/read_classes_emu.cpp, tools/near_emu.cpp, tools/dup_sets_emu.cpp, tools/lane_index_emu.cpp): the 256 lanes of a
 // workgroup are fibers (ucontext) that a round-robin scheduler switches at the collectives - __syncthreads is a
 // rendezvous of the workgroup, __ballot and __shfl of a wave -, LDS is the kernel's static storage, an atomic add or
 // minimum or a compare-and-swap is a plain one (one fiber runs at a time), and the qualifiers are empty.  Include it, then the kernel's
@@ -15,10 +15,17 @@
 // starts the fibers of a workgroup from lane 255 down; run_grid runs the workgroups of a launch one after the other
 // (a workgroup still runs to its end before the next begins), in a seeded permutation of (x, y) if asked.  emu_counts
 // holds the scheduling points passed and the compare-and-swaps that lost - found another value than expected - since
-// emu_counts_clear() (run_grid returns those of its launch), the latter by emu_cas_tag, which the emulator sets before a launch (kEmuTable, kEmuUnion).  The
+// emu_counts_clear() (run_grid returns those of its launch), the latter by emu_cas_tag, which the emulator sets before a launch (kEmuTable, kEmuUnion).
+// The plain atomicCAS counts under kEmuLds, whatever the tag: the kernels use it on their tables in LDS alone
+// (k_li_tally, k_lh_tally), and there without a load before it - a lane that meets an entry another key took long ago
+// finds "another value" too, under every schedule.  So it counts as lost when the word held `expect` as the lane
+// arrived at the scheduling point and no longer did after it: another lane took the free entry in between, which is
+// what a lost claim is, and what the schedule that never hands over cannot produce.  The
 // emulation is sequentially consistent: every fiber sees every store at once.  With -DWAVE_EMU_TORN_CAS the
 // compare-and-swap is broken on purpose - a scheduling point between its load and its store - for the emulators' tests
-// to show that they notice (=2: in the compare-and-swaps tagged kEmuUnion alone); nothing else builds that way.
+// to show that they notice (without a value: in the __hip_atomic compare-and-swaps, whatever their tag; =2: in those
+// tagged kEmuUnion alone; =3: in the plain atomicCAS alone, so that each build of an emulator that has both kinds
+// shows one of them); nothing else builds that way.
 // -DWAVE_EMU_TORN_ADD breaks atomicAdd the same way, for an emulator whose kernels take their places by adds
 // (tools/lane_consensus_emu.cpp).
 // -DWAVE_EMU_UNIT_DEFS: the emulator includes csrc/read_classes.inc and csrc/tile_classes.inc (the head of the tiledups unit),
@@ -106,14 +113,14 @@ static int __shfl(int v, int src) {
 #define __ffs __builtin_ffs
 // ---- the schedule: what happens at a scheduling point
 enum EmuPolicy { kEmuNever, kEmuThird, kEmuAlways };
-enum { kEmuTable = 0, kEmuUnion = 1 };
-struct EmuCounts { long points, lost[2]; };
+enum { kEmuTable = 0, kEmuUnion = 1, kEmuLds = 2 };
+struct EmuCounts { long points, lost[3]; };
 static EmuCounts emu_counts;
 static int emu_cas_tag = kEmuTable;
 static EmuPolicy emu_policy = kEmuNever; static bool emu_reverse = false; static uint64_t emu_rng = 1;
 static uint64_t emu_next() { emu_rng ^= emu_rng << 13; emu_rng ^= emu_rng >> 7; emu_rng ^= emu_rng << 17; return emu_rng; }      // (xorshift64: the inputs keep rand())
 static void emu_schedule(EmuPolicy policy, bool reverse, uint64_t seed) { emu_policy = policy; emu_reverse = reverse; emu_rng = seed * 0x9E3779B97F4A7C15ull | 1; }
-static void emu_counts_clear() { emu_counts = EmuCounts{0, {0, 0}}; }
+static void emu_counts_clear() { emu_counts = EmuCounts{0, {0, 0, 0}}; }
 static void emu_point() {
     emu_counts.points++;
     if (emu_policy == kEmuAlways || (emu_policy == kEmuThird && emu_next() % 3 == 0)) yield_();
@@ -123,7 +130,17 @@ template <class T, class U> static T atomicAdd(T *p, U v) { emu_point(); T o = *
 #else
 template <class T, class U> static T atomicAdd(T *p, U v) { emu_point(); T o = *p; *p += (T)v; return o; }
 #endif
-template <class T> static T atomicCAS(T *p, T expect, T v) { emu_point(); T o = *p; if (o == expect) *p = v; return o; }
+template <class T> static T atomicCAS(T *p, T expect, T v) {
+    const bool was_free = *p == expect;
+    emu_point();
+    const T o = *p;
+    if (o != expect) { emu_counts.lost[kEmuLds] += was_free; return o; }
+#ifdef WAVE_EMU_TORN_CAS
+    if (WAVE_EMU_TORN_CAS == 3) emu_point();       // (the deliberate bug, as below)
+#endif
+    *p = v;
+    return o;
+}
 template <class T, class U> static T atomicMin(T *p, U v) { emu_point(); T o = *p; if ((T)v < o) *p = (T)v; return o; }
 template <class T, class U> static T atomicOr(T *p, U v) { emu_point(); T o = *p; *p |= (T)v; return o; }
 // the clang builtins of the kernels that say their memory order and scope: the order and the scope mean nothing here
@@ -135,7 +152,7 @@ template <class T, class U> static bool __hip_atomic_compare_exchange_strong(T *
     const T o = *p;
     if (o != *expect) { emu_counts.lost[emu_cas_tag]++; *expect = o; return false; }
 #ifdef WAVE_EMU_TORN_CAS
-    if (WAVE_EMU_TORN_CAS != 2 || emu_cas_tag == kEmuUnion) emu_point();      // (the deliberate bug: another fiber may store between the load and the store)
+    if (WAVE_EMU_TORN_CAS == 1 || (WAVE_EMU_TORN_CAS == 2 && emu_cas_tag == kEmuUnion)) emu_point();      // (the deliberate bug: another fiber may store between the load and the store)
 #endif
     *p = (T)v;
     return true;
@@ -200,7 +217,7 @@ static EmuCounts run_grid(unsigned gx, unsigned gy, void (*kernel)(), bool permu
     for (size_t i = 0; i < order.size(); i++) order[i] = (unsigned)i;
     if (permute) for (size_t i = order.size(); i > 1; i--) std::swap(order[i - 1], order[emu_next() % i]);
     for (unsigned b : order) { run_block(b % gx, b / gx, kernel); if (emu_after_block) emu_after_block(b % gx, b / gx); }
-    return EmuCounts{emu_counts.points - before.points, {emu_counts.lost[0] - before.lost[0], emu_counts.lost[1] - before.lost[1]}};
+    return EmuCounts{emu_counts.points - before.points, {emu_counts.lost[0] - before.lost[0], emu_counts.lost[1] - before.lost[1], emu_counts.lost[2] - before.lost[2]}};
 }
 #ifndef WAVE_EMU_UNIT_DEFS
 #define WD_LANE_PASS_EMU

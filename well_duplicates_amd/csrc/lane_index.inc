@@ -211,6 +211,9 @@ constexpr int kLiProbe = 8;
 static_assert(kLaneRun < 65536, "a 16-bit field must hold a run's wells");
 static_assert((kLiSlots & (kLiSlots - 1)) == 0, "the LDS table is a power of two");
 
+// the entry of the LDS table at which the probes of group gl begin
+__device__ inline uint32_t li_home(uint32_t gl) { return (gl * 0x9E3779B1u) >> 23 & (kLiSlots - 1); }
+
 __device__ inline void li_add_row(uint32_t *row, uint32_t pf, unsigned long long cls)
 {
     if (pf)
@@ -288,7 +291,7 @@ __global__ void __launch_bounds__(kTdBlock) k_li_tally(const int *__restrict__ t
             }
         }
         if (add_pf) {
-            uint32_t e = (gl * 0x9E3779B1u) >> 23 & (kLiSlots - 1);
+            uint32_t e = li_home(gl);
             int p = 0;
             for (; p < kLiProbe; p++, e = (e + 1) & (kLiSlots - 1)) {
                 const uint32_t old = atomicCAS(&s_key[e], kInvalid, gl);
@@ -377,6 +380,7 @@ __global__ void __launch_bounds__(kTdBlock) k_li_rows(const uint32_t *__restrict
 
 }  // namespace
 
+#ifndef WD_LANE_INDEX_EMU                          // (tools/lane_index_emu.cpp: the kernels above on the CPU, a fiber per lane)
 // the index part of an accumulator: the host side (the device side is the caller's index workspace)
 struct wd_lane_index {
     int I;
@@ -622,3 +626,4 @@ try {
 } WD_CATCH
 
 }  // extern "C"
+#endif
