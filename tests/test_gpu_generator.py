@@ -1,10 +1,13 @@
 """Device neighbour-index generator (wd_targets_from_coords) against the numpy generator,
 which tests/test_synth_and_generator.py pins to the reference's prepare_cluster_indexes.py
-output (sha256) - sampled centres and the all-centres mode."""
+output (sha256) - sampled centres and the all-centres mode -, and against a plain reference at the
+edges no honeycomb reaches (tests/genrings_cases.py, which tests/test_genrings_emu.py also runs through
+the kernel's source on the CPU): the window, exact ring radii, the capacity, refused calls."""
 
 import numpy as np
 import pytest
 
+import genrings_cases as gc
 from helpers import fixture_targets
 from well_duplicates_amd import cluster_indexes, synth, workload
 from well_duplicates_amd.scanner import Scanner
@@ -47,8 +50,58 @@ def test_all_centres_equal_numpy_generator(sc, rows, cols, levels):
         assert (a == b).all()
 
 
+def _call(sc, case):
+    return sc.targets_from_coords(case.x, case.y, case.centres, levels=case.levels, max_dists=case.max_dists)
+
+
+def _assert_targets(sc, want):
+    got = sc.get_targets()
+    for a, b, what in zip(got, want, ("centre", "lvl_off", "nbr")):
+        assert a.dtype == b.dtype and a.shape == b.shape and (a == b).all(), what
+
+
+@pytest.mark.parametrize("name", gc.NAMES)
+def test_edge_cases_equal_plain_reference(sc, name):
+    """The window's ends and clamps, wells at exactly a ring's radius (off the axes too, and at the ABI's largest),
+    2048 matches and 2049, rings whose indices interleave, several centres, tables of one and two wells, a jittered
+    honeycomb (tests/genrings_cases.py): the device CSR is the plain reference's, or the call is refused."""
+    case = gc.case(name)
+    if case.error:
+        with pytest.raises(RuntimeError):
+            _call(sc, case)
+        return
+    T, P = _call(sc, case)
+    assert (T, P) == (case.want[0].shape[0], case.want[2].shape[0])
+    _assert_targets(sc, case.want)
+
+
+def test_a_refused_call_leaves_the_installed_targets_and_a_clean_status(sc):
+    """Both refusals - more than 2048 matches (fill pass) and an empty ring (count pass) - leave the targets of the
+    call before them installed, and the status word clear for the next valid call."""
+    first, full = gc.case("order"), gc.case("capacity_2048")
+    _call(sc, first)
+    _assert_targets(sc, first.want)
+    for refused in ("capacity_2049", "window_last_ring_empty"):
+        with pytest.raises(RuntimeError):
+            _call(sc, gc.case(refused))
+        _assert_targets(sc, first.want)
+    T, P = _call(sc, full)                                  # one match below the refusal, right after one
+    assert (T, P) == (1, gc.CAPACITY)
+    _assert_targets(sc, full.want)
+    with pytest.raises(RuntimeError):
+        _call(sc, gc.case("one_well"))
+    _assert_targets(sc, full.want)
+    T, P = _call(sc, gc.case("boundaries"))
+    _assert_targets(sc, gc.case("boundaries").want)
+
+
 def test_window_limit_and_errors(sc):
-    # wells further than 20000 records away are never neighbours, however close in pixels
+    # the window on the device: of five wells 10 px from the centre at records c - 20001, c - 20000, c + 1,
+    # c + 20001 and c + 20002, the three in the middle are its neighbours
+    w = gc.case("window")
+    assert _call(sc, w) == (1, 3)
+    assert sc.get_targets()[2].tolist() == [2, gc.WINDOW + 3, 2 * gc.WINDOW + 3]
+    # everything within 40 px of everything: every centre's window holds far more than 2048 wells inside the outer ring
     n = 50000
     x = np.full(n, 1000, np.int32)
     y = (1000 + (np.arange(n) % 5) * 10).astype(np.int32)      # everything within 40 px of everything

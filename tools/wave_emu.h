@@ -1,6 +1,6 @@
 // wave_emu.h - what a kernel's source needs to run on the CPU as it stands (tools/lane_mismatch_emu.cpp,
 // tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp, tools/lane_hops_emu.cpp, tools/lane_gc_emu.cpp, tools/lane_consensus_emu.cpp,
-// tools/read_classes_emu.cpp, tools/near_emu.cpp, tools/dup_sets_emu.cpp, tools/lane_index_emu.cpp): the 256 lanes of a
+// tools/read_classes_emu.cpp, tools/near_emu.cpp, tools/dup_sets_emu.cpp, tools/lane_index_emu.cpp, tools/gen_rings_emu.cpp): the 256 lanes of a
 // workgroup are fibers (ucontext) that a round-robin scheduler switches at the collectives - __syncthreads is a
 // rendezvous of the workgroup, __ballot and __shfl of a wave -, LDS is the kernel's static storage, an atomic add or
 // minimum or a compare-and-swap is a plain one (one fiber runs at a time), and the qualifiers are empty.  Include it, then the kernel's
@@ -27,7 +27,8 @@
 // tagged kEmuUnion alone; =3: in the plain atomicCAS alone, so that each build of an emulator that has both kinds
 // shows one of them); nothing else builds that way.
 // -DWAVE_EMU_TORN_ADD breaks atomicAdd the same way, for an emulator whose kernels take their places by adds
-// (tools/lane_consensus_emu.cpp).
+// (tools/lane_consensus_emu.cpp; tools/gen_rings_emu.cpp, which clears emu_torn_add for its count pass so that the
+// fill pass's claim of an LDS slot alone is broken).
 // -DWAVE_EMU_UNIT_DEFS: the emulator includes csrc/read_classes.inc and csrc/tile_classes.inc (the head of the tiledups unit),
 // which define kTdBlock, kSpread, kFpCycles, kLdCmpWords, kInvalid, kMaxCycles, align256 and spread_row themselves:
 // this header then leaves them, and lane_pass.inc, out.  tools/dup_sets_emu.cpp defines it too: csrc/dup_sets.inc
@@ -125,10 +126,14 @@ static void emu_point() {
     emu_counts.points++;
     if (emu_policy == kEmuAlways || (emu_policy == kEmuThird && emu_next() % 3 == 0)) yield_();
 }
+// emu_add_hook, if set, sees every atomicAdd as it takes effect - the word, what it held, the lane (emu_lane): an
+// emulator that wants to know in which order the lanes took their places (tools/gen_rings_emu.cpp).
+static void (*emu_add_hook)(const void *p, long long old) = nullptr;
 #ifdef WAVE_EMU_TORN_ADD                           // (the deliberate bug of an add: another fiber may add between its load and its store)
-template <class T, class U> static T atomicAdd(T *p, U v) { emu_point(); T o = *p; emu_point(); *p = o + (T)v; return o; }
+static bool emu_torn_add = true;                   // (an emulator may confine the bug to some of its launches)
+template <class T, class U> static T atomicAdd(T *p, U v) { emu_point(); T o = *p; if (emu_torn_add) emu_point(); *p = o + (T)v; if (emu_add_hook) emu_add_hook(p, (long long)o); return o; }
 #else
-template <class T, class U> static T atomicAdd(T *p, U v) { emu_point(); T o = *p; *p += (T)v; return o; }
+template <class T, class U> static T atomicAdd(T *p, U v) { emu_point(); T o = *p; *p += (T)v; if (emu_add_hook) emu_add_hook(p, (long long)o); return o; }
 #endif
 template <class T> static T atomicCAS(T *p, T expect, T v) {
     const bool was_free = *p == expect;
