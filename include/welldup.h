@@ -112,7 +112,7 @@ int wd_synchronize(wd_ctx *ctx);
  * frees nothing - no unpinning of the ingest ring, no stream destruction, 25 ms less per run).
  * Read-only (wd_get_option; -1 before the first dense scan of the current targets):
  * "dense_uniform_groups" (64-target groups of consecutive centres that share their neighbour
- * offsets), "dense_window_groups" (those scanned through signature windows in LDS),
+ * offsets), "dense_window_groups" (those scanned through signature windows in LDS: 0 while "dense_windows" is 0),
  * "dense_window_dwords" (LDS dwords per wave of the largest window), "dense_sym_on" (1: the tables
  * built last are those of the one-ended compare), "line_walk_blocks" (workgroups per tile of the line
  * walk's tables: -1 not built, 0 = the walk does not apply to these targets), "lane_top_passes" (histogram passes

@@ -247,8 +247,11 @@ def test_fuzz_window_groups(seed):
                     blocks, pt = tb.count(mode, k, per_target=True)
                     assert sc.get_option("dense_sym_on") == (1 if is_sym and opts["dense_sym"] else 0), (seed, opts, is_sym)
                     # clean input (with ring flips a union of (ring, offset) pairs may outgrow the 128
-                    # elements a window group holds): the path under test is the one that ran
-                    if p_mess == 0.0 and p_flip == 0.0 and T >= 128:
+                    # elements a window group holds): the path under test is the one that ran - and with the
+                    # windows switched off, none of them
+                    if not opts["dense_windows"]:
+                        assert sc.get_option("dense_window_groups") == 0, (seed, opts)
+                    elif p_mess == 0.0 and p_flip == 0.0 and T >= 128:
                         assert sc.get_option("dense_window_groups") >= (T // 64) // 2, sc.get_option("dense_window_groups")
                     for i in range(n_tiles):
                         got = pt[i].astype(np.int64)

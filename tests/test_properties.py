@@ -73,8 +73,8 @@ def test_report_equals_reference_restatement(lane_dupl, verbose, levels):
 
 def _lev2_equal_length(a: str, b: str) -> int:
     """The closed form the dense path uses for Levenshtein <= 2 on equal-length reads
-    (csrc/scan_dense.inc: lev2_window / lev2_words), restated on strings: the distance if it is
-    <= 2, else 3."""
+    (csrc/dense_forms.inc: lev2_window and its kin), restated on strings: the distance if it is
+    <= 2, else 3.  (The forms themselves, compiled from the source: tests/test_dense_forms.py.)"""
     mism = [i for i in range(len(a)) if a[i] != b[i]]
     if len(mism) <= 2:
         return len(mism)

@@ -2,7 +2,7 @@
 //
 // The reference's production default is `-e 2` with the Levenshtein metric
 // (count_well_duplicates.py:200, :252, :258, :282-283).  For reads of equal length, distance <= 2
-// is one of two things (scan_dense.inc: lev2_window; tests/test_properties.py checks it against the
+// is one of two things (dense_forms.inc: lev2_window; tests/test_properties.py checks it against the
 // textbook DP): at most two substitutions, or one deletion plus one insertion with exact matches
 // everywhere else - the reads agree before the first mismatching cycle p and after the last one t,
 // and in between one is the other shifted by one cycle:

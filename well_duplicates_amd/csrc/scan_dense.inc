@@ -25,7 +25,7 @@
 //                   counters (each mask transition is applied once, so the histograms come out
 //                   exact whatever the order);
 //   k_dense_reduce  folds the per-tile counter slots into out_tile.
-// Levenshtein <= 2 (the reference's default) rides the same kernels: see lev2_window below.
+// Levenshtein <= 2 (the reference's default) rides the same kernels: see lev2_window (dense_forms.inc).
 // Since round 2 most groups of 64 consecutive centres compare from LDS windows (k_dense_windows,
 // k_dense_pairs_win); since round 3, where the neighbour relation is symmetric (every well a centre:
 // k_dense_symcheck), every pair is compared once, from its lower well, and recorded at both ends
@@ -36,7 +36,6 @@
 // branch-free survivor test, the register-rotated software pipeline, and nothing but loads and
 // LDS traffic inside its loop.
 // (kDenseChainVersion, kSigCycles, kRowGroups, kDenseMaxK: wd_shared.h - the dispatch needs them too)
-constexpr uint32_t kSigLow = 0x09249249u;                   // bit 0 of each 3-bit field
 constexpr int kDenseSlots = 64;       // counter slots per tile (power of two): same-line atomics serialise
 constexpr int kMaxSeg = 16;           // window groups: runs of consecutive signatures staged in LDS per wave
 constexpr int kWinMaxK = 128;         // ... for groups whose targets have at most this many different neighbour offsets
@@ -128,28 +127,10 @@ struct TilePlanes {
     __device__ inline gbytes at(int j) const { return STRIDED ? base + (int64_t)j * stride : as_global(tbl[j]); }
 };
 
-// Four wells at a time: the base codes of the 4 bytes of a dword, each in its own byte lane
-// (0..3 = byte & 3, 4 = the byte was 0, a no-call).
-__device__ inline uint32_t codes4(uint32_t v)
-{
-    const uint32_t zero = ~(((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v) & 0x80808080u;     // bit 7 where byte == 0
-    return (v & 0x03030303u) | (zero >> 5);
-}
-
-// Ten cycles of wells i .. i+3, one dword per plane (4 wells) -> one 30-bit word per well.
-// Cycles are first paired inside the byte lanes (6 bits per lane), so the per-well unpacking
-// happens 5 times instead of 10.
-__device__ inline void fold10x4(const uint32_t (&v)[10], uint32_t (&out)[4])
-{
-    out[0] = out[1] = out[2] = out[3] = 0;
-#pragma unroll
-    for (int m = 0; m < 5; m++) {
-        const uint32_t pr = codes4(v[2 * m]) | (codes4(v[2 * m + 1]) << 3);
-#pragma unroll
-        for (int b = 0; b < 4; b++)
-            out[b] |= ((pr >> (8 * b)) & 0x3Fu) << (6 * m);
-    }
-}
+// The pure forms - codes4, fold10x4, sig_mismatches, lev2_window, transpose4x4, the readers of a packed row,
+// row_lev2, lev2_screen, lev2_window16, screen_mismatches, lev2_masks - and kSigLow, kScreenCycles, kRowCycles,
+// kRowDw: a file of their own, which tools/dense_forms_check.cpp compiles for the CPU.
+#include "dense_forms.inc"
 
 // Ten cycles (planes j0 .. j0+9, all present) of wells i .. i+3 -> one 30-bit word per well.
 // NT: non-temporal loads, for kernels that stream the planes once.
@@ -167,8 +148,6 @@ __device__ inline void pack10x4(const TilePlanes<STRIDED> &pl, int j0, long long
                   : *(const __attribute__((address_space(1))) uint32_t *)(p[f] + i);
     fold10x4(v, out);
 }
-
-constexpr int kScreenCycles = 16;      // Levenshtein screen word: cycles 0..15, 2 bits each
 
 // Sixteen cycles (planes 0..15, all present) of wells i .. i+3 -> the signature word (cycles 0..9,
 // exact) and the screen word per well: byte & 3 per cycle, so a no-call (byte 0) reads as A - fine
@@ -265,71 +244,6 @@ __global__ __launch_bounds__(kBlock) void k_dense_sig(DenseArgs a)
             out2[w] = sgn;
         }
     }
-}
-
-// mismatching cycles among those folded into two signatures
-__device__ inline int sig_mismatches(uint32_t x, uint32_t y)
-{
-    const uint32_t d = x ^ y;
-    return __popc((d | (d >> 1) | (d >> 2)) & kSigLow);
-}
-
-// Levenshtein distance <= 2 between strings of EQUAL length is one of two things: at most two
-// substitutions, or one deletion plus one insertion with exact matches everywhere else - the
-// strings agree up to the first mismatch p and after the last mismatch t, and in between one is
-// the other shifted by one position (b[i] == a[i+1] on [p, t), or b[i] == a[i-1] on (p, t]).
-// On a prefix the same test is a necessary condition.  (tests/test_properties.py checks this
-// characterisation against the textbook DP.)  Returns the distance if it is <= 2, else 3.
-// a, b: up to 10 cycles, 3 bits each (unused high fields equal in both).
-__device__ inline int lev2_window(uint32_t a, uint32_t b)
-{
-    const uint32_t x = a ^ b;
-    const uint32_t m0 = (x | (x >> 1) | (x >> 2)) & kSigLow;
-    const int h = __popc(m0);
-    if (h <= 2)
-        return h;
-    const int pb = __ffs((int)m0) - 1;                               // 3 * first mismatching field
-    const int tb = 31 - __clz((int)m0);                              // 3 * last mismatching field
-    const uint32_t rng = ((1u << tb) - (1u << pb)) & kSigLow;        // fields [p, t)
-    const uint32_t xp = (a >> 3) ^ b;                                // b[i] against a[i+1]
-    if ((((xp | (xp >> 1) | (xp >> 2)) & kSigLow) & rng) == 0)
-        return 2;
-    const uint32_t xm = (a << 3) ^ b;                                // b[i] against a[i-1]
-    if ((((xm | (xm >> 1) | (xm >> 2)) & kSigLow) & (rng << 3)) == 0)
-        return 2;
-    return 3;
-}
-
-// The same over whole reads held as `words` 30-bit words of 10 cycles (a: centre, b: neighbour).
-__device__ inline int lev2_words(const uint32_t *a, const uint32_t *b, int words)
-{
-    int h = 0, first = -1, last = -1;                               // positions in bits: 30 * word + 3 * field
-    for (int w = 0; w < words; w++) {
-        const uint32_t x = a[w] ^ b[w];
-        const uint32_t m0 = (x | (x >> 1) | (x >> 2)) & kSigLow;
-        if (m0) {
-            h += __popc(m0);
-            if (first < 0)
-                first = 30 * w + __ffs((int)m0) - 1;
-            last = 30 * w + 31 - __clz((int)m0);
-        }
-    }
-    if (h <= 2)
-        return h;
-    bool up = true, down = true;                                     // b == a shifted by +1 / -1 in between
-    for (int w = 0; w < words; w++) {
-        // this word's share of the bit ranges [first, last) and [first + 3, last + 3)
-        const int lo = min(max(first - 30 * w, 0), 30), hi = min(max(last - 30 * w, 0), 30);
-        const int lo2 = min(max(first + 3 - 30 * w, 0), 30), hi2 = min(max(last + 3 - 30 * w, 0), 30);
-        const uint32_t rng = ((1u << hi) - (1u << lo)) & kSigLow;
-        const uint32_t rng2 = ((1u << hi2) - (1u << lo2)) & kSigLow;
-        const uint32_t a_next = w + 1 < words ? a[w + 1] : 0u, a_prev = w ? a[w - 1] : 0u;
-        const uint32_t xp = ((a[w] >> 3) | ((a_next & 7u) << 27)) ^ b[w];
-        const uint32_t xm = (((a[w] << 3) & 0x3FFFFFFFu) | (a_prev >> 27)) ^ b[w];
-        up = up && ((((xp | (xp >> 1) | (xp >> 2)) & kSigLow) & rng) == 0);
-        down = down && ((((xm | (xm >> 1) | (xm >> 2)) & kSigLow) & rng2) == 0);
-    }
-    return (up || down) ? 2 : 3;
 }
 
 // Was (will) this batch be packed?  Every wave of k_dense_pack and k_dense_verify asks the same
@@ -445,20 +359,6 @@ __global__ __launch_bounds__(1024) void k_dense_rank_blocks(DenseArgs a)
 // are two instructions per cycle ((v & 0x03030303) << 2f, or-ed), the no-call bits five (exact non-zero
 // test per byte, rotated into a byte of flags), and a 4 x 4 byte transpose (8 v_perm) per 16 cycles
 // hands every well its own dwords: about 8 instructions per dword loaded.
-constexpr int kRowCycles = 160;                       // cycles a row holds
-constexpr int kRowDw = 16;                            // dwords per row (15 used)
-
-__device__ inline void transpose4x4(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3, uint32_t (&r)[4])
-{
-    // r[b] = {a0.byte b, a1.byte b, a2.byte b, a3.byte b}
-    const uint32_t p0 = __builtin_amdgcn_perm(a1, a0, 0x05010400u), p1 = __builtin_amdgcn_perm(a1, a0, 0x07030602u);
-    const uint32_t q0 = __builtin_amdgcn_perm(a3, a2, 0x05010400u), q1 = __builtin_amdgcn_perm(a3, a2, 0x07030602u);
-    r[0] = __builtin_amdgcn_perm(q0, p0, 0x05040100u);
-    r[1] = __builtin_amdgcn_perm(q0, p0, 0x07060302u);
-    r[2] = __builtin_amdgcn_perm(q1, p1, 0x05040100u);
-    r[3] = __builtin_amdgcn_perm(q1, p1, 0x07060302u);
-}
-
 // The grid may hold fewer workgroups than the tile has blocks of kBlock * VEC wells (gridDim.x of them
 // per tile): each then walks the tile with a stride - a bounded footprint, so that the compare stage of
 // the next part finds wave slots beside it (launch_dense).
@@ -557,76 +457,6 @@ __global__ __launch_bounds__(kBlock) void k_dense_pack(DenseArgs a)
                 }
         }
     }
-}
-
-// ---- readers of a packed row (k_dense_verify) ----
-// bit r of a 16-bit value -> bit 2r
-__device__ inline uint32_t spread16(uint32_t x)
-{
-    x = (x | (x << 8)) & 0x00FF00FFu;
-    x = (x | (x << 4)) & 0x0F0F0F0Fu;
-    x = (x | (x << 2)) & 0x33333333u;
-    return (x | (x << 1)) & 0x55555555u;
-}
-
-// mismatching cycles among cycles kSigCycles .. L-1 of two rows (no-call = a fifth symbol)
-__device__ inline int row_mismatches(const uint32_t *ra, const uint32_t *rb, int L)
-{
-    int mm = 0;
-    // (unrolled with the bound as a predicate: as a loop over a run-time count the rows are indexed through
-    // s_set_gpr_idx and copied into place first)
-#pragma unroll
-    for (int k = 0; k < kRowCycles / 32; k++) {
-        const uint32_t xl = ra[3 * k] ^ rb[3 * k], xh = ra[3 * k + 1] ^ rb[3 * k + 1], nd = ra[3 * k + 2] ^ rb[3 * k + 2];
-        const int m = __popc(((xl | (xl >> 1)) & 0x55555555u) | spread16(nd & 0xFFFFu)) +
-                      __popc(((xh | (xh >> 1)) & 0x55555555u) | spread16(nd >> 16));
-        mm += kSigCycles + 32 * k < L ? m : 0;
-    }
-    return mm;
-}
-
-// eight cycles (chunk c of group k) of a row as the 4-bit codes of lev2_stream.inc
-__device__ inline uint32_t row_codes8(const uint32_t *r, int k, int c)
-{
-    uint32_t x = (r[3 * k + (c >> 1)] >> (16 * (c & 1))) & 0xFFFFu;          // bases: two bits per cycle
-    x = (x | (x << 8)) & 0x00FF00FFu;
-    x = (x | (x << 4)) & 0x0F0F0F0Fu;
-    x = (x | (x << 2)) & 0x33333333u;                                         // ... in the low half of every nibble
-    uint32_t y = (r[3 * k + 2] >> (8 * c)) & 0xFFu;                           // not a no-call: one bit per cycle
-    y = (y | (y << 12)) & 0x000F000Fu;
-    y = (y | (y << 6)) & 0x03030303u;
-    y = (y | (y << 3)) & 0x11111111u;                                         // ... in bit 0 of every nibble
-    return x | (y << 2);
-}
-
-// the first cycles of a read as the exact signature word holds them (3 bits each, no-call = 4) -> those codes
-__device__ inline uint32_t sig_codes(uint32_t sig, int first, int n)
-{
-    uint32_t w = 0;
-    for (int f = 0; f < n; f++) {
-        const uint32_t sgn = (sig >> (3 * (first + f))) & 7u;
-        w |= (sgn < 4u ? (4u | sgn) : 0u) << (4 * f);
-    }
-    return w;
-}
-
-// Levenshtein distance of two whole reads if it is <= 2, else 3: the signature words for the first
-// kSigCycles cycles, the rows for the rest, through the streaming closed form (lev2_stream.inc)
-__device__ inline int row_lev2(uint32_t sig_a, uint32_t sig_b, const uint32_t *ra, const uint32_t *rb, int L)
-{
-    uint32_t st = lev2_init();
-    const int n0 = min(L, kSigCycles);
-    st = lev2_step(st, sig_codes(sig_a, 0, min(n0, 8)), sig_codes(sig_b, 0, min(n0, 8)), min(n0, 8));
-    if (n0 > 8)
-        st = lev2_step(st, sig_codes(sig_a, 8, n0 - 8), sig_codes(sig_b, 8, n0 - 8), n0 - 8);
-    for (int k = 0; k < kRowCycles / 32 && lev2_alive(st); k++)
-        for (int c = 0; c < 4; c++) {
-            const int n = min(8, L - (kSigCycles + 32 * k + 8 * c));
-            if (n <= 0)
-                break;
-            st = lev2_step(st, row_codes8(ra, k, c), row_codes8(rb, k, c), n);
-        }
-    return lev2_alive(st) ? lev2_dist(st) : 3;
 }
 
 // Neighbour lists regrouped for the lane-per-target kernel: for each group of 64 consecutive
@@ -1094,58 +924,6 @@ __device__ inline void wait_vmcnt(int n)
 __device__ inline void lds_dma_dword(const void *base, uint32_t voff, uint32_t lds)
 {
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" : : "s"(lds), "v"(voff), "s"(base) : "memory");
-}
-
-// The Levenshtein <= 2 screen of the compare stage, on screen words (16 cycles, 2 bits each; ah =
-// a >> 2, al = a << 2), without branches.  Equal-length reads within distance 2 differ by at most
-// two substitutions, or one is the other shifted by one cycle between the first mismatch p and
-// the last one t (lev2_window) - then a cycle that mismatches both in place and against the
-// shifted copy can only be t (b[i] = a[i+1] on [p, t)) or p (b[i] = a[i-1] on (p, t]).  Returns
-// <= 1 if the pair may be within distance 2 on these cycles, which is necessary for being within
-// distance 2 on the whole read.  Random reads pass with probability ~1e-4, so the survivors are
-// the duplicates; k_dense_verify decides them exactly.  (tests/test_properties.py checks the screen
-// against the textbook distance.)
-__device__ inline uint32_t lev2_screen(uint32_t a, uint32_t ah, uint32_t al, uint32_t b)
-{
-    const uint32_t x0 = a ^ b, xp = ah ^ b, xm = al ^ b;
-    uint32_t m0 = (x0 | (x0 >> 1)) & 0x55555555u;
-    // (opaque: otherwise the compiler distributes the two ANDs below over the ORs and spends six
-    // three-input logic instructions per pair instead of three)
-    asm volatile("" : "+v"(m0));
-    const uint32_t up = (xp | (xp >> 1)) & m0;
-    const uint32_t dn = (xm | (xm >> 1)) & m0;
-    // popc(m0) - 1 <= 1 for one or two mismatches; identical words have up = dn = 0
-    return min(min((uint32_t)__popc(m0) - 1u, (uint32_t)__popc(up)), (uint32_t)__popc(dn));
-}
-
-// lev2_window on screen words (up to 16 cycles, 2 bits each): the exact distance of the two
-// 16-cycle prefixes as the screen sees them (a no-call reads as A) if it is <= 2, else 3 - what
-// lev2_screen only bounds.  k_dense_mark runs it on the screen's survivors.
-__device__ inline int lev2_window16(uint32_t a, uint32_t b)
-{
-    const uint32_t x = a ^ b;
-    const uint32_t m0 = (x | (x >> 1)) & 0x55555555u;
-    const int h = __popc(m0);
-    if (h <= 2)
-        return h;
-    const int pb = __ffs((int)m0) - 1;                               // 2 * first mismatching field
-    const int tb = 31 - __clz((int)m0);                              // 2 * last mismatching field
-    const uint32_t rng = ((1u << tb) - (1u << pb)) & 0x55555555u;    // fields [p, t)
-    const uint32_t xp = (a >> 2) ^ b;                                // b[i] against a[i+1]
-    if ((((xp | (xp >> 1)) & 0x55555555u) & rng) == 0)
-        return 2;
-    const uint32_t xm = (a << 2) ^ b;                                // b[i] against a[i-1]
-    if ((((xm | (xm >> 1)) & 0x55555555u) & (rng << 2)) == 0)
-        return 2;
-    return 3;
-}
-
-// mismatching cycles among the (up to 16) folded into two screen words: a lower bound of the
-// reads' Hamming distance (a no-call reads as A)
-__device__ inline uint32_t screen_mismatches(uint32_t x, uint32_t y)
-{
-    const uint32_t d = x ^ y;
-    return (uint32_t)__popc((d | (d >> 1)) & 0x55555555u);
 }
 
 // sum over the wave's lanes (wave-uniform result): an inclusive scan inside each row of 16 lanes
@@ -2037,21 +1815,7 @@ __device__ inline int lev2_gather(const TilePlanes<STRIDED> &pl, int L, uint32_t
             mm[ch] = __ballot(in && a_prev != b0);          // b[j] against a[j-1]
         }
     }
-    const int h = __popcll(m0[0]) + __popcll(m0[1]) + __popcll(m0[2]);
-    if (h <= 2)
-        return h;
-    const int first = m0[0] ? __builtin_ctzll(m0[0]) : m0[1] ? 64 + __builtin_ctzll(m0[1]) : 128 + __builtin_ctzll(m0[2]);
-    const int last = m0[2] ? 191 - __builtin_clzll(m0[2]) : m0[1] ? 127 - __builtin_clzll(m0[1]) : 63 - __builtin_clzll(m0[0]);
-    bool up = true, down = true;
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        auto below = [](int n) -> uint64_t { return n >= 64 ? ~0ull : n <= 0 ? 0ull : ((1ull << n) - 1); };
-        const uint64_t rng = below(last - 64 * ch) & ~below(first - 64 * ch);              // [first, last)
-        const uint64_t rng2 = below(last + 1 - 64 * ch) & ~below(first + 1 - 64 * ch);     // (first, last]
-        up = up && (mp[ch] & rng) == 0;
-        down = down && (mm[ch] & rng2) == 0;
-    }
-    return (up || down) ? 2 : 3;
+    return lev2_masks(m0, mp, mm);
 }
 
 // Survivors of the signature, one wave per 64 group regions of a tile (blockIdx.y = tile), their

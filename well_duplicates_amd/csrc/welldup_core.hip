@@ -491,7 +491,8 @@ try {
     // read-only, -1 before the first dense scan of the current targets: 64-target groups of
     // consecutive centres with common neighbour offsets, and those scanned through LDS windows
     else if (n == "dense_uniform_groups") *value = ctx->n_uniform_groups;
-    else if (n == "dense_window_groups") *value = ctx->n_window_groups;
+    // (with "dense_windows" off no group is: the tables' count would say which path the tables allow, not which ran)
+    else if (n == "dense_window_groups") *value = ctx->n_window_groups < 0 || ctx->dense_windows ? ctx->n_window_groups : 0;
     else if (n == "dense_window_dwords") *value = ctx->win_dwords;
     // read-only: histogram passes the last wd_lane_top took (-1 before the first), and the most it can take
     else if (n == "lane_top_passes") *value = ctx->lane_top_passes;

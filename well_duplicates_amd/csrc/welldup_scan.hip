@@ -367,7 +367,7 @@ try {
 
     // lane-per-target kernel: many small targets (every well a centre), Hamming family
     // lev2: the reference's default, Levenshtein <= 2, has a closed form for equal-length reads
-    // (scan_dense.inc: lev2_window) and needs the packed rows, i.e. L <= 160
+    // (dense_forms.inc: lev2_window) and needs the packed rows, i.e. L <= 160
     const bool lev2 = lev && kk == 2 && L <= 40 * kRowGroups;
     const bool dense_ok = (!lev || lev2) && ctx->early_exit && L >= 1 && ctx->k_max <= kDenseMaxK &&
                           levels <= 8 && kk <= 2 && kk >= 0 &&    // levels: 8-bit hit masks
