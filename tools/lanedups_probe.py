@@ -68,13 +68,20 @@ reservation and the scatter read of a lane without a voted family: their floor -
 (after the near finish; its copies are mostly pairs, which do not vote), the `--equal` lane (one Large family: no list,
 no vote) and a lane of three tiles whose wells repeat the first of every three (every well in a voted family of three:
 the longest list there is).
+`--umi U [--umi-e E] [--max-family M]` times LaneDups.umi_add per tile beside LaneDups.index_add of the same planes, and
+LaneDups.umi(E, M) (the lane's duplicates split by molecular identifier, include/welldup_laneumi.h) per tile of the lane
+beside LaneDups.consensus(0, M), the equality finish and Scanner.stream_read_gbs over 16 bytes per well - label, members
+and the UMI keys: what the pass reads of a lane of pairs -, on three inputs: the planted lane (the UMI planes are U
+further cycles of the same synthetic tiles: a planted copy carries its original's UMI), the `--equal` lane (one Large
+family: counted, never looked into) and a lane of three tiles whose odd wells repeat their left neighbour, their UMI
+too but for its last cycle (pairs only: k_lu_pairs does everything, a quarter of the pairs equal, the others one apart).
 For per-kernel times run it under
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/lanedups_probe.py
 
 (the k_ld_* rows of the stats are this stage, k_li_* the index part, k_lm_* the mismatch pass, k_lg_* the distance pass,
 k_lq_* the quality part, k_ls_* the saturation pass, k_lt_* the top pass, k_lh_* the hops pass, k_lgc_* the GC pass,
-k_lc_* the consensus pass, k_td_* the per-tile classes, k_dense_* the scan)."""
+k_lc_* the consensus pass and the gather of the UMI pass, k_lu_* the UMI pass, k_td_* the per-tile classes, k_dense_* the scan)."""
 import argparse
 import os
 import sys
@@ -121,6 +128,11 @@ ap.add_argument("--consensus", action="store_true",
                 help="also time LaneDups.consensus(K, M) beside mismatches(K), the equality finish and a pure read of "
                      "label and members (needs --hamming; three inputs with --equal)")
 ap.add_argument("--max-family", type=int, default=256, metavar="M", help="the largest family of --consensus that votes")
+ap.add_argument("--umi", type=int, default=0, metavar="U",
+                help="also time LaneDups.umi_add beside index_add and LaneDups.umi(E, M) beside consensus(0, M), the "
+                     "equality finish and a pure read of label, members and keys, with U UMI cycles (1..20; three inputs "
+                     "with --equal)")
+ap.add_argument("--umi-e", type=int, default=1, metavar="E", help="the differing cycles of --umi that are one molecule (0..3)")
 ap.add_argument("--quality", action="store_true",
                 help="also time LaneDups.qual_add beside add and LaneDups.qualities(K) beside mismatches(K) (needs "
                      "--hamming; three inputs with --equal)")
@@ -133,6 +145,10 @@ if a.quality and not a.hamming:
     ap.error("--quality needs --hamming K")
 if a.hops and not a.index:
     ap.error("--hops needs --index I")
+if a.umi and not 1 <= a.umi <= 20:
+    ap.error("--umi takes 1..20 cycles")
+if not 0 <= a.umi_e <= 3:
+    ap.error("--umi-e takes 0..3")
 QUALITY_BINS = [0, 2, 10, 20, 25, 30, 35, 40]         # the CLI's default
 
 n = a.rows * a.cols
@@ -612,4 +628,111 @@ if a.distance or a.saturation or a.top or a.gc:
         time_gc(nb, 3, n_fin, "every odd well a copy of its left neighbour, three tiles")
     nb.close()
     three.free()
+
+
+def time_umi(acc, tiles_n, t_finish, t_umi_add, t_index_add, what):
+    """LaneDups.umi(E, M) and, on the same labels, LaneDups.consensus(0, M), each after a first call that pays for loading
+    the kernels; and a pure read of 16 bytes per well, from the accumulator's own workspace"""
+    acc.umi(a.umi_e, a.max_family)
+    (urow, utiles), t_u = clock(lambda: acc.umi(a.umi_e, a.max_family))
+    (urow0, _), t_u0 = clock(lambda: acc.umi(0, a.max_family))
+    acc.consensus(0, max(3, a.max_family))
+    crow, t_c = clock(lambda: acc.consensus(0, max(3, a.max_family)))
+    nbytes = tiles_n * n * 16
+    gbs = sc.stream_read_gbs(acc.d_ws, min(nbytes, acc.ws_bytes))
+    t_read = nbytes / gbs / 1e6
+    assert urow[1] == urow[0] - urow[4] and urow[11:19].sum() == urow[3] and urow[19:].sum() == urow[4] and \
+        urow[19] == urow[2] and (utiles.sum(axis=0) == urow[:3]).all() and urow0[4] == urow0[5] == urow[5] and \
+        urow[3] >= crow[0][0] + crow[0][8], "the UMI rows do not add up"
+    print("%s: umi, %d cycles, E %d, max_family %d: %d families of %d wells, %d molecules (%d at E 0), %d redundant, %d lone, "
+          "%d families split, %d wells with N; %d large families of %d wells left out; MolPerFamily %s; MoleculeSize %s"
+          % (what, a.umi, a.umi_e, a.max_family, urow[3], urow[0], urow[4], urow0[4], urow[1], urow[2], urow[6], urow[8], urow[9],
+             urow[10], " ".join(str(v) for v in urow[11:19]), " ".join(str(v) for v in urow[19:])))
+    print("  %-22s %9.3f ms  (%.4f ms per tile; index_add of the same planes: %.4f; umi_add / index_add = %.2f)"
+          % ("lane umi_add", t_umi_add, t_umi_add / tiles_n, t_index_add / tiles_n, t_umi_add / t_index_add))
+    print("  %-22s %9.3f ms  (%.4f ms per tile; E 0: %.4f; a pure read of label, members and keys, 16 bytes per well: %.4f ms "
+          "per tile at %.0f GB/s; umi / read = %.2f; consensus(0): %.4f; umi / consensus = %.2f; the equality finish: %.4f)"
+          % ("lane umi", t_u, t_u / tiles_n, t_u0 / tiles_n, t_read / tiles_n, gbs, t_u / t_read, t_c / tiles_n, t_u / t_c,
+             t_finish / tiles_n))
+
+
+if a.umi:
+    print("umi part: %d UMI cycles, workspace %.2f GB, scratch %.2f GB"
+          % (a.umi, sc.lane_umi_workspace_bytes(n, a.tiles, a.umi) / 1e9, sc.lane_umi_scratch_bytes(a.tiles, n) / 1e9))
+    # the planted lane: the UMI planes are the cycles behind the read's, of the same synthetic tiles
+    tb, utb = TileBatch(sc, a.batch, a.cycles, n), TileBatch(sc, a.batch, a.umi, n)
+    lu = LaneDups(sc, n, a.tiles, a.cycles)
+    lu.index_begin(a.umi)
+    lu.umi_begin(a.umi)
+    u_uadd = u_iadd = 0.0
+    for bi, tiles in enumerate(batches):
+        if len(tiles) != tb.n_tiles:
+            tb, utb = TileBatch(sc, len(tiles), a.cycles, n, reuse=tb), TileBatch(sc, len(tiles), a.umi, n, reuse=utb)
+        fill(tb, tiles)
+        for s_, t in enumerate(tiles):
+            for c in range(a.umi):
+                sc.synth_plane(utb.plane_ptr(s_, c), spec, 1, 1101 + t, a.cycles + c)
+        sc.synchronize()
+        lu.add(tb, tiles)
+        if bi == 0:                                  # (the first call of a kernel pays for loading it)
+            warm = LaneDups(sc, n, len(tiles), a.cycles)
+            warm.index_begin(a.umi)
+            warm.umi_begin(a.umi)
+            warm.index_add(utb, list(range(len(tiles))))
+            warm.umi_add(utb, list(range(len(tiles))))
+            warm.close()
+        _, dt = clock(lambda: lu.index_add(utb, tiles))
+        u_iadd += dt
+        _, dt = clock(lambda: lu.umi_add(utb, tiles))
+        u_uadd += dt
+    _, u_fin = clock(lambda: lu.finish())
+    assert (lu.umi_keys() == lu.index_keys()).all(), "the UMI keys differ from the index keys of the same planes"
+    time_umi(lu, max(1, a.tiles), u_fin, u_uadd, u_iadd, "the planted lane")
+    lu.close()
+    tb.free()
+    utb.free()
+    three, uthree = TileBatch(sc, 3, a.cycles, n), TileBatch(sc, 3, a.umi, n)
+    if a.equal:
+        for s in range(3):
+            three.upload_tile(s, [np.full(n, 0x42 + (c % 4), dtype=np.uint8) for c in range(a.cycles)], np.ones(n, dtype=np.uint8))
+            for c in range(a.umi):
+                sc.synth_plane(uthree.plane_ptr(s, c), spec, 1, 1101 + s, a.cycles + c)
+        sc.synchronize()
+        eq = LaneDups(sc, n, 3, a.cycles)
+        eq.index_begin(a.umi)
+        eq.umi_begin(a.umi)
+        eq.add(three, [0, 1, 2])
+        _, e_iadd = clock(lambda: eq.index_add(uthree, [0, 1, 2]))
+        _, e_uadd = clock(lambda: eq.umi_add(uthree, [0, 1, 2]))
+        _, e_fin = clock(lambda: eq.finish())
+        time_umi(eq, 3, e_fin, e_uadd, e_iadd, "every read equal, three tiles")
+        assert eq.umi(a.umi_e, a.max_family)[0][9:11].tolist() == [1, 3 * n], "the equal lane is not one Large family"
+        eq.close()
+    # three tiles without planted copies whose wells of odd index repeat the well to their left, cycle by cycle, and its
+    # UMI but for the last cycle
+    bare = synth.SynthSpec(seed=5, n_clusters=n, row=a.cols, plant_per_64k=0)
+    for s in range(3):
+        sc.h2d(three.filter_ptr(s), np.ones(n, dtype=np.uint8))
+        for c in range(a.cycles + a.umi):
+            dst = three.plane_ptr(s, c) if c < a.cycles else uthree.plane_ptr(s, c - a.cycles)
+            sc.synth_plane(dst, bare, 1, 1101 + s, c)
+            sc.synchronize()
+            if c < a.cycles + a.umi - 1:
+                plane = sc.d2h(dst, n, np.uint8).copy()
+                plane[1::2] = plane[0::2][:plane[1::2].size]
+                sc.h2d(dst, plane)
+    sc.synchronize()
+    pr = LaneDups(sc, n, 3, a.cycles)
+    pr.index_begin(a.umi)
+    pr.umi_begin(a.umi)
+    pr.add(three, [0, 1, 2])
+    _, p_iadd = clock(lambda: pr.index_add(uthree, [0, 1, 2]))
+    _, p_uadd = clock(lambda: pr.umi_add(uthree, [0, 1, 2]))
+    _, p_fin = clock(lambda: pr.finish())
+    time_umi(pr, 3, p_fin, p_uadd, p_iadd, "every odd well a copy of its left neighbour, three tiles")
+    prow = pr.umi(0, a.max_family)[0]
+    assert prow[3] >= 3 * (n // 2) - 3 and prow[11 + 2:19].sum() == 0, "the families are not pairs"
+    pr.close()
+    three.free()
+    uthree.free()
 sc.close()

@@ -237,6 +237,22 @@ LANECONSENSUS_MAX_FAMILY = 4096
 LANECONSENSUS_LANE_COLS = 20
 LANECONSENSUS_TILE_COLS = 4
 
+# name -> (restype, argtypes); every symbol include/welldup_laneumi.h declares beyond those above
+LANEUMI_PROTOTYPES = {
+    "wd_lane_umi_workspace": (_i, [_i64, _i, _i, ctypes.POINTER(_sz)]),
+    "wd_lane_umi_begin": (_i, [_vp, _i, _vp, _sz]),
+    "wd_lane_umi_add": (_i, [_vp, _i, ctypes.POINTER(_i), _pp]),
+    "wd_lane_umi_scratch": (_i, [_i, _i64, ctypes.POINTER(_sz)]),
+    "wd_lane_umi": (_i, [_vp, _i, _i, _vp, _sz, _vp, _vp]),
+}
+LANEUMI_MAX_CYCLES = 20
+LANEUMI_MAX_E = 3
+LANEUMI_MAX_FAMILY = 1024
+LANEUMI_LANE_COLS = 27
+LANEUMI_TILE_COLS = 3
+LANEUMI_BINS = 8
+LANEUMI_BIN_NAMES = ("1", "2", "3", "4", "5-8", "9-16", "17-64", "65+")
+
 _lib = None
 
 
@@ -323,7 +339,7 @@ def unit_of_kernel(kernel: str) -> str:
         return "ingest"
     if kernel.startswith("k_sets"):
         return "sets"
-    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_", "k_ls_", "k_lt_", "k_lh_", "k_lgc_", "k_lc_")):
+    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_", "k_ls_", "k_lt_", "k_lh_", "k_lgc_", "k_lc_", "k_lu_")):
         return "tiledups"
     return "scan"
 
@@ -387,7 +403,8 @@ def load():
             list(LANEINDEX_PROTOTYPES.items()) + list(LANEMISMATCH_PROTOTYPES.items()) + \
             list(LANEDISTANCE_PROTOTYPES.items()) + list(LANEQUALITY_PROTOTYPES.items()) + \
             list(LANESATURATION_PROTOTYPES.items()) + list(LANETOP_PROTOTYPES.items()) + \
-            list(LANEHOPS_PROTOTYPES.items()) + list(LANEGC_PROTOTYPES.items()) + list(LANECONSENSUS_PROTOTYPES.items()):
+            list(LANEHOPS_PROTOTYPES.items()) + list(LANEGC_PROTOTYPES.items()) + list(LANECONSENSUS_PROTOTYPES.items()) + \
+            list(LANEUMI_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

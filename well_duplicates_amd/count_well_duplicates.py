@@ -26,7 +26,8 @@ Differences from the reference, all deliberate:
     --lane-dups-hamming, --lane-dups-index, --lane-dups-mismatches, --lane-dups-distance, --lane-dups-quality,
     --lane-dups-saturation, --lane-dups-top, --lane-dups-top-out, --lane-dups-hops, --lane-dups-hops-mismatches,
     --lane-dups-hops-out, --lane-dups-gc, --lane-dups-gc-bins, --lane-dups-gc-max-n, --lane-dups-gc-out,
-    --lane-dups-consensus, --lane-dups-consensus-max-d, --lane-dups-consensus-max-family, --lane-dups-consensus-out;
+    --lane-dups-consensus, --lane-dups-consensus-max-d, --lane-dups-consensus-max-family, --lane-dups-consensus-out,
+    --lane-dups-umi, --lane-dups-umi-mismatches, --lane-dups-umi-max-family, --lane-dups-umi-out;
   * --all-wells --dup-sets groups every tile's wells into duplicate sets and follows each lane's report
     with their counts and the exact duplication (report.write_dup_sets);
   * --all-wells --tile-dups groups every tile's PF wells into classes of equal reads, wherever on the tile they
@@ -61,6 +62,10 @@ Differences from the reference, all deliberate:
     --lane-dups-consensus lets every family of three or more wells vote: the base most of its members call at a cycle
     is the molecule's, a member that disagrees made the error - the lane's error profile by cycle and by direction,
     G>T apart from T>G, which the comparison with a first well cannot give (report.write_lane_consensus);
+    --lane-dups-umi RANGES reads a unique molecular identifier at those cycles and splits every class or cluster by it:
+    two wells with the same read and different UMIs are two molecules - the lane's duplication and library size with
+    the UMI beside those without, the copies that are molecules of their own, and the UMI reads merged as read errors
+    (report.write_lane_umi);
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
@@ -361,7 +366,47 @@ def parse_args(argv=None):
     p.add_argument("--lane-dups-consensus-out", default=None, metavar="FILE",
                    help="with --lane-dups-consensus: also write every cell of the call matrix that is not zero to FILE, "
                         "tab-separated: lane, cycle, consensus, call, count")
+    p.add_argument("--lane-dups-umi", default=None, metavar="RANGES",
+                   help="with --lane-dups: the cycles of a unique molecular identifier (UMI), given as --lane-dups-index "
+                        "takes its cycles, 1..%d in all, among the scanned cycles or not.  The wells of every class "
+                        "(every cluster with --lane-dups-hamming K) are grouped by their UMI read: two wells with the "
+                        "same read and different UMIs are two molecules, not copies.  Printed after every other block of "
+                        "the lane: the families looked into and those left out, the lane's duplication and library size "
+                        "as they were and with the UMI, the share of the copies that are molecules of their own, the UMI "
+                        "reads merged as read errors, and the families by their molecules and the molecules by their "
+                        "wells.  Takes 16 bytes of device memory per well of the lane: 8 for the UMI reads, 8 for the "
+                        "pass" % _lib.LANEUMI_MAX_CYCLES)
+    p.add_argument("--lane-dups-umi-mismatches", type=int, default=None, metavar="E",
+                   help="with --lane-dups-umi: two UMI reads of a family that differ at up to E cycles (0..%d, default 1) "
+                        "are one molecule read with an error; molecules are the connected components under that rule "
+                        "(single linkage).  0: only equal UMI reads are one molecule" % _lib.LANEUMI_MAX_E)
+    p.add_argument("--lane-dups-umi-max-family", type=int, default=None, metavar="M",
+                   help="with --lane-dups-umi: a family of more than M wells (2..%d, default 256) is counted and not "
+                        "looked into: its copies stay copies" % _lib.LANEUMI_MAX_FAMILY)
+    p.add_argument("--lane-dups-umi-out", default=None, metavar="FILE",
+                   help="with --lane-dups-umi: also write the two histograms and the tile rows to FILE, tab-separated: "
+                        "lane, table, key, wells, umi_redundant, lone")
     args = p.parse_args(argv)
+    if args.lane_dups_umi is not None and not args.lane_dups:
+        p.error("--lane-dups-umi needs --lane-dups")
+    for flag, value in (("mismatches", args.lane_dups_umi_mismatches), ("max-family", args.lane_dups_umi_max_family),
+                        ("out", args.lane_dups_umi_out)):
+        if value is not None and args.lane_dups_umi is None:
+            p.error("--lane-dups-umi-%s needs --lane-dups-umi" % flag)
+    if args.lane_dups_umi is not None:
+        try:
+            ranges = workload.parse_cycles(0, 0, args.lane_dups_umi)
+        except ValueError:
+            ranges = [(0, 0)]
+        if any(not 0 <= a < b for a, b in ranges):
+            p.error("--lane-dups-umi takes ranges of cycles as --cycles does, eg. 0-8 or 151-160")
+        n_umi = sum(b - a for a, b in ranges)
+        if not 1 <= n_umi <= _lib.LANEUMI_MAX_CYCLES:
+            p.error("--lane-dups-umi takes 1..%d cycles, not %d" % (_lib.LANEUMI_MAX_CYCLES, n_umi))
+    if args.lane_dups_umi_mismatches is not None and not 0 <= args.lane_dups_umi_mismatches <= _lib.LANEUMI_MAX_E:
+        p.error("--lane-dups-umi-mismatches takes 0..%d, not %d" % (_lib.LANEUMI_MAX_E, args.lane_dups_umi_mismatches))
+    if args.lane_dups_umi_max_family is not None and not 2 <= args.lane_dups_umi_max_family <= _lib.LANEUMI_MAX_FAMILY:
+        p.error("--lane-dups-umi-max-family takes 2..%d, not %d" % (_lib.LANEUMI_MAX_FAMILY, args.lane_dups_umi_max_family))
     if args.lane_dups_consensus and not args.lane_dups:
         p.error("--lane-dups-consensus needs --lane-dups")
     for flag, value in (("max-d", args.lane_dups_consensus_max_d), ("max-family", args.lane_dups_consensus_max_family),
@@ -616,17 +661,17 @@ def lane_cluster_members(class_labels: np.ndarray, cluster_labels: np.ndarray):
 
 def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0, index: int = 0,
                          mismatch: int = 0, distance: int = 0, quality: int = 0, saturation: int = 0, top: int = 0,
-                         hops: int = 0, gc: int = 0, consensus: int = 0):
+                         hops: int = 0, gc: int = 0, consensus: int = 0, umi: int = 0, umi_scratch: int = 0):
     """--lane-dups: the accumulator's workspace - with --lane-dups-hamming plus the scratch of the near finish, with
     --lane-dups-index plus the index workspace, with --lane-dups-mismatches or --lane-dups-distance plus that pass's
     scratch, with --lane-dups-quality plus the quality workspace and that pass's scratch, with --lane-dups-saturation,
-    --lane-dups-top, --lane-dups-hops, --lane-dups-gc or --lane-dups-consensus plus that pass's scratch - against the
-    free device memory,
+    --lane-dups-top, --lane-dups-hops, --lane-dups-gc or --lane-dups-consensus plus that pass's scratch, with
+    --lane-dups-umi plus the UMI workspace (umi) and that pass's scratch (umi_scratch) - against the free device memory,
     before anything is loaded."""
-    need += scratch + index + mismatch + distance + quality + saturation + top + hops + gc + consensus
+    need += scratch + index + mismatch + distance + quality + saturation + top + hops + gc + consensus + umi + umi_scratch
     if need > free:
         raise MemoryError("--lane-dups needs %.2f GB of device memory for a lane of %d tiles x %d wells x %d cycles "
-                          "(%d bytes%s%s%s%s%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
+                          "(%d bytes%s%s%s%s%s%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
                               need / 1e9, tiles, wells, cycles, need,
                               ", %d of them for --lane-dups-hamming" % scratch if scratch else "",
                               ", %d of them for --lane-dups-index" % index if index else "",
@@ -638,6 +683,7 @@ def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: i
                               ", %d of them for --lane-dups-hops" % hops if hops else "",
                               ", %d of them for --lane-dups-gc" % gc if gc else "",
                               ", %d of them for --lane-dups-consensus" % consensus if consensus else "",
+                              ", %d of them for --lane-dups-umi" % (umi + umi_scratch) if umi + umi_scratch else "",
                               free / 1e9, free))
 
 
@@ -651,7 +697,7 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
                dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0, lane_near=0, lane_pair_budget=0,
                lane_index=None, lane_mismatch=None, lane_distance=None, lane_quality=None, lane_saturation=None,
-               lane_top=0, lane_hops=None, lane_gc=None, lane_consensus=None):
+               lane_top=0, lane_hops=None, lane_gc=None, lane_consensus=None, lane_umi=None):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
@@ -693,6 +739,10 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     lane_consensus = (D, max family) (with lane_dups): after every other pass of the lane LaneDups.consensus(D, max
     family): into["lconsensus"][lane] = LaneConsensusCounts, on the labels the lane was left with, its cycles numbered by
     cycle_list.
+    lane_umi = (UMI cycles, E, max family) (with lane_dups): every batch gets a further TileBatch of the UMI cycles,
+    loaded by the same job list as the index batch and fed to LaneDups.umi_add, reused and released with the scan
+    batch; after every other pass of the lane LaneDups.umi(E, max family): into["lumi"][lane] = LaneUmiCounts, on the
+    labels the lane was left with.
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -707,6 +757,8 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     levels = lvl_off.shape[1] - 1
     index_cycles, index_lengths, index_share = lane_index if lane_index else ([], [], 1.0)
     assert not index_cycles or (lane_dups and interleave == 1)
+    umi_cycles, umi_e, umi_family = lane_umi if lane_umi else ([], 0, 0)
+    assert not umi_cycles or (lane_dups and interleave == 1)
     counts, logs = (into["counts"], into["logs"]) if into else ({}, {})
     batches = []                            # (lane, [tiles]), never across a lane's end: an error stays its lane's (start_ahead)
     for lane, tiles in lane_tiles:
@@ -725,7 +777,7 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                     room = 700
             except (OSError, IndexError, RuntimeError, AssertionError):
                 pass                            # (whatever is wrong with the first tile is reported when it is loaded)
-            per = max(1, room // max(1, len(cycle_list) + len(index_cycles) + 1))
+            per = max(1, room // max(1, len(cycle_list) + len(index_cycles) + len(umi_cycles) + 1))
             n_batches = max(1, -(-len(tiles) // per))
             tb_n = max(1, -(-len(tiles) // n_batches))
         batches += [(lane, tiles[b0:b0 + tb_n]) for b0 in range(0, len(tiles), tb_n)]
@@ -736,6 +788,7 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     tiles_of_lane = {lane: list(tiles) for lane, tiles in lane_tiles}
     spare = []                              # finished ones whose buffers the next batch takes over
     index_tb, index_spare = {}, []          # id(scan batch) -> its batch of index cycles; finished ones
+    umi_tb, umi_spare = {}, []              # the same for the UMI cycles
 
     def start(batch):
         """Submit every load of a batch; returns at once."""
@@ -757,16 +810,22 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
         if index_cycles:
             index_tb[id(tb)] = TileBatch(sc, len(chunk), len(index_cycles), n_clusters,
                                          reuse=index_spare.pop() if index_spare else None)
+        if umi_cycles:
+            umi_tb[id(tb)] = TileBatch(sc, len(chunk), len(umi_cycles), n_clusters,
+                                       reuse=umi_spare.pop() if umi_spare else None)
         _lap("  batch of %d tiles: buffers" % len(chunk))
         # ingest: every (tile, cycle) file is gunzipped into pinned memory and copied to the GPU
         # by libwelldup (wd_load_bcl_gz).  Runs without .bcl.gz files are NovaSeq runs: the
         # tile's block of the lane/surface .cbcl is gunzipped on the host and expanded on the
         # GPU (wd_load_cbcl_tile), which needs the tile's filter first.
-        # a job: (slot, cycle, where its plane goes); the index cycles' planes go to the batch of their own
+        # a job: (slot, cycle, where its plane goes); the index and the UMI cycles' planes go to batches of their own
         jobs = [(i, cycle_list[c], tb.plane_ptr(i, c)) for i in range(len(handles)) for c in range(len(cycle_list))]
         if index_cycles:
             itb = index_tb[id(tb)]
             jobs += [(i, cyc, itb.plane_ptr(i, c)) for i in range(len(handles)) for c, cyc in enumerate(index_cycles)]
+        if umi_cycles:
+            utb = umi_tb[id(tb)]
+            jobs += [(i, cyc, utb.plane_ptr(i, c)) for i in range(len(handles)) for c, cyc in enumerate(umi_cycles)]
         batch = None                        # which files the GPU decoder gets as one batch
         if gpu_inflate and jobs:
             if os.path.exists(handles[0].plane_path(cycle_list[0])):
@@ -824,15 +883,19 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
 
     def release(tb, keep=False):
         live.remove(tb)
-        itb = index_tb.pop(id(tb), None)
+        itb, utb = index_tb.pop(id(tb), None), umi_tb.pop(id(tb), None)
         if keep:
             spare.append(tb)
             if itb is not None:
                 index_spare.append(itb)
+            if utb is not None:
+                umi_spare.append(utb)
         else:
             tb.free()
             if itb is not None:
                 itb.free()
+            if utb is not None:
+                utb.free()
 
     try:
         # three batches on their way at any time: one's files are read and copied while the one before
@@ -890,12 +953,16 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                             ld.index_begin(len(index_cycles))
                         if lane_quality is not None:
                             ld.qual_begin(lane_quality[0])
+                        if umi_cycles:
+                            ld.umi_begin(len(umi_cycles))
                     lane_acc["lane"] = lane
                 ld.add(tb, [names.index(t) for t in chunk])
                 if lane_quality is not None:
                     ld.qual_add(tb, [names.index(t) for t in chunk])
                 if index_cycles:
                     ld.index_add(index_tb[id(tb)], [names.index(t) for t in chunk])
+                if umi_cycles:
+                    ld.umi_add(umi_tb[id(tb)], [names.index(t) for t in chunk])
                 if last_batch_of[lane] == bi:
                     got = ld.finish(labels=lane_dups > 1, hamming=lane_near, pair_budget=lane_pair_budget)
                     lane_row, tile_rows, lane_labels = got[:3]
@@ -947,6 +1014,11 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                         into["lconsensus"][lane] = report.LaneConsensusCounts.from_rows(
                             *ld.consensus(*lane_consensus), names, lane_near, lane_consensus[0], lane_consensus[1],
                             (into["lnear"][lane] if lane_near else into["ldups"][lane]).pf, cycle_list)
+                    if umi_cycles:
+                        left = into["lnear"][lane] if lane_near else into["ldups"][lane]
+                        into["lumi"][lane] = report.LaneUmiCounts.from_rows(
+                            *ld.umi(umi_e, umi_family), names, lane_near, umi_e, umi_family, len(umi_cycles), left.pf,
+                            left.redundant)
                     del lane_labels, got
                 _lap("batch %d: lane classes" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
@@ -1204,6 +1276,10 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 consensus = (args.lane_dups_consensus_max_d if args.lane_dups_consensus_max_d is not None else
                              mismatch_d if mismatch_d is not None else lane_near_k,
                              args.lane_dups_consensus_max_family or 256)
+            umi_cycles = [c for s, e in workload.parse_cycles(0, 0, args.lane_dups_umi) for c in range(s, e)] \
+                if args.lane_dups_umi else []
+            umi = (umi_cycles, 1 if args.lane_dups_umi_mismatches is None else args.lane_dups_umi_mismatches,
+                   args.lane_dups_umi_max_family or 256) if umi_cycles else None
             ntn = 5 + 2 * levels + len(report.CLASS_BIN_NAMES) if near_k else 0
             rows = np.zeros((len(mine), ncnt + nsets + ntd + ntn), dtype=np.int64)
             logs = {}
@@ -1257,6 +1333,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 if args.lane_dups_consensus:
                     report.write_lane_consensus(lane, results["lconsensus"][lane], verbose=not args.summary_only,
                                                 out=out_fh)
+                if umi is not None:
+                    report.write_lane_umi(lane, results["lumi"][lane], verbose=not args.summary_only, out=out_fh)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
@@ -1265,7 +1343,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
                            "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}, "lnear": {}, "lindex": {},
                            "lmindex": {}, "lmismatch": {}, "ldistance": {}, "lquality": {}, "lsaturation": {}, "ltop": {},
-                           "lhops": {}, "lgc": {}, "lconsensus": {}}
+                           "lhops": {}, "lgc": {}, "lconsensus": {}, "lumi": {}}
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
@@ -1310,7 +1388,11 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                          gc=sc.lane_gc_scratch_bytes(len(tiles), len(cycle_list))
                                          if args.lane_dups_gc else 0,
                                          consensus=sc.lane_consensus_scratch_bytes(len(tiles), n_targets, len(cycle_list))
-                                         if consensus is not None else 0)
+                                         if consensus is not None else 0,
+                                         umi=sc.lane_umi_workspace_bytes(n_targets, len(tiles), len(umi_cycles))
+                                         if umi is not None else 0,
+                                         umi_scratch=sc.lane_umi_scratch_bytes(len(tiles), n_targets)
+                                         if umi is not None else 0)
                 if err is None:             # (a rank whose setup failed has nothing to scan: it goes to the flag)
                     scan_lanes(sc, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                                max(0, args.tile_batch), args.threads,
@@ -1333,7 +1415,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                lane_hops=(1 if args.lane_dups_hops_mismatches is None else args.lane_dups_hops_mismatches,
                                           args.lane_dups_hops) if args.lane_dups_hops is not None else None,
                                lane_gc=(gc_max_n, args.lane_dups_gc_bins or 20) if args.lane_dups_gc else None,
-                               lane_consensus=consensus)
+                               lane_consensus=consensus, lane_umi=umi)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
                     if args.tile_dups_out and near_k:
@@ -1356,6 +1438,10 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                         with open(args.lane_dups_consensus_out, "w") as fh:
                             for i, lane in enumerate(sorted(results["lconsensus"], key=lanes.index)):
                                 report.write_lane_consensus_tsv(lane, results["lconsensus"][lane], fh, header=i == 0)
+                    if args.lane_dups_umi_out:
+                        with open(args.lane_dups_umi_out, "w") as fh:
+                            for i, lane in enumerate(sorted(results["lumi"], key=lanes.index)):
+                                report.write_lane_umi_tsv(lane, results["lumi"][lane], fh, header=i == 0)
                     if args.lane_dups_out:
                         write_lane_members(args.lane_dups_out, results["lmembers"],
                                            index=([e - s for s, e in index_ranges], results["lmindex"])

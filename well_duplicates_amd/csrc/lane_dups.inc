@@ -397,6 +397,7 @@ __global__ void __launch_bounds__(kTdBlock) k_ld_span_sum(const int *__restrict_
 #ifndef WD_TILEDUPS_EMU                            // (tools/read_classes_emu.cpp, tools/near_emu.cpp: the kernels above on the CPU, a fiber per lane)
 struct wd_lane_index;                              // lane_index.inc: the index part of an accumulator
 struct wd_lane_quality;                            // lane_quality.inc: the quality part of an accumulator
+struct wd_lane_umi_part;                           // lane_umi.inc: the UMI part of an accumulator
 
 // the host side of an accumulator (the device side is the caller's workspace)
 struct wd_lane_dups {
@@ -413,6 +414,7 @@ struct wd_lane_dups {
     std::vector<int64_t> eq_lane, eq_tiles;
     std::shared_ptr<wd_lane_index> index;          // null unless wd_lane_index_begin has been called
     std::shared_ptr<wd_lane_quality> qual;         // null unless wd_lane_qual_begin has been called
+    std::shared_ptr<wd_lane_umi_part> umi;         // null unless wd_lane_umi_begin has been called
 };
 
 namespace {

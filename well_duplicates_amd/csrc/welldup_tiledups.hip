@@ -27,6 +27,8 @@
 // most frequent reads and their spread of welldup_lanetop.h.  lane_gc.inc (after lane_distance.inc) reads the labels, the members
 // and every row of the lane: its duplication against its reads' GC content of welldup_lanegc.h.  lane_consensus.inc (after
 // it) gathers the members of every family and counts their calls against the family's vote: welldup_laneconsensus.h.
+// lane_umi.inc (after it) groups the wells of every family by their UMI read, packed by lane_index.inc's kernel and
+// gathered by lane_consensus.inc's: welldup_laneumi.h.
 #include <memory>
 
 #include "wd_ctx.h"
@@ -237,4 +239,5 @@ try {
 #include "lane_distance.inc"  // how far apart a lane's duplicate copies lie (include/welldup_lanedistance.h)
 #include "lane_gc.inc"        // a lane's duplication against its reads' GC content (include/welldup_lanegc.h)
 #include "lane_consensus.inc" // a lane's errors against its families' vote (include/welldup_laneconsensus.h)
+#include "lane_umi.inc"       // a lane's duplicates split by molecular identifier (include/welldup_laneumi.h)
 #include "lane_quality.inc"   // reported base quality against a lane's duplicate copies (include/welldup_lanequality.h)

@@ -1711,3 +1711,129 @@ def write_lane_consensus_tsv(lane, counts: LaneConsensusCounts, out, header: boo
             for b in range(5):
                 if cell[a][b]:
                     print("%s\t%i\t%s\t%s\t%i" % (lane, cycle, CODE_NAMES[a], CODE_NAMES[b], cell[a][b]), file=out)
+
+
+# ---- --lane-dups-umi: a lane's duplicates split by molecular identifier (include/welldup_laneumi.h) ----
+LANE_UMI_MAX_E = 3
+LANE_UMI_MIN_FAMILY, LANE_UMI_MAX_FAMILY = 2, 1024
+LANE_UMI_MAX_CYCLES = 20
+LANE_UMI_BIN_NAMES = ("1", "2", "3", "4", "5-8", "9-16", "17-64", "65+")
+LANE_UMI_TILE_COLS = 3
+LANE_UMI_LANE_COLS = LANE_UMI_TILE_COLS + 8 + 2 * len(LANE_UMI_BIN_NAMES)
+
+
+@dataclass
+class LaneUmiCounts:
+    """A lane's duplicates split by molecular identifier (include/welldup_laneumi.h, LaneDups.umi): the lane row's
+    columns, per tile (by the tile's name) [Wells, UmiRedundant, Lone], and of the finish whose labels were split the
+    lane's PF wells and its redundant wells."""
+    k: int = 0
+    max_e: int = 0
+    max_family: int = 256
+    umi_cycles: int = 0
+    pf: int = 0
+    redundant: int = 0
+    wells: int = 0
+    umi_redundant: int = 0
+    lone: int = 0
+    families: int = 0
+    molecules: int = 0
+    distinct_umis: int = 0
+    split_families: int = 0
+    split_wells: int = 0
+    with_n: int = 0
+    large: int = 0
+    large_wells: int = 0
+    per_family: List[int] = field(default_factory=lambda: [0] * len(LANE_UMI_BIN_NAMES))
+    sizes: List[int] = field(default_factory=lambda: [0] * len(LANE_UMI_BIN_NAMES))
+    tiles: Dict[str, List[int]] = field(default_factory=dict)
+
+    @classmethod
+    def from_rows(cls, lane_row: Sequence[int], tile_rows: Sequence[Sequence[int]], tile_names: Sequence, k: int, max_e: int,
+                  max_family: int, umi_cycles: int, pf: int, redundant: int) -> "LaneUmiCounts":
+        """The two results of LaneDups.umi(max_e, max_family); tile_names as LaneDupCounts.from_rows takes them; k: the
+        K of --lane-dups-hamming; umi_cycles: U; pf, redundant: PF and Redundant of the finish's lane row."""
+        b = [int(v) for v in lane_row]
+        n = len(LANE_UMI_BIN_NAMES)
+        assert len(b) == LANE_UMI_LANE_COLS and 0 <= max_e <= LANE_UMI_MAX_E
+        assert LANE_UMI_MIN_FAMILY <= max_family <= LANE_UMI_MAX_FAMILY and 1 <= umi_cycles <= LANE_UMI_MAX_CYCLES
+        tiles = {}
+        for name, row in zip(tile_names, tile_rows):
+            assert len(row) == LANE_UMI_TILE_COLS
+            if name is not None:
+                tiles[name] = [int(v) for v in row]
+        return cls(int(k), int(max_e), int(max_family), int(umi_cycles), int(pf), int(redundant), *b[:11], b[11:11 + n],
+                   b[11 + n:], tiles)
+
+    def to_rows(self):
+        """-> (lane row, tile rows in sorted order of the tiles' names)"""
+        return ([self.wells, self.umi_redundant, self.lone, self.families, self.molecules, self.distinct_umis,
+                 self.split_families, self.split_wells, self.with_n, self.large, self.large_wells] + list(self.per_family) +
+                list(self.sizes), [list(self.tiles[t]) for t in sorted(self.tiles)])
+
+    @property
+    def redundant_with_umi(self) -> int:
+        """The redundant wells once the UMI is looked at: UmiRedundant, and the copies of the large families, which
+        are counted as before."""
+        return self.umi_redundant + self.large_wells - self.large
+
+    @property
+    def own_molecules(self) -> int:
+        """The former "copies" that are molecules of their own: Molecules - Families."""
+        return self.molecules - self.families
+
+    def merged_rate(self) -> Optional[float]:
+        """The UMI reads merged as read errors - DistinctUmis - Molecules - per UMI base of the gathered wells; None
+        without one."""
+        bases = self.wells * self.umi_cycles
+        return (self.distinct_umis - self.molecules) / bases if bases else None
+
+
+def write_lane_umi(lane, counts: LaneUmiCounts, verbose: bool = False, out=None) -> None:
+    """The block that follows every other block of a lane under --lane-dups-umi: per-tile lines (verbose; tiles in
+    sorted order as write_report), then the summary: the gathered and the large families, the lane's duplication as it
+    was and with the UMI - its redundant wells UmiRedundant plus the copies of the large families, which are counted
+    as before -, the library size from each (library_size), the share of the former copies that are molecules of
+    their own, the UMI reads merged as read errors as a rate per UMI base, and the two histograms."""
+    out = out or sys.stdout
+    c = counts
+    share = lambda v, of: v / of if of else 0.0
+    size_text = lambda s: "n/a" if s is None else "%.0f" % s
+    print(file=out)
+    if verbose:
+        for tile in sorted(c.tiles):
+            t = c.tiles[tile]
+            print("LaneUmi: %s\tTile: %s\tWells: %i\tUmiRedundant: %i\tLone: %i" % (lane, tile, t[0], t[1], t[2]), file=out)
+    print("LaneUmiSummary: %s\tTiles: %i\tHamming: %i\tUmiCycles: %i\tMismatches: %i\tMaxFamily: %i\tFamilies: %i\tWells: %i "
+          "(%.5f of PF)\tMolecules: %i\tDistinctUmis: %i\tUmiRedundant: %i\tLone: %i\tSplitFamilies: %i (%.5f of Families)\t"
+          "SplitWells: %i\tWithN: %i\tLarge left out: %i (%i wells)" % (
+              lane, len(c.tiles), c.k, c.umi_cycles, c.max_e, c.max_family, c.families, c.wells, share(c.wells, c.pf),
+              c.molecules, c.distinct_umis, c.umi_redundant, c.lone, c.split_families, share(c.split_families, c.families),
+              c.split_wells, c.with_n, c.large, c.large_wells), file=out)
+    with_umi = c.redundant_with_umi
+    print("Lane duplication (Redundant/PF wells): {:.2%}\twith the UMI: {:.2%} ({:d} redundant wells, {:d} before)".format(
+        share(c.redundant, c.pf), share(with_umi, c.pf), with_umi, c.redundant), file=out)
+    print("Estimated library size (distinct/X = 1 - exp(-PF/X)): %s\twith the UMI: %s" % (
+        size_text(library_size(c.pf, c.pf - c.redundant)), size_text(library_size(c.pf, c.pf - with_umi))), file=out)
+    copies = c.wells - c.families
+    print("Copies that are molecules of their own: %i of %i (%.5f)" % (c.own_molecules, copies, share(c.own_molecules, copies)),
+          file=out)
+    rate = c.merged_rate()
+    print("UMI reads merged as read errors: %i (%s per UMI base)" % (c.distinct_umis - c.molecules,
+                                                                     "n/a" if rate is None else "%.3e" % rate), file=out)
+    print("MoleculesPerFamily: %s" % "\t".join("%s: %i" % (n, v) for n, v in zip(LANE_UMI_BIN_NAMES, c.per_family)), file=out)
+    print("MoleculeSizes: %s" % "\t".join("%s: %i" % (n, v) for n, v in zip(LANE_UMI_BIN_NAMES, c.sizes)), file=out)
+
+
+def write_lane_umi_tsv(lane, counts: LaneUmiCounts, out, header: bool = True) -> None:
+    """--lane-dups-umi-out: the two histograms and the tile rows - lane, table (per_family, size or tile), the bin or
+    the tile's name, and three counts (a histogram's line holds its count and two zeros; a tile's Wells, UmiRedundant
+    and Lone)."""
+    if header:
+        print("lane\ttable\tkey\twells\tumi_redundant\tlone", file=out)
+    for table, values in (("per_family", counts.per_family), ("size", counts.sizes)):
+        for name, v in zip(LANE_UMI_BIN_NAMES, values):
+            print("%s\t%s\t%s\t%i\t0\t0" % (lane, table, name, v), file=out)
+    for tile in sorted(counts.tiles):
+        t = counts.tiles[tile]
+        print("%s\ttile\t%s\t%i\t%i\t%i" % (lane, tile, t[0], t[1], t[2]), file=out)

@@ -336,6 +336,16 @@ class Scanner:
         counters)."""
         return self._workspace_bytes(self._lib.wd_lane_consensus_scratch, max_tiles, n_clusters, L)
 
+    def lane_umi_workspace_bytes(self, n_clusters: int, max_tiles: int, U: int) -> int:
+        """Device bytes the UMI part of a lane's accumulator needs: 8 per well plus the pointer tables
+        (wd_lane_umi_workspace; U outside 1..20 raises ValueError)."""
+        return self._workspace_bytes(self._lib.wd_lane_umi_workspace, n_clusters, max_tiles, U)
+
+    def lane_umi_scratch_bytes(self, max_tiles: int, n_clusters: int) -> int:
+        """Device bytes LaneDups.umi needs beside the accumulator's workspace (wd_lane_umi_scratch: 8 bytes per well of
+        the lane - where a family's range begins, the member list and the family table - plus the counters)."""
+        return self._workspace_bytes(self._lib.wd_lane_umi_scratch, max_tiles, n_clusters)
+
     def lane_hops_scratch_bytes(self, max_tiles: int, M: int) -> int:
         """Device bytes LaneDups.hops needs beside the accumulator's workspaces for M listed keys
         (wd_lane_hops_scratch: the counters, the listing and the (M + 1)^2 cells of the matrix; it does not depend on
@@ -565,6 +575,7 @@ class LaneDups:
         self.d_labels = self.d_near_labels = 0
         self.d_index, self.index_bytes, self.I, self.index_listed = 0, 0, 0, 0
         self.d_qual, self.qual_bytes, self.qual_edges = 0, 0, None
+        self.d_umi, self.umi_bytes, self.U = 0, 0, 0
         self.refused = None
         self._h = None
         try:
@@ -587,6 +598,8 @@ class LaneDups:
             self._index_begin()
         if self.qual_edges is not None:
             self._qual_begin()
+        if self.U:
+            self._umi_begin()
 
     def _with_scratch(self, nbytes: int, call):
         """call(scratch pointer, nbytes) -> a return code, checked; the scratch lives for the call."""
@@ -749,6 +762,79 @@ class LaneDups:
         rows, keys = rows[:n.value], keys[:n.value]
         order = np.lexsort((keys, -rows[:, 0]))
         return lane_row, other, rows[order], keys[order]
+
+    # ---- the lane's duplicates split by molecular identifier (include/welldup_laneumi.h)
+    def umi_begin(self, U: int):
+        """Gives the lane a UMI part of U cycles (1..20), before any finish; the accumulator owns and frees its
+        workspace.  A lane may carry an index part and a UMI part at once."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        if self.U:
+            raise ValueError("umi_begin is called once")
+        nbytes = self.sc.lane_umi_workspace_bytes(self.N, self.max_tiles, int(U))
+        self.d_umi, self.umi_bytes = self.sc.malloc(max(1, nbytes)), nbytes
+        try:
+            self.U = int(U)
+            self._umi_begin()
+        except Exception:
+            self.sc.free(self.d_umi)
+            self.d_umi, self.umi_bytes, self.U = 0, 0, 0
+            raise
+
+    def _umi_begin(self):
+        self.sc._ck(self.sc._lib.wd_lane_umi_begin(self._h, self.U, ctypes.c_void_p(self.d_umi), self.umi_bytes))
+
+    def umi_add(self, tables, tile_indices: Sequence[int], well_stride: int = 1):
+        """Packs the UMI reads of resident tiles.  tables: a TileBatch of the U UMI cycles, or the ctypes pointer
+        tables Scanner._tables makes (the planes n x U; the filters are not looked at); tile_indices as `add`
+        takes them.  Independent of `add` in order and batching."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        idx = [int(t) for t in tile_indices]
+        if isinstance(tables, TileBatch):
+            tb = tables
+            if len(idx) != tb.n_tiles or tb.L != self.U or tb.N != self.N:
+                raise ValueError("the batch has %d tiles of %d wells and %d cycles; %d indices for a lane of %d wells "
+                                 "and %d UMI cycles" % (tb.n_tiles, tb.N, tb.L, len(idx), self.N, self.U))
+            tables, well_stride = tb.tables, tb.interleave
+        pt = tables[0]
+        if self.U and len(pt) < len(idx) * self.U:
+            raise ValueError("the plane table must hold n_tiles x U pointers")
+        ti = (ctypes.c_int * max(1, len(idx)))(*idx)
+        self.sc.set_option("well_stride", well_stride)
+        try:
+            self.sc._ck(self.sc._lib.wd_lane_umi_add(self._h, len(idx), ti, pt))
+        finally:
+            self.sc.set_option("well_stride", 1)
+
+    def umi_keys(self) -> np.ndarray:
+        """uint64 [max_tiles * N]: the UMI read of every well that got UMI planes, packed as index_keys packs an
+        index read (the key array of the UMI workspace; it lies where include/welldup_laneumi.h's arithmetic puts it:
+        behind the plane pointers and the tile indices)."""
+        up = lambda v: (v + 255) // 256 * 256
+        at = up(8 * self.max_tiles * self.U) + up(4 * self.max_tiles)
+        return self.sc.d2h(self.d_umi + at, 8 * self.N * self.max_tiles, np.uint64)
+
+    def umi(self, max_e: int = 0, max_family: int = 256):
+        """After finish() of a lane with a UMI part, any number of times, before or after every other pass
+        (wd_lane_umi, include/welldup_laneumi.h): the wells of every family of 2 .. max_family wells under the labels
+        the finish left are grouped by their UMI read - a molecule is a connected component under "at most max_e UMI
+        cycles differ" -, a larger family is counted and not looked into.
+        -> (lane row int64 [27]: [Wells, UmiRedundant, Lone, Families, Molecules, DistinctUmis, SplitFamilies,
+        SplitWells, WithN, LargeFamilies, LargeWells, MolPerFamily[8], MoleculeSize[8]], the histograms in bins of 1, 2,
+        3, 4, 5-8, 9-16, 17-64 and 65 or more; tile rows int64 [max_tiles, 3]: [Wells, UmiRedundant, Lone] by the well's
+        own tile).  The scratch is allocated for the call and released.  max_e outside 0..3, max_family outside 2..1024,
+        a lane without a UMI part, a tile that has reads but no UMI planes (or the reverse) or a call before a
+        successful finish raises ValueError."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        lane_row = np.zeros(_lib.LANEUMI_LANE_COLS, dtype=np.int64)
+        tile_rows = np.zeros((self.max_tiles, _lib.LANEUMI_TILE_COLS), dtype=np.int64)
+        self._with_scratch(self.sc.lane_umi_scratch_bytes(self.max_tiles, self.N),
+                           lambda d_scratch, sbytes: self.sc._lib.wd_lane_umi(
+                               self._h, int(max_e), int(max_family), d_scratch, sbytes,
+                               lane_row.ctypes.data_as(ctypes.c_void_p), tile_rows.ctypes.data_as(ctypes.c_void_p)))
+        return lane_row, tile_rows
 
     def add(self, tb: "TileBatch", tile_indices: Sequence[int]):
         """Adds the tiles of a resident batch (a plane per cycle); tile_indices[i]: slot i's number in the lane,
@@ -999,10 +1085,10 @@ class LaneDups:
     def close(self):
         """Drops the lane, finished or not, and frees the workspace."""
         self._end()
-        for ptr in (self.d_ws, self.d_labels, self.d_near_labels, self.d_index, self.d_qual):
+        for ptr in (self.d_ws, self.d_labels, self.d_near_labels, self.d_index, self.d_qual, self.d_umi):
             if ptr:
                 self.sc.free(ptr)
-        self.d_ws = self.d_labels = self.d_near_labels = self.d_index = self.d_qual = 0
+        self.d_ws = self.d_labels = self.d_near_labels = self.d_index = self.d_qual = self.d_umi = 0
 
 
 class TileBatch:
