@@ -75,13 +75,20 @@ and the UMI keys: what the pass reads of a lane of pairs -, on three inputs: the
 further cycles of the same synthetic tiles: a planted copy carries its original's UMI), the `--equal` lane (one Large
 family: counted, never looked into) and a lane of three tiles whose odd wells repeat their left neighbour, their UMI
 too but for its last cycle (pairs only: k_lu_pairs does everything, a quarter of the pairs equal, the others one apart).
+`--keep [--min-q Q]` times LaneDups.keep(Q) (the best well of each family as a keep mask, include/welldup_lanekeep.h) per
+tile of the lane, with and without the masks, beside LaneDups.gc(0), LaneDups.qualities(0), the equality finish and
+Scanner.stream_read_gbs over as many bytes as the pass reads - every quality row, label and members in k_lk_score, label,
+members and the score in k_lk_mark: 4 ceil(cycles / 10) + 18 bytes per well -, on three inputs: the planted lane (a
+planted copy carries its original's qualities: every family ties and its root stays, one atomic per family member),
+the `--equal` lane with one quality and the `--equal` lane with random qualities (one family holds every well: the
+case the grouping and the two skips of k_lk_score exist for).
 For per-kernel times run it under
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/lanedups_probe.py
 
 (the k_ld_* rows of the stats are this stage, k_li_* the index part, k_lm_* the mismatch pass, k_lg_* the distance pass,
 k_lq_* the quality part, k_ls_* the saturation pass, k_lt_* the top pass, k_lh_* the hops pass, k_lgc_* the GC pass,
-k_lc_* the consensus pass and the gather of the UMI pass, k_lu_* the UMI pass, k_td_* the per-tile classes, k_dense_* the scan)."""
+k_lc_* the consensus pass and the gather of the UMI pass, k_lu_* the UMI pass, k_lk_* the keep pass, k_td_* the per-tile classes, k_dense_* the scan)."""
 import argparse
 import os
 import sys
@@ -136,7 +143,13 @@ ap.add_argument("--umi-e", type=int, default=1, metavar="E", help="the differing
 ap.add_argument("--quality", action="store_true",
                 help="also time LaneDups.qual_add beside add and LaneDups.qualities(K) beside mismatches(K) (needs "
                      "--hamming; three inputs with --equal)")
+ap.add_argument("--keep", action="store_true",
+                help="also time LaneDups.keep(Q) beside gc(0), qualities(0), the equality finish and a pure read of as many "
+                     "bytes (three inputs with --equal)")
+ap.add_argument("--min-q", type=int, default=15, metavar="Q", help="the min_q of --keep (0..63)")
 a = ap.parse_args()
+if not 0 <= a.min_q <= 63:
+    ap.error("--min-q takes 0..63")
 if a.mismatches and not a.hamming:
     ap.error("--mismatches needs --hamming K")
 if a.consensus and not a.hamming:
@@ -735,4 +748,76 @@ if a.umi:
     pr.close()
     three.free()
     uthree.free()
+
+
+def time_keep(acc, tiles_n, t_finish, what):
+    """LaneDups.keep(Q) without and with the masks and, on the same labels, LaneDups.gc(0) and LaneDups.qualities(0), each
+    after a first call that pays for loading the kernels; and a pure read of as many bytes as the pass reads, from the
+    accumulator's own quality workspace"""
+    acc.keep(a.min_q)
+    (krow, ktiles), t_k = clock(lambda: acc.keep(a.min_q))
+    (_, _, masks), t_km = clock(lambda: acc.keep(a.min_q, masks=True))
+    acc.gc(0)
+    (grow, _, _), t_g = clock(lambda: acc.gc(0))
+    acc.qualities(0)
+    q, t_q = clock(lambda: acc.qualities(0))
+    nbytes = tiles_n * n * (4 * ((a.cycles + 9) // 10) + 18)
+    gbs = sc.stream_read_gbs(acc.d_qual, min(nbytes, acc.qual_bytes))
+    t_read = nbytes / gbs / 1e6
+    weight = np.array([max(e for e in QUALITY_BINS if e <= v) for v in range(64)])
+    weight[weight < a.min_q] = 0
+    assert krow[0] == krow[1] + krow[2] == grow[0] and krow[2] == grow[3] and krow[6] == grow[2] and \
+        (ktiles.sum(axis=0) == krow[:6]).all() and krow[9:].sum() == krow[6] and krow[7] == krow[6] - krow[9] == krow[3] and \
+        krow[4] + krow[5] == (weight * q[2]).sum() and sum(int(m.sum()) for m in masks.values()) == krow[1], \
+        "the keep rows do not add up"
+    print("%s: keep, min_q %d: %d PF wells, %d kept, %d dropped, %d families, %d of them moved; mean score per base of the kept "
+          "%.3f, of the families' first wells %.3f, of the dropped %.3f; families by gain %s"
+          % (what, a.min_q, krow[0], krow[1], krow[2], krow[6], krow[7], krow[4] / max(1, krow[1] * a.cycles),
+             krow[8] / max(1, krow[6] * a.cycles), krow[5] / max(1, krow[2] * a.cycles), " ".join(str(v) for v in krow[9:])))
+    print("  %-22s %9.3f ms  (%.4f ms per tile; with the masks: %.4f; %.1f MB per tile at %.0f GB/s; a pure read of as many "
+          "bytes: %.4f ms per tile at %.0f GB/s; keep / read = %.2f; gc(0): %.4f; keep / gc = %.2f; qualities(0): %.4f; the "
+          "equality finish: %.4f)"
+          % ("lane keep", t_k, t_k / tiles_n, t_km / tiles_n, nbytes / tiles_n / 1e6, nbytes / t_k / 1e6, t_read / tiles_n, gbs,
+             t_k / t_read, t_g / tiles_n, t_k / t_g, t_q / tiles_n, t_finish / tiles_n))
+
+
+if a.keep:
+    print("keep pass: quality workspace %.2f GB, scratch %.2f GB"
+          % (sc.lane_qual_workspace_bytes(n, a.tiles, a.cycles) / 1e9, sc.lane_keep_scratch_bytes(a.tiles, n) / 1e9))
+    tb = TileBatch(sc, a.batch, a.cycles, n)
+    lk = LaneDups(sc, n, a.tiles, a.cycles)
+    lk.qual_begin(QUALITY_BINS)
+    for tiles in batches:
+        if len(tiles) != tb.n_tiles:
+            tb = TileBatch(sc, len(tiles), a.cycles, n, reuse=tb)
+        fill(tb, tiles)
+        lk.add(tb, tiles)
+        lk.qual_add(tb, tiles)
+    _, k_fin = clock(lambda: lk.finish())
+    time_keep(lk, max(1, a.tiles), k_fin, "the planted lane")
+    lk.close()
+    tb.free()
+    if a.equal:
+        three = TileBatch(sc, 3, a.cycles, n)
+        rng = np.random.default_rng(13)
+        for name, random_q in (("every read equal with one quality, three tiles", False),
+                               ("every read equal with random qualities, three tiles", True)):
+            for c in range(a.cycles):
+                plane = (rng.integers(1, 64, n).astype(np.uint8) << 2 if random_q else np.uint8(37 << 2)) | np.uint8(c % 4)
+                plane = np.ascontiguousarray(np.broadcast_to(plane, (n,)), dtype=np.uint8)
+                for s in range(3):                   # (the other two tiles: the same qualities, shifted along the tile)
+                    sc.h2d(three.plane_ptr(s, c), np.roll(plane, 1009 * s) if random_q and s else plane)
+            for s in range(3):
+                sc.h2d(three.filter_ptr(s), np.ones(n, dtype=np.uint8))
+            sc.synchronize()
+            eq = LaneDups(sc, n, 3, a.cycles)
+            eq.qual_begin(QUALITY_BINS)
+            eq.add(three, [0, 1, 2])
+            eq.qual_add(three, [0, 1, 2])
+            _, e_fin = clock(lambda: eq.finish())
+            time_keep(eq, 3, e_fin, name)
+            erow = eq.keep(a.min_q)[0]
+            assert erow[1] == 1 and erow[6] == 1 and (erow[7] == 0 or random_q), "the equal lane is not one family with one well kept"
+            eq.close()
+        three.free()
 sc.close()

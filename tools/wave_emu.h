@@ -1,5 +1,5 @@
 // wave_emu.h - what a kernel's source needs to run on the CPU as it stands (tools/lane_mismatch_emu.cpp,
-// tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp, tools/lane_hops_emu.cpp, tools/lane_gc_emu.cpp, tools/lane_consensus_emu.cpp, tools/lane_umi_emu.cpp,
+// tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp, tools/lane_hops_emu.cpp, tools/lane_gc_emu.cpp, tools/lane_consensus_emu.cpp, tools/lane_umi_emu.cpp, tools/lane_keep_emu.cpp,
 // tools/read_classes_emu.cpp, tools/near_emu.cpp, tools/dup_sets_emu.cpp, tools/lane_index_emu.cpp, tools/gen_rings_emu.cpp): the 256 lanes of a
 // workgroup are fibers (ucontext) that a round-robin scheduler switches at the collectives - __syncthreads is a
 // rendezvous of the workgroup, __ballot and __shfl of a wave -, LDS is the kernel's static storage, an atomic add or
@@ -26,6 +26,8 @@
 // to show that they notice (without a value: in the __hip_atomic compare-and-swaps, whatever their tag; =2: in those
 // tagged kEmuUnion alone; =3: in the plain atomicCAS alone, so that each build of an emulator that has both kinds
 // shows one of them); nothing else builds that way.
+// -DWAVE_EMU_TORN_MIN breaks atomicMin the same way - a scheduling point between its load and its store, so that a
+// lane writes over a smaller value another lane stored in between (tools/lane_keep_emu.cpp); off by default.
 // -DWAVE_EMU_TORN_ADD breaks atomicAdd the same way, for an emulator whose kernels take their places by adds
 // (tools/lane_consensus_emu.cpp; tools/gen_rings_emu.cpp, which clears emu_torn_add for its count pass so that the
 // fill pass's claim of an LDS slot alone is broken).
@@ -146,7 +148,13 @@ template <class T> static T atomicCAS(T *p, T expect, T v) {
     *p = v;
     return o;
 }
-template <class T, class U> static T atomicMin(T *p, U v) { emu_point(); T o = *p; if ((T)v < o) *p = (T)v; return o; }
+// emu_mins counts the atomicMin calls since an emulator last cleared it (tools/lane_keep_emu.cpp holds a kernel to a bound on them).
+static long emu_mins = 0;
+#ifdef WAVE_EMU_TORN_MIN                           // (the deliberate bug of a minimum: another fiber may lower the word between its load and its store)
+template <class T, class U> static T atomicMin(T *p, U v) { emu_point(); emu_mins++; T o = *p; emu_point(); if ((T)v < o) *p = (T)v; return o; }
+#else
+template <class T, class U> static T atomicMin(T *p, U v) { emu_point(); emu_mins++; T o = *p; if ((T)v < o) *p = (T)v; return o; }
+#endif
 template <class T, class U> static T atomicOr(T *p, U v) { emu_point(); T o = *p; *p |= (T)v; return o; }
 // the clang builtins of the kernels that say their memory order and scope: the order and the scope mean nothing here
 #define __HIP_MEMORY_SCOPE_AGENT 4

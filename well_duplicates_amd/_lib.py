@@ -253,6 +253,18 @@ LANEUMI_TILE_COLS = 3
 LANEUMI_BINS = 8
 LANEUMI_BIN_NAMES = ("1", "2", "3", "4", "5-8", "9-16", "17-64", "65+")
 
+# name -> (restype, argtypes); every symbol include/welldup_lanekeep.h declares beyond those above
+LANEKEEP_PROTOTYPES = {
+    "wd_lane_keep_scratch": (_i, [_i, _i64, ctypes.POINTER(_sz)]),
+    "wd_lane_keep": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp]),
+}
+LANEKEEP_LANE_COLS = 17
+LANEKEEP_TILE_COLS = 6
+LANEKEEP_GAIN_BINS = 8
+LANEKEEP_MAX_Q = 63
+LANEKEEP_DEFAULT_MIN_Q = 15
+LANEKEEP_GAIN_NAMES = ("0", "1-9", "10-19", "20-49", "50-99", "100-199", "200-499", "500+")
+
 _lib = None
 
 
@@ -339,7 +351,7 @@ def unit_of_kernel(kernel: str) -> str:
         return "ingest"
     if kernel.startswith("k_sets"):
         return "sets"
-    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_", "k_ls_", "k_lt_", "k_lh_", "k_lgc_", "k_lc_", "k_lu_")):
+    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_", "k_ls_", "k_lt_", "k_lh_", "k_lgc_", "k_lc_", "k_lu_", "k_lk_")):
         return "tiledups"
     return "scan"
 
@@ -404,7 +416,7 @@ def load():
             list(LANEDISTANCE_PROTOTYPES.items()) + list(LANEQUALITY_PROTOTYPES.items()) + \
             list(LANESATURATION_PROTOTYPES.items()) + list(LANETOP_PROTOTYPES.items()) + \
             list(LANEHOPS_PROTOTYPES.items()) + list(LANEGC_PROTOTYPES.items()) + list(LANECONSENSUS_PROTOTYPES.items()) + \
-            list(LANEUMI_PROTOTYPES.items()):
+            list(LANEUMI_PROTOTYPES.items()) + list(LANEKEEP_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

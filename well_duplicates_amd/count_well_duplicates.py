@@ -27,7 +27,8 @@ Differences from the reference, all deliberate:
     --lane-dups-saturation, --lane-dups-top, --lane-dups-top-out, --lane-dups-hops, --lane-dups-hops-mismatches,
     --lane-dups-hops-out, --lane-dups-gc, --lane-dups-gc-bins, --lane-dups-gc-max-n, --lane-dups-gc-out,
     --lane-dups-consensus, --lane-dups-consensus-max-d, --lane-dups-consensus-max-family, --lane-dups-consensus-out,
-    --lane-dups-umi, --lane-dups-umi-mismatches, --lane-dups-umi-max-family, --lane-dups-umi-out;
+    --lane-dups-umi, --lane-dups-umi-mismatches, --lane-dups-umi-max-family, --lane-dups-umi-out,
+    --lane-dups-keep, --lane-dups-keep-min-q, --lane-dups-keep-out;
   * --all-wells --dup-sets groups every tile's wells into duplicate sets and follows each lane's report
     with their counts and the exact duplication (report.write_dup_sets);
   * --all-wells --tile-dups groups every tile's PF wells into classes of equal reads, wherever on the tile they
@@ -66,6 +67,9 @@ Differences from the reference, all deliberate:
     two wells with the same read and different UMIs are two molecules - the lane's duplication and library size with
     the UMI beside those without, the copies that are molecules of their own, and the UMI reads merged as read errors
     (report.write_lane_umi);
+    --lane-dups-keep acts on all of it: of every class or cluster the well with the highest summed base quality is
+    kept and the others are dropped (report.write_lane_keep), and --lane-dups-keep-out DIR writes the lane's .filter
+    files with the PF bit cleared on the dropped wells - a deduplicated lane for every downstream converter;
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
@@ -73,6 +77,7 @@ from __future__ import annotations
 
 import math
 import os
+import struct
 import sys
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 from concurrent.futures import ThreadPoolExecutor
@@ -386,7 +391,32 @@ def parse_args(argv=None):
     p.add_argument("--lane-dups-umi-out", default=None, metavar="FILE",
                    help="with --lane-dups-umi: also write the two histograms and the tile rows to FILE, tab-separated: "
                         "lane, table, key, wells, umi_redundant, lone")
+    p.add_argument("--lane-dups-keep", action="store_true",
+                   help="with --lane-dups: of every class (every cluster with --lane-dups-hamming K) keep the well with "
+                        "the highest sum of reported base qualities at or above --lane-dups-keep-min-q - the choice of "
+                        "Picard's MarkDuplicates; the first well among equals - and drop the others, and print, after "
+                        "every other block of the lane, the kept and the dropped wells, the families whose kept well is "
+                        "not their first well, the mean score per base of the kept, the first and the dropped wells, and "
+                        "the families by what the choice gained.  A quality counts as the lower edge of its bin "
+                        "(--lane-dups-quality-bins): exact where the edges are the instrument's levels, a lower bound "
+                        "otherwise.  Keeps the reported qualities beside the reads as --lane-dups-quality does (given or "
+                        "not) and takes 10 bytes of device memory per well of the lane besides.  One well per UMI "
+                        "molecule (--lane-dups-umi) is not offered: the molecules are not kept after that pass")
+    p.add_argument("--lane-dups-keep-min-q", type=int, default=None, metavar="Q",
+                   help="with --lane-dups-keep: a base counts from quality Q on (0..%d, default %d)"
+                        % (_lib.LANEKEEP_MAX_Q, _lib.LANEKEEP_DEFAULT_MIN_Q))
+    p.add_argument("--lane-dups-keep-out", default=None, metavar="DIR",
+                   help="with --lane-dups-keep: for every scanned tile write DIR/L00<lane>/<the name of the tile's .filter "
+                        "file>, the tile's filter file with the PF bit cleared on every dropped well.  Put in place of "
+                        "the run directory's own files they make bcl2fastq or BCL Convert emit the deduplicated lane")
     args = p.parse_args(argv)
+    if args.lane_dups_keep and not args.lane_dups:
+        p.error("--lane-dups-keep needs --lane-dups")
+    for flag, value in (("min-q", args.lane_dups_keep_min_q), ("out", args.lane_dups_keep_out)):
+        if value is not None and not args.lane_dups_keep:
+            p.error("--lane-dups-keep-%s needs --lane-dups-keep" % flag)
+    if args.lane_dups_keep_min_q is not None and not 0 <= args.lane_dups_keep_min_q <= _lib.LANEKEEP_MAX_Q:
+        p.error("--lane-dups-keep-min-q takes 0..%d, not %d" % (_lib.LANEKEEP_MAX_Q, args.lane_dups_keep_min_q))
     if args.lane_dups_umi is not None and not args.lane_dups:
         p.error("--lane-dups-umi needs --lane-dups")
     for flag, value in (("mismatches", args.lane_dups_umi_mismatches), ("max-family", args.lane_dups_umi_max_family),
@@ -456,7 +486,7 @@ def parse_args(argv=None):
             p.error("--lane-dups-saturation-%s takes %d..%d, not %d" % (flag, lo, hi, value))
     if args.lane_dups_quality and not args.lane_dups:
         p.error("--lane-dups-quality needs --lane-dups")
-    if args.lane_dups_quality_bins is not None and not args.lane_dups_quality:
+    if args.lane_dups_quality_bins is not None and not (args.lane_dups_quality or args.lane_dups_keep):
         p.error("--lane-dups-quality-bins needs --lane-dups-quality")
     if args.lane_dups_quality_max_d is not None and not args.lane_dups_quality:
         p.error("--lane-dups-quality-max-d needs --lane-dups-quality")
@@ -661,17 +691,19 @@ def lane_cluster_members(class_labels: np.ndarray, cluster_labels: np.ndarray):
 
 def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0, index: int = 0,
                          mismatch: int = 0, distance: int = 0, quality: int = 0, saturation: int = 0, top: int = 0,
-                         hops: int = 0, gc: int = 0, consensus: int = 0, umi: int = 0, umi_scratch: int = 0):
+                         hops: int = 0, gc: int = 0, consensus: int = 0, umi: int = 0, umi_scratch: int = 0,
+                         keep: int = 0):
     """--lane-dups: the accumulator's workspace - with --lane-dups-hamming plus the scratch of the near finish, with
     --lane-dups-index plus the index workspace, with --lane-dups-mismatches or --lane-dups-distance plus that pass's
     scratch, with --lane-dups-quality plus the quality workspace and that pass's scratch, with --lane-dups-saturation,
     --lane-dups-top, --lane-dups-hops, --lane-dups-gc or --lane-dups-consensus plus that pass's scratch, with
-    --lane-dups-umi plus the UMI workspace (umi) and that pass's scratch (umi_scratch) - against the free device memory,
-    before anything is loaded."""
-    need += scratch + index + mismatch + distance + quality + saturation + top + hops + gc + consensus + umi + umi_scratch
+    --lane-dups-umi plus the UMI workspace (umi) and that pass's scratch (umi_scratch), with --lane-dups-keep plus that
+    pass's scratch (keep; and the quality workspace, in `quality`, if --lane-dups-quality has not asked for it) -
+    against the free device memory, before anything is loaded."""
+    need += scratch + index + mismatch + distance + quality + saturation + top + hops + gc + consensus + umi + umi_scratch + keep
     if need > free:
         raise MemoryError("--lane-dups needs %.2f GB of device memory for a lane of %d tiles x %d wells x %d cycles "
-                          "(%d bytes%s%s%s%s%s%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
+                          "(%d bytes%s%s%s%s%s%s%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
                               need / 1e9, tiles, wells, cycles, need,
                               ", %d of them for --lane-dups-hamming" % scratch if scratch else "",
                               ", %d of them for --lane-dups-index" % index if index else "",
@@ -684,6 +716,7 @@ def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: i
                               ", %d of them for --lane-dups-gc" % gc if gc else "",
                               ", %d of them for --lane-dups-consensus" % consensus if consensus else "",
                               ", %d of them for --lane-dups-umi" % (umi + umi_scratch) if umi + umi_scratch else "",
+                              ", %d of them for --lane-dups-keep" % keep if keep else "",
                               free / 1e9, free))
 
 
@@ -697,7 +730,7 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
                dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0, lane_near=0, lane_pair_budget=0,
                lane_index=None, lane_mismatch=None, lane_distance=None, lane_quality=None, lane_saturation=None,
-               lane_top=0, lane_hops=None, lane_gc=None, lane_consensus=None, lane_umi=None):
+               lane_top=0, lane_hops=None, lane_gc=None, lane_consensus=None, lane_umi=None, lane_keep=None):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
@@ -743,6 +776,10 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     loaded by the same job list as the index batch and fed to LaneDups.umi_add, reused and released with the scan
     batch; after every other pass of the lane LaneDups.umi(E, max family): into["lumi"][lane] = LaneUmiCounts, on the
     labels the lane was left with.
+    lane_keep = (min_q, edges, out directory or None) (with lane_dups): the accumulator gets a quality part with these
+    bins unless lane_quality has given it one (the two share it), and after every other pass of the lane
+    LaneDups.keep(min_q): into["lkeep"][lane] = LaneKeepCounts, on the labels the lane was left with; with a
+    directory the lane's filter files go there at once (write_lane_keep_filters), the masks are not kept.
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -759,6 +796,7 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     assert not index_cycles or (lane_dups and interleave == 1)
     umi_cycles, umi_e, umi_family = lane_umi if lane_umi else ([], 0, 0)
     assert not umi_cycles or (lane_dups and interleave == 1)
+    qual_edges = lane_quality[0] if lane_quality is not None else lane_keep[1] if lane_keep is not None else None
     counts, logs = (into["counts"], into["logs"]) if into else ({}, {})
     batches = []                            # (lane, [tiles]), never across a lane's end: an error stays its lane's (start_ahead)
     for lane, tiles in lane_tiles:
@@ -951,13 +989,13 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                         ld = lane_acc["ld"] = LaneDups(sc, n_clusters, len(names), len(cycle_list))
                         if index_cycles:
                             ld.index_begin(len(index_cycles))
-                        if lane_quality is not None:
-                            ld.qual_begin(lane_quality[0])
+                        if qual_edges is not None:
+                            ld.qual_begin(qual_edges)
                         if umi_cycles:
                             ld.umi_begin(len(umi_cycles))
                     lane_acc["lane"] = lane
                 ld.add(tb, [names.index(t) for t in chunk])
-                if lane_quality is not None:
+                if qual_edges is not None:
                     ld.qual_add(tb, [names.index(t) for t in chunk])
                 if index_cycles:
                     ld.index_add(index_tb[id(tb)], [names.index(t) for t in chunk])
@@ -1019,6 +1057,14 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                         into["lumi"][lane] = report.LaneUmiCounts.from_rows(
                             *ld.umi(umi_e, umi_family), names, lane_near, umi_e, umi_family, len(umi_cycles), left.pf,
                             left.redundant)
+                    if lane_keep is not None:
+                        kept = ld.keep(lane_keep[0], masks=lane_keep[2] is not None)
+                        into["lkeep"][lane] = report.LaneKeepCounts.from_rows(kept[0], kept[1], names, lane_near, lane_keep[0],
+                                                                              qual_edges, len(cycle_list))
+                        if lane_keep[2] is not None:
+                            write_lane_keep_filters(lane_keep[2], lane, {t: reader.get_tile(lane, t) for t in names},
+                                                    {names[ti]: m for ti, m in kept[2].items()})
+                        del kept
                     del lane_labels, got
                 _lap("batch %d: lane classes" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
@@ -1117,6 +1163,30 @@ def write_lane_members(path, members, index=None):
                               for a, b, c, d, e, f in zip(*cols))
             else:
                 fh.writelines("%s\t%s\t%d\t%s\t%d\n" % (lane, names[a], b, names[c], d) for a, b, c, d in zip(*cols))
+
+
+def write_keep_filter(path, filter_bytes: np.ndarray, mask: np.ndarray):
+    """A .filter file as bcl.Tile.read_filter reads it: the 12-byte header (0, 3, N), then N bytes, each the input
+    file's byte with bit 0 replaced by the mask's - 1 for a kept well, 0 for any other."""
+    filt, mask = np.asarray(filter_bytes, dtype=np.uint8), np.asarray(mask, dtype=np.uint8)
+    if filt.shape != mask.shape or filt.ndim != 1:
+        raise ValueError("a filter of %s bytes and a mask of %s" % (filt.shape, mask.shape))
+    with open(path, "wb") as fh:
+        fh.write(struct.pack("<III", 0, 3, filt.shape[0]))
+        fh.write(((filt & 0xFE) | (mask & 1)).astype(np.uint8).tobytes())
+
+
+def write_lane_keep_filters(out_dir, lane, tiles, masks):
+    """--lane-dups-keep-out: out_dir/L00<lane>/<the name of the tile's own .filter file> for every tile of masks
+    ({tile: uint8 [N]}, LaneDups.keep's by the tile's name); tiles = {tile: its bcl.Tile}.  -> the paths written."""
+    lane_dir = str(lane) if str(lane).startswith("L") else "L%03d" % int(lane)
+    os.makedirs(os.path.join(out_dir, lane_dir), exist_ok=True)
+    paths = []
+    for tile in sorted(masks, key=str):
+        path = os.path.join(out_dir, lane_dir, os.path.basename(tiles[tile].filter_file))
+        write_keep_filter(path, tiles[tile].read_filter(), masks[tile])
+        paths.append(path)
+    return paths
 
 
 def main(argv=None, exiting=False):
@@ -1280,6 +1350,10 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 if args.lane_dups_umi else []
             umi = (umi_cycles, 1 if args.lane_dups_umi_mismatches is None else args.lane_dups_umi_mismatches,
                    args.lane_dups_umi_max_family or 256) if umi_cycles else None
+            keep = None
+            if args.lane_dups_keep:
+                keep = (_lib.LANEKEEP_DEFAULT_MIN_Q if args.lane_dups_keep_min_q is None else args.lane_dups_keep_min_q,
+                        args.lane_dups_quality_edges, args.lane_dups_keep_out)
             ntn = 5 + 2 * levels + len(report.CLASS_BIN_NAMES) if near_k else 0
             rows = np.zeros((len(mine), ncnt + nsets + ntd + ntn), dtype=np.int64)
             logs = {}
@@ -1335,6 +1409,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                                 out=out_fh)
                 if umi is not None:
                     report.write_lane_umi(lane, results["lumi"][lane], verbose=not args.summary_only, out=out_fh)
+                if keep is not None:
+                    report.write_lane_keep(lane, results["lkeep"][lane], verbose=not args.summary_only, out=out_fh)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
@@ -1343,7 +1419,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
                            "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}, "lnear": {}, "lindex": {},
                            "lmindex": {}, "lmismatch": {}, "ldistance": {}, "lquality": {}, "lsaturation": {}, "ltop": {},
-                           "lhops": {}, "lgc": {}, "lconsensus": {}, "lumi": {}}
+                           "lhops": {}, "lgc": {}, "lconsensus": {}, "lumi": {}, "lkeep": {}}
 
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
@@ -1375,8 +1451,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                          distance=sc.lane_distance_scratch_bytes(
                                              n_targets, len(tiles), len(tiles) <= _lib.LANEDISTANCE_MATRIX_MAX_TILES)
                                          if args.lane_dups_distance else 0,
-                                         quality=sc.lane_qual_workspace_bytes(n_targets, len(tiles), len(cycle_list)) +
-                                         sc.lane_qual_scratch_bytes(len(tiles)) if quality_d is not None else 0,
+                                         quality=(sc.lane_qual_workspace_bytes(n_targets, len(tiles), len(cycle_list)) +
+                                                  sc.lane_qual_scratch_bytes(len(tiles)))
+                                         if quality_d is not None or keep is not None else 0,
                                          saturation=sc.lane_saturation_scratch_bytes(n_targets, len(tiles),
                                                                                      saturation[4] > 0)
                                          if saturation is not None else 0,
@@ -1392,7 +1469,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                          umi=sc.lane_umi_workspace_bytes(n_targets, len(tiles), len(umi_cycles))
                                          if umi is not None else 0,
                                          umi_scratch=sc.lane_umi_scratch_bytes(len(tiles), n_targets)
-                                         if umi is not None else 0)
+                                         if umi is not None else 0,
+                                         keep=sc.lane_keep_scratch_bytes(len(tiles), n_targets) if keep is not None else 0)
                 if err is None:             # (a rank whose setup failed has nothing to scan: it goes to the flag)
                     scan_lanes(sc, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                                max(0, args.tile_batch), args.threads,
@@ -1415,7 +1493,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                lane_hops=(1 if args.lane_dups_hops_mismatches is None else args.lane_dups_hops_mismatches,
                                           args.lane_dups_hops) if args.lane_dups_hops is not None else None,
                                lane_gc=(gc_max_n, args.lane_dups_gc_bins or 20) if args.lane_dups_gc else None,
-                               lane_consensus=consensus, lane_umi=umi)
+                               lane_consensus=consensus, lane_umi=umi, lane_keep=keep)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
                     if args.tile_dups_out and near_k:

@@ -15,7 +15,8 @@
 // (lane_top.inc) read label, members and the rows.  k_lh_tally (lane_hops.inc) reads label and the index workspace's
 // key, which k_li_pack alone writes (lane_index.inc, wd_lane_index_add, which refuses after a finish).  k_lgc_tally
 // (lane_gc.inc) reads label, members and every row of the lane.  k_lc_reserve and k_lc_scatter (lane_consensus.inc) read
-// label and members, k_lc_vote members and the rows of the voted families.
+// label and members, k_lc_vote members and the rows of the voted families.  k_lk_score and k_lk_mark (lane_keep.inc)
+// read label, members and the quality rows.
 #include "welldup_lanemismatch.h"
 
 namespace {

@@ -504,4 +504,9 @@ try {
 } WD_CATCH
 
 }  // extern "C"
+
+// What comes after this file in the unit is included from here, as lane_saturation.inc includes this file: the best
+// well of each of a lane's families (include/welldup_lanekeep.h), which reads the quality part of lane_quality.inc and
+// uses nothing of this file.
+#include "lane_keep.inc"
 #endif

@@ -28,7 +28,9 @@
 // and every row of the lane: its duplication against its reads' GC content of welldup_lanegc.h.  lane_consensus.inc (after
 // it) gathers the members of every family and counts their calls against the family's vote: welldup_laneconsensus.h.
 // lane_umi.inc (after it) groups the wells of every family by their UMI read, packed by lane_index.inc's kernel and
-// gathered by lane_consensus.inc's: welldup_laneumi.h.
+// gathered by lane_consensus.inc's: welldup_laneumi.h.  lane_keep.inc, which lane_top.inc includes at its end and
+// which so comes after all of lane_quality.inc, reads the labels, the members and the quality rows: the best well of
+// each family as a keep mask of welldup_lanekeep.h.
 #include <memory>
 
 #include "wd_ctx.h"

@@ -1837,3 +1837,80 @@ def write_lane_umi_tsv(lane, counts: LaneUmiCounts, out, header: bool = True) ->
     for tile in sorted(counts.tiles):
         t = counts.tiles[tile]
         print("%s\ttile\t%s\t%i\t%i\t%i" % (lane, tile, t[0], t[1], t[2]), file=out)
+
+
+LANE_KEEP_GAIN_NAMES = ("0", "1-9", "10-19", "20-49", "50-99", "100-199", "200-499", "500+")
+LANE_KEEP_TILE_COLS = 6
+LANE_KEEP_LANE_COLS = LANE_KEEP_TILE_COLS + 3 + len(LANE_KEEP_GAIN_NAMES)
+
+
+@dataclass
+class LaneKeepCounts:
+    """The best well of each of a lane's families (include/welldup_lanekeep.h, LaneDups.keep): the lane row's columns,
+    and per tile (by the tile's name) [PF, Kept, Dropped, MovedIn, SumKept, SumDropped]."""
+    k: int = 0
+    min_q: int = 15
+    cycles: int = 0
+    edges: List[int] = field(default_factory=lambda: [0])
+    pf: int = 0
+    kept: int = 0
+    dropped: int = 0
+    moved_in: int = 0
+    sum_kept: int = 0
+    sum_dropped: int = 0
+    families: int = 0
+    moved: int = 0
+    sum_roots: int = 0
+    gains: List[int] = field(default_factory=lambda: [0] * len(LANE_KEEP_GAIN_NAMES))
+    tiles: Dict[str, List[int]] = field(default_factory=dict)
+
+    @classmethod
+    def from_rows(cls, lane_row: Sequence[int], tile_rows: Sequence[Sequence[int]], tile_names: Sequence, k: int,
+                  min_q: int, edges: Sequence[int], cycles: int) -> "LaneKeepCounts":
+        """The two rows of LaneDups.keep(min_q); tile_names as LaneDupCounts.from_rows takes them; k: the K of
+        --lane-dups-hamming; edges: the quality bins' lower edges; cycles: the scanned cycles."""
+        b = [int(v) for v in lane_row]
+        assert len(b) == LANE_KEEP_LANE_COLS and 0 <= min_q <= 63
+        tiles = {}
+        for name, row in zip(tile_names, tile_rows):
+            assert len(row) == LANE_KEEP_TILE_COLS
+            if name is not None:
+                tiles[name] = [int(v) for v in row]
+        return cls(int(k), int(min_q), int(cycles), [int(e) for e in edges], *b[:9], b[9:], tiles)
+
+    @property
+    def weights(self) -> List[int]:
+        """the weight of every bin: its lower edge from min_q on"""
+        return [e if e >= self.min_q else 0 for e in self.edges]
+
+    def per_base(self, total: int, wells: int) -> Optional[float]:
+        """a summed score as a mean per base of `wells` wells; None without a base"""
+        return total / (wells * self.cycles) if wells and self.cycles else None
+
+
+def write_lane_keep(lane, counts: LaneKeepCounts, verbose: bool = False, out=None) -> None:
+    """The block that follows every other block of a lane under --lane-dups-keep: per-tile lines (verbose; tiles in
+    sorted order as write_report), then the summary - the kept and the dropped wells and their shares of PF, the
+    families and those whose kept well is not their first well -, the mean score per base of the kept wells (the
+    families' representatives and the single reads), of the first wells of the families and of the dropped wells, and
+    the families by gain."""
+    out = out or sys.stdout
+    c = counts
+    share = lambda v, of: v / of if of else 0.0
+    num = lambda v: "n/a" if v is None else "%.3f" % v
+    print(file=out)
+    if verbose:
+        for tile in sorted(c.tiles):
+            t = c.tiles[tile]
+            print("LaneKeep: %s\tTile: %s\tPF: %i\tKept: %i\tDropped: %i (%.5f)\tMovedIn: %i\tMeanScore kept: %s\tdropped: %s" % (
+                lane, tile, t[0], t[1], t[2], share(t[2], t[0]), t[3], num(c.per_base(t[4], t[1])),
+                num(c.per_base(t[5], t[2]))), file=out)
+    print("LaneKeepSummary: %s\tTiles: %i\tHamming: %i\tMinQ: %i\tCycles: %i\tWeights: %s\tPF: %i\tKept: %i (%.5f)\t"
+          "Dropped: %i (%.5f)\tFamilies: %i\tMoved: %i (%.5f of Families)" % (
+              lane, len(c.tiles), c.k, c.min_q, c.cycles, ",".join(str(w) for w in c.weights), c.pf, c.kept,
+              share(c.kept, c.pf), c.dropped, share(c.dropped, c.pf), c.families, c.moved, share(c.moved, c.families)),
+          file=out)
+    print("Mean score per base\tkept wells: %s\tfirst wells of families: %s\tdropped wells: %s" % (
+        num(c.per_base(c.sum_kept, c.kept)), num(c.per_base(c.sum_roots, c.families)),
+        num(c.per_base(c.sum_dropped, c.dropped))), file=out)
+    print("FamiliesByGain: %s" % "\t".join("%s: %i" % (n, v) for n, v in zip(LANE_KEEP_GAIN_NAMES, c.gains)), file=out)

@@ -346,6 +346,12 @@ class Scanner:
         the lane - where a family's range begins, the member list and the family table - plus the counters)."""
         return self._workspace_bytes(self._lib.wd_lane_umi_scratch, max_tiles, n_clusters)
 
+    def lane_keep_scratch_bytes(self, max_tiles: int, n_clusters: int) -> int:
+        """Device bytes LaneDups.keep needs beside the accumulator's workspaces (wd_lane_keep_scratch: 10 bytes per well
+        of the lane - the best of the family rooted there and the well's score - plus the counters, the tile indices and
+        the mask pointers)."""
+        return self._workspace_bytes(self._lib.wd_lane_keep_scratch, max_tiles, n_clusters)
+
     def lane_hops_scratch_bytes(self, max_tiles: int, M: int) -> int:
         """Device bytes LaneDups.hops needs beside the accumulator's workspaces for M listed keys
         (wd_lane_hops_scratch: the counters, the listing and the (M + 1)^2 cells of the matrix; it does not depend on
@@ -577,6 +583,7 @@ class LaneDups:
         self.d_qual, self.qual_bytes, self.qual_edges = 0, 0, None
         self.d_umi, self.umi_bytes, self.U = 0, 0, 0
         self.refused = None
+        self.added = []                                  # the tile indices given to add, in that order
         self._h = None
         try:
             self._begin(self.d_ws, self.ws_bytes)
@@ -593,6 +600,7 @@ class LaneDups:
     def restart(self):
         """Drops what has been added and begins another lane of the same shape in the same workspace."""
         self._end()
+        self.added = []
         self._begin(self.d_ws, self.ws_bytes)
         if self.I:
             self._index_begin()
@@ -855,6 +863,7 @@ class LaneDups:
         self.sc.set_option("well_stride", well_stride)
         try:
             self.sc._ck(self.sc._lib.wd_lane_dups_add(self._h, len(tile_indices), ti, pt, ft))
+            self.added.extend(int(t) for t in tile_indices)
         finally:
             self.sc.set_option("well_stride", 1)
 
@@ -943,6 +952,46 @@ class LaneDups:
                                self._h, int(max_n), d_scratch, sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
                                tile_rows.ctypes.data_as(ctypes.c_void_p), hist.ctypes.data_as(ctypes.c_void_p)))
         return lane_row, tile_rows, hist
+
+    def keep(self, min_q: int = _lib.LANEKEEP_DEFAULT_MIN_Q, masks: bool = False):
+        """After finish(), any number of times, before or after every other pass, on an accumulator with a quality part
+        (wd_lane_keep, include/welldup_lanekeep.h): of every family - a class, or a cluster under a near finish - the
+        well with the largest score is kept, the smallest id among equals, and the others are dropped; a well's score
+        is the sum over its cycles of its quality bin's lower edge where that is at least min_q.
+        -> (lane row int64 [17]: [PF, Kept, Dropped, MovedIn, SumKept, SumDropped, Families, Moved, SumRoots, GainBins
+        x 8], tile rows int64 [max_tiles, 6]: the first six by the well's own tile), and with `masks` a third: {tile
+        index: uint8 [N], 1 for a kept well and 0 for any other} for every tile that was added.  The scratch is
+        allocated for the call and released.  min_q outside 0..63, a call before a successful finish or without
+        qual_begin, or a tile that has reads but no qualities (or the reverse) raises ValueError."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        lane_row = np.zeros(_lib.LANEKEEP_LANE_COLS, dtype=np.int64)
+        tile_rows = np.zeros((self.max_tiles, _lib.LANEKEEP_TILE_COLS), dtype=np.int64)
+        tiles = sorted(self.added) if masks else []
+        d_masks = self.sc.malloc(max(1, len(tiles) * self.N)) if tiles else 0
+        try:
+            table = None
+            if tiles:
+                ptrs = [None] * self.max_tiles
+                for i, t in enumerate(tiles):
+                    ptrs[t] = d_masks + i * self.N
+                table = (ctypes.c_void_p * self.max_tiles)(*ptrs)
+            self._with_scratch(self.sc.lane_keep_scratch_bytes(self.max_tiles, self.N),
+                               lambda d_scratch, sbytes: self.sc._lib.wd_lane_keep(
+                                   self._h, int(min_q), d_scratch, sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
+                                   tile_rows.ctypes.data_as(ctypes.c_void_p), table))
+            if not masks:
+                return lane_row, tile_rows
+            out = {}
+            if tiles and self.N:
+                flat = self.sc.d2h(d_masks, len(tiles) * self.N, np.uint8).reshape(len(tiles), self.N)
+                out = {t: flat[i].copy() for i, t in enumerate(tiles)}
+            else:
+                out = {t: np.zeros(0, dtype=np.uint8) for t in tiles}
+            return lane_row, tile_rows, out
+        finally:
+            if d_masks:
+                self.sc.free(d_masks)
 
     def consensus(self, max_d: int = 0, max_family: int = 256):
         """After finish(), any number of times, before or after every other pass (wd_lane_consensus,
