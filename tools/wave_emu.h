@@ -1,6 +1,7 @@
 // wave_emu.h - what a kernel's source needs to run on the CPU as it stands (tools/lane_mismatch_emu.cpp,
 // tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp, tools/lane_hops_emu.cpp, tools/lane_gc_emu.cpp, tools/lane_consensus_emu.cpp, tools/lane_umi_emu.cpp, tools/lane_keep_emu.cpp,
-// tools/read_classes_emu.cpp, tools/near_emu.cpp, tools/dup_sets_emu.cpp, tools/lane_index_emu.cpp, tools/gen_rings_emu.cpp): the 256 lanes of a
+// tools/read_classes_emu.cpp, tools/near_emu.cpp, tools/dup_sets_emu.cpp, tools/lane_index_emu.cpp, tools/gen_rings_emu.cpp,
+// tools/scan_queue_emu.cpp): the 256 lanes of a
 // workgroup are fibers (ucontext) that a round-robin scheduler switches at the collectives - __syncthreads is a
 // rendezvous of the workgroup, __ballot and __shfl of a wave -, LDS is the kernel's static storage, an atomic add or
 // minimum or a compare-and-swap is a plain one (one fiber runs at a time), and the qualifiers are empty.  Include it, then the kernel's
@@ -52,7 +53,10 @@ static int4 make_int4(int x, int y, int z, int w) { return int4{x, y, z, w}; }
 struct uint2 { uint32_t x, y; };
 static uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{x, y}; }
 struct D3 { unsigned x, y, z; };
-constexpr int kEmuBlock = 256, kWave = 64;
+constexpr int kEmuBlock = 256;
+#ifndef WD_SHARED_H                                // (an emulator that included csrc/wd_shared.h before this header has the library's kWave)
+constexpr int kWave = 64;
+#endif
 #ifndef WAVE_EMU_UNIT_DEFS
 constexpr int kTdBlock = kEmuBlock, kSpread = 64, kFpCycles = 10, kLdCmpWords = 8;
 constexpr uint32_t kInvalid = 0xFFFFFFFFu;
@@ -73,9 +77,10 @@ asm(".text\n.globl emu_switch\n.type emu_switch,@function\nemu_switch:\n"
     "movq %rsp, (%rdi)\nmovq %rsi, %rsp\n"
     "popq %r15\npopq %r14\npopq %r13\npopq %r12\npopq %rbx\npopq %rbp\nret\n");
 #endif
-static D3 g_block;
+static D3 g_block, g_grid;
 #define threadIdx (D3{(unsigned)emu_lane, 0, 0})
 #define blockIdx g_block
+#define gridDim g_grid                             // (run_grid sets it: the launch's workgroups)
 #ifdef WAVE_EMU_FAST
 static void yield_() { emu_switch(&emu_fib[emu_lane].sp, emu_sched_sp); }
 #else
@@ -109,6 +114,23 @@ static int __shfl(int v, int src) {
     w.count++; if (!wave_complete_(w)) await_(w.gen, g);
     return w.val[par][src];
 }
+// the wave's other rendezvous (csrc/scan_queue.inc): a lane takes the value of the lane `d` below it (its own, where there
+// is none), of lane `src`, or of the first lane that stands at the call; the barrier of a wave is a rendezvous without a
+// value, and the fence that goes with it says nothing here - the emulation is sequentially consistent.
+static int __shfl_up(int v, int d) { const int lane = emu_lane % kWave; const int o = __shfl(v, lane >= d ? lane - d : lane); return o; }
+static int emu_readfirstlane(int v) {
+    WaveSync &w = emu_ws[emu_lane / kWave]; long g = w.gen; int par = g & 1, lane = emu_lane % kWave;
+    if (w.count == 0) w.pred[par] = 0;
+    w.pred[par] |= 1ull << lane; w.val[par][lane] = v;
+    w.count++; if (!wave_complete_(w)) await_(w.gen, g);
+    return w.val[par][__builtin_ctzll(w.pred[par])];
+}
+#define __builtin_amdgcn_readlane(v, src) __shfl((int)(v), (src))
+#define __builtin_amdgcn_readfirstlane(v) emu_readfirstlane((int)(v))
+#define __builtin_amdgcn_wave_barrier() ((void)__ballot(false))
+#define __builtin_amdgcn_fence(order, scope) ((void)0)
+// __attribute__((address_space(1))) of the kernels' global pointers: an empty attribute on the host
+#define address_space(n)
 #define __popcll __builtin_popcountll
 #define __ffsll __builtin_ffsll
 #define __clzll __builtin_clzll
@@ -171,7 +193,8 @@ template <class T, class U> static bool __hip_atomic_compare_exchange_strong(T *
     return true;
 }
 template <class T, class U> static T __hip_atomic_fetch_min(T *p, U v, int, int) { emu_point(); T o = *p; if ((T)v < o) *p = (T)v; return o; }
-template <class T, class U> static T __hip_atomic_fetch_add(T *p, U v, int, int) { emu_point(); T o = *p; *p += (T)v; return o; }
+template <class T, class U> static T __hip_atomic_fetch_add(T *p, U v, int, int) { return atomicAdd(p, v); }      // (a scheduling point, torn with -DWAVE_EMU_TORN_ADD, seen by emu_add_hook)
+template <class T, class U> static T __hip_atomic_fetch_or(T *p, U v, int, int) { return atomicOr(p, v); }
 template <class T, class U> static T __hip_atomic_fetch_sub(T *p, U v, int, int) { emu_point(); T o = *p; *p -= (T)v; return o; }
 template <class T, class U> static T __hip_atomic_exchange(T *p, U v, int, int) { emu_point(); T o = *p; *p = (T)v; return o; }
 #define __builtin_nontemporal_load(p) (*(p))
@@ -185,7 +208,7 @@ static unsigned long long *spread_row(unsigned long long *cnt, size_t row, int w
 #define __host__
 #define __global__
 #define __shared__ static
-#define __launch_bounds__(x)
+#define __launch_bounds__(...)
 #define __restrict__
 // ---- a workgroup: every fiber runs `kernel` (the emulator's call of its kernel with its arguments) to the end
 static void (*g_kernel)();
@@ -226,6 +249,7 @@ static void run_block(unsigned bx, unsigned by, void (*kernel)()) {
 static void (*emu_after_block)(unsigned bx, unsigned by) = nullptr;
 static EmuCounts run_grid(unsigned gx, unsigned gy, void (*kernel)(), bool permute = false) {
     const EmuCounts before = emu_counts;
+    g_grid = D3{gx, gy, 1};
     std::vector<unsigned> order((size_t)gx * gy);
     for (size_t i = 0; i < order.size(); i++) order[i] = (unsigned)i;
     if (permute) for (size_t i = order.size(); i > 1; i--) std::swap(order[i - 1], order[emu_next() % i]);

@@ -24,6 +24,15 @@ __device__ inline uint32_t ldb(gbytes p, uint32_t i)
 #endif
 }
 
+// The dynamic LDS block of a kernel, sized at the launch.  In the CPU emulation (tools/scan_queue_emu.cpp, which
+// defines WD_EMU) it is a heap block of exactly the launch's bytes, so that a carve-up which is longer than the
+// host's figure (scan_q_lds_dwords) is an access the address sanitizer reports.
+#ifdef WD_EMU
+#define WD_DYNAMIC_LDS(name) uint32_t *const name = emu_dynamic_lds
+#else
+#define WD_DYNAMIC_LDS(name) extern __shared__ uint32_t name[]
+#endif
+
 // Symbol code of a BCL byte: 0 -> 4 ('N'), else byte & 3 (bcl_direct_reader.py:352-361).
 __device__ inline uint32_t code_of(uint32_t b)
 {

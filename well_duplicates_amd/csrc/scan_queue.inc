@@ -39,14 +39,28 @@ constexpr int kFinishInPlace = 40;  // survivors of a pass's first round from wh
 static_assert(kQCap >= kPass && kQCap >= kFinishAllMax,
               "after a drain one pass must fit the queue, and q_finish_all adds up its pieces in the idle queue buffer");
 
+// WD_Q_CHECK(event, value, bound): nothing on the device.  The CPU emulation (tools/scan_queue_emu.cpp) defines it to
+// count the event, to note the value it came with (the queue's occupancy) and to assert the bound - what the comments
+// here promise, checked where it is relied on.
+#ifndef WD_Q_CHECK
+#define WD_Q_CHECK(event, value, bound)
+#endif
+
 // A field of k_scan_q's kernel argument (ScanArgs is its only one), loaded WHERE IT IS USED.  Left to
 // the compiler every field is fetched at the top of the kernel and then occupies scalar registers to
 // its last use - the arguments of the tally phase and of the once-in-a-thousand duplicate path across
 // the whole streaming loop, where the scalar file is what spills.
+// (CPU emulation, WD_EMU: the same offset read from a host copy of the ScanArgs the launch was given, a heap block of
+// sizeof(ScanArgs) bytes - the offsetof arithmetic of WD_LATE_ARG is then what a wrong offset shows in.)
 template <typename T>
 __device__ inline T late_arg(int offset)
 {
     static_assert(sizeof(T) == 4 || sizeof(T) == 8, "one or two dwords");
+#ifdef WD_EMU
+    T v;
+    memcpy(&v, emu_kernarg + offset, sizeof(T));
+    return v;
+#else
     const __attribute__((address_space(4))) char *kp =
         (const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr();
     T v;
@@ -55,6 +69,7 @@ __device__ inline T late_arg(int offset)
     else
         asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(kp), "s"(offset) : "memory");
     return v;
+#endif
 }
 #define WD_LATE_ARG(field) late_arg<decltype(ScanArgs::field)>((int)offsetof(ScanArgs, field))
 
@@ -167,6 +182,7 @@ __device__ inline void q_finish_all(const QEnv &v, const uint2 *qa, uint2 *qb, i
 {
     const int L = v.L, k = v.k;
     const int pieces = (L - j + kFinishPiece - 1) / kFinishPiece;       // per entry, >= 1 (j < L)
+    WD_Q_CHECK(finish_all, n, n >= 1 && n <= kFinishAllMax && n <= kQCap && j < L);     // (qb, a queue buffer, takes n sums)
     for (int i = lane; i < n; i += kWave)
         qb[i].x = 0u;
     q_wave_sync();
@@ -206,6 +222,7 @@ template <bool STRIDED, int MAXB = 8, int WS = 1>
 __device__ inline void q_drain(const QEnv &v, uint2 *q_a, uint2 *q_b, int &qn, int j0, int lane)
 {
     q_wave_sync();
+    WD_Q_CHECK(drain, qn, qn >= 0 && qn <= kQCap);
     const int L = v.L, k = v.k;
     int j = min(j0, L);
     // cycles of the first drain round (then 2, 4, .. MAXB; measured).  Interleaved: the rest of the group the
@@ -255,6 +272,7 @@ __device__ inline void q_drain(const QEnv &v, uint2 *q_a, uint2 *q_b, int &qn, i
                     qb[pos] = make_uint2(idx, (ent.y & 0xFF00FFFFu) | ((uint32_t)min(mm, 255) << 16));
                 }
                 n2 += __popcll(m);
+                WD_Q_CHECK(compact, n2, n2 <= n);
             }
         }
         q_wave_sync();
@@ -396,6 +414,7 @@ template <bool STRIDED, int WS = 1>
 __device__ inline void q_drain_lev2(const QEnv &v, uint2 *q_a, uint2 *q_b, int &qn, int j0, int lane)
 {
     q_wave_sync();
+    WD_Q_CHECK(drain, qn, qn >= 0 && qn <= kQCap);
     const int L = v.L;
     constexpr int NB = WS == 4 ? 24 : 8;                                 // cycles of the longest round (planes: 16 would
                                                                          // spill registers in every kernel that drains)
@@ -475,6 +494,7 @@ __device__ inline void q_drain_lev2(const QEnv &v, uint2 *q_a, uint2 *q_b, int &
                     qb[pos] = make_uint2(idx, (ent.y & 0xFF000FFFu) | (st << 12));
                 }
                 n2 += __popcll(m);
+                WD_Q_CHECK(compact, n2, n2 <= n);
             }
         }
         q_wave_sync();
@@ -499,7 +519,7 @@ __global__ __launch_bounds__(kBlock, LEVH > 0 ? 4 : (WS == 4 ? WD_Q_OCC_IL : 6))
                   "two for the first round of Levenshtein <= 2 / <= 3");
     using Entry = typename std::conditional<LEVH <= 0, uint2, uint4>::type;
     using LevS = LevState<(LEVH > 0 ? LEVH : 1)>;
-    extern __shared__ uint32_t smem[];
+    WD_DYNAMIC_LDS(smem);
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int levels = a.levels;
@@ -733,6 +753,7 @@ __global__ __launch_bounds__(kBlock, LEVH > 0 ? 4 : (WS == 4 ? WD_Q_OCC_IL : 6))
                         } else {
                             const int n0 = __popcll(m0), n1 = __popcll(m1);
                             if (n0 + n1 >= kFinishInPlace) {
+                                WD_Q_CHECK(in_place, n0 + n1, n0 + n1 <= kPass);
                                 // A third of the pass still alive after the first round: reads of low diversity.
                                 // Through the queue every survivor would fetch its centre's byte beside its own,
                                 // cycle after cycle (twice the loads of the first round's scheme, where the centre
@@ -780,8 +801,11 @@ __global__ __launch_bounds__(kBlock, LEVH > 0 ? 4 : (WS == 4 ? WD_Q_OCC_IL : 6))
                                     q_record_dup(env, tl, e1, mm1);
                                 continue;
                             }
-                            if (qn + n0 + n1 > kQCap)
+                            if (qn + n0 + n1 > kQCap) {
+                                WD_Q_CHECK(drain_mid, qn, qn <= kQCap);
                                 q_drain<STRIDED, 8, WS>(env, (uint2 *)q_a, (uint2 *)q_b, qn, B1, lane);
+                            }
+                            WD_Q_CHECK(push, qn + n0 + n1, qn + n0 + n1 <= kQCap);
                             q_push((uint2 *)q_a, qn, m0, al0, i0_3,
                                    ((uint32_t)tl << 24) | ((uint32_t)min(mm0, 255) << 16) | (uint32_t)e0);
                             q_push((uint2 *)q_a, qn + n0, m1, al1, i1_3,
@@ -816,6 +840,7 @@ __global__ __launch_bounds__(kBlock, LEVH > 0 ? 4 : (WS == 4 ? WD_Q_OCC_IL : 6))
                         } else {
                             const int n0 = __popcll(m0), n1 = __popcll(m1);
                             if (WS == 1 && n0 + n1 >= kFinishInPlace) {
+                                WD_Q_CHECK(in_place, n0 + n1, n0 + n1 <= kPass);
                                 // (low diversity: the pass is finished where it stands, as in the Hamming family.
                                 // Not in the interleaved layout: there the queue's rounds of two dwords per entry
                                 // are the better deal - measured, every read equal: 19.5 us per tile through the
@@ -849,8 +874,11 @@ __global__ __launch_bounds__(kBlock, LEVH > 0 ? 4 : (WS == 4 ? WD_Q_OCC_IL : 6))
                                     q_record_dup(env, tl, e1, lev2_dist(s1));
                                 continue;
                             }
-                            if (qn + n0 + n1 > kQCap)
+                            if (qn + n0 + n1 > kQCap) {
+                                WD_Q_CHECK(drain_mid, qn, qn <= kQCap);
                                 q_drain_lev2<STRIDED, WS>(env, (uint2 *)q_a, (uint2 *)q_b, qn, B1, lane);
+                            }
+                            WD_Q_CHECK(push, qn + n0 + n1, qn + n0 + n1 <= kQCap);
                             q_push((uint2 *)q_a, qn, m0, al0, i0_3, ((uint32_t)tl << 24) | (st0 << 12) | (uint32_t)e0);
                             q_push((uint2 *)q_a, qn + n0, m1, al1, i1_3, ((uint32_t)tl << 24) | (st1 << 12) | (uint32_t)e1);
                             qn += n0 + n1;

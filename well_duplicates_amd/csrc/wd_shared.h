@@ -1,7 +1,12 @@
 // wd_shared.h - what every translation unit of libwelldup.so sees: the C ABI, the constants and the
 // argument blocks that cross from the launch code of one unit into another.  Internal (not installed).
+// With WD_EMU defined - the CPU emulation of k_scan_q, tools/scan_queue_emu.cpp - it includes nothing of HIP and
+// none of the host's libraries: the constants, ScanArgs and ScanRare are then the library's own, not copies.
 #ifndef WD_SHARED_H
 #define WD_SHARED_H
+#ifdef WD_EMU
+#include <stdint.h>
+#else
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -31,6 +36,7 @@
 #include <utility>
 #include <string>
 #include <vector>
+#endif
 
 #include "welldup.h"
 
