@@ -33,6 +33,14 @@ def first_round(fam, layout, k, queue_first):
 
 
 class Case:
+    MAX_SLOTS = K_MAX_PASSES * K_PASS         # the most slots of a target (tests/linewalk_cases.py: the line walk takes more)
+
+    def instantiation(self):
+        """-> (first round, the kernel's name as wd_last_kernel() reports it)"""
+        B1 = first_round(self.fam, self.layout, self.kk, self.queue_first)
+        return B1, "k_scan_q<%s, %d, %d, %d>" % ("false" if self.layout == "ptr" else "true", B1, -1 if self.fam == "lev2" else 0,
+                                                 4 if self.layout == "il" else 1)
+
     def __init__(self, name, fam, layout, k, L, tpb, levels, n, lists, tiles, queue_first=0, sort=False, per_target=True,
                  hit_cap=1 << 20, check_empty=False, tags=()):
         """lists: per target (centre, [neighbour wells], level cuts [levels + 1] into them); tiles: [(planes, filt)]"""
@@ -41,13 +49,11 @@ class Case:
         self.queue_first, self.sort, self.per_target, self.hit_cap, self.check_empty = queue_first, sort, per_target, hit_cap, check_empty
         self.tags = set(tags)
         self.kk = min(k, L)                   # what the kernel is given: wd_scan_async caps the threshold at the read's length
-        self.B1 = first_round(fam, layout, self.kk, queue_first)
-        self.kernel = "k_scan_q<%s, %d, %d, %d>" % ("false" if layout == "ptr" else "true", self.B1, -1 if fam == "lev2" else 0,
-                                                    4 if layout == "il" else 1)
+        self.B1, self.kernel = self.instantiation()
         self.centre = np.array([c for c, _, _ in lists], dtype=np.int32)
         off, nbr, at = [], [], 0
         for _, wells, cuts in lists:
-            assert len(cuts) == levels + 1 and cuts[0] == 0 and cuts[-1] == len(wells) <= K_MAX_PASSES * K_PASS
+            assert len(cuts) == levels + 1 and cuts[0] == 0 and cuts[-1] == len(wells) <= self.MAX_SLOTS
             off.append([at + c for c in cuts])
             nbr += list(wells)
             at += len(wells)
@@ -70,14 +76,12 @@ class Case:
         return self.centre[order], self.lvl_off[order], order.astype(np.int32)
 
 
-_truth = {}
-
-
 def truth(case):
     """-> dict(out_tile int64 [tiles, 1 + 5 levels] as the kernel counts - first / last as histograms -, out_pt uint32
-    [tiles, T, levels] with INVALID rows, hits int32 [H, 4] {tile, target, slot, dist}, status).  Computed once."""
-    if case.name in _truth:
-        return _truth[case.name]
+    [tiles, T, levels] with INVALID rows, hits int32 [H, 4] {tile, target, slot, dist}, status).  Computed once, and kept
+    with the case (not by its name: tests/linewalk_cases.py has cases of the same names)."""
+    if getattr(case, "_truth", None) is not None:
+        return case._truth
     levels, T = case.levels, case.T
     empty = (np.diff(case.lvl_off, axis=1) <= 0).any(axis=1)
     slots = np.arange(case.nbr.shape[0])
@@ -100,18 +104,20 @@ def truth(case):
         out_pt.append(np.where(valid[:, None] == 1, dups, -1).astype(np.int64) & 0xFFFFFFFF)
         ok = (valid[tgt] == 1) & (dist <= (0 if case.mode == 0 else case.k))
         hits.append(np.stack([np.full(ok.sum(), i), tgt[ok], slots[ok], dist[ok]], axis=1))
-    _truth[case.name] = dict(out_tile=np.array(out_tile, dtype=np.int64), out_pt=np.array(out_pt).astype(np.uint32),
-                             hits=np.concatenate(hits).astype(np.int32), status=status)
-    return _truth[case.name]
+    case._truth = dict(out_tile=np.array(out_tile, dtype=np.int64), out_pt=np.array(out_pt).astype(np.uint32),
+                       hits=np.concatenate(hits).astype(np.int32), status=status)
+    return case._truth
 
 
-def write_case(path, case):
-    """The file tools/scan_queue_emu.cpp reads (its head says how)."""
+def write_case(path, case, line_pairs=0, extra=()):
+    """The file tools/scan_queue_emu.cpp reads (tools/scan_emu_common.h says how); line_pairs and extra - int32 words behind
+    the hit records - are the line walk's (tests/linewalk_cases.py, tools/scan_lines_emu.cpp)."""
     t = truth(case)
     centre, lvl_off, perm = case.view()
+    extra = np.asarray(extra, dtype="<i4")
     head = np.array([0x31435153, FAMILIES.index(case.fam), LAYOUTS.index(case.layout), case.B1, case.n, len(case.tiles), case.T,
                      case.levels, case.L, case.kk, case.tpb, perm is not None, case.per_target, case.check_empty, case.hit_cap,
-                     t["hits"].shape[0], case.nbr.shape[0], t["status"], 0, 0], dtype="<i4")
+                     t["hits"].shape[0], case.nbr.shape[0], t["status"], line_pairs, extra.shape[0]], dtype="<i4")
     with open(path, "wb") as fh:
         for a in (head, centre.astype("<i4"), lvl_off.astype("<i4"), case.nbr.astype("<i4")):
             fh.write(a.tobytes())
@@ -125,6 +131,7 @@ def write_case(path, case):
         if case.per_target:
             fh.write(t["out_pt"].astype("<u4").tobytes())
         fh.write(t["hits"].astype("<i4").tobytes())
+        fh.write(extra.tobytes())
 
 
 # ---- geometry ------------------------------------------------------------------------------------------------------

@@ -21,7 +21,7 @@ K_MAX_PASSES = 4            # wd_shared.h:46         kMaxPasses
 K_FINISH_ALL_MAX = 64       # scan_queue.inc:23      kFinishAllMax
 K_QCAP = 128                # scan_queue.inc:25      WD_QCAP -> kQCap (:30)
 K_FINISH_IN_PLACE = 40      # scan_queue.inc:37      kFinishInPlace
-K_LW_TARGETS = 256          # scan_lines.inc:26      kLwTargets (build_line_tables' other cut, welldup_lines.hip:143)
+K_LW_TARGETS = 256          # scan_lines.inc:26      kLwTargets (make_line_tables' other cut, line_tables.inc)
 K_LW_PAIRS = 12288          # scan_lines.inc:27      kLwPairs
 K_LW_STEP = 128             # scan_lines.inc:29      kLwStep = 2 * kWave
 K_LW_QCAP = 128             # scan_lines.inc:30      kLwQCap
@@ -202,8 +202,8 @@ def deal_queue(valid, K: int, tpb: int):
 
 
 def deal_lines(T: int, K: int, line_pairs: int):
-    """k_scan_lines: the pairs in (target, slot) order cut into blocks of line_pairs (build_line_tables,
-    welldup_lines.hip:140; its cut at 256 targets must not come first), a wave's steps are windows of 128
+    """k_scan_lines: the pairs in (target, slot) order cut into blocks of line_pairs (make_line_tables,
+    line_tables.inc; its cut at 256 targets must not come first), a wave's steps are windows of 128
     consecutive pairs taken in turn (scan_lines.inc:214).  -> [block][wave] -> [(first pair, pairs)]"""
     P = T * K
     assert line_pairs % (K_WAVES * K_LW_STEP) == 0 and line_pairs // K + 2 <= K_LW_TARGETS

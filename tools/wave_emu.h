@@ -1,7 +1,7 @@
 // wave_emu.h - what a kernel's source needs to run on the CPU as it stands (tools/lane_mismatch_emu.cpp,
 // tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp, tools/lane_hops_emu.cpp, tools/lane_gc_emu.cpp, tools/lane_consensus_emu.cpp, tools/lane_umi_emu.cpp, tools/lane_keep_emu.cpp,
 // tools/read_classes_emu.cpp, tools/near_emu.cpp, tools/dup_sets_emu.cpp, tools/lane_index_emu.cpp, tools/gen_rings_emu.cpp,
-// tools/scan_queue_emu.cpp): the 256 lanes of a
+// tools/scan_queue_emu.cpp, tools/scan_lines_emu.cpp): the 256 lanes of a
 // workgroup are fibers (ucontext) that a round-robin scheduler switches at the collectives - __syncthreads is a
 // rendezvous of the workgroup, __ballot and __shfl of a wave -, LDS is the kernel's static storage, an atomic add or
 // minimum or a compare-and-swap is a plain one (one fiber runs at a time), and the qualifiers are empty.  Include it, then the kernel's
@@ -32,6 +32,8 @@
 // -DWAVE_EMU_TORN_ADD breaks atomicAdd the same way, for an emulator whose kernels take their places by adds
 // (tools/lane_consensus_emu.cpp; tools/gen_rings_emu.cpp, which clears emu_torn_add for its count pass so that the
 // fill pass's claim of an LDS slot alone is broken).
+// -DWAVE_EMU_TORN_OR breaks atomicOr the same way (tools/scan_lines_emu.cpp: the hit-level masks four targets share a
+// word of).
 // -DWAVE_EMU_UNIT_DEFS: the emulator includes csrc/read_classes.inc and csrc/tile_classes.inc (the head of the tiledups unit),
 // which define kTdBlock, kSpread, kFpCycles, kLdCmpWords, kInvalid, kMaxCycles, align256 and spread_row themselves:
 // this header then leaves them, and lane_pass.inc, out.  tools/dup_sets_emu.cpp defines it too: csrc/dup_sets.inc
@@ -125,6 +127,27 @@ static int emu_readfirstlane(int v) {
     w.count++; if (!wave_complete_(w)) await_(w.gen, g);
     return w.val[par][__builtin_ctzll(w.pred[par])];
 }
+// DPP (csrc/scan_lines.inc: lw_wave_sum), by the ISA's account of it and not by what its caller needs: the wave is four
+// rows of 16 lanes, a row four banks of 4.  row_shr:n (0x111 .. 0x11F) reads the lane n below in the same row,
+// row_bcast:15 (0x142) lane 15 of the row before, row_bcast:31 (0x143) lane 31 in rows 2 and 3.  A lane whose row or
+// bank the masks switch off keeps `old`; one whose source lies outside its row (or, for the broadcasts, does not
+// exist) gets 0 with bound_ctrl and keeps `old` without.  Any other control word is not emulated: abort.
+static int emu_update_dpp(int old, int src, int ctrl, int row_mask, int bank_mask, bool bound_ctrl) {
+    WaveSync &w = emu_ws[emu_lane / kWave]; long g = w.gen; int par = g & 1, lane = emu_lane % kWave;
+    w.val[par][lane] = src;
+    w.count++; if (!wave_complete_(w)) await_(w.gen, g);
+    const int row = lane / 16, in_row = lane % 16;
+    int from = -1;
+    if (ctrl >= 0x111 && ctrl <= 0x11F) from = in_row >= (ctrl & 0xF) ? lane - (ctrl & 0xF) : -1;
+    else if (ctrl == 0x142) from = row >= 1 ? row * 16 - 1 : -1;
+    else if (ctrl == 0x143) from = row >= 2 ? 31 : -1;
+    else { fprintf(stderr, "wave_emu.h: DPP control word 0x%X is not emulated\n", ctrl); abort(); }
+    if (!((row_mask >> row) & 1) || !((bank_mask >> (in_row / 4)) & 1)) return old;
+    if (from < 0) return bound_ctrl ? 0 : old;
+    return w.val[par][from];
+}
+#define __builtin_amdgcn_update_dpp(old, src, ctrl, row_mask, bank_mask, bound_ctrl) \
+    emu_update_dpp((int)(old), (int)(src), (ctrl), (row_mask), (bank_mask), (bound_ctrl))
 #define __builtin_amdgcn_readlane(v, src) __shfl((int)(v), (src))
 #define __builtin_amdgcn_readfirstlane(v) emu_readfirstlane((int)(v))
 #define __builtin_amdgcn_wave_barrier() ((void)__ballot(false))
@@ -177,7 +200,11 @@ template <class T, class U> static T atomicMin(T *p, U v) { emu_point(); emu_min
 #else
 template <class T, class U> static T atomicMin(T *p, U v) { emu_point(); emu_mins++; T o = *p; if ((T)v < o) *p = (T)v; return o; }
 #endif
+#ifdef WAVE_EMU_TORN_OR                            // (the deliberate bug of an or: another fiber may set bits of the word between its load and its store)
+template <class T, class U> static T atomicOr(T *p, U v) { emu_point(); T o = *p; emu_point(); *p = o | (T)v; return o; }
+#else
 template <class T, class U> static T atomicOr(T *p, U v) { emu_point(); T o = *p; *p |= (T)v; return o; }
+#endif
 // the clang builtins of the kernels that say their memory order and scope: the order and the scope mean nothing here
 #define __HIP_MEMORY_SCOPE_AGENT 4
 template <class T> static T __hip_atomic_load(const T *p, int, int) { emu_point(); return *p; }

@@ -85,7 +85,7 @@ void k_scan_lines(LineArgs a)
     static_assert(LEVH == 0 || LEVH == kLev2Closed, "equality / Hamming, or Levenshtein <= 2 by the closed form");
     static_assert(WS == 1 || (WS == 4 && STRIDED && (B1 == 4 || B1 == 8)), "interleaved: whole dwords of four cycles");
     constexpr int NLD = WS == 4 ? B1 / 4 : B1;               // loads per pair of the first round
-    extern __shared__ uint32_t smem[];
+    WD_DYNAMIC_LDS(smem);                                    // (device_common.inc: a heap block of the launch's bytes in the CPU emulation)
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int levels = a.s.levels, L = a.s.L, k = a.s.k;
@@ -285,6 +285,7 @@ void k_scan_lines(LineArgs a)
                     } else {
                         const int n0 = __popcll(ma), n1 = __popcll(mb);
                         if (n0 + n1 >= kLwInPlace) {
+                            WD_Q_CHECK(in_place, n0 + n1, n0 + n1 <= kLwStep);
                             // A third of the step's pairs still alive after the first round: reads of low diversity
                             // (amplicons, failed cycles).  Through the queue every one of them would be written,
                             // read back and compacted round after round - this step is finished where it stands,
@@ -341,11 +342,13 @@ void k_scan_lines(LineArgs a)
                             continue;
                         }
                         if (qn + n0 + n1 > kLwQCap) {
+                            WD_Q_CHECK(drain_mid, qn, qn <= kLwQCap);
                             if constexpr (LEVH == 0)
                                 q_drain<STRIDED, 8, WS>(env, q_a, q_b, qn, B1, lane);
                             else
                                 q_drain_lev2<STRIDED, WS>(env, q_a, q_b, qn, B1, lane);
                         }
+                        WD_Q_CHECK(push, qn + n0 + n1, qn + n0 + n1 <= kLwQCap);
                         q_push(q_a, qn, ma, al0, w0_3, (lt0 << 24) | t0 | e0);
                         q_push(q_a, qn + n0, mb, al1, w1_3, (lt1 << 24) | t1 | e1);
                         qn += n0 + n1;

@@ -16,6 +16,7 @@ namespace {
 #include "lev2_stream.inc"
 #include "scan_queue.inc"
 #include "scan_lines.inc"
+#include "line_tables.inc"
 
 }  // namespace
 
@@ -83,85 +84,16 @@ int build_line_tables(wd_ctx *ctx)
     WD_LW_HIP(hipMemcpy(cen.data(), ctx->d_centre, cen.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     WD_LW_HIP(hipMemcpy(off.data(), ctx->d_lvl_off, off.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     WD_LW_HIP(hipMemcpy(nbr.data(), ctx->d_nbr, nbr.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    // (well, target, slot) of every pair; a target's slots are [off[t][0], off[t][levels]) of nbr
-    struct Pair { int32_t well, t; uint32_t slot; };
-    std::vector<Pair> pairs;
-    pairs.reserve((size_t)P);
-    for (int t = 0; t < T; t++) {
-        const int32_t b = off[(size_t)t * row], e = off[(size_t)t * row + levels];
-        if (b < 0 || e > P || e < b)
-            return WD_OK;
-        for (int32_t i = b; i < e; i++)
-            pairs.push_back(Pair{nbr[(size_t)i], t, (uint32_t)(i - b)});
-    }
-    if (pairs.empty())
-        return WD_OK;
-    {
-        // by well, stable (equal wells stay in target order): three counting passes of 11 bits - a comparison
-        // sort of a few million pairs would be a tenth of a second of every run's start-up
-        std::vector<Pair> tmp(pairs.size());
-        int32_t lo_well = pairs[0].well;
-        for (const Pair &q : pairs)
-            lo_well = std::min(lo_well, q.well);
-        for (int pass = 0; pass < 3; pass++) {
-            std::vector<size_t> cnt(2049, 0);
-            const int sh = 11 * pass;
-            auto digit = [&](const Pair &q) { return (size_t)(((uint32_t)(q.well - lo_well) >> sh) & 2047u); };
-            for (const Pair &q : pairs)
-                cnt[digit(q) + 1]++;
-            for (int d = 0; d < 2048; d++)
-                cnt[(size_t)d + 1] += cnt[(size_t)d];
-            for (const Pair &q : pairs)
-                tmp[cnt[digit(q)]++] = q;
-            pairs.swap(tmp);
-        }
-        // (33 bits of spread would need a fourth pass: wells are int32 and tiles hold a few million)
-        if ((uint32_t)(pairs.back().well - lo_well) >> 31)
-            return WD_OK;
-        for (size_t i = 1; i < pairs.size(); i++)
-            if (pairs[i - 1].well > pairs[i].well) {                 // (spread above 2^33 cannot happen; belt and braces)
-                std::stable_sort(pairs.begin(), pairs.end(), [](const Pair &x, const Pair &y) { return x.well < y.well; });
-                break;
-            }
-    }
-    const size_t n = pairs.size();
-    std::vector<int32_t> well(n);
-    std::vector<uint32_t> meta(n), btgt;
-    std::vector<int4> blk;
-    std::vector<int> local((size_t)T, -1), seen_in((size_t)T, -1);
-    std::vector<char> counted((size_t)T, 0);
-    size_t first = 0;
+    // the pairs, sorted by neighbour well and cut into blocks: plain C++ (line_tables.inc)
+    LineTables lt;
     const size_t per_block = (size_t)(ctx->line_pairs > 0 ? ctx->line_pairs : kLwPairs);
-    int tmax = 0;
-    while (first < n) {
-        const int b = (int)blk.size();
-        const size_t tgt0 = btgt.size();
-        size_t i = first;
-        for (; i < n && i - first < per_block; i++) {
-            const int t = pairs[i].t;
-            if (seen_in[(size_t)t] != b) {
-                if (btgt.size() - tgt0 == (size_t)kLwTargets)
-                    break;                                       // the block's target table is full
-                seen_in[(size_t)t] = b;
-                local[(size_t)t] = (int)(btgt.size() - tgt0);
-                btgt.push_back((uint32_t)t | (counted[(size_t)t] ? 0u : 0x80000000u));   // the first block to see it owns it
-                counted[(size_t)t] = 1;
-            }
-            well[i] = pairs[i].well;
-            meta[i] = ((uint32_t)local[(size_t)t] << 16) | pairs[i].slot;
-        }
-        blk.push_back(make_int4((int)first, (int)(i - first), (int)tgt0, (int)(btgt.size() - tgt0)));
-        tmax = std::max(tmax, (int)(btgt.size() - tgt0));
-        first = i;
-    }
-    ctx->lw_tmax = (tmax + 3) & ~3;
-    // (a target without a single pair would never be counted: has_empty_level excludes it)
-    std::vector<int32_t> bcen(btgt.size()), boff(btgt.size() * row);
-    for (size_t i = 0; i < btgt.size(); i++) {
-        const size_t t = (size_t)(btgt[i] & 0x7FFFFFFFu);
-        bcen[i] = cen[t];
-        memcpy(&boff[i * row], &off[t * row], row * sizeof(int32_t));
-    }
+    if (!make_line_tables(cen.data(), off.data(), nbr.data(), T, levels, P, per_block, ctx->k_max, ctx->has_empty_level, lt))
+        return WD_OK;
+    const std::vector<int32_t> &well = lt.well, &bcen = lt.bcen, &boff = lt.boff;
+    const std::vector<uint32_t> &meta = lt.meta, &btgt = lt.btgt;
+    const std::vector<int4> &blk = lt.blk;
+    const size_t n = well.size();
+    ctx->lw_tmax = lt.tmax;
     // all five tables or none: a failure half way frees what it has
     auto upload = [&](auto *&dst, const void *src, size_t bytes) -> hipError_t {
         hipError_t e = hipMalloc((void **)&dst, bytes);
