@@ -82,6 +82,9 @@ members and the score in k_lk_mark: 4 ceil(cycles / 10) + 18 bytes per well -, o
 planted copy carries its original's qualities: every family ties and its root stays, one atomic per family member),
 the `--equal` lane with one quality and the `--equal` lane with random qualities (one family holds every well: the
 case the grouping and the two skips of k_lk_score exist for).
+`--umi U --keep --keep-umi` gives the three lanes of `--umi` a quality part too and times, on each, LaneDups.umi(E, M,
+molecules=True) beside umi(E, M) - the same rows, and 8 bytes per well written (include/welldup_lanemolecules.h) - and
+LaneDups.keep(Q, by_molecule=True) beside keep(Q): the same kernels on the molecules.
 For per-kernel times run it under
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/lanedups_probe.py
@@ -146,6 +149,9 @@ ap.add_argument("--quality", action="store_true",
 ap.add_argument("--keep", action="store_true",
                 help="also time LaneDups.keep(Q) beside gc(0), qualities(0), the equality finish and a pure read of as many "
                      "bytes (three inputs with --equal)")
+ap.add_argument("--keep-umi", action="store_true",
+                help="with --umi U and --keep: also time LaneDups.umi(E, M, molecules=True) beside umi(E, M) and "
+                     "LaneDups.keep(Q, by_molecule=True) beside keep(Q), on the three lanes of --umi")
 ap.add_argument("--min-q", type=int, default=15, metavar="Q", help="the min_q of --keep (0..63)")
 a = ap.parse_args()
 if not 0 <= a.min_q <= 63:
@@ -158,6 +164,8 @@ if a.quality and not a.hamming:
     ap.error("--quality needs --hamming K")
 if a.hops and not a.index:
     ap.error("--hops needs --index I")
+if a.keep_umi and not (a.umi and a.keep):
+    ap.error("--keep-umi needs --umi U and --keep")
 if a.umi and not 1 <= a.umi <= 20:
     ap.error("--umi takes 1..20 cycles")
 if not 0 <= a.umi_e <= 3:
@@ -669,6 +677,29 @@ def time_umi(acc, tiles_n, t_finish, t_umi_add, t_index_add, what):
              t_finish / tiles_n))
 
 
+def time_molecules(acc, tiles_n, what):
+    """LaneDups.umi(E, M, molecules=True) beside umi(E, M) and LaneDups.keep(Q, by_molecule=True) beside keep(Q), each
+    after a first call that pays for loading the kernels (and, for the molecules, for allocating their region)"""
+    acc.umi(a.umi_e, a.max_family, molecules=True)
+    (mrow, mtiles), t_m = clock(lambda: acc.umi(a.umi_e, a.max_family, molecules=True))
+    (urow, utiles), t_u = clock(lambda: acc.umi(a.umi_e, a.max_family))
+    acc.keep(a.min_q)
+    (krow, _), t_k = clock(lambda: acc.keep(a.min_q))
+    acc.keep(a.min_q, by_molecule=True)
+    (brow, btiles), t_b = clock(lambda: acc.keep(a.min_q, by_molecule=True))
+    assert (mrow == urow).all() and (mtiles == utiles).all(), "the rows of umi(molecules=True) are not those of umi()"
+    assert brow[0] == brow[1] + brow[2] == krow[0] and brow[2] == urow[1] + urow[10] - urow[9] <= krow[2] and \
+        brow[6] == urow[4] - urow[19] + urow[9] and brow[1] == krow[1] - krow[6] + urow[4] + urow[9] and \
+        (btiles.sum(axis=0) == brow[:6]).all() and brow[9:].sum() == brow[6], "the rows by molecule do not add up"
+    print("%s: keep by molecule, E %d, max_family %d, min_q %d: %d PF wells, %d kept (%d by family), %d dropped (%d), %d "
+          "molecules of two or more wells (%d families), %d of them moved (%d)"
+          % (what, a.umi_e, a.max_family, a.min_q, brow[0], brow[1], krow[1], brow[2], krow[2], brow[6], krow[6], brow[7], krow[7]))
+    print("  %-22s %9.3f ms  (%.4f ms per tile; umi(E, M): %.4f; molecules / umi = %.2f; 8 bytes per well written: %.1f MB per tile)"
+          % ("lane umi, molecules", t_m, t_m / tiles_n, t_u / tiles_n, t_m / t_u, 8 * n / 1e6))
+    print("  %-22s %9.3f ms  (%.4f ms per tile; keep(Q): %.4f; by molecule / by family = %.2f)"
+          % ("lane keep, by molecule", t_b, t_b / tiles_n, t_k / tiles_n, t_b / t_k))
+
+
 if a.umi:
     print("umi part: %d UMI cycles, workspace %.2f GB, scratch %.2f GB"
           % (a.umi, sc.lane_umi_workspace_bytes(n, a.tiles, a.umi) / 1e9, sc.lane_umi_scratch_bytes(a.tiles, n) / 1e9))
@@ -677,6 +708,8 @@ if a.umi:
     lu = LaneDups(sc, n, a.tiles, a.cycles)
     lu.index_begin(a.umi)
     lu.umi_begin(a.umi)
+    if a.keep_umi:
+        lu.qual_begin(QUALITY_BINS)
     u_uadd = u_iadd = 0.0
     for bi, tiles in enumerate(batches):
         if len(tiles) != tb.n_tiles:
@@ -687,6 +720,8 @@ if a.umi:
                 sc.synth_plane(utb.plane_ptr(s_, c), spec, 1, 1101 + t, a.cycles + c)
         sc.synchronize()
         lu.add(tb, tiles)
+        if a.keep_umi:
+            lu.qual_add(tb, tiles)
         if bi == 0:                                  # (the first call of a kernel pays for loading it)
             warm = LaneDups(sc, n, len(tiles), a.cycles)
             warm.index_begin(a.umi)
@@ -701,6 +736,8 @@ if a.umi:
     _, u_fin = clock(lambda: lu.finish())
     assert (lu.umi_keys() == lu.index_keys()).all(), "the UMI keys differ from the index keys of the same planes"
     time_umi(lu, max(1, a.tiles), u_fin, u_uadd, u_iadd, "the planted lane")
+    if a.keep_umi:
+        time_molecules(lu, max(1, a.tiles), "the planted lane")
     lu.close()
     tb.free()
     utb.free()
@@ -714,11 +751,17 @@ if a.umi:
         eq = LaneDups(sc, n, 3, a.cycles)
         eq.index_begin(a.umi)
         eq.umi_begin(a.umi)
+        if a.keep_umi:
+            eq.qual_begin(QUALITY_BINS)
         eq.add(three, [0, 1, 2])
+        if a.keep_umi:
+            eq.qual_add(three, [0, 1, 2])
         _, e_iadd = clock(lambda: eq.index_add(uthree, [0, 1, 2]))
         _, e_uadd = clock(lambda: eq.umi_add(uthree, [0, 1, 2]))
         _, e_fin = clock(lambda: eq.finish())
         time_umi(eq, 3, e_fin, e_uadd, e_iadd, "every read equal, three tiles")
+        if a.keep_umi:
+            time_molecules(eq, 3, "every read equal, three tiles")
         assert eq.umi(a.umi_e, a.max_family)[0][9:11].tolist() == [1, 3 * n], "the equal lane is not one Large family"
         eq.close()
     # three tiles without planted copies whose wells of odd index repeat the well to their left, cycle by cycle, and its
@@ -738,11 +781,17 @@ if a.umi:
     pr = LaneDups(sc, n, 3, a.cycles)
     pr.index_begin(a.umi)
     pr.umi_begin(a.umi)
+    if a.keep_umi:
+        pr.qual_begin(QUALITY_BINS)
     pr.add(three, [0, 1, 2])
+    if a.keep_umi:
+        pr.qual_add(three, [0, 1, 2])
     _, p_iadd = clock(lambda: pr.index_add(uthree, [0, 1, 2]))
     _, p_uadd = clock(lambda: pr.umi_add(uthree, [0, 1, 2]))
     _, p_fin = clock(lambda: pr.finish())
     time_umi(pr, 3, p_fin, p_uadd, p_iadd, "every odd well a copy of its left neighbour, three tiles")
+    if a.keep_umi:
+        time_molecules(pr, 3, "every odd well a copy of its left neighbour, three tiles")
     prow = pr.umi(0, a.max_family)[0]
     assert prow[3] >= 3 * (n // 2) - 3 and prow[11 + 2:19].sum() == 0, "the families are not pairs"
     pr.close()

@@ -265,6 +265,14 @@ LANEKEEP_MAX_Q = 63
 LANEKEEP_DEFAULT_MIN_Q = 15
 LANEKEEP_GAIN_NAMES = ("0", "1-9", "10-19", "20-49", "50-99", "100-199", "200-499", "500+")
 
+# name -> (restype, argtypes); every symbol include/welldup_lanemolecules.h declares beyond those above
+LANEMOLECULES_PROTOTYPES = {
+    "wd_lane_molecules_bytes": (_i, [_i, _i64, ctypes.POINTER(_sz)]),
+    "wd_lane_umi_molecules": (_i, [_vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _sz]),
+    "wd_lane_keep_molecules": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp]),
+    "wd_lane_molecules_part": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+}
+
 _lib = None
 
 
@@ -416,7 +424,7 @@ def load():
             list(LANEDISTANCE_PROTOTYPES.items()) + list(LANEQUALITY_PROTOTYPES.items()) + \
             list(LANESATURATION_PROTOTYPES.items()) + list(LANETOP_PROTOTYPES.items()) + \
             list(LANEHOPS_PROTOTYPES.items()) + list(LANEGC_PROTOTYPES.items()) + list(LANECONSENSUS_PROTOTYPES.items()) + \
-            list(LANEUMI_PROTOTYPES.items()) + list(LANEKEEP_PROTOTYPES.items()):
+            list(LANEUMI_PROTOTYPES.items()) + list(LANEKEEP_PROTOTYPES.items()) + list(LANEMOLECULES_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

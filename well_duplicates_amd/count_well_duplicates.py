@@ -28,7 +28,7 @@ Differences from the reference, all deliberate:
     --lane-dups-hops-out, --lane-dups-gc, --lane-dups-gc-bins, --lane-dups-gc-max-n, --lane-dups-gc-out,
     --lane-dups-consensus, --lane-dups-consensus-max-d, --lane-dups-consensus-max-family, --lane-dups-consensus-out,
     --lane-dups-umi, --lane-dups-umi-mismatches, --lane-dups-umi-max-family, --lane-dups-umi-out,
-    --lane-dups-keep, --lane-dups-keep-min-q, --lane-dups-keep-out;
+    --lane-dups-keep, --lane-dups-keep-min-q, --lane-dups-keep-out, --lane-dups-keep-umi;
   * --all-wells --dup-sets groups every tile's wells into duplicate sets and follows each lane's report
     with their counts and the exact duplication (report.write_dup_sets);
   * --all-wells --tile-dups groups every tile's PF wells into classes of equal reads, wherever on the tile they
@@ -69,7 +69,8 @@ Differences from the reference, all deliberate:
     (report.write_lane_umi);
     --lane-dups-keep acts on all of it: of every class or cluster the well with the highest summed base quality is
     kept and the others are dropped (report.write_lane_keep), and --lane-dups-keep-out DIR writes the lane's .filter
-    files with the PF bit cleared on the dropped wells - a deduplicated lane for every downstream converter;
+    files with the PF bit cleared on the dropped wells - a deduplicated lane for every downstream converter; with
+    --lane-dups-keep-umi (and --lane-dups-umi) one well is kept per UMI molecule, not per class or cluster;
   * the resident layout is chosen per run (--layout auto): sampled scans the interleaved-by-four layout
     serves (the reference's default -e 2 among them) keep their cycles interleaved, everything else planes.
 """
@@ -401,7 +402,14 @@ def parse_args(argv=None):
                         "(--lane-dups-quality-bins): exact where the edges are the instrument's levels, a lower bound "
                         "otherwise.  Keeps the reported qualities beside the reads as --lane-dups-quality does (given or "
                         "not) and takes 10 bytes of device memory per well of the lane besides.  One well per UMI "
-                        "molecule (--lane-dups-umi) is not offered: the molecules are not kept after that pass")
+                        "molecule instead of per family: --lane-dups-keep-umi")
+    p.add_argument("--lane-dups-keep-umi", action="store_true",
+                   help="with --lane-dups-keep and --lane-dups-umi: keep one well per UMI molecule, not per family - the "
+                        "best well of every molecule the --lane-dups-umi block counts (at its --lane-dups-umi-mismatches "
+                        "and --lane-dups-umi-max-family; a family above max-family stays one molecule), so that a well the "
+                        "UMI shows to be a molecule of its own is not dropped.  The keep block and the "
+                        "--lane-dups-keep-out files are then per molecule, and the summary line ends in By: molecule.  "
+                        "Takes 8 bytes of device memory per well of the lane besides")
     p.add_argument("--lane-dups-keep-min-q", type=int, default=None, metavar="Q",
                    help="with --lane-dups-keep: a base counts from quality Q on (0..%d, default %d)"
                         % (_lib.LANEKEEP_MAX_Q, _lib.LANEKEEP_DEFAULT_MIN_Q))
@@ -415,6 +423,10 @@ def parse_args(argv=None):
     for flag, value in (("min-q", args.lane_dups_keep_min_q), ("out", args.lane_dups_keep_out)):
         if value is not None and not args.lane_dups_keep:
             p.error("--lane-dups-keep-%s needs --lane-dups-keep" % flag)
+    if args.lane_dups_keep_umi and not args.lane_dups_keep:
+        p.error("--lane-dups-keep-umi needs --lane-dups-keep")
+    if args.lane_dups_keep_umi and args.lane_dups_umi is None:
+        p.error("--lane-dups-keep-umi needs --lane-dups-umi")
     if args.lane_dups_keep_min_q is not None and not 0 <= args.lane_dups_keep_min_q <= _lib.LANEKEEP_MAX_Q:
         p.error("--lane-dups-keep-min-q takes 0..%d, not %d" % (_lib.LANEKEEP_MAX_Q, args.lane_dups_keep_min_q))
     if args.lane_dups_umi is not None and not args.lane_dups:
@@ -692,18 +704,20 @@ def lane_cluster_members(class_labels: np.ndarray, cluster_labels: np.ndarray):
 def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0, index: int = 0,
                          mismatch: int = 0, distance: int = 0, quality: int = 0, saturation: int = 0, top: int = 0,
                          hops: int = 0, gc: int = 0, consensus: int = 0, umi: int = 0, umi_scratch: int = 0,
-                         keep: int = 0):
+                         keep: int = 0, molecules: int = 0):
     """--lane-dups: the accumulator's workspace - with --lane-dups-hamming plus the scratch of the near finish, with
     --lane-dups-index plus the index workspace, with --lane-dups-mismatches or --lane-dups-distance plus that pass's
     scratch, with --lane-dups-quality plus the quality workspace and that pass's scratch, with --lane-dups-saturation,
     --lane-dups-top, --lane-dups-hops, --lane-dups-gc or --lane-dups-consensus plus that pass's scratch, with
     --lane-dups-umi plus the UMI workspace (umi) and that pass's scratch (umi_scratch), with --lane-dups-keep plus that
-    pass's scratch (keep; and the quality workspace, in `quality`, if --lane-dups-quality has not asked for it) -
-    against the free device memory, before anything is loaded."""
-    need += scratch + index + mismatch + distance + quality + saturation + top + hops + gc + consensus + umi + umi_scratch + keep
+    pass's scratch (keep; and the quality workspace, in `quality`, if --lane-dups-quality has not asked for it), with
+    --lane-dups-keep-umi plus the molecule region (molecules) - against the free device memory, before anything is
+    loaded."""
+    need += (scratch + index + mismatch + distance + quality + saturation + top + hops + gc + consensus + umi + umi_scratch + keep +
+             molecules)
     if need > free:
         raise MemoryError("--lane-dups needs %.2f GB of device memory for a lane of %d tiles x %d wells x %d cycles "
-                          "(%d bytes%s%s%s%s%s%s%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
+                          "(%d bytes%s%s%s%s%s%s%s%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
                               need / 1e9, tiles, wells, cycles, need,
                               ", %d of them for --lane-dups-hamming" % scratch if scratch else "",
                               ", %d of them for --lane-dups-index" % index if index else "",
@@ -717,6 +731,7 @@ def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: i
                               ", %d of them for --lane-dups-consensus" % consensus if consensus else "",
                               ", %d of them for --lane-dups-umi" % (umi + umi_scratch) if umi + umi_scratch else "",
                               ", %d of them for --lane-dups-keep" % keep if keep else "",
+                              ", %d of them for --lane-dups-keep-umi" % molecules if molecules else "",
                               free / 1e9, free))
 
 
@@ -776,8 +791,9 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     loaded by the same job list as the index batch and fed to LaneDups.umi_add, reused and released with the scan
     batch; after every other pass of the lane LaneDups.umi(E, max family): into["lumi"][lane] = LaneUmiCounts, on the
     labels the lane was left with.
-    lane_keep = (min_q, edges, out directory or None) (with lane_dups): the accumulator gets a quality part with these
-    bins unless lane_quality has given it one (the two share it), and after every other pass of the lane
+    lane_keep = (min_q, edges, out directory or None[, by molecule]) (with lane_dups; by molecule needs lane_umi: the
+    UMI pass then writes its molecules down, LaneDups.umi(molecules=True), and the keep reads them,
+    by_molecule=True): the accumulator gets a quality part with these bins unless lane_quality has given it one (the two share it), and after every other pass of the lane
     LaneDups.keep(min_q): into["lkeep"][lane] = LaneKeepCounts, on the labels the lane was left with; with a
     directory the lane's filter files go there at once (write_lane_keep_filters), the masks are not kept.
 
@@ -795,6 +811,8 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     index_cycles, index_lengths, index_share = lane_index if lane_index else ([], [], 1.0)
     assert not index_cycles or (lane_dups and interleave == 1)
     umi_cycles, umi_e, umi_family = lane_umi if lane_umi else ([], 0, 0)
+    keep_umi = lane_keep is not None and len(lane_keep) > 3 and bool(lane_keep[3])      # one well per UMI molecule
+    assert not keep_umi or umi_cycles
     assert not umi_cycles or (lane_dups and interleave == 1)
     qual_edges = lane_quality[0] if lane_quality is not None else lane_keep[1] if lane_keep is not None else None
     counts, logs = (into["counts"], into["logs"]) if into else ({}, {})
@@ -1055,12 +1073,13 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                     if umi_cycles:
                         left = into["lnear"][lane] if lane_near else into["ldups"][lane]
                         into["lumi"][lane] = report.LaneUmiCounts.from_rows(
-                            *ld.umi(umi_e, umi_family), names, lane_near, umi_e, umi_family, len(umi_cycles), left.pf,
-                            left.redundant)
+                            *ld.umi(umi_e, umi_family, molecules=keep_umi), names, lane_near, umi_e, umi_family,
+                            len(umi_cycles), left.pf, left.redundant)
                     if lane_keep is not None:
-                        kept = ld.keep(lane_keep[0], masks=lane_keep[2] is not None)
+                        kept = ld.keep(lane_keep[0], masks=lane_keep[2] is not None, by_molecule=keep_umi)
                         into["lkeep"][lane] = report.LaneKeepCounts.from_rows(kept[0], kept[1], names, lane_near, lane_keep[0],
-                                                                              qual_edges, len(cycle_list))
+                                                                              qual_edges, len(cycle_list),
+                                                                              by="molecule" if keep_umi else None)
                         if lane_keep[2] is not None:
                             write_lane_keep_filters(lane_keep[2], lane, {t: reader.get_tile(lane, t) for t in names},
                                                     {names[ti]: m for ti, m in kept[2].items()})
@@ -1353,7 +1372,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
             keep = None
             if args.lane_dups_keep:
                 keep = (_lib.LANEKEEP_DEFAULT_MIN_Q if args.lane_dups_keep_min_q is None else args.lane_dups_keep_min_q,
-                        args.lane_dups_quality_edges, args.lane_dups_keep_out)
+                        args.lane_dups_quality_edges, args.lane_dups_keep_out, args.lane_dups_keep_umi)
             ntn = 5 + 2 * levels + len(report.CLASS_BIN_NAMES) if near_k else 0
             rows = np.zeros((len(mine), ncnt + nsets + ntd + ntn), dtype=np.int64)
             logs = {}
@@ -1470,7 +1489,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                          if umi is not None else 0,
                                          umi_scratch=sc.lane_umi_scratch_bytes(len(tiles), n_targets)
                                          if umi is not None else 0,
-                                         keep=sc.lane_keep_scratch_bytes(len(tiles), n_targets) if keep is not None else 0)
+                                         keep=sc.lane_keep_scratch_bytes(len(tiles), n_targets) if keep is not None else 0,
+                                         molecules=sc.lane_molecules_bytes(len(tiles), n_targets)
+                                         if args.lane_dups_keep_umi else 0)
                 if err is None:             # (a rank whose setup failed has nothing to scan: it goes to the flag)
                     scan_lanes(sc, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                                max(0, args.tile_batch), args.threads,

@@ -415,6 +415,10 @@ struct wd_lane_dups {
     std::shared_ptr<wd_lane_index> index;          // null unless wd_lane_index_begin has been called
     std::shared_ptr<wd_lane_quality> qual;         // null unless wd_lane_qual_begin has been called
     std::shared_ptr<wd_lane_umi_part> umi;         // null unless wd_lane_umi_begin has been called
+    // the molecule part: the caller's region wd_lane_umi_molecules filled last, with its max_e and max_family; null
+    // after a call of it that failed and after a later finish of either kind (include/welldup_lanemolecules.h)
+    uint8_t *mol = nullptr;
+    int mol_e = 0, mol_family = 0;
 };
 
 namespace {
@@ -684,6 +688,8 @@ try {
 
 int wd_lane_dups_finish(wd_lane_dups *ld, int64_t *lane_row, int64_t *tile_rows, uint32_t *const *labels_dev)
 try {
+    if (ld)
+        ld->mol = nullptr;                                             // (the molecule part does not outlive a call of a finish)
     if (!ld || !lane_row || !tile_rows)
         return WD_ERR_ARG;
     wd_ctx *ctx = ld->ctx;

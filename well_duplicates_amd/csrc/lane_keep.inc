@@ -14,6 +14,9 @@
 // writes label and members, and that nobody does after a successful finish, is said at the head of lane_mismatch.inc
 // and of lane_gc.inc; the quality rows are written by k_lq_pack alone, in wd_lane_qual_add, which refuses after a
 // finish.  This pass joins those lists as a reader.
+// wd_lane_keep_molecules (include/welldup_lanemolecules.h) is the same host body and the same two kernels with the
+// accumulator's molecule part - mol and molmem, written by wd_lane_umi_molecules (lane_umi.inc) in the form of label
+// and members - in the places of label and members: "family" then reads "UMI molecule of two or more wells".
 #include "welldup_lanekeep.h"
 
 namespace {
@@ -334,11 +337,15 @@ int wd_lane_keep_scratch(int max_tiles, int64_t wells_per_tile, size_t *bytes)
     return WD_OK;
 }
 
-int wd_lane_keep(wd_lane_dups *ld, int min_q, void *scratch_dev, size_t scratch_bytes, int64_t *lane_row,
-                 int64_t *tile_rows, uint8_t *const *keep_dev)
-try {
-    if (!ld || !lane_row || !tile_rows)
-        return WD_ERR_ARG;
+}  // extern "C"
+
+namespace {
+
+// wd_lane_keep and wd_lane_keep_molecules: one body.  label and members are the finish's, or the mol and molmem of the
+// molecule part, which have their form (lane_umi.inc).
+int lk_run(wd_lane_dups *ld, int min_q, void *scratch_dev, size_t scratch_bytes, int64_t *lane_row, int64_t *tile_rows,
+           uint8_t *const *keep_dev, const uint32_t *label, const uint32_t *members)
+{
     wd_ctx *ctx = ld->ctx;
     wd_lane_quality *lq = ld->qual.get();
     const int64_t N = ld->N;
@@ -402,7 +409,6 @@ try {
     if (const int rc = p.upload(d_tidx))
         return rc;
     WD_HIP(ctx, hipMemcpyAsync(d_maskp, h_mask.data(), (size_t)T * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
-    const uint32_t *label = (const uint32_t *)(ld->ws + ld->lay.label), *members = (const uint32_t *)(ld->ws + ld->lay.members);
     hipLaunchKernelGGL(k_lk_score, p.grid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, label, members,
                        (const uint32_t *)(lq->ws + lq->lay.qrows), ld->lay.words, wts, score, best);
     WD_HIP(ctx, hipGetLastError());
@@ -414,6 +420,34 @@ try {
         return rc;
     lane_pass_rows(f_t, T, tile_rows, lane_row, &f_l, kLkLaneCnt);
     return WD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wd_lane_keep(wd_lane_dups *ld, int min_q, void *scratch_dev, size_t scratch_bytes, int64_t *lane_row,
+                 int64_t *tile_rows, uint8_t *const *keep_dev)
+try {
+    if (!ld || !lane_row || !tile_rows)
+        return WD_ERR_ARG;
+    return lk_run(ld, min_q, scratch_dev, scratch_bytes, lane_row, tile_rows, keep_dev,
+                  (const uint32_t *)(ld->ws + ld->lay.label), (const uint32_t *)(ld->ws + ld->lay.members));
+} WD_CATCH
+
+int wd_lane_keep_molecules(wd_lane_dups *ld, int min_q, void *scratch_dev, size_t scratch_bytes, int64_t *lane_row,
+                           int64_t *tile_rows, uint8_t *const *keep_dev)
+try {
+    if (!ld || !lane_row || !tile_rows)
+        return WD_ERR_ARG;
+    if (!ld->mol)
+        return fail(ld->ctx, WD_ERR_ARG, "lane keep by molecule comes after a successful wd_lane_umi_molecules since the finish");
+    const LmolLayout ml = lmol_layout_of(ld->max_tiles, ld->N);
+    const uintptr_t m0 = (uintptr_t)ld->mol, s0 = (uintptr_t)scratch_dev;
+    if (scratch_dev && m0 < s0 + scratch_bytes && s0 < m0 + ml.bytes)
+        return fail(ld->ctx, WD_ERR_ARG, "lane keep: the scratch overlaps the molecule region");
+    return lk_run(ld, min_q, scratch_dev, scratch_bytes, lane_row, tile_rows, keep_dev, (const uint32_t *)(ld->mol + ml.mol),
+                  (const uint32_t *)(ld->mol + ml.molmem));
 } WD_CATCH
 
 }  // extern "C"

@@ -16,7 +16,8 @@
 // key, which k_li_pack alone writes (lane_index.inc, wd_lane_index_add, which refuses after a finish).  k_lgc_tally
 // (lane_gc.inc) reads label, members and every row of the lane.  k_lc_reserve and k_lc_scatter (lane_consensus.inc) read
 // label and members, k_lc_vote members and the rows of the voted families.  k_lk_score and k_lk_mark (lane_keep.inc)
-// read label, members and the quality rows.
+// read label, members and the quality rows - or, launched by wd_lane_keep_molecules, the caller's mol and molmem in
+// their places, which k_lu_pairs_mol and k_lu_group_mol (lane_umi.inc) wrote from label, members and the UMI keys.
 #include "welldup_lanemismatch.h"
 
 namespace {

@@ -218,6 +218,8 @@ int wd_lane_near_dups_finish(wd_lane_dups *ld, int k, void *scratch_dev, size_t 
                              int64_t *lane_row, int64_t *tile_rows, uint32_t *const *labels_dev,
                              int64_t *near_lane_row, int64_t *near_tile_rows, uint32_t *const *near_labels_dev)
 try {
+    if (ld)
+        ld->mol = nullptr;                                             // (the molecule part does not outlive a call of a finish)
     if (!ld || !lane_row || !tile_rows || !near_lane_row || !near_tile_rows)
         return WD_ERR_ARG;
     wd_ctx *ctx = ld->ctx;

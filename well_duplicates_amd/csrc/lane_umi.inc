@@ -29,7 +29,29 @@
 // a component does depend on where the members landed in the list, and nothing is counted of it - each component's
 // smallest global id and size are gathered at it by an atomic minimum and adds.  Every output is a sum over families,
 // molecules or wells of such values: integer adds, which commute.
-#include "welldup_laneumi.h"
+//
+// wd_lane_umi_molecules (include/welldup_lanemolecules.h): the same four launches with k_lu_pairs_mol and k_lu_group_mol
+// in the places of k_lu_pairs and k_lu_group - the same device bodies, instantiated with kEmit -, which also write the
+// caller's mol and molmem, a word per well each: the molecule's first well, and at that well the molecule's other
+// wells, in the form the finish leaves label and members, so that k_lk_score and k_lk_mark (lane_keep.inc) run on them
+// as they stand.  Who writes which word - every word of both arrays is written in a call exactly once, so the region
+// may hold anything before and nothing clears it:
+//   - a well of a tile never added: a memset of the tile's part of each array, queued by the host;
+//   - a well of a pair (a family of two): the lane of k_lu_pairs_mol that walks the COPY, which holds both keys and d.
+//     It writes both wells' entries; the lane that walks the pair's root writes nothing;
+//   - a well of a gathered family of 3 .. max_family wells: the lane of k_lu_group_mol that holds the member - a
+//     family is one wave's, its range holds each member once (lane_consensus.inc), and a member is one lane's in the
+//     closure (n <= 64) and in the last loop (n > 64).  The lane of k_lu_pairs_mol that walks it writes nothing;
+//   - every other well of an added tile - not PF, Single, or of a Large family -: the lane of k_lu_pairs_mol that
+//     walks it (a well of a run is walked by one lane of one workgroup).
+// The four cases partition the wells by label and members[label] alone, which no launch of the call writes, so two
+// launches never disagree about whose a well is.  Why the values are exact and do not depend on the order of
+// execution: a pair's entries are a function of its two keys; in a family of up to 64 wells the label a lane ends with
+// is the fixed point said above and the size a popcount over the wave; in a larger one mn[r] and sz[r] are final
+// after the wave has met, whichever member number r is.  A molecule's first well has its smallest id, and a Large
+// family's root the smallest of the family, so "a root has the smallest id of its family" (lane_keep.inc) holds for
+// molecules too.
+#include "welldup_lanemolecules.h"
 
 namespace {
 
@@ -92,6 +114,21 @@ LuLayout lu_layout_of(int max_tiles, int64_t N)
     return l;
 }
 
+// the molecule region of a call (include/welldup_lanemolecules.h states the arithmetic)
+struct LmolLayout {
+    size_t mol, molmem, bytes;
+};
+
+LmolLayout lmol_layout_of(int max_tiles, int64_t N)
+{
+    LmolLayout l;
+    const size_t wells = (size_t)max_tiles * (size_t)N;
+    l.mol = 0;
+    l.molmem = align256(l.mol + wells * 4);
+    l.bytes = align256(l.molmem + wells * 4);
+    return l;
+}
+
 // the workgroups of k_lu_group for a lane of `wells` wells: no more than its families of three can be
 unsigned lu_group_groups(size_t wells)
 {
@@ -138,6 +175,32 @@ struct LuTile {
     }
 };
 
+// ---- the molecules as an array (include/welldup_lanemolecules.h) -----------------------------------
+// the one store of a well's entry (the emulator counts them: every word is written once)
+__device__ inline void lu_emit(uint32_t *mol, uint32_t *molmem, uint32_t g, uint32_t first, uint32_t more)
+{
+#ifdef WD_LANE_MOL_EMU_STORE
+    WD_LANE_MOL_EMU_STORE(g);
+#endif
+    mol[g] = first;
+    molmem[g] = more;
+}
+
+// What the pairs walk writes for a well g of its run that is not the copy of a pair: not PF, Single, or of a Large
+// family, which counts as one molecule as the finish left it.  A pair's root is left to its copy's lane, a member of
+// a gathered family of three or more to k_lu_group_mol.
+__device__ inline void lu_emit_rest(uint32_t *mol, uint32_t *molmem, uint32_t g, uint32_t lab,
+                                    const uint32_t *__restrict__ members, int max_family)
+{
+    if (lab == kInvalid) {
+        lu_emit(mol, molmem, g, kInvalid, 0u);
+        return;
+    }
+    const uint32_t mem = members[lab];
+    if (mem == 0u || mem + 1u > (uint32_t)max_family)                // (mem == 0: lab == g, a Single)
+        lu_emit(mol, molmem, g, lab, lab == g ? mem : 0u);
+}
+
 // ---- pairs --------------------------------------------------------------------------------------
 // LaneRun's grid and walk.  The copy of a family of two (a PF well that is not its root and whose root has one
 // member) loads its own key and key[label] and accounts for both wells of the pair.  The first well of a molecule
@@ -146,11 +209,11 @@ struct LuTile {
 // histograms over the whole walk, the copy's own tile likewise (a run lies on one tile), the root's tile through
 // wave_by_key on label / N for the tile the wave met last - and added once per wave, or once per wave and change of
 // the root's tile.  The pairs fill two bins of each histogram: one molecule of two wells, or two of one.
-__global__ void __launch_bounds__(kTdBlock) k_lu_pairs(const int *__restrict__ tile_idx, int64_t N,
-                                                        const uint32_t *__restrict__ label,
-                                                        const uint32_t *__restrict__ members,
-                                                        const uint2 *__restrict__ key, int max_e,
-                                                        unsigned long long *cnt_t, unsigned long long *cnt_l)
+template <bool kEmit>
+__device__ inline void lu_pairs(const int *__restrict__ tile_idx, int64_t N, const uint32_t *__restrict__ label,
+                                const uint32_t *__restrict__ members, const uint2 *__restrict__ key, int max_e,
+                                unsigned long long *cnt_t, unsigned long long *cnt_l, int max_family, uint32_t *mol,
+                                uint32_t *molmem)
 {
     const LaneRun run(tile_idx, N);
     const int lane = threadIdx.x & (kWave - 1);
@@ -170,7 +233,13 @@ __global__ void __launch_bounds__(kTdBlock) k_lu_pairs(const int *__restrict__ t
                 equal = d == 0;
                 wn_a = lu_with_n(a);
                 wn_b = lu_with_n(b);
-            }
+                if constexpr (kEmit) {                                 // both wells of the pair are this lane's
+                    const uint32_t lo = min(lab, (uint32_t)g64), hi = max(lab, (uint32_t)g64);
+                    lu_emit(mol, molmem, lo, lo, joined ? 1u : 0u);
+                    lu_emit(mol, molmem, hi, joined ? lo : hi, 0u);
+                }
+            } else if constexpr (kEmit)
+                lu_emit_rest(mol, molmem, (uint32_t)g64, lab, members, max_family);
         }
         const unsigned long long b_pair = __ballot(pair);
         if (!b_pair)                                                  // (the same for the whole wave)
@@ -209,6 +278,27 @@ __global__ void __launch_bounds__(kTdBlock) k_lu_pairs(const int *__restrict__ t
             atomicAdd(c + kLuSize + 0, 2ull * n_split);               // of one well each
         }
     }
+}
+
+__global__ void __launch_bounds__(kTdBlock) k_lu_pairs(const int *__restrict__ tile_idx, int64_t N,
+                                                        const uint32_t *__restrict__ label,
+                                                        const uint32_t *__restrict__ members,
+                                                        const uint2 *__restrict__ key, int max_e,
+                                                        unsigned long long *cnt_t, unsigned long long *cnt_l)
+{
+    lu_pairs<false>(tile_idx, N, label, members, key, max_e, cnt_t, cnt_l, 0, nullptr, nullptr);
+}
+
+// k_lu_pairs, and every well of the run that is not of a gathered family gets its entry of mol and molmem (the head
+// of the file says who writes which word).
+__global__ void __launch_bounds__(kTdBlock) k_lu_pairs_mol(const int *__restrict__ tile_idx, int64_t N,
+                                                            const uint32_t *__restrict__ label,
+                                                            const uint32_t *__restrict__ members,
+                                                            const uint2 *__restrict__ key, int max_e, int max_family,
+                                                            unsigned long long *cnt_t, unsigned long long *cnt_l,
+                                                            uint32_t *mol, uint32_t *molmem)
+{
+    lu_pairs<true>(tile_idx, N, label, members, key, max_e, cnt_t, cnt_l, max_family, mol, molmem);
 }
 
 // ---- grouping -----------------------------------------------------------------------------------
@@ -253,11 +343,11 @@ __device__ inline void lu_tally(bool active, uint32_t id, bool first, uint32_t s
 // Work per family is bounded by max_family^2 / 64 key comparisons per lane (n / 64 chunks, each against at most n
 // members; at n <= 64 n comparisons and at most n rounds of n shuffles), so the last wave to finish is at most one
 // family of max_family wells behind the others: at 1024 wells 16 384 comparisons per lane.
-__global__ void __launch_bounds__(kTdBlock) k_lu_group(int64_t N, const uint32_t *__restrict__ members,
-                                                        const uint2 *__restrict__ key, int max_e, uint32_t W, int groups,
-                                                        const unsigned long long *__restrict__ cursor,
-                                                        const uint32_t *__restrict__ slot, const uint32_t *__restrict__ region,
-                                                        unsigned long long *cnt_t, unsigned long long *cnt_l)
+template <bool kEmit>
+__device__ inline void lu_group(int64_t N, const uint32_t *__restrict__ members, const uint2 *__restrict__ key, int max_e,
+                                uint32_t W, int groups, const unsigned long long *__restrict__ cursor,
+                                const uint32_t *__restrict__ slot, const uint32_t *__restrict__ region,
+                                unsigned long long *cnt_t, unsigned long long *cnt_l, uint32_t *mol, uint32_t *molmem)
 {
     __shared__ uint32_t s_par[kLuWaves][kLuMaxFamily], s_min[kLuWaves][kLuMaxFamily], s_size[kLuWaves][kLuMaxFamily];
     __shared__ uint32_t s_hist[2 * kLuBins];                          // MolPerFamily, MoleculeSize
@@ -313,6 +403,9 @@ __global__ void __launch_bounds__(kTdBlock) k_lu_group(int64_t N, const uint32_t
             distinct += (unsigned long long)__popcll(__ballot(active && !dup));
             with_n += (unsigned long long)__popcll(__ballot(active && lu_with_n(k)));
             lu_tally(active, id, first, size, N, lane, tl, cnt_t, s_hist);
+            if constexpr (kEmit)
+                if (active)
+                    lu_emit(mol, molmem, id, lab, first ? size - 1u : 0u);
         } else {
             for (uint32_t i = (uint32_t)lane; i < n; i += kWave) {
                 par[i] = i;
@@ -358,6 +451,8 @@ __global__ void __launch_bounds__(kTdBlock) k_lu_group(int64_t N, const uint32_t
                     id = lc_member(region, root, start, ia);
                     first = mn[r] == id;
                     size = sz[r];
+                    if constexpr (kEmit)
+                        lu_emit(mol, molmem, id, mn[r], first ? size - 1u : 0u);
                 }
                 m += (uint32_t)__popcll(__ballot(first));
                 lu_tally(active, id, first, size, N, lane, tl, cnt_t, s_hist);
@@ -389,6 +484,26 @@ __global__ void __launch_bounds__(kTdBlock) k_lu_group(int64_t N, const uint32_t
     __syncthreads();
     if (threadIdx.x < 2 * kLuBins && s_hist[threadIdx.x])
         atomicAdd(spread_row(cnt_l, 0, kLuLaneCnt) + kLuPerFamily + threadIdx.x, (unsigned long long)s_hist[threadIdx.x]);
+}
+
+__global__ void __launch_bounds__(kTdBlock) k_lu_group(int64_t N, const uint32_t *__restrict__ members,
+                                                        const uint2 *__restrict__ key, int max_e, uint32_t W, int groups,
+                                                        const unsigned long long *__restrict__ cursor,
+                                                        const uint32_t *__restrict__ slot, const uint32_t *__restrict__ region,
+                                                        unsigned long long *cnt_t, unsigned long long *cnt_l)
+{
+    lu_group<false>(N, members, key, max_e, W, groups, cursor, slot, region, cnt_t, cnt_l, nullptr, nullptr);
+}
+
+// k_lu_group, and every member of a gathered family of three or more wells gets its entry of mol and molmem.
+__global__ void __launch_bounds__(kTdBlock) k_lu_group_mol(int64_t N, const uint32_t *__restrict__ members,
+                                                            const uint2 *__restrict__ key, int max_e, uint32_t W, int groups,
+                                                            const unsigned long long *__restrict__ cursor,
+                                                            const uint32_t *__restrict__ slot,
+                                                            const uint32_t *__restrict__ region, unsigned long long *cnt_t,
+                                                            unsigned long long *cnt_l, uint32_t *mol, uint32_t *molmem)
+{
+    lu_group<true>(N, members, key, max_e, W, groups, cursor, slot, region, cnt_t, cnt_l, mol, molmem);
 }
 
 }  // namespace
@@ -515,11 +630,25 @@ int wd_lane_umi_scratch(int max_tiles, int64_t wells_per_tile, size_t *bytes)
     return WD_OK;
 }
 
-int wd_lane_umi(wd_lane_dups *ld, int max_e, int max_family, void *scratch_dev, size_t scratch_bytes, int64_t *lane_row,
-                int64_t *tile_rows)
-try {
-    if (!ld || !lane_row || !tile_rows)
+int wd_lane_molecules_bytes(int max_tiles, int64_t wells_per_tile, size_t *bytes)
+{
+    size_t scratch = 0;
+    if (!bytes)
         return WD_ERR_ARG;
+    if (const int rc = wd_lane_umi_scratch(max_tiles, wells_per_tile, &scratch))
+        return rc;
+    *bytes = lmol_layout_of(max_tiles, wells_per_tile).bytes;
+    return WD_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// wd_lane_umi and wd_lane_umi_molecules: one body.  Without `emit` the counting kernels run and mol_dev is not looked at.
+int lu_run(wd_lane_dups *ld, int max_e, int max_family, void *scratch_dev, size_t scratch_bytes, int64_t *lane_row,
+           int64_t *tile_rows, bool emit, void *mol_dev, size_t mol_bytes)
+{
     wd_ctx *ctx = ld->ctx;
     const int64_t N = ld->N;
     const int T = ld->max_tiles;
@@ -542,10 +671,30 @@ try {
     if (const int rc = p.scratch(scratch_dev, scratch_bytes, lay.bytes, "scratch smaller than wd_lane_umi_scratch",
                                  "lane umi: the scratch must be in device memory"))
         return rc;
+    const LmolLayout ml = lmol_layout_of(T, N);
+    if (emit) {
+        if (!mol_dev || mol_bytes < ml.bytes)
+            return fail(ctx, WD_ERR_ARG, "lane umi: the molecule region is smaller than wd_lane_molecules_bytes");
+        if (!on_device(mol_dev))
+            return fail(ctx, WD_ERR_ARG, "lane umi: the molecule region must be in device memory");
+        const uintptr_t m0 = (uintptr_t)mol_dev, s0 = (uintptr_t)scratch_dev;
+        if (m0 < s0 + scratch_bytes && s0 < m0 + mol_bytes)
+            return fail(ctx, WD_ERR_ARG, "lane umi: the molecule region overlaps the scratch");
+    }
+    uint32_t *mol = emit ? (uint32_t *)((uint8_t *)mol_dev + ml.mol) : nullptr;
+    uint32_t *molmem = emit ? (uint32_t *)((uint8_t *)mol_dev + ml.molmem) : nullptr;
     memset(lane_row, 0, WD_LANEUMI_LANE_COLS * sizeof(int64_t));
     memset(tile_rows, 0, (size_t)T * kLuTileCnt * sizeof(int64_t));
-    if (!p.start())
-        return p.rc;
+    if (!p.start()) {
+        if (p.rc != WD_OK || !emit || N == 0 || T == 0)
+            return p.rc;
+        if (bind_device(ctx))                                          // wells but no tile: no well is PF
+            return WD_ERR_HIP;
+        WD_HIP(ctx, hipMemsetAsync(mol, 0xFF, 4 * (size_t)T * (size_t)N, ctx->stream));
+        WD_HIP(ctx, hipMemsetAsync(molmem, 0, 4 * (size_t)T * (size_t)N, ctx->stream));
+        WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return WD_OK;
+    }
     uint8_t *sc = (uint8_t *)scratch_dev;
     unsigned long long *cnt_t = (unsigned long long *)(sc + lay.cnt_t);
     unsigned long long *cnt_l = (unsigned long long *)(sc + lay.cnt_l);
@@ -561,15 +710,29 @@ try {
     WD_HIP(ctx, hipMemsetAsync(sc, 0, lay.cleared, ctx->stream));
     if (const int rc = p.upload(d_tidx))
         return rc;
-    hipLaunchKernelGGL(k_lu_pairs, p.grid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, label, members, key, max_e, cnt_t, cnt_l);
+    if (emit) {
+        for (int t = 0; t < T; t++)                                    // a tile never added: no well of it is PF
+            if (!ld->added[t]) {
+                WD_HIP(ctx, hipMemsetAsync(mol + (size_t)t * (size_t)N, 0xFF, 4 * (size_t)N, ctx->stream));
+                WD_HIP(ctx, hipMemsetAsync(molmem + (size_t)t * (size_t)N, 0, 4 * (size_t)N, ctx->stream));
+            }
+        hipLaunchKernelGGL(k_lu_pairs_mol, p.grid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, label, members, key, max_e,
+                           max_family, cnt_t, cnt_l, mol, molmem);
+    } else
+        hipLaunchKernelGGL(k_lu_pairs, p.grid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, label, members, key, max_e, cnt_t,
+                           cnt_l);
     WD_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_lc_reserve, p.grid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, label, members, max_family, W, cursor,
                        slot, region, cnt_r);
     WD_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_lc_scatter, p.grid, dim3(kTdBlock), 0, ctx->stream, d_tidx, N, label, members, max_family, slot, region);
     WD_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_lu_group, dim3(groups), dim3(kTdBlock), 0, ctx->stream, N, members, key, max_e, W, (int)groups, cursor,
-                       slot, region, cnt_t, cnt_l);
+    if (emit)
+        hipLaunchKernelGGL(k_lu_group_mol, dim3(groups), dim3(kTdBlock), 0, ctx->stream, N, members, key, max_e, W, (int)groups,
+                           cursor, slot, region, cnt_t, cnt_l, mol, molmem);
+    else
+        hipLaunchKernelGGL(k_lu_group, dim3(groups), dim3(kTdBlock), 0, ctx->stream, N, members, key, max_e, W, (int)groups,
+                           cursor, slot, region, cnt_t, cnt_l);
     WD_HIP(ctx, hipGetLastError());
     SpreadFetch f_t(cnt_t, (size_t)T, kLuTileCnt), f_l(cnt_l, 1, kLuLaneCnt), f_r(cnt_r, 1, kLcLaneCnt);
     if (const int rc = spread_fetch(ctx, {&f_t, &f_l, &f_r}))
@@ -590,6 +753,44 @@ try {
     f_r.sum(0, c);
     lane_row[kLuTileCnt + 6] = (int64_t)c[kLcLarge];
     lane_row[kLuTileCnt + 7] = (int64_t)c[kLcLargeWells];
+    return WD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wd_lane_umi(wd_lane_dups *ld, int max_e, int max_family, void *scratch_dev, size_t scratch_bytes, int64_t *lane_row,
+                int64_t *tile_rows)
+try {
+    if (!ld || !lane_row || !tile_rows)
+        return WD_ERR_ARG;
+    return lu_run(ld, max_e, max_family, scratch_dev, scratch_bytes, lane_row, tile_rows, false, nullptr, 0);
+} WD_CATCH
+
+int wd_lane_umi_molecules(wd_lane_dups *ld, int max_e, int max_family, void *scratch_dev, size_t scratch_bytes,
+                          int64_t *lane_row, int64_t *tile_rows, void *mol_dev, size_t mol_bytes)
+try {
+    if (ld)
+        ld->mol = nullptr;                                             // a call that fails, in whatever way, leaves no molecule part
+    if (!ld || !lane_row || !tile_rows)
+        return WD_ERR_ARG;
+    if (const int rc = lu_run(ld, max_e, max_family, scratch_dev, scratch_bytes, lane_row, tile_rows, true, mol_dev, mol_bytes))
+        return rc;
+    ld->mol = (uint8_t *)mol_dev;
+    ld->mol_e = max_e;
+    ld->mol_family = max_family;
+    return WD_OK;
+} WD_CATCH
+
+int wd_lane_molecules_part(wd_lane_dups *ld, int *max_e, int *max_family)
+try {
+    if (!ld || !max_e || !max_family)
+        return WD_ERR_ARG;
+    if (!ld->mol)
+        return fail(ld->ctx, WD_ERR_ARG, "lane molecules: the accumulator has no molecule part");
+    *max_e = ld->mol_e;
+    *max_family = ld->mol_family;
     return WD_OK;
 } WD_CATCH
 

@@ -1863,20 +1863,23 @@ class LaneKeepCounts:
     sum_roots: int = 0
     gains: List[int] = field(default_factory=lambda: [0] * len(LANE_KEEP_GAIN_NAMES))
     tiles: Dict[str, List[int]] = field(default_factory=dict)
+    by: Optional[str] = None                       # "molecule" under --lane-dups-keep-umi, "family" if said; None: not said
 
     @classmethod
     def from_rows(cls, lane_row: Sequence[int], tile_rows: Sequence[Sequence[int]], tile_names: Sequence, k: int,
-                  min_q: int, edges: Sequence[int], cycles: int) -> "LaneKeepCounts":
+                  min_q: int, edges: Sequence[int], cycles: int, by: Optional[str] = None) -> "LaneKeepCounts":
         """The two rows of LaneDups.keep(min_q); tile_names as LaneDupCounts.from_rows takes them; k: the K of
-        --lane-dups-hamming; edges: the quality bins' lower edges; cycles: the scanned cycles."""
+        --lane-dups-hamming; edges: the quality bins' lower edges; cycles: the scanned cycles; by: "molecule" for the
+        rows of keep(by_molecule=True) (include/welldup_lanemolecules.h), whose "families" are UMI molecules of two or
+        more wells."""
         b = [int(v) for v in lane_row]
-        assert len(b) == LANE_KEEP_LANE_COLS and 0 <= min_q <= 63
+        assert len(b) == LANE_KEEP_LANE_COLS and 0 <= min_q <= 63 and by in (None, "family", "molecule")
         tiles = {}
         for name, row in zip(tile_names, tile_rows):
             assert len(row) == LANE_KEEP_TILE_COLS
             if name is not None:
                 tiles[name] = [int(v) for v in row]
-        return cls(int(k), int(min_q), int(cycles), [int(e) for e in edges], *b[:9], b[9:], tiles)
+        return cls(int(k), int(min_q), int(cycles), [int(e) for e in edges], *b[:9], b[9:], tiles, by)
 
     @property
     def weights(self) -> List[int]:
@@ -1893,11 +1896,13 @@ def write_lane_keep(lane, counts: LaneKeepCounts, verbose: bool = False, out=Non
     sorted order as write_report), then the summary - the kept and the dropped wells and their shares of PF, the
     families and those whose kept well is not their first well -, the mean score per base of the kept wells (the
     families' representatives and the single reads), of the first wells of the families and of the dropped wells, and
-    the families by gain."""
+    the families by gain.  With counts.by the summary line ends in "By: family" or "By: molecule", and by molecule
+    (--lane-dups-keep-umi) the block says molecules where it says families."""
     out = out or sys.stdout
     c = counts
     share = lambda v, of: v / of if of else 0.0
     num = lambda v: "n/a" if v is None else "%.3f" % v
+    groups, of_groups = ("Molecules", "molecules") if c.by == "molecule" else ("Families", "families")
     print(file=out)
     if verbose:
         for tile in sorted(c.tiles):
@@ -1906,11 +1911,11 @@ def write_lane_keep(lane, counts: LaneKeepCounts, verbose: bool = False, out=Non
                 lane, tile, t[0], t[1], t[2], share(t[2], t[0]), t[3], num(c.per_base(t[4], t[1])),
                 num(c.per_base(t[5], t[2]))), file=out)
     print("LaneKeepSummary: %s\tTiles: %i\tHamming: %i\tMinQ: %i\tCycles: %i\tWeights: %s\tPF: %i\tKept: %i (%.5f)\t"
-          "Dropped: %i (%.5f)\tFamilies: %i\tMoved: %i (%.5f of Families)" % (
+          "Dropped: %i (%.5f)\t%s: %i\tMoved: %i (%.5f of %s)%s" % (
               lane, len(c.tiles), c.k, c.min_q, c.cycles, ",".join(str(w) for w in c.weights), c.pf, c.kept,
-              share(c.kept, c.pf), c.dropped, share(c.dropped, c.pf), c.families, c.moved, share(c.moved, c.families)),
-          file=out)
-    print("Mean score per base\tkept wells: %s\tfirst wells of families: %s\tdropped wells: %s" % (
-        num(c.per_base(c.sum_kept, c.kept)), num(c.per_base(c.sum_roots, c.families)),
+              share(c.kept, c.pf), c.dropped, share(c.dropped, c.pf), groups, c.families, c.moved, share(c.moved, c.families),
+              groups, "\tBy: %s" % c.by if c.by else ""), file=out)
+    print("Mean score per base\tkept wells: %s\tfirst wells of %s: %s\tdropped wells: %s" % (
+        num(c.per_base(c.sum_kept, c.kept)), of_groups, num(c.per_base(c.sum_roots, c.families)),
         num(c.per_base(c.sum_dropped, c.dropped))), file=out)
-    print("FamiliesByGain: %s" % "\t".join("%s: %i" % (n, v) for n, v in zip(LANE_KEEP_GAIN_NAMES, c.gains)), file=out)
+    print("%sByGain: %s" % (groups, "\t".join("%s: %i" % (n, v) for n, v in zip(LANE_KEEP_GAIN_NAMES, c.gains))), file=out)

@@ -346,6 +346,11 @@ class Scanner:
         the lane - where a family's range begins, the member list and the family table - plus the counters)."""
         return self._workspace_bytes(self._lib.wd_lane_umi_scratch, max_tiles, n_clusters)
 
+    def lane_molecules_bytes(self, max_tiles: int, n_clusters: int) -> int:
+        """Device bytes of the molecule region LaneDups.umi(molecules=True) fills (wd_lane_molecules_bytes: 8 bytes per
+        well of the lane)."""
+        return self._workspace_bytes(self._lib.wd_lane_molecules_bytes, max_tiles, n_clusters)
+
     def lane_keep_scratch_bytes(self, max_tiles: int, n_clusters: int) -> int:
         """Device bytes LaneDups.keep needs beside the accumulator's workspaces (wd_lane_keep_scratch: 10 bytes per well
         of the lane - the best of the family rooted there and the well's score - plus the counters, the tile indices and
@@ -582,6 +587,7 @@ class LaneDups:
         self.d_index, self.index_bytes, self.I, self.index_listed = 0, 0, 0, 0
         self.d_qual, self.qual_bytes, self.qual_edges = 0, 0, None
         self.d_umi, self.umi_bytes, self.U = 0, 0, 0
+        self.d_mol, self.mol_bytes = 0, 0                # the molecule region (umi(molecules=True))
         self.refused = None
         self.added = []                                  # the tile indices given to add, in that order
         self._h = None
@@ -823,7 +829,7 @@ class LaneDups:
         at = up(8 * self.max_tiles * self.U) + up(4 * self.max_tiles)
         return self.sc.d2h(self.d_umi + at, 8 * self.N * self.max_tiles, np.uint64)
 
-    def umi(self, max_e: int = 0, max_family: int = 256):
+    def umi(self, max_e: int = 0, max_family: int = 256, molecules: bool = False):
         """After finish() of a lane with a UMI part, any number of times, before or after every other pass
         (wd_lane_umi, include/welldup_laneumi.h): the wells of every family of 2 .. max_family wells under the labels
         the finish left are grouped by their UMI read - a molecule is a connected component under "at most max_e UMI
@@ -833,16 +839,53 @@ class LaneDups:
         3, 4, 5-8, 9-16, 17-64 and 65 or more; tile rows int64 [max_tiles, 3]: [Wells, UmiRedundant, Lone] by the well's
         own tile).  The scratch is allocated for the call and released.  max_e outside 0..3, max_family outside 2..1024,
         a lane without a UMI part, a tile that has reads but no UMI planes (or the reverse) or a call before a
-        successful finish raises ValueError."""
+        successful finish raises ValueError.
+        With `molecules` the same rows come from wd_lane_umi_molecules (include/welldup_lanemolecules.h), which also
+        writes every well's molecule into a region the accumulator owns - allocated on the first such call, freed by
+        close() -: what keep(by_molecule=True) then reads and umi_molecules() downloads."""
         if self._h is None:
             raise ValueError("the accumulator is closed")
         lane_row = np.zeros(_lib.LANEUMI_LANE_COLS, dtype=np.int64)
         tile_rows = np.zeros((self.max_tiles, _lib.LANEUMI_TILE_COLS), dtype=np.int64)
+        if molecules:
+            if not self.d_mol:
+                self.mol_bytes = self.sc.lane_molecules_bytes(self.max_tiles, self.N)
+                self.d_mol = self.sc.malloc(max(1, self.mol_bytes))
+            self._with_scratch(self.sc.lane_umi_scratch_bytes(self.max_tiles, self.N),
+                               lambda d_scratch, sbytes: self.sc._lib.wd_lane_umi_molecules(
+                                   self._h, int(max_e), int(max_family), d_scratch, sbytes,
+                                   lane_row.ctypes.data_as(ctypes.c_void_p), tile_rows.ctypes.data_as(ctypes.c_void_p),
+                                   ctypes.c_void_p(self.d_mol), self.mol_bytes))
+            return lane_row, tile_rows
         self._with_scratch(self.sc.lane_umi_scratch_bytes(self.max_tiles, self.N),
                            lambda d_scratch, sbytes: self.sc._lib.wd_lane_umi(
                                self._h, int(max_e), int(max_family), d_scratch, sbytes,
                                lane_row.ctypes.data_as(ctypes.c_void_p), tile_rows.ctypes.data_as(ctypes.c_void_p)))
         return lane_row, tile_rows
+
+    def molecule_part(self):
+        """-> (max_e, max_family) of the umi(molecules=True) whose molecules keep(by_molecule=True) would read now, or
+        None: there has been none since the finish, or the last one failed (wd_lane_molecules_part)."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        e, mf = ctypes.c_int(), ctypes.c_int()
+        if self.sc._lib.wd_lane_molecules_part(self._h, ctypes.byref(e), ctypes.byref(mf)) != _lib.OK:
+            return None
+        return e.value, mf.value
+
+    def umi_molecules(self):
+        """-> (mol, molmem), uint32 [max_tiles, N] each: what the last umi(molecules=True) wrote (the two arrays of
+        include/welldup_lanemolecules.h, molmem 4 * max_tiles * N bytes, rounded up to 256, behind mol).  ValueError
+        before the first such call."""
+        if not self.d_mol:
+            raise ValueError("umi_molecules comes after umi(molecules=True)")
+        wells = self.max_tiles * self.N
+        at = (4 * wells + 255) // 256 * 256
+        shape = (self.max_tiles, self.N)
+        if not wells:
+            return np.zeros(shape, dtype=np.uint32), np.zeros(shape, dtype=np.uint32)
+        return (self.sc.d2h(self.d_mol, 4 * wells, np.uint32).reshape(shape),
+                self.sc.d2h(self.d_mol + at, 4 * wells, np.uint32).reshape(shape))
 
     def add(self, tb: "TileBatch", tile_indices: Sequence[int]):
         """Adds the tiles of a resident batch (a plane per cycle); tile_indices[i]: slot i's number in the lane,
@@ -953,7 +996,7 @@ class LaneDups:
                                tile_rows.ctypes.data_as(ctypes.c_void_p), hist.ctypes.data_as(ctypes.c_void_p)))
         return lane_row, tile_rows, hist
 
-    def keep(self, min_q: int = _lib.LANEKEEP_DEFAULT_MIN_Q, masks: bool = False):
+    def keep(self, min_q: int = _lib.LANEKEEP_DEFAULT_MIN_Q, masks: bool = False, by_molecule: bool = False):
         """After finish(), any number of times, before or after every other pass, on an accumulator with a quality part
         (wd_lane_keep, include/welldup_lanekeep.h): of every family - a class, or a cluster under a near finish - the
         well with the largest score is kept, the smallest id among equals, and the others are dropped; a well's score
@@ -962,9 +1005,15 @@ class LaneDups:
         x 8], tile rows int64 [max_tiles, 6]: the first six by the well's own tile), and with `masks` a third: {tile
         index: uint8 [N], 1 for a kept well and 0 for any other} for every tile that was added.  The scratch is
         allocated for the call and released.  min_q outside 0..63, a call before a successful finish or without
-        qual_begin, or a tile that has reads but no qualities (or the reverse) raises ValueError."""
+        qual_begin, or a tile that has reads but no qualities (or the reverse) raises ValueError.
+        by_molecule: one well per UMI molecule, not per family (wd_lane_keep_molecules,
+        include/welldup_lanemolecules.h): the molecules are those of the last umi(molecules=True) since the finish;
+        without one ValueError."""
         if self._h is None:
             raise ValueError("the accumulator is closed")
+        if by_molecule and not self.d_mol:
+            raise ValueError("keep(by_molecule=True) comes after umi(molecules=True)")
+        entry = self.sc._lib.wd_lane_keep_molecules if by_molecule else self.sc._lib.wd_lane_keep
         lane_row = np.zeros(_lib.LANEKEEP_LANE_COLS, dtype=np.int64)
         tile_rows = np.zeros((self.max_tiles, _lib.LANEKEEP_TILE_COLS), dtype=np.int64)
         tiles = sorted(self.added) if masks else []
@@ -977,7 +1026,7 @@ class LaneDups:
                     ptrs[t] = d_masks + i * self.N
                 table = (ctypes.c_void_p * self.max_tiles)(*ptrs)
             self._with_scratch(self.sc.lane_keep_scratch_bytes(self.max_tiles, self.N),
-                               lambda d_scratch, sbytes: self.sc._lib.wd_lane_keep(
+                               lambda d_scratch, sbytes: entry(
                                    self._h, int(min_q), d_scratch, sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
                                    tile_rows.ctypes.data_as(ctypes.c_void_p), table))
             if not masks:
@@ -1134,10 +1183,10 @@ class LaneDups:
     def close(self):
         """Drops the lane, finished or not, and frees the workspace."""
         self._end()
-        for ptr in (self.d_ws, self.d_labels, self.d_near_labels, self.d_index, self.d_qual, self.d_umi):
+        for ptr in (self.d_ws, self.d_labels, self.d_near_labels, self.d_index, self.d_qual, self.d_umi, self.d_mol):
             if ptr:
                 self.sc.free(ptr)
-        self.d_ws = self.d_labels = self.d_near_labels = self.d_index = self.d_qual = self.d_umi = 0
+        self.d_ws = self.d_labels = self.d_near_labels = self.d_index = self.d_qual = self.d_umi = self.d_mol = 0
 
 
 class TileBatch:
