@@ -78,15 +78,17 @@ from __future__ import annotations
 
 import math
 import os
-import struct
 import sys
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 from concurrent.futures import ThreadPoolExecutor
+from types import SimpleNamespace
 
 import numpy as np
 
 from . import bcl as bcl_direct_reader
 from . import _lib, report, workload
+from .lane_passes import (DEFAULT_QUALITY_BINS, LANE_PASSES, check_cycle_ranges, check_options, dest,  # noqa: F401
+                          parse_quality_bins, resolve_passes, write_keep_filter, write_lane_keep_filters)
 from .report import LENGTH, TALLY, output_writer  # noqa: F401  (reference module surface)
 from .scanner import INVALID_TARGET, LaneDups, Scanner, TileBatch, compare_mode
 from .targets import load_targets, load_targets_csr
@@ -418,96 +420,7 @@ def parse_args(argv=None):
                         "file>, the tile's filter file with the PF bit cleared on every dropped well.  Put in place of "
                         "the run directory's own files they make bcl2fastq or BCL Convert emit the deduplicated lane")
     args = p.parse_args(argv)
-    if args.lane_dups_keep and not args.lane_dups:
-        p.error("--lane-dups-keep needs --lane-dups")
-    for flag, value in (("min-q", args.lane_dups_keep_min_q), ("out", args.lane_dups_keep_out)):
-        if value is not None and not args.lane_dups_keep:
-            p.error("--lane-dups-keep-%s needs --lane-dups-keep" % flag)
-    if args.lane_dups_keep_umi and not args.lane_dups_keep:
-        p.error("--lane-dups-keep-umi needs --lane-dups-keep")
-    if args.lane_dups_keep_umi and args.lane_dups_umi is None:
-        p.error("--lane-dups-keep-umi needs --lane-dups-umi")
-    if args.lane_dups_keep_min_q is not None and not 0 <= args.lane_dups_keep_min_q <= _lib.LANEKEEP_MAX_Q:
-        p.error("--lane-dups-keep-min-q takes 0..%d, not %d" % (_lib.LANEKEEP_MAX_Q, args.lane_dups_keep_min_q))
-    if args.lane_dups_umi is not None and not args.lane_dups:
-        p.error("--lane-dups-umi needs --lane-dups")
-    for flag, value in (("mismatches", args.lane_dups_umi_mismatches), ("max-family", args.lane_dups_umi_max_family),
-                        ("out", args.lane_dups_umi_out)):
-        if value is not None and args.lane_dups_umi is None:
-            p.error("--lane-dups-umi-%s needs --lane-dups-umi" % flag)
-    if args.lane_dups_umi is not None:
-        try:
-            ranges = workload.parse_cycles(0, 0, args.lane_dups_umi)
-        except ValueError:
-            ranges = [(0, 0)]
-        if any(not 0 <= a < b for a, b in ranges):
-            p.error("--lane-dups-umi takes ranges of cycles as --cycles does, eg. 0-8 or 151-160")
-        n_umi = sum(b - a for a, b in ranges)
-        if not 1 <= n_umi <= _lib.LANEUMI_MAX_CYCLES:
-            p.error("--lane-dups-umi takes 1..%d cycles, not %d" % (_lib.LANEUMI_MAX_CYCLES, n_umi))
-    if args.lane_dups_umi_mismatches is not None and not 0 <= args.lane_dups_umi_mismatches <= _lib.LANEUMI_MAX_E:
-        p.error("--lane-dups-umi-mismatches takes 0..%d, not %d" % (_lib.LANEUMI_MAX_E, args.lane_dups_umi_mismatches))
-    if args.lane_dups_umi_max_family is not None and not 2 <= args.lane_dups_umi_max_family <= _lib.LANEUMI_MAX_FAMILY:
-        p.error("--lane-dups-umi-max-family takes 2..%d, not %d" % (_lib.LANEUMI_MAX_FAMILY, args.lane_dups_umi_max_family))
-    if args.lane_dups_consensus and not args.lane_dups:
-        p.error("--lane-dups-consensus needs --lane-dups")
-    for flag, value in (("max-d", args.lane_dups_consensus_max_d), ("max-family", args.lane_dups_consensus_max_family),
-                        ("out", args.lane_dups_consensus_out)):
-        if value is not None and not args.lane_dups_consensus:
-            p.error("--lane-dups-consensus-%s needs --lane-dups-consensus" % flag)
-    if args.lane_dups_consensus_max_d is not None and not 0 <= args.lane_dups_consensus_max_d <= _lib.LANECONSENSUS_MAX_D:
-        p.error("--lane-dups-consensus-max-d takes 0..%d, not %d" % (_lib.LANECONSENSUS_MAX_D, args.lane_dups_consensus_max_d))
-    if args.lane_dups_consensus_max_family is not None and \
-            not 3 <= args.lane_dups_consensus_max_family <= _lib.LANECONSENSUS_MAX_FAMILY:
-        p.error("--lane-dups-consensus-max-family takes 3..%d, not %d" % (_lib.LANECONSENSUS_MAX_FAMILY,
-                                                                          args.lane_dups_consensus_max_family))
-    if args.lane_dups_gc and not args.lane_dups:
-        p.error("--lane-dups-gc needs --lane-dups")
-    for flag, value in (("bins", args.lane_dups_gc_bins), ("max-n", args.lane_dups_gc_max_n), ("out", args.lane_dups_gc_out)):
-        if value is not None and not args.lane_dups_gc:
-            p.error("--lane-dups-gc-%s needs --lane-dups-gc" % flag)
-    if args.lane_dups_gc_bins is not None and not report.LANE_GC_MIN_BINS <= args.lane_dups_gc_bins <= report.LANE_GC_MAX_BINS:
-        p.error("--lane-dups-gc-bins takes %d..%d, not %d" % (report.LANE_GC_MIN_BINS, report.LANE_GC_MAX_BINS,
-                                                              args.lane_dups_gc_bins))
-    if args.lane_dups_gc_max_n is not None and args.lane_dups_gc_max_n < 0:
-        p.error("--lane-dups-gc-max-n takes 0..the number of scanned cycles, not %d" % args.lane_dups_gc_max_n)
-    if args.lane_dups_hops is not None and args.lane_dups_index is None:
-        p.error("--lane-dups-hops needs --lane-dups-index")
-    if args.lane_dups_hops is not None and args.lane_dups_hops < 0:
-        p.error("--lane-dups-hops takes the number of library pairs to list, not %d" % args.lane_dups_hops)
-    if args.lane_dups_hops_mismatches is not None and args.lane_dups_hops is None:
-        p.error("--lane-dups-hops-mismatches needs --lane-dups-hops")
-    if args.lane_dups_hops_mismatches is not None and not 0 <= args.lane_dups_hops_mismatches <= _lib.LANEHOPS_MAX_E:
-        p.error("--lane-dups-hops-mismatches takes 0..%d, not %d" % (_lib.LANEHOPS_MAX_E, args.lane_dups_hops_mismatches))
-    if args.lane_dups_hops_out is not None and args.lane_dups_hops is None:
-        p.error("--lane-dups-hops-out needs --lane-dups-hops")
-    if args.lane_dups_top is not None and not args.lane_dups:
-        p.error("--lane-dups-top needs --lane-dups")
-    if args.lane_dups_top_out is not None and args.lane_dups_top is None:
-        p.error("--lane-dups-top-out needs --lane-dups-top")
-    if args.lane_dups_top is not None and not 1 <= args.lane_dups_top <= _lib.LANETOP_MAX:
-        p.error("--lane-dups-top takes 1..%d, not %d" % (_lib.LANETOP_MAX, args.lane_dups_top))
-    if args.lane_dups_saturation and not args.lane_dups:
-        p.error("--lane-dups-saturation needs --lane-dups")
-    for flag, value, lo, hi in (("steps", args.lane_dups_saturation_steps, 1, _lib.LANESATURATION_MAX_STEPS),
-                                ("seed", args.lane_dups_saturation_seed, 0, (1 << 32) - 1),
-                                ("radius", args.lane_dups_saturation_radius, 0, _lib.LANESATURATION_MAX_RADIUS)):
-        if value is not None and not args.lane_dups_saturation:
-            p.error("--lane-dups-saturation-%s needs --lane-dups-saturation" % flag)
-        if value is not None and not lo <= value <= hi:
-            p.error("--lane-dups-saturation-%s takes %d..%d, not %d" % (flag, lo, hi, value))
-    if args.lane_dups_quality and not args.lane_dups:
-        p.error("--lane-dups-quality needs --lane-dups")
-    if args.lane_dups_quality_bins is not None and not (args.lane_dups_quality or args.lane_dups_keep):
-        p.error("--lane-dups-quality-bins needs --lane-dups-quality")
-    if args.lane_dups_quality_max_d is not None and not args.lane_dups_quality:
-        p.error("--lane-dups-quality-max-d needs --lane-dups-quality")
-    if args.lane_dups_quality_max_d is not None and not 0 <= args.lane_dups_quality_max_d <= _lib.LANEQUALITY_MAX_D:
-        p.error("--lane-dups-quality-max-d takes 0..%d, not %d" % (_lib.LANEQUALITY_MAX_D, args.lane_dups_quality_max_d))
-    try:
-        args.lane_dups_quality_edges = parse_quality_bins(args.lane_dups_quality_bins)
-    except ValueError as e:
-        p.error("--lane-dups-quality-bins: %s" % e)
+    check_options(args, p.error)                # the passes after a lane's finish: lane_passes.LANE_PASSES
     if not args.coord_file and not args.all_wells:
         p.error("the following arguments are required: -f/--coord_file (or --all-wells)")
     if args.layout == "interleaved" and (args.all_wells or (args.edit_distance > 3 and not args.hamming)):
@@ -547,56 +460,14 @@ def parse_args(argv=None):
     if args.lane_dups_index is not None and not args.lane_dups:
         p.error("--lane-dups-index needs --lane-dups")
     if args.lane_dups_index is not None:
-        try:
-            ranges = workload.parse_cycles(0, 0, args.lane_dups_index)
-        except ValueError:
-            ranges = [(0, 0)]
-        if any(not 0 <= a < b for a, b in ranges):
-            p.error("--lane-dups-index takes ranges of cycles as --cycles does, eg. 151-159,159-167")
-        n_index = sum(b - a for a, b in ranges)
-        if not 1 <= n_index <= _lib.LANEINDEX_MAX_CYCLES:
-            p.error("--lane-dups-index takes 1..%d cycles, not %d" % (_lib.LANEINDEX_MAX_CYCLES, n_index))
-    if args.lane_dups_mismatches and args.lane_dups_hamming is None:
-        p.error("--lane-dups-mismatches needs --lane-dups-hamming K with K >= 1 (under equality every copy is identical "
-                "to the first well of its class: there is nothing to profile)")
-    if args.lane_dups_mismatches_max_d is not None and not args.lane_dups_mismatches:
-        p.error("--lane-dups-mismatches-max-d needs --lane-dups-mismatches")
-    if args.lane_dups_mismatches_max_d is not None and not 0 <= args.lane_dups_mismatches_max_d <= _lib.LANEMISMATCH_MAX_D:
-        p.error("--lane-dups-mismatches-max-d takes 0..%d, not %d" % (_lib.LANEMISMATCH_MAX_D,
-                                                                     args.lane_dups_mismatches_max_d))
-    if args.lane_dups_distance and not args.lane_dups:
-        p.error("--lane-dups-distance needs --lane-dups")
-    if not 0 <= args.lane_dups_distance_radius <= _lib.LANEDISTANCE_MAX_RADIUS:
-        p.error("--lane-dups-distance-radius takes 0..%d, not %d" % (_lib.LANEDISTANCE_MAX_RADIUS,
-                                                                    args.lane_dups_distance_radius))
+        check_cycle_ranges(p.error, "--lane-dups-index", args.lane_dups_index, "151-159,159-167",
+                           _lib.LANEINDEX_MAX_CYCLES)
     if not 0.0 < args.lane_dups_index_min_share <= 1.0:
         p.error("--lane-dups-index-min-share takes a share in (0, 1], not %g" % args.lane_dups_index_min_share)
     if args.lane_dups and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         p.error("--lane-dups runs in a single process only: under WORLD_SIZE > 1 a lane's tiles are spread over the "
                 "ranks, and the classes of a lane need all of them in one GPU's table")
     return args
-
-
-DEFAULT_QUALITY_BINS = [0, 2, 10, 20, 25, 30, 35, 40]
-
-
-def parse_quality_bins(text):
-    """--lane-dups-quality-bins E0,E1,.. -> the edges (None: the default); ValueError says what is wrong with them."""
-    if text is None:
-        return list(DEFAULT_QUALITY_BINS)
-    try:
-        edges = [int(e) for e in text.split(",")]
-    except ValueError:
-        raise ValueError("a comma-separated list of integers, not %r" % text)
-    if not 1 <= len(edges) <= _lib.LANEQUALITY_MAX_BINS:
-        raise ValueError("1..%d lower edges, not %d" % (_lib.LANEQUALITY_MAX_BINS, len(edges)))
-    if edges[0] != 0:
-        raise ValueError("the first edge is 0 (every quality has a bin), not %d" % edges[0])
-    if any(b < a for a, b in zip(edges, edges[1:])):
-        raise ValueError("the edges ascend")
-    if edges[-1] >= _lib.LANEQUALITY_VALUES:
-        raise ValueError("a quality is at most %d, not %d" % (_lib.LANEQUALITY_VALUES - 1, edges[-1]))
-    return edges
 
 
 _T0 = [0.0]
@@ -701,37 +572,28 @@ def lane_cluster_members(class_labels: np.ndarray, cluster_labels: np.ndarray):
     return ti, w, lab // class_labels.shape[1], lab % class_labels.shape[1], cti, cw
 
 
-def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, scratch: int = 0, index: int = 0,
-                         mismatch: int = 0, distance: int = 0, quality: int = 0, saturation: int = 0, top: int = 0,
-                         hops: int = 0, gc: int = 0, consensus: int = 0, umi: int = 0, umi_scratch: int = 0,
-                         keep: int = 0, molecules: int = 0):
-    """--lane-dups: the accumulator's workspace - with --lane-dups-hamming plus the scratch of the near finish, with
-    --lane-dups-index plus the index workspace, with --lane-dups-mismatches or --lane-dups-distance plus that pass's
-    scratch, with --lane-dups-quality plus the quality workspace and that pass's scratch, with --lane-dups-saturation,
-    --lane-dups-top, --lane-dups-hops, --lane-dups-gc or --lane-dups-consensus plus that pass's scratch, with
-    --lane-dups-umi plus the UMI workspace (umi) and that pass's scratch (umi_scratch), with --lane-dups-keep plus that
-    pass's scratch (keep; and the quality workspace, in `quality`, if --lane-dups-quality has not asked for it), with
-    --lane-dups-keep-umi plus the molecule region (molecules) - against the free device memory, before anything is
-    loaded."""
-    need += (scratch + index + mismatch + distance + quality + saturation + top + hops + gc + consensus + umi + umi_scratch + keep +
-             molecules)
+# check_lane_dups_fits' keywords and the flag each is reported under, in the order of the message's clauses: the
+# label stage's two, then every pass's own (keywords of one flag make one clause)
+_FIT_CLAUSES = (("scratch", "--lane-dups-hamming"), ("index", "--lane-dups-index")) + \
+    tuple(clause for p in LANE_PASSES for clause in p.fit)
+
+
+def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, **parts):
+    """--lane-dups: the accumulator's workspace plus `parts`, the device bytes by _FIT_CLAUSES' keywords - scratch: the
+    near finish; index: the index workspace; a pass's own: its scratch and the part of the accumulator it asks for
+    (LanePass.bytes) - against the free device memory, before anything is loaded."""
+    unknown = set(parts) - {keyword for keyword, _ in _FIT_CLAUSES}
+    if unknown:
+        raise TypeError("check_lane_dups_fits() got an unexpected keyword argument %r" % sorted(unknown)[0])
+    by_flag = {}
+    for keyword, flag in _FIT_CLAUSES:
+        by_flag[flag] = by_flag.get(flag, 0) + parts.get(keyword, 0)
+    need += sum(by_flag.values())
     if need > free:
         raise MemoryError("--lane-dups needs %.2f GB of device memory for a lane of %d tiles x %d wells x %d cycles "
-                          "(%d bytes%s%s%s%s%s%s%s%s%s%s%s%s%s), and %.2f GB (%d bytes) are free" % (
+                          "(%d bytes%s), and %.2f GB (%d bytes) are free" % (
                               need / 1e9, tiles, wells, cycles, need,
-                              ", %d of them for --lane-dups-hamming" % scratch if scratch else "",
-                              ", %d of them for --lane-dups-index" % index if index else "",
-                              ", %d of them for --lane-dups-mismatches" % mismatch if mismatch else "",
-                              ", %d of them for --lane-dups-distance" % distance if distance else "",
-                              ", %d of them for --lane-dups-quality" % quality if quality else "",
-                              ", %d of them for --lane-dups-saturation" % saturation if saturation else "",
-                              ", %d of them for --lane-dups-top" % top if top else "",
-                              ", %d of them for --lane-dups-hops" % hops if hops else "",
-                              ", %d of them for --lane-dups-gc" % gc if gc else "",
-                              ", %d of them for --lane-dups-consensus" % consensus if consensus else "",
-                              ", %d of them for --lane-dups-umi" % (umi + umi_scratch) if umi + umi_scratch else "",
-                              ", %d of them for --lane-dups-keep" % keep if keep else "",
-                              ", %d of them for --lane-dups-keep-umi" % molecules if molecules else "",
+                              "".join(", %d of them for %s" % (b, flag) for flag, b in by_flag.items() if b),
                               free / 1e9, free))
 
 
@@ -744,8 +606,7 @@ def index_listing(min_share: float, pf: int):
 def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells, tile_batch,
                threads, want_log, overlap=True, interleave=1, gpu_inflate=True, lane_done=None, into=None,
                dup_sets=0, tile_dups=0, tile_near=0, pair_budget=0, lane_dups=0, lane_near=0, lane_pair_budget=0,
-               lane_index=None, lane_mismatch=None, lane_distance=None, lane_quality=None, lane_saturation=None,
-               lane_top=0, lane_hops=None, lane_gc=None, lane_consensus=None, lane_umi=None, lane_keep=None):
+               lane_index=None, lane_passes=()):
     """lane_tiles: [(lane, [tiles])] in the order they are reported -> ({(lane, tile): TileCounts},
     {(lane, tile): [log lines]}); `lane_done(lane)` is called when a lane's last tile has been scanned.
     dup_sets (needs `into`): 1 = the duplicate sets of every tile too (into["sets"][(lane, tile)] = DupSetCounts),
@@ -766,36 +627,11 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     the GPU decoder and the .cbcl path alike - and which is fed to LaneDups.index_add, reused and released with the
     scan batch; after the lane's finish into["lindex"][lane] = LaneIndexCounts (on the clusters under lane_near), and
     with the members into["lmindex"][lane] = the index read of every row of into["lmembers"][lane].
-    lane_mismatch = D (with lane_near): after the lane's finish, and after its index finish, LaneDups.mismatches(D):
-    into["lmismatch"][lane] = LaneMismatchCounts, its cycles numbered by cycle_list.
-    lane_distance = (x, y, radius) (with lane_dups; x, y: the coordinates of a tile's wells): after everything else
-    of the lane LaneDups.distances(x, y, radius), with TilePairs up to 4096 tiles: into["ldistance"][lane] =
-    LaneDistanceCounts, on the labels the lane was left with.
-    lane_quality = (edges, D) (with lane_dups): the accumulator gets a quality part with these bins, every batch is
-    fed to LaneDups.qual_add beside add, and after everything else of the lane LaneDups.qualities(D):
-    into["lquality"][lane] = LaneQualityCounts, on the labels the lane was left with.
-    lane_saturation = (steps, seed, x, y, radius) (with lane_dups; x, y: the coordinates of a tile's wells, or None
-    with radius 0): after everything else of the lane LaneDups.saturation(steps, seed, x, y, radius):
-    into["lsaturation"][lane] = LaneSaturationCounts, on the labels the lane was left with.
-    lane_top = N > 0 (with lane_dups): after every other pass of the lane LaneDups.top(N): into["ltop"][lane] =
-    LaneTopCounts, on the labels the lane was left with.
-    lane_hops = (E, pairs to list) (with lane_index): after every other pass of the lane LaneDups.hops(cycles of the
-    first index range, E, the keys of the first 1024 groups the index finish listed): into["lhops"][lane] =
-    LaneHopCounts, on the labels the lane was left with.
-    lane_gc = (max_n, bins) (with lane_dups): after every other pass of the lane LaneDups.gc(max_n): into["lgc"][lane] =
-    LaneGCCounts, on the labels the lane was left with.
-    lane_consensus = (D, max family) (with lane_dups): after every other pass of the lane LaneDups.consensus(D, max
-    family): into["lconsensus"][lane] = LaneConsensusCounts, on the labels the lane was left with, its cycles numbered by
-    cycle_list.
-    lane_umi = (UMI cycles, E, max family) (with lane_dups): every batch gets a further TileBatch of the UMI cycles,
-    loaded by the same job list as the index batch and fed to LaneDups.umi_add, reused and released with the scan
-    batch; after every other pass of the lane LaneDups.umi(E, max family): into["lumi"][lane] = LaneUmiCounts, on the
-    labels the lane was left with.
-    lane_keep = (min_q, edges, out directory or None[, by molecule]) (with lane_dups; by molecule needs lane_umi: the
-    UMI pass then writes its molecules down, LaneDups.umi(molecules=True), and the keep reads them,
-    by_molecule=True): the accumulator gets a quality part with these bins unless lane_quality has given it one (the two share it), and after every other pass of the lane
-    LaneDups.keep(min_q): into["lkeep"][lane] = LaneKeepCounts, on the labels the lane was left with; with a
-    directory the lane's filter files go there at once (write_lane_keep_filters), the masks are not kept.
+    lane_passes = [(LanePass, params)] (lane_passes.resolve_passes; with lane_dups): after the lane's finish, and after
+    its index finish, every pass runs in the list's order on the labels the lane was left with:
+    into[pass.key][lane] = pass.run(the accumulator, the lane's context, params).  The parts of the accumulator that
+    are fed batch by batch - the qualities beside the reads, a further TileBatch of UMI cycles - are there when a
+    pass of the list asks for them (LanePass.parts).  What each pass takes and does stands with its entry.
 
     Pipelined: while the GPU scans batch n (and its report rows and log lines are put together),
     batch n + 1 is being inflated and batch n + 2 read and copied, each into a TileBatch of its own
@@ -810,11 +646,20 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     levels = lvl_off.shape[1] - 1
     index_cycles, index_lengths, index_share = lane_index if lane_index else ([], [], 1.0)
     assert not index_cycles or (lane_dups and interleave == 1)
-    umi_cycles, umi_e, umi_family = lane_umi if lane_umi else ([], 0, 0)
-    keep_umi = lane_keep is not None and len(lane_keep) > 3 and bool(lane_keep[3])      # one well per UMI molecule
-    assert not keep_umi or umi_cycles
-    assert not umi_cycles or (lane_dups and interleave == 1)
-    qual_edges = lane_quality[0] if lane_quality is not None else lane_keep[1] if lane_keep is not None else None
+    # the side cycle sets: each gets a further TileBatch per scan batch, loaded by the batch's job list, fed to
+    # LaneDups.<name>_add, reused and released with the scan batch (tb: id(scan batch) -> its side batch; spare: finished
+    # ones).  The index cycles belong to the label stage; the others, and the quality part, are asked for by passes
+    side = lambda name, cycles: SimpleNamespace(name=name, cycles=cycles, tb={}, spare=[])      # noqa: E731
+    sides = [side("index", index_cycles)] if index_cycles else []
+    qual_edges = None
+    for p, params in lane_passes:
+        parts = p.parts(params)
+        qual_edges = parts.get("quality") if qual_edges is None else qual_edges
+        sides += [side(name, cycles) for name, cycles in parts.get("sides", {}).items()]
+    assert not sides or (lane_dups and interleave == 1)
+    begins = [(s.name, len(s.cycles)) for s in sides]       # LaneDups.<name>_begin(argument), in this order:
+    if qual_edges is not None:
+        begins.insert(bool(index_cycles), ("qual", qual_edges))     # the index, the qualities, the passes' sides
     counts, logs = (into["counts"], into["logs"]) if into else ({}, {})
     batches = []                            # (lane, [tiles]), never across a lane's end: an error stays its lane's (start_ahead)
     for lane, tiles in lane_tiles:
@@ -833,7 +678,7 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                     room = 700
             except (OSError, IndexError, RuntimeError, AssertionError):
                 pass                            # (whatever is wrong with the first tile is reported when it is loaded)
-            per = max(1, room // max(1, len(cycle_list) + len(index_cycles) + len(umi_cycles) + 1))
+            per = max(1, room // max(1, len(cycle_list) + sum(len(s.cycles) for s in sides) + 1))
             n_batches = max(1, -(-len(tiles) // per))
             tb_n = max(1, -(-len(tiles) // n_batches))
         batches += [(lane, tiles[b0:b0 + tb_n]) for b0 in range(0, len(tiles), tb_n)]
@@ -843,8 +688,6 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
     lane_acc = {"ld": None, "lane": None}   # the LaneDups of the lane being scanned
     tiles_of_lane = {lane: list(tiles) for lane, tiles in lane_tiles}
     spare = []                              # finished ones whose buffers the next batch takes over
-    index_tb, index_spare = {}, []          # id(scan batch) -> its batch of index cycles; finished ones
-    umi_tb, umi_spare = {}, []              # the same for the UMI cycles
 
     def start(batch):
         """Submit every load of a batch; returns at once."""
@@ -863,25 +706,18 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
         tb = TileBatch(sc, len(chunk), len(cycle_list), n_clusters, interleave=interleave,
                        reuse=spare.pop() if spare else None)
         live.append(tb)
-        if index_cycles:
-            index_tb[id(tb)] = TileBatch(sc, len(chunk), len(index_cycles), n_clusters,
-                                         reuse=index_spare.pop() if index_spare else None)
-        if umi_cycles:
-            umi_tb[id(tb)] = TileBatch(sc, len(chunk), len(umi_cycles), n_clusters,
-                                       reuse=umi_spare.pop() if umi_spare else None)
+        for s in sides:
+            s.tb[id(tb)] = TileBatch(sc, len(chunk), len(s.cycles), n_clusters, reuse=s.spare.pop() if s.spare else None)
         _lap("  batch of %d tiles: buffers" % len(chunk))
         # ingest: every (tile, cycle) file is gunzipped into pinned memory and copied to the GPU
         # by libwelldup (wd_load_bcl_gz).  Runs without .bcl.gz files are NovaSeq runs: the
         # tile's block of the lane/surface .cbcl is gunzipped on the host and expanded on the
         # GPU (wd_load_cbcl_tile), which needs the tile's filter first.
-        # a job: (slot, cycle, where its plane goes); the index and the UMI cycles' planes go to batches of their own
+        # a job: (slot, cycle, where its plane goes); the planes of the side cycles go to batches of their own
         jobs = [(i, cycle_list[c], tb.plane_ptr(i, c)) for i in range(len(handles)) for c in range(len(cycle_list))]
-        if index_cycles:
-            itb = index_tb[id(tb)]
-            jobs += [(i, cyc, itb.plane_ptr(i, c)) for i in range(len(handles)) for c, cyc in enumerate(index_cycles)]
-        if umi_cycles:
-            utb = umi_tb[id(tb)]
-            jobs += [(i, cyc, utb.plane_ptr(i, c)) for i in range(len(handles)) for c, cyc in enumerate(umi_cycles)]
+        for s in sides:
+            stb = s.tb[id(tb)]
+            jobs += [(i, cyc, stb.plane_ptr(i, c)) for i in range(len(handles)) for c, cyc in enumerate(s.cycles)]
         batch = None                        # which files the GPU decoder gets as one batch
         if gpu_inflate and jobs:
             if os.path.exists(handles[0].plane_path(cycle_list[0])):
@@ -939,19 +775,11 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
 
     def release(tb, keep=False):
         live.remove(tb)
-        itb, utb = index_tb.pop(id(tb), None), umi_tb.pop(id(tb), None)
-        if keep:
-            spare.append(tb)
-            if itb is not None:
-                index_spare.append(itb)
-            if utb is not None:
-                umi_spare.append(utb)
-        else:
-            tb.free()
-            if itb is not None:
-                itb.free()
-            if utb is not None:
-                utb.free()
+        for mine, its_spare in [(tb, spare)] + [(s.tb.pop(id(tb), None), s.spare) for s in sides]:
+            if mine is not None and keep:
+                its_spare.append(mine)
+            elif mine is not None:
+                mine.free()
 
     try:
         # three batches on their way at any time: one's files are read and copied while the one before
@@ -1005,20 +833,15 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                             ld.close()
                         lane_acc["ld"] = None
                         ld = lane_acc["ld"] = LaneDups(sc, n_clusters, len(names), len(cycle_list))
-                        if index_cycles:
-                            ld.index_begin(len(index_cycles))
-                        if qual_edges is not None:
-                            ld.qual_begin(qual_edges)
-                        if umi_cycles:
-                            ld.umi_begin(len(umi_cycles))
+                        for name, argument in begins:
+                            getattr(ld, name + "_begin")(argument)
                     lane_acc["lane"] = lane
-                ld.add(tb, [names.index(t) for t in chunk])
+                slots = [names.index(t) for t in chunk]
+                ld.add(tb, slots)
                 if qual_edges is not None:
-                    ld.qual_add(tb, [names.index(t) for t in chunk])
-                if index_cycles:
-                    ld.index_add(index_tb[id(tb)], [names.index(t) for t in chunk])
-                if umi_cycles:
-                    ld.umi_add(umi_tb[id(tb)], [names.index(t) for t in chunk])
+                    ld.qual_add(tb, slots)
+                for s in sides:
+                    getattr(ld, s.name + "_add")(s.tb[id(tb)], slots)
                 if last_batch_of[lane] == bi:
                     got = ld.finish(labels=lane_dups > 1, hamming=lane_near, pair_budget=lane_pair_budget)
                     lane_row, tile_rows, lane_labels = got[:3]
@@ -1029,6 +852,7 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                             into["lmembers"][lane] = (names,) + lane_cluster_members(lane_labels, got[5])
                     elif lane_labels is not None:
                         into["lmembers"][lane] = (names,) + lane_members(lane_labels)
+                    listing = final = None
                     if index_cycles:
                         final = got[3] if lane_near else lane_row      # the row of the labels the lane was left with
                         listing = ld.index_finish(*index_listing(index_share, int(final[0])))
@@ -1036,55 +860,13 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                         if lane_labels is not None:
                             m = into["lmembers"][lane]
                             into["lmindex"][lane] = ld.index_keys()[m[1] * n_clusters + m[2]]
-                    if lane_mismatch is not None:
-                        into["lmismatch"][lane] = report.LaneMismatchCounts.from_rows(
-                            *ld.mismatches(lane_mismatch), names, lane_near, lane_mismatch, cycle_list)
-                    if lane_distance is not None:
-                        lx, ly, radius = lane_distance
-                        area = float(int(lx.max()) - int(lx.min())) * float(int(ly.max()) - int(ly.min())) if len(lx) else 0.0
-                        into["ldistance"][lane] = report.LaneDistanceCounts.from_rows(
-                            *ld.distances(lx, ly, radius, matrix=len(names) <= _lib.LANEDISTANCE_MATRIX_MAX_TILES), names,
-                            radius, into["lnear"][lane] if lane_near else into["ldups"][lane], area)
-                    if lane_quality is not None:
-                        into["lquality"][lane] = report.LaneQualityCounts.from_rows(
-                            *ld.qualities(lane_quality[1]), names, lane_near, lane_quality[1], lane_quality[0])
-                    if lane_saturation is not None:
-                        steps, seed, lx, ly, radius = lane_saturation
-                        into["lsaturation"][lane] = report.LaneSaturationCounts.from_rows(
-                            *ld.saturation(steps, seed, lx, ly, radius), seed, radius,
-                            into["lnear"][lane] if lane_near else into["ldups"][lane], lane_near)
-                    if lane_top:
-                        into["ltop"][lane] = report.LaneTopCounts.from_rows(
-                            *ld.top(lane_top), lane_top, n_clusters, names,
-                            into["lnear"][lane] if lane_near else into["ldups"][lane], lane_near)
-                    if lane_hops is not None:
-                        keys = listing[3][:_lib.LANEHOPS_MAX_LISTED]
-                        pf = [int(v) for v in listing[2][:len(keys), 0]]
-                        into["lhops"][lane] = report.LaneHopCounts.from_rows(
-                            *ld.hops(index_lengths[0], lane_hops[0], keys), keys, pf + [int(final[0]) - sum(pf)],
-                            index_lengths, names, lane_hops[0], lane_near, lane_hops[1])
-                    if lane_gc is not None:
-                        into["lgc"][lane] = report.LaneGCCounts.from_rows(*ld.gc(lane_gc[0]), names, lane_gc[0], lane_gc[1],
-                                                                          lane_near)
-                    if lane_consensus is not None:
-                        into["lconsensus"][lane] = report.LaneConsensusCounts.from_rows(
-                            *ld.consensus(*lane_consensus), names, lane_near, lane_consensus[0], lane_consensus[1],
-                            (into["lnear"][lane] if lane_near else into["ldups"][lane]).pf, cycle_list)
-                    if umi_cycles:
-                        left = into["lnear"][lane] if lane_near else into["ldups"][lane]
-                        into["lumi"][lane] = report.LaneUmiCounts.from_rows(
-                            *ld.umi(umi_e, umi_family, molecules=keep_umi), names, lane_near, umi_e, umi_family,
-                            len(umi_cycles), left.pf, left.redundant)
-                    if lane_keep is not None:
-                        kept = ld.keep(lane_keep[0], masks=lane_keep[2] is not None, by_molecule=keep_umi)
-                        into["lkeep"][lane] = report.LaneKeepCounts.from_rows(kept[0], kept[1], names, lane_near, lane_keep[0],
-                                                                              qual_edges, len(cycle_list),
-                                                                              by="molecule" if keep_umi else None)
-                        if lane_keep[2] is not None:
-                            write_lane_keep_filters(lane_keep[2], lane, {t: reader.get_tile(lane, t) for t in names},
-                                                    {names[ti]: m for ti, m in kept[2].items()})
-                        del kept
-                    del lane_labels, got
+                    del lane_labels, got        # (lane-sized; `final` is a row of counters)
+                    context = SimpleNamespace(names=names, n_clusters=n_clusters, cycle_list=cycle_list, lane_near=lane_near,
+                                              left=into["lnear"][lane] if lane_near else into["ldups"][lane],
+                                              listing=listing, final=final, index_lengths=index_lengths,
+                                              reader=reader, lane=lane)
+                    for p, params in lane_passes:
+                        into[p.key][lane] = p.run(ld, context, params)
                 _lap("batch %d: lane classes" % bi)
             hits, seq_bytes, seq_wells = None, {}, {}
             if want_log:
@@ -1132,7 +914,7 @@ def scan_lanes(sc: Scanner, reader, lane_tiles, cycle_list, mode, k, csr, wells,
             lane_acc["ld"].close()
         for tb in list(live):
             release(tb)
-        for tb in spare + index_spare:
+        for tb in spare + [stb for s in sides for stb in s.spare]:
             tb.free()
     return counts, logs
 
@@ -1182,30 +964,6 @@ def write_lane_members(path, members, index=None):
                               for a, b, c, d, e, f in zip(*cols))
             else:
                 fh.writelines("%s\t%s\t%d\t%s\t%d\n" % (lane, names[a], b, names[c], d) for a, b, c, d in zip(*cols))
-
-
-def write_keep_filter(path, filter_bytes: np.ndarray, mask: np.ndarray):
-    """A .filter file as bcl.Tile.read_filter reads it: the 12-byte header (0, 3, N), then N bytes, each the input
-    file's byte with bit 0 replaced by the mask's - 1 for a kept well, 0 for any other."""
-    filt, mask = np.asarray(filter_bytes, dtype=np.uint8), np.asarray(mask, dtype=np.uint8)
-    if filt.shape != mask.shape or filt.ndim != 1:
-        raise ValueError("a filter of %s bytes and a mask of %s" % (filt.shape, mask.shape))
-    with open(path, "wb") as fh:
-        fh.write(struct.pack("<III", 0, 3, filt.shape[0]))
-        fh.write(((filt & 0xFE) | (mask & 1)).astype(np.uint8).tobytes())
-
-
-def write_lane_keep_filters(out_dir, lane, tiles, masks):
-    """--lane-dups-keep-out: out_dir/L00<lane>/<the name of the tile's own .filter file> for every tile of masks
-    ({tile: uint8 [N]}, LaneDups.keep's by the tile's name); tiles = {tile: its bcl.Tile}.  -> the paths written."""
-    lane_dir = str(lane) if str(lane).startswith("L") else "L%03d" % int(lane)
-    os.makedirs(os.path.join(out_dir, lane_dir), exist_ok=True)
-    paths = []
-    for tile in sorted(masks, key=str):
-        path = os.path.join(out_dir, lane_dir, os.path.basename(tiles[tile].filter_file))
-        write_keep_filter(path, tiles[tile].read_filter(), masks[tile])
-        paths.append(path)
-    return paths
 
 
 def main(argv=None, exiting=False):
@@ -1273,7 +1031,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
         # ONE failure flag
         sc, err = None, None
         lanes, tiles, cycles, cycle_list, mode, k = [], [], [], [], 0, 0
-        reader = csr = None
+        reader = csr = xy = None
         wells = np.zeros(0, dtype=np.int64)
         n_targets = 0
         try:
@@ -1343,36 +1101,9 @@ def _main(args, log, wdist, rank, world, device, opener, early):
             lane_near_k = args.lane_dups_hamming or 0
             index_ranges = workload.parse_cycles(0, 0, args.lane_dups_index) if args.lane_dups_index else []
             index_cycles = [c for s, e in index_ranges for c in range(s, e)]
-            mismatch_d = None
-            if args.lane_dups_mismatches:
-                mismatch_d = lane_near_k if args.lane_dups_mismatches_max_d is None else args.lane_dups_mismatches_max_d
-            quality_d = None
-            if args.lane_dups_quality:
-                quality_d = args.lane_dups_quality_max_d if args.lane_dups_quality_max_d is not None else \
-                    mismatch_d if mismatch_d is not None else lane_near_k
-            saturation = None
-            if args.lane_dups_saturation:
-                radius = args.lane_dups_saturation_radius if args.lane_dups_saturation_radius is not None else \
-                    args.lane_dups_distance_radius if args.lane_dups_distance else 0
-                saturation = (20 if args.lane_dups_saturation_steps is None else args.lane_dups_saturation_steps,
-                              args.lane_dups_saturation_seed or 0, xy[0] if radius else None, xy[1] if radius else None,
-                              radius)
-            gc_max_n = args.lane_dups_gc_max_n or 0
-            if args.lane_dups_gc and gc_max_n > len(cycle_list):
-                raise ValueError("--lane-dups-gc-max-n takes 0..%d, the scanned cycles, not %d" % (len(cycle_list), gc_max_n))
-            consensus = None
-            if args.lane_dups_consensus:
-                consensus = (args.lane_dups_consensus_max_d if args.lane_dups_consensus_max_d is not None else
-                             mismatch_d if mismatch_d is not None else lane_near_k,
-                             args.lane_dups_consensus_max_family or 256)
-            umi_cycles = [c for s, e in workload.parse_cycles(0, 0, args.lane_dups_umi) for c in range(s, e)] \
-                if args.lane_dups_umi else []
-            umi = (umi_cycles, 1 if args.lane_dups_umi_mismatches is None else args.lane_dups_umi_mismatches,
-                   args.lane_dups_umi_max_family or 256) if umi_cycles else None
-            keep = None
-            if args.lane_dups_keep:
-                keep = (_lib.LANEKEEP_DEFAULT_MIN_Q if args.lane_dups_keep_min_q is None else args.lane_dups_keep_min_q,
-                        args.lane_dups_quality_edges, args.lane_dups_keep_out, args.lane_dups_keep_umi)
+            # the passes after a lane's finish that the command line asks for, with their parameters
+            run = SimpleNamespace(xy=xy, cycle_list=cycle_list, n_wells=n_targets, n_tiles=len(tiles))
+            lane_passes = resolve_passes(args, run) if err is None else []
             ntn = 5 + 2 * levels + len(report.CLASS_BIN_NAMES) if near_k else 0
             rows = np.zeros((len(mine), ncnt + nsets + ntd + ntn), dtype=np.int64)
             logs = {}
@@ -1408,28 +1139,8 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                                 out=out_fh, equal=results["ldups"][lane])
                 if index_cycles:
                     report.write_lane_index_dups(lane, results["lindex"][lane], hamming=lane_near_k, out=out_fh)
-                if args.lane_dups_mismatches:
-                    report.write_lane_mismatches(lane, results["lmismatch"][lane], verbose=not args.summary_only, out=out_fh)
-                if args.lane_dups_distance:
-                    report.write_lane_distances(lane, results["ldistance"][lane], verbose=not args.summary_only, out=out_fh)
-                if args.lane_dups_quality:
-                    report.write_lane_qualities(lane, results["lquality"][lane], verbose=not args.summary_only, out=out_fh)
-                if args.lane_dups_saturation:
-                    report.write_lane_saturation(lane, results["lsaturation"][lane], verbose=not args.summary_only,
-                                                 out=out_fh)
-                if args.lane_dups_top is not None:
-                    report.write_lane_top(lane, results["ltop"][lane], verbose=not args.summary_only, out=out_fh)
-                if args.lane_dups_hops is not None:
-                    report.write_lane_hops(lane, results["lhops"][lane], verbose=not args.summary_only, out=out_fh)
-                if args.lane_dups_gc:
-                    report.write_lane_gc(lane, results["lgc"][lane], verbose=not args.summary_only, out=out_fh)
-                if args.lane_dups_consensus:
-                    report.write_lane_consensus(lane, results["lconsensus"][lane], verbose=not args.summary_only,
-                                                out=out_fh)
-                if umi is not None:
-                    report.write_lane_umi(lane, results["lumi"][lane], verbose=not args.summary_only, out=out_fh)
-                if keep is not None:
-                    report.write_lane_keep(lane, results["lkeep"][lane], verbose=not args.summary_only, out=out_fh)
+                for p, _ in lane_passes:
+                    p.write(lane, results[p.key][lane], verbose=not args.summary_only, out=out_fh)
 
             try:
                 lane_tiles = [(lane, [t for (ln, t) in mine if ln == lane]) for lane in lanes] if err is None else []
@@ -1437,9 +1148,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 # scan_lanes fills these, lane_done reads them
                 results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
                            "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}, "lnear": {}, "lindex": {},
-                           "lmindex": {}, "lmismatch": {}, "ldistance": {}, "lquality": {}, "lsaturation": {}, "ltop": {},
-                           "lhops": {}, "lgc": {}, "lconsensus": {}, "lumi": {}, "lkeep": {}}
-
+                           "lmindex": {}, **{p.key: {} for p in LANE_PASSES}}
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
                         c = results["counts"][(lane, t)]
@@ -1459,39 +1168,13 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 if err is None and args.lane_dups:
                     # before anything is loaded: a lane's accumulator has to fit beside the batches
                     import torch
+                    parts = {"scratch": sc.lane_near_scratch_bytes(n_targets, len(tiles), len(cycle_list), lane_near_k),
+                             "index": sc.lane_index_workspace_bytes(n_targets, len(tiles), len(index_cycles))
+                             if index_cycles else 0}
+                    for p, params in lane_passes:       # (a region two passes share comes under one keyword, once)
+                        parts.update(p.bytes(sc, run, params))
                     check_lane_dups_fits(sc.lane_dups_workspace_bytes(n_targets, len(tiles), len(cycle_list)),
-                                         torch.cuda.mem_get_info(device)[0], len(tiles), n_targets, len(cycle_list),
-                                         scratch=sc.lane_near_scratch_bytes(n_targets, len(tiles), len(cycle_list),
-                                                                            lane_near_k),
-                                         index=sc.lane_index_workspace_bytes(n_targets, len(tiles), len(index_cycles))
-                                         if index_cycles else 0,
-                                         mismatch=sc.lane_mismatch_scratch_bytes(len(tiles), len(cycle_list))
-                                         if mismatch_d is not None else 0,
-                                         distance=sc.lane_distance_scratch_bytes(
-                                             n_targets, len(tiles), len(tiles) <= _lib.LANEDISTANCE_MATRIX_MAX_TILES)
-                                         if args.lane_dups_distance else 0,
-                                         quality=(sc.lane_qual_workspace_bytes(n_targets, len(tiles), len(cycle_list)) +
-                                                  sc.lane_qual_scratch_bytes(len(tiles)))
-                                         if quality_d is not None or keep is not None else 0,
-                                         saturation=sc.lane_saturation_scratch_bytes(n_targets, len(tiles),
-                                                                                     saturation[4] > 0)
-                                         if saturation is not None else 0,
-                                         top=sc.lane_top_scratch_bytes(n_targets, len(tiles), len(cycle_list),
-                                                                       args.lane_dups_top)
-                                         if args.lane_dups_top is not None else 0,
-                                         hops=sc.lane_hops_scratch_bytes(len(tiles), _lib.LANEHOPS_MAX_LISTED)
-                                         if args.lane_dups_hops is not None else 0,
-                                         gc=sc.lane_gc_scratch_bytes(len(tiles), len(cycle_list))
-                                         if args.lane_dups_gc else 0,
-                                         consensus=sc.lane_consensus_scratch_bytes(len(tiles), n_targets, len(cycle_list))
-                                         if consensus is not None else 0,
-                                         umi=sc.lane_umi_workspace_bytes(n_targets, len(tiles), len(umi_cycles))
-                                         if umi is not None else 0,
-                                         umi_scratch=sc.lane_umi_scratch_bytes(len(tiles), n_targets)
-                                         if umi is not None else 0,
-                                         keep=sc.lane_keep_scratch_bytes(len(tiles), n_targets) if keep is not None else 0,
-                                         molecules=sc.lane_molecules_bytes(len(tiles), n_targets)
-                                         if args.lane_dups_keep_umi else 0)
+                                         torch.cuda.mem_get_info(device)[0], len(tiles), n_targets, len(cycle_list), **parts)
                 if err is None:             # (a rank whose setup failed has nothing to scan: it goes to the flag)
                     scan_lanes(sc, reader, lane_tiles, cycle_list, mode, k, csr, wells,
                                max(0, args.tile_batch), args.threads,
@@ -1506,41 +1189,19 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                                lane_near=lane_near_k, lane_pair_budget=args.lane_dups_pair_budget,
                                lane_index=(index_cycles, [e - s for s, e in index_ranges],
                                            args.lane_dups_index_min_share) if index_cycles else None,
-                               lane_mismatch=mismatch_d,
-                               lane_distance=(xy[0], xy[1], args.lane_dups_distance_radius)
-                               if args.lane_dups_distance else None,
-                               lane_quality=(args.lane_dups_quality_edges, quality_d) if quality_d is not None else None,
-                               lane_saturation=saturation, lane_top=args.lane_dups_top or 0,
-                               lane_hops=(1 if args.lane_dups_hops_mismatches is None else args.lane_dups_hops_mismatches,
-                                          args.lane_dups_hops) if args.lane_dups_hops is not None else None,
-                               lane_gc=(gc_max_n, args.lane_dups_gc_bins or 20) if args.lane_dups_gc else None,
-                               lane_consensus=consensus, lane_umi=umi, lane_keep=keep)
+                               lane_passes=lane_passes)
                     if args.dup_sets_out:
                         write_set_members(args.dup_sets_out, results["members"])
                     if args.tile_dups_out and near_k:
                         write_cluster_members(args.tile_dups_out, results["tnmembers"])
                     elif args.tile_dups_out:
                         write_set_members(args.tile_dups_out, results["tmembers"], column="class")
-                    if args.lane_dups_top_out:
-                        with open(args.lane_dups_top_out, "w") as fh:
-                            for i, lane in enumerate(sorted(results["ltop"], key=lanes.index)):
-                                report.write_lane_top_tsv(lane, results["ltop"][lane], fh, header=i == 0)
-                    if args.lane_dups_hops_out:
-                        with open(args.lane_dups_hops_out, "w") as fh:
-                            for i, lane in enumerate(sorted(results["lhops"], key=lanes.index)):
-                                report.write_lane_hops_tsv(lane, results["lhops"][lane], fh, header=i == 0)
-                    if args.lane_dups_gc_out:
-                        with open(args.lane_dups_gc_out, "w") as fh:
-                            for i, lane in enumerate(sorted(results["lgc"], key=lanes.index)):
-                                report.write_lane_gc_tsv(lane, results["lgc"][lane], fh, header=i == 0)
-                    if args.lane_dups_consensus_out:
-                        with open(args.lane_dups_consensus_out, "w") as fh:
-                            for i, lane in enumerate(sorted(results["lconsensus"], key=lanes.index)):
-                                report.write_lane_consensus_tsv(lane, results["lconsensus"][lane], fh, header=i == 0)
-                    if args.lane_dups_umi_out:
-                        with open(args.lane_dups_umi_out, "w") as fh:
-                            for i, lane in enumerate(sorted(results["lumi"], key=lanes.index)):
-                                report.write_lane_umi_tsv(lane, results["lumi"][lane], fh, header=i == 0)
+                    for p in LANE_PASSES:
+                        path = getattr(args, dest(p.out[0])) if p.out else None
+                        if path:
+                            with open(path, "w") as fh:
+                                for i, lane in enumerate(sorted(results[p.key], key=lanes.index)):
+                                    p.out[1](lane, results[p.key][lane], fh, header=i == 0)
                     if args.lane_dups_out:
                         write_lane_members(args.lane_dups_out, results["lmembers"],
                                            index=([e - s for s, e in index_ranges], results["lmindex"])
