@@ -441,6 +441,61 @@ std::vector<int> ld_tiles_added(const wd_lane_dups *ld)
     return tiles;
 }
 
+// ---- what the accumulator's parts share ------------------------------------------------------------------
+// Beside its reads an accumulator carries up to three side parts - the index keys and the UMI keys (lane_index.inc),
+// the packed qualities (lane_quality.inc) -, each fed by an add of its own that records the tiles it was given.
+// The phrases of a part that do not compose from its head are handed over whole, as LanePass's are (lane_pass.inc).
+struct LanePartSay {
+    const char *head;                              // "lane index": what the composed messages begin with
+    const char *unbegun, *stride, *tables;         // add: the part was never begun, an interleaved layout, a null table
+    const char *cycles, *small;                    // begin of a key part: "index" cycles, a workspace too small
+};
+
+// What the four adds open with, in the order they have always checked - a call wrong in two ways fails on the same
+// one.  added: the part's tiles so far, null for a part never begun; tables: the entry's other tables are there.
+// WD_OK with n_tiles > 0: `seen` is `added` with the call's tiles marked, which the entry swaps in once it has succeeded.
+int lane_add_open(wd_lane_dups *ld, const std::vector<char> *added, int n_tiles, const int *tile_index, bool tables,
+                  const LanePartSay &say, std::vector<char> &seen)
+{
+    if (!ld || n_tiles < 0)
+        return WD_ERR_ARG;
+    wd_ctx *ctx = ld->ctx;
+    const std::string head = std::string(say.head) + ": ";
+    if (!added)
+        return fail(ctx, WD_ERR_ARG, say.unbegun);
+    if (ld->finished || ld->resolved)                                  // (resolved: a near finish was refused)
+        return fail(ctx, WD_ERR_ARG, head + "add after finish");
+    if (ctx->well_stride != 1)
+        return fail(ctx, WD_ERR_ARG, say.stride);
+    if (n_tiles == 0)
+        return WD_OK;
+    if (!tile_index || !tables)
+        return fail(ctx, WD_ERR_ARG, say.tables);
+    if (n_tiles > ld->max_tiles)
+        return fail(ctx, WD_ERR_ARG, head + "more tiles than the lane has room for");
+    seen = *added;
+    for (int i = 0; i < n_tiles; i++) {
+        const int t = tile_index[i];
+        if (t < 0 || t >= ld->max_tiles)
+            return fail(ctx, WD_ERR_ARG, head + "tile index " + std::to_string(t) + " out of range");
+        if (seen[t])
+            return fail(ctx, WD_ERR_ARG, head + "tile index " + std::to_string(t) + " used twice");
+        seen[t] = 1;
+    }
+    return WD_OK;
+}
+
+// The part's tiles are the lane's tiles: a pass that reads a part reads it at the wells the finish labelled.
+// head: the caller's, what = "index planes", "UMI planes" or "qualities".
+int lane_part_tiles(const wd_lane_dups *ld, const std::vector<char> &added, const std::string &head, const std::string &what)
+{
+    for (int t = 0; t < ld->max_tiles; t++)
+        if (added[t] != ld->added[t])
+            return fail(ld->ctx, WD_ERR_ARG, head + ": tile index " + std::to_string(t) +
+                                                 (ld->added[t] ? " was added without " + what : " got " + what + " but was never added"));
+    return WD_OK;
+}
+
 // The rows of the label array as it stands (class representatives, or the cluster roots of lane_near.inc, with
 // the members counted at them), over the tiles in d_tidx: the table is cleared and keyed by (label, tile),
 // k_ld_classes / k_ld_span_count / k_ld_span_sum add to the counters, which come down and are summed.  PF per
@@ -628,30 +683,17 @@ try {
 int wd_lane_dups_add(wd_lane_dups *ld, int n_tiles, const int *tile_index, const uint8_t *const *planes,
                      const uint8_t *const *filter)
 try {
-    if (!ld || n_tiles < 0)
-        return WD_ERR_ARG;
+    std::vector<char> seen;
+    if (const int rc = lane_add_open(ld, ld ? &ld->added : nullptr, n_tiles, tile_index, filter && (planes || !ld || ld->L <= 0),
+                                     {"lane duplicates", nullptr, "lane duplicates read a plane per cycle (well_stride 1)",
+                                      "null tile index, plane or filter table"},
+                                     seen))
+        return rc;
+    if (n_tiles == 0)
+        return WD_OK;
     wd_ctx *ctx = ld->ctx;
     const int L = ld->L;
     const int64_t N = ld->N;
-    if (ld->finished || ld->resolved)                                  // (resolved: a near finish was refused)
-        return fail(ctx, WD_ERR_ARG, "lane duplicates: add after finish");
-    if (ctx->well_stride != 1)
-        return fail(ctx, WD_ERR_ARG, "lane duplicates read a plane per cycle (well_stride 1)");
-    if (n_tiles == 0)
-        return WD_OK;
-    if (!tile_index || !filter || (L > 0 && !planes))
-        return fail(ctx, WD_ERR_ARG, "null tile index, plane or filter table");
-    if (n_tiles > ld->max_tiles)
-        return fail(ctx, WD_ERR_ARG, "lane duplicates: more tiles than the lane has room for");
-    std::vector<char> seen(ld->added);
-    for (int i = 0; i < n_tiles; i++) {
-        const int t = tile_index[i];
-        if (t < 0 || t >= ld->max_tiles)
-            return fail(ctx, WD_ERR_ARG, "lane duplicates: tile index " + std::to_string(t) + " out of range");
-        if (seen[t])
-            return fail(ctx, WD_ERR_ARG, "lane duplicates: tile index " + std::to_string(t) + " used twice");
-        seen[t] = 1;
-    }
     bool aligned4;
     if (const int rc = check_tables(ctx, "lane duplicates: ", n_tiles, L, planes, filter, nullptr, &aligned4))
         return rc;

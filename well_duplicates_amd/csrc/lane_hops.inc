@@ -246,11 +246,9 @@ try {
     wd_lane_index *li = ld->index.get();
     if (!li)
         return fail(ctx, WD_ERR_ARG, "lane hops: the lane has no index part (wd_lane_index_begin)");
-    for (int t = 0; t < T; t++)
-        if (li->added[t] != ld->added[t])
-            return fail(ctx, WD_ERR_ARG, "lane index: tile index " + std::to_string(t) +
-                                             (ld->added[t] ? " was added without index planes" : " got index planes but was never added"));
-    const int I = li->I;
+    if (const int rc = lane_part_tiles(ld, li->added, "lane index", "index planes"))      // (the part's head, not the pass's)
+        return rc;
+    const int I = li->cycles;
     if (split < 1 || split > I)
         return fail(ctx, WD_ERR_ARG, "lane hops: split is 1.." + std::to_string(I) + ", not " + std::to_string(split));
     if (max_e < 0 || max_e > kLhMaxE)

@@ -31,6 +31,12 @@ constexpr int kLiGroups = 0, kLiSpans = 1, kLiMixedClasses = 2;
 constexpr int kLiOtherCnt = 8;                     // per copy: the Other row
 constexpr int kLiStage = kLiCols + 1;              // uint64 per listed group on its way to the host: the row, the key
 
+// a key part's share of its workspace (LaneKeyPart below): the plane pointers and the tile indices of an add, the
+// keys, and the whole's size
+struct LaneKeyLayout {
+    size_t planes, tidx, key, bytes;
+};
+
 // the index workspace (include/welldup_laneindex.h states the arithmetic)
 struct LiLayout {
     size_t cnt_l, other, listed, planes, tidx, key, glabel, cnt, bytes;
@@ -53,6 +59,8 @@ LiLayout li_layout_of(int64_t N, int max_tiles, int I)
 }
 
 // ---- pack ---------------------------------------------------------------------------------------
+// The key pack of both key parts of an accumulator (LaneKeyPart below): lane_key_add launches it for the index read
+// into the index workspace and for the UMI read into the UMI workspace (lane_umi.inc).
 // I <= 20 cycles are at most two words of plane_pass: they stay in registers and are stored as the well's key, eight
 // bytes a well - a lane of the VEC4 kernel stores 32 consecutive bytes, no staging in LDS is needed.
 // VEC4 (every plane 4-byte aligned): grid (ceil(N / 1024), n_tiles of the batch), a lane packs wells 4 i .. 4 i + 3.
@@ -381,17 +389,110 @@ __global__ void __launch_bounds__(kTdBlock) k_li_rows(const uint32_t *__restrict
 }  // namespace
 
 #ifndef WD_LANE_INDEX_EMU                          // (tools/lane_index_emu.cpp: the kernels above on the CPU, a fiber per lane)
-// the index part of an accumulator: the host side (the device side is the caller's index workspace)
-struct wd_lane_index {
-    int I;
+// ---- the key part -----------------------------------------------------------------------------------------
+// An accumulator's index part and its UMI part (lane_umi.inc) are one thing twice: a key of up to two words per well,
+// packed by k_li_pack from the planes of 1 .. WD_LANEINDEX_MAX_CYCLES cycles into a workspace of the caller's that
+// holds the two pointer tables of an add and the key array.  This is the host side of it; the four entries
+// wd_lane_index_begin / _add and wd_lane_umi_begin / _add hand their phrases to the two bodies below.
+struct LaneKeyPart {
+    int cycles = 0;
+    LaneKeyLayout at = {};
+    uint8_t *ws = nullptr;
+    std::vector<char> added;                       // by tile index: planes given
+};
+
+// the index part of an accumulator: the key part, and the groups' side of the index workspace
+struct wd_lane_index : LaneKeyPart {
     LiLayout lay;
-    uint8_t *ws;
-    std::vector<char> added;                       // by tile index: index planes given
-    bool tallied;                                  // the group rows stand at the representatives
-    int64_t groups, spans, mixed_classes;
+    bool tallied = false;                          // the group rows stand at the representatives
+    int64_t groups = 0, spans = 0, mixed_classes = 0;
 };
 
 namespace {
+
+LaneKeyLayout li_key_layout_of(int64_t N, int max_tiles, int I)
+{
+    const LiLayout l = li_layout_of(N, max_tiles, I);
+    return {l.planes, l.tidx, l.key, l.bytes};
+}
+
+// wd_lane_index_begin and wd_lane_umi_begin: `slot` is the part's place in the accumulator, which gets a new part.
+template <class Part>
+int lane_key_begin(wd_lane_dups *ld, std::shared_ptr<Part> wd_lane_dups::*slot, int cycles, int max_cycles,
+                   LaneKeyLayout (*layout_of)(int64_t, int, int), void *workspace_dev, size_t workspace_bytes,
+                   const LanePartSay &say)
+{
+    if (!ld)
+        return WD_ERR_ARG;
+    wd_ctx *ctx = ld->ctx;
+    const std::string head = std::string(say.head) + ": ";
+    if (cycles < 1 || cycles > max_cycles)
+        return fail(ctx, WD_ERR_ARG, head + "1.." + std::to_string(max_cycles) + " " + say.cycles + " cycles, not " +
+                                         std::to_string(cycles));
+    if (ld->finished || ld->resolved)
+        return fail(ctx, WD_ERR_ARG, head + "begin after finish");
+    if (ld->*slot)
+        return fail(ctx, WD_ERR_ARG, head + "begin is called once");
+    const LaneKeyLayout lay = layout_of(ld->N, ld->max_tiles, cycles);
+    if (!workspace_dev || workspace_bytes < lay.bytes)
+        return fail(ctx, WD_ERR_ARG, say.small);
+    if (!on_device(workspace_dev))
+        return fail(ctx, WD_ERR_ARG, head + "the workspace must be in device memory");
+    auto part = std::make_shared<Part>();
+    part->cycles = cycles;
+    part->at = lay;
+    part->ws = (uint8_t *)workspace_dev;
+    part->added.assign((size_t)ld->max_tiles, 0);
+    ld->*slot = part;
+    return WD_OK;
+}
+
+// wd_lane_index_add and wd_lane_umi_add: the keys of a batch of tiles.  part: null when the part was never begun.
+int lane_key_add(wd_lane_dups *ld, LaneKeyPart *part, int n_tiles, const int *tile_index, const uint8_t *const *planes,
+                 const LanePartSay &say)
+{
+    std::vector<char> seen;
+    if (const int rc = lane_add_open(ld, part ? &part->added : nullptr, n_tiles, tile_index, planes != nullptr, say, seen))
+        return rc;
+    if (n_tiles == 0)
+        return WD_OK;
+    wd_ctx *ctx = ld->ctx;
+    const int64_t N = ld->N;
+    const int I = part->cycles;
+    bool aligned4 = true;
+    for (size_t i = 0; i < (size_t)n_tiles * I; i++) {
+        if (!planes[i])
+            return fail(ctx, WD_ERR_ARG, "null plane pointer");
+        aligned4 = aligned4 && ((uintptr_t)planes[i] & 3u) == 0;
+    }
+    for (int i = 0; i < n_tiles; i++)
+        if (N > 0 && !on_device(planes[(size_t)i * I]))
+            return fail(ctx, WD_ERR_ARG, std::string(say.head) + ": planes must be in device memory");
+    if (bind_device(ctx))
+        return WD_ERR_HIP;
+    if (N > 0) {
+        const uint8_t **d_planes = (const uint8_t **)(part->ws + part->at.planes);
+        int *d_tidx = (int *)(part->ws + part->at.tidx);
+        uint2 *key = (uint2 *)(part->ws + part->at.key);
+        WD_HIP(ctx, hipMemcpyAsync(d_planes, planes, (size_t)n_tiles * I * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
+        WD_HIP(ctx, hipMemcpyAsync(d_tidx, tile_index, n_tiles * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        if (aligned4)
+            hipLaunchKernelGGL(k_li_pack<true>, dim3((unsigned)((N + 4 * kTdBlock - 1) / (4 * kTdBlock)), (unsigned)n_tiles),
+                               dim3(kTdBlock), 0, ctx->stream, d_planes, d_tidx, I, N, key);
+        else
+            hipLaunchKernelGGL(k_li_pack<false>, dim3((unsigned)((N + kTdBlock - 1) / kTdBlock), (unsigned)n_tiles),
+                               dim3(kTdBlock), 0, ctx->stream, d_planes, d_tidx, I, N, key);
+        WD_HIP(ctx, hipGetLastError());
+        // (the pointer tables are the next call's too, and the caller may reuse the planes at once)
+        WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    part->added.swap(seen);
+    return WD_OK;
+}
+
+const LanePartSay kLiSay = {"lane index", "lane index: add before wd_lane_index_begin",
+                            "lane index reads a plane per cycle (well_stride 1)", "null tile index or plane table",
+                            "index", "workspace smaller than wd_lane_index_workspace"};
 
 // Groups, subgroups and the tally, once: the labels cannot change after a successful finish.
 int li_tally(wd_lane_dups *ld, const std::vector<int> &tiles)
@@ -455,92 +556,16 @@ int wd_lane_index_workspace(int64_t N, int max_tiles, int I, size_t *bytes)
 
 int wd_lane_index_begin(wd_lane_dups *ld, int I, void *workspace_dev, size_t workspace_bytes)
 try {
-    if (!ld)
-        return WD_ERR_ARG;
-    wd_ctx *ctx = ld->ctx;
-    if (I < 1 || I > WD_LANEINDEX_MAX_CYCLES)
-        return fail(ctx, WD_ERR_ARG, "lane index: 1.." + std::to_string(WD_LANEINDEX_MAX_CYCLES) + " index cycles, not " +
-                                         std::to_string(I));
-    if (ld->finished || ld->resolved)
-        return fail(ctx, WD_ERR_ARG, "lane index: begin after finish");
-    if (ld->index)
-        return fail(ctx, WD_ERR_ARG, "lane index: begin is called once");
-    const LiLayout lay = li_layout_of(ld->N, ld->max_tiles, I);
-    if (!workspace_dev || workspace_bytes < lay.bytes)
-        return fail(ctx, WD_ERR_ARG, "workspace smaller than wd_lane_index_workspace");
-    if (!on_device(workspace_dev))
-        return fail(ctx, WD_ERR_ARG, "lane index: the workspace must be in device memory");
-    auto li = std::make_shared<wd_lane_index>();
-    li->I = I;
-    li->lay = lay;
-    li->ws = (uint8_t *)workspace_dev;
-    li->added.assign((size_t)ld->max_tiles, 0);
-    li->tallied = false;
-    li->groups = li->spans = li->mixed_classes = 0;
-    ld->index = li;
+    if (const int rc = lane_key_begin(ld, &wd_lane_dups::index, I, WD_LANEINDEX_MAX_CYCLES, li_key_layout_of, workspace_dev,
+                                      workspace_bytes, kLiSay))
+        return rc;
+    ld->index->lay = li_layout_of(ld->N, ld->max_tiles, I);
     return WD_OK;
 } WD_CATCH
 
 int wd_lane_index_add(wd_lane_dups *ld, int n_tiles, const int *tile_index, const uint8_t *const *index_planes)
 try {
-    if (!ld || n_tiles < 0)
-        return WD_ERR_ARG;
-    wd_ctx *ctx = ld->ctx;
-    wd_lane_index *li = ld->index.get();
-    const int64_t N = ld->N;
-    if (!li)
-        return fail(ctx, WD_ERR_ARG, "lane index: add before wd_lane_index_begin");
-    if (ld->finished || ld->resolved)
-        return fail(ctx, WD_ERR_ARG, "lane index: add after finish");
-    if (ctx->well_stride != 1)
-        return fail(ctx, WD_ERR_ARG, "lane index reads a plane per cycle (well_stride 1)");
-    if (n_tiles == 0)
-        return WD_OK;
-    if (!tile_index || !index_planes)
-        return fail(ctx, WD_ERR_ARG, "null tile index or plane table");
-    if (n_tiles > ld->max_tiles)
-        return fail(ctx, WD_ERR_ARG, "lane index: more tiles than the lane has room for");
-    const int I = li->I;
-    std::vector<char> seen(li->added);
-    for (int i = 0; i < n_tiles; i++) {
-        const int t = tile_index[i];
-        if (t < 0 || t >= ld->max_tiles)
-            return fail(ctx, WD_ERR_ARG, "lane index: tile index " + std::to_string(t) + " out of range");
-        if (seen[t])
-            return fail(ctx, WD_ERR_ARG, "lane index: tile index " + std::to_string(t) + " used twice");
-        seen[t] = 1;
-    }
-    bool aligned4 = true;
-    for (size_t i = 0; i < (size_t)n_tiles * I; i++) {
-        if (!index_planes[i])
-            return fail(ctx, WD_ERR_ARG, "null plane pointer");
-        aligned4 = aligned4 && ((uintptr_t)index_planes[i] & 3u) == 0;
-    }
-    for (int i = 0; i < n_tiles; i++)
-        if (N > 0 && !on_device(index_planes[(size_t)i * I]))
-            return fail(ctx, WD_ERR_ARG, "lane index: planes must be in device memory");
-    if (bind_device(ctx))
-        return WD_ERR_HIP;
-    if (N > 0) {
-        uint8_t *iws = li->ws;
-        const uint8_t **d_planes = (const uint8_t **)(iws + li->lay.planes);
-        int *d_tidx = (int *)(iws + li->lay.tidx);
-        uint2 *key = (uint2 *)(iws + li->lay.key);
-        WD_HIP(ctx, hipMemcpyAsync(d_planes, index_planes, (size_t)n_tiles * I * sizeof(void *), hipMemcpyHostToDevice,
-                                   ctx->stream));
-        WD_HIP(ctx, hipMemcpyAsync(d_tidx, tile_index, n_tiles * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        if (aligned4)
-            hipLaunchKernelGGL(k_li_pack<true>, dim3((unsigned)((N + 4 * kTdBlock - 1) / (4 * kTdBlock)), (unsigned)n_tiles),
-                               dim3(kTdBlock), 0, ctx->stream, d_planes, d_tidx, I, N, key);
-        else
-            hipLaunchKernelGGL(k_li_pack<false>, dim3((unsigned)((N + kTdBlock - 1) / kTdBlock), (unsigned)n_tiles),
-                               dim3(kTdBlock), 0, ctx->stream, d_planes, d_tidx, I, N, key);
-        WD_HIP(ctx, hipGetLastError());
-        // (the pointer tables are the next call's too, and the caller may reuse the planes at once)
-        WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    li->added.swap(seen);
-    return WD_OK;
+    return lane_key_add(ld, ld ? ld->index.get() : nullptr, n_tiles, tile_index, index_planes, kLiSay);
 } WD_CATCH
 
 int wd_lane_index_finish(wd_lane_dups *ld, int64_t min_pf, int64_t cap, int64_t *lane_index_row, int64_t *other_row,
@@ -554,10 +579,8 @@ try {
         return fail(ctx, WD_ERR_ARG, "lane index: finish before wd_lane_index_begin");
     if (!ld->finished)
         return fail(ctx, WD_ERR_ARG, "lane index: finish comes after a successful finish of the lane");
-    for (int t = 0; t < ld->max_tiles; t++)
-        if (li->added[t] != ld->added[t])
-            return fail(ctx, WD_ERR_ARG, "lane index: tile index " + std::to_string(t) +
-                                             (ld->added[t] ? " was added without index planes" : " got index planes but was never added"));
+    if (const int rc = lane_part_tiles(ld, li->added, "lane index", "index planes"))
+        return rc;
     const std::vector<int> tiles = ld_tiles_added(ld);
     const int64_t N = ld->N;
     unsigned long long h_other[kLiOtherCnt] = {0}, listed = 0;

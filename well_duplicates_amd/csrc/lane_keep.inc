@@ -362,10 +362,8 @@ int lk_run(wd_lane_dups *ld, int min_q, void *scratch_dev, size_t scratch_bytes,
     if (const int rc = p.scratch(scratch_dev, scratch_bytes, lay.bytes, "scratch smaller than wd_lane_keep_scratch",
                                  "lane keep: the scratch must be in device memory"))
         return rc;
-    for (int t = 0; t < T; t++)
-        if (lq->added[t] != ld->added[t])
-            return fail(ctx, WD_ERR_ARG, "lane keep: tile index " + std::to_string(t) +
-                                             (ld->added[t] ? " was added without qualities" : " got qualities but was never added"));
+    if (const int rc = lane_part_tiles(ld, lq->added, "lane keep", "qualities"))
+        return rc;
     std::vector<uint8_t *> h_mask((size_t)T, nullptr);
     if (keep_dev && N > 0)
         for (int t = 0; t < T; t++) {

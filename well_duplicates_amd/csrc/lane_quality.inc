@@ -430,33 +430,19 @@ try {
 int wd_lane_qual_add(wd_lane_dups *ld, int n_tiles, const int *tile_index, const uint8_t *const *planes,
                      const uint8_t *const *filter)
 try {
-    if (!ld || n_tiles < 0)
-        return WD_ERR_ARG;
-    wd_ctx *ctx = ld->ctx;
-    wd_lane_quality *lq = ld->qual.get();
-    const int L = ld->L;
-    const int64_t N = ld->N;
-    if (!lq)
-        return fail(ctx, WD_ERR_ARG, "lane qualities: add before wd_lane_qual_begin");
-    if (ld->finished || ld->resolved)
-        return fail(ctx, WD_ERR_ARG, "lane qualities: add after finish");
-    if (ctx->well_stride != 1)
-        return fail(ctx, WD_ERR_ARG, "lane qualities read a plane per cycle (well_stride 1)");
+    wd_lane_quality *lq = ld ? ld->qual.get() : nullptr;
+    std::vector<char> seen;
+    if (const int rc = lane_add_open(ld, lq ? &lq->added : nullptr, n_tiles, tile_index, filter && (planes || !ld || ld->L <= 0),
+                                     {"lane qualities", "lane qualities: add before wd_lane_qual_begin",
+                                      "lane qualities read a plane per cycle (well_stride 1)",
+                                      "null tile index, plane or filter table"},
+                                     seen))
+        return rc;
     if (n_tiles == 0)
         return WD_OK;
-    if (!tile_index || !filter || (L > 0 && !planes))
-        return fail(ctx, WD_ERR_ARG, "null tile index, plane or filter table");
-    if (n_tiles > ld->max_tiles)
-        return fail(ctx, WD_ERR_ARG, "lane qualities: more tiles than the lane has room for");
-    std::vector<char> seen(lq->added);
-    for (int i = 0; i < n_tiles; i++) {
-        const int t = tile_index[i];
-        if (t < 0 || t >= ld->max_tiles)
-            return fail(ctx, WD_ERR_ARG, "lane qualities: tile index " + std::to_string(t) + " out of range");
-        if (seen[t])
-            return fail(ctx, WD_ERR_ARG, "lane qualities: tile index " + std::to_string(t) + " used twice");
-        seen[t] = 1;
-    }
+    wd_ctx *ctx = ld->ctx;
+    const int L = ld->L;
+    const int64_t N = ld->N;
     bool aligned4;
     if (const int rc = check_tables(ctx, "lane qualities: ", n_tiles, L, planes, filter, nullptr, &aligned4))
         return rc;
@@ -520,10 +506,8 @@ try {
     if (const int rc = p.scratch(scratch_dev, scratch_bytes, lay.bytes, "scratch smaller than wd_lane_qual_scratch",
                                  "lane qualities: the scratch must be in device memory"))
         return rc;
-    for (int t = 0; t < T; t++)
-        if (lq->added[t] != ld->added[t])
-            return fail(ctx, WD_ERR_ARG, "lane qualities: tile index " + std::to_string(t) +
-                                             (ld->added[t] ? " was added without qualities" : " got qualities but was never added"));
+    if (const int rc = lane_part_tiles(ld, lq->added, "lane qualities", "qualities"))
+        return rc;
     memset(lane_row, 0, WD_LANEQUALITY_LANE_COLS * sizeof(int64_t));
     memset(tile_rows, 0, (size_t)T * kLqTileCnt * sizeof(int64_t));
     memset(qhist, 0, kLqValues * sizeof(int64_t));

@@ -76,14 +76,10 @@ constexpr int kLuGroups = 2048;                    // workgroups of k_lu_group a
 // give the small ones their occupancy back; it has not been tried.
 static_assert(kLuWaves * 3 * kLuMaxFamily * 4 + 2 * kLuBins * 4 <= 53 * 1024, "three workgroups per CU");
 
-// the UMI workspace (include/welldup_laneumi.h states the arithmetic)
-struct LuWsLayout {
-    size_t planes, tidx, key, bytes;
-};
-
-LuWsLayout lu_ws_layout_of(int64_t N, int max_tiles, int U)
+// the UMI workspace (include/welldup_laneumi.h states the arithmetic): the index workspace without its counters in front
+LaneKeyLayout lu_ws_layout_of(int64_t N, int max_tiles, int U)
 {
-    LuWsLayout l;
+    LaneKeyLayout l;
     const size_t t = (size_t)max_tiles, wells = (size_t)N * t;
     l.planes = 0;
     l.tidx = align256(l.planes + t * (size_t)U * sizeof(void *));
@@ -509,13 +505,11 @@ __global__ void __launch_bounds__(kTdBlock) k_lu_group_mol(int64_t N, const uint
 }  // namespace
 
 #ifndef WD_LANE_UMI_EMU                            // (tools/lane_umi_emu.cpp: the kernels above on the CPU, a fiber per lane)
-// the UMI part of an accumulator: the host side (the device side is the caller's UMI workspace)
-struct wd_lane_umi_part {
-    int U;
-    LuWsLayout lay;
-    uint8_t *ws;
-    std::vector<char> added;                       // by tile index: UMI planes given
-};
+// the UMI part of an accumulator: lane_index.inc's key part, in the caller's UMI workspace
+struct wd_lane_umi_part : LaneKeyPart {};
+
+const LanePartSay kLuSay = {"lane umi", "lane umi: add before wd_lane_umi_begin", "lane umi reads a plane per cycle (well_stride 1)",
+                            "null tile index or plane table", "UMI", "workspace smaller than wd_lane_umi_workspace"};
 
 extern "C" {
 
@@ -534,90 +528,13 @@ int wd_lane_umi_workspace(int64_t N, int max_tiles, int U, size_t *bytes)
 
 int wd_lane_umi_begin(wd_lane_dups *ld, int U, void *workspace_dev, size_t workspace_bytes)
 try {
-    if (!ld)
-        return WD_ERR_ARG;
-    wd_ctx *ctx = ld->ctx;
-    if (U < 1 || U > WD_LANEUMI_MAX_CYCLES)
-        return fail(ctx, WD_ERR_ARG, "lane umi: 1.." + std::to_string(WD_LANEUMI_MAX_CYCLES) + " UMI cycles, not " +
-                                         std::to_string(U));
-    if (ld->finished || ld->resolved)
-        return fail(ctx, WD_ERR_ARG, "lane umi: begin after finish");
-    if (ld->umi)
-        return fail(ctx, WD_ERR_ARG, "lane umi: begin is called once");
-    const LuWsLayout lay = lu_ws_layout_of(ld->N, ld->max_tiles, U);
-    if (!workspace_dev || workspace_bytes < lay.bytes)
-        return fail(ctx, WD_ERR_ARG, "workspace smaller than wd_lane_umi_workspace");
-    if (!on_device(workspace_dev))
-        return fail(ctx, WD_ERR_ARG, "lane umi: the workspace must be in device memory");
-    auto lu = std::make_shared<wd_lane_umi_part>();
-    lu->U = U;
-    lu->lay = lay;
-    lu->ws = (uint8_t *)workspace_dev;
-    lu->added.assign((size_t)ld->max_tiles, 0);
-    ld->umi = lu;
-    return WD_OK;
+    return lane_key_begin(ld, &wd_lane_dups::umi, U, WD_LANEUMI_MAX_CYCLES, lu_ws_layout_of, workspace_dev, workspace_bytes,
+                          kLuSay);
 } WD_CATCH
 
 int wd_lane_umi_add(wd_lane_dups *ld, int n_tiles, const int *tile_index, const uint8_t *const *umi_planes)
 try {
-    if (!ld || n_tiles < 0)
-        return WD_ERR_ARG;
-    wd_ctx *ctx = ld->ctx;
-    wd_lane_umi_part *lu = ld->umi.get();
-    const int64_t N = ld->N;
-    if (!lu)
-        return fail(ctx, WD_ERR_ARG, "lane umi: add before wd_lane_umi_begin");
-    if (ld->finished || ld->resolved)
-        return fail(ctx, WD_ERR_ARG, "lane umi: add after finish");
-    if (ctx->well_stride != 1)
-        return fail(ctx, WD_ERR_ARG, "lane umi reads a plane per cycle (well_stride 1)");
-    if (n_tiles == 0)
-        return WD_OK;
-    if (!tile_index || !umi_planes)
-        return fail(ctx, WD_ERR_ARG, "null tile index or plane table");
-    if (n_tiles > ld->max_tiles)
-        return fail(ctx, WD_ERR_ARG, "lane umi: more tiles than the lane has room for");
-    const int U = lu->U;
-    std::vector<char> seen(lu->added);
-    for (int i = 0; i < n_tiles; i++) {
-        const int t = tile_index[i];
-        if (t < 0 || t >= ld->max_tiles)
-            return fail(ctx, WD_ERR_ARG, "lane umi: tile index " + std::to_string(t) + " out of range");
-        if (seen[t])
-            return fail(ctx, WD_ERR_ARG, "lane umi: tile index " + std::to_string(t) + " used twice");
-        seen[t] = 1;
-    }
-    bool aligned4 = true;
-    for (size_t i = 0; i < (size_t)n_tiles * U; i++) {
-        if (!umi_planes[i])
-            return fail(ctx, WD_ERR_ARG, "null plane pointer");
-        aligned4 = aligned4 && ((uintptr_t)umi_planes[i] & 3u) == 0;
-    }
-    for (int i = 0; i < n_tiles; i++)
-        if (N > 0 && !on_device(umi_planes[(size_t)i * U]))
-            return fail(ctx, WD_ERR_ARG, "lane umi: planes must be in device memory");
-    if (bind_device(ctx))
-        return WD_ERR_HIP;
-    if (N > 0) {
-        uint8_t *uws = lu->ws;
-        const uint8_t **d_planes = (const uint8_t **)(uws + lu->lay.planes);
-        int *d_tidx = (int *)(uws + lu->lay.tidx);
-        uint2 *key = (uint2 *)(uws + lu->lay.key);
-        WD_HIP(ctx, hipMemcpyAsync(d_planes, umi_planes, (size_t)n_tiles * U * sizeof(void *), hipMemcpyHostToDevice,
-                                   ctx->stream));
-        WD_HIP(ctx, hipMemcpyAsync(d_tidx, tile_index, n_tiles * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        if (aligned4)
-            hipLaunchKernelGGL(k_li_pack<true>, dim3((unsigned)((N + 4 * kTdBlock - 1) / (4 * kTdBlock)), (unsigned)n_tiles),
-                               dim3(kTdBlock), 0, ctx->stream, d_planes, d_tidx, U, N, key);
-        else
-            hipLaunchKernelGGL(k_li_pack<false>, dim3((unsigned)((N + kTdBlock - 1) / kTdBlock), (unsigned)n_tiles),
-                               dim3(kTdBlock), 0, ctx->stream, d_planes, d_tidx, U, N, key);
-        WD_HIP(ctx, hipGetLastError());
-        // (the pointer tables are the next call's too, and the caller may reuse the planes at once)
-        WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    lu->added.swap(seen);
-    return WD_OK;
+    return lane_key_add(ld, ld ? ld->umi.get() : nullptr, n_tiles, tile_index, umi_planes, kLuSay);
 } WD_CATCH
 
 int wd_lane_umi_scratch(int max_tiles, int64_t wells_per_tile, size_t *bytes)
@@ -658,10 +575,8 @@ int lu_run(wd_lane_dups *ld, int max_e, int max_family, void *scratch_dev, size_
         return fail(ctx, WD_ERR_ARG, "lane umi: the pass needs wd_lane_umi_begin");
     if (const int rc = p.finished("lane umi comes after a successful finish of the lane"))
         return rc;
-    for (int t = 0; t < T; t++)
-        if (lu->added[t] != ld->added[t])
-            return fail(ctx, WD_ERR_ARG, "lane umi: tile index " + std::to_string(t) +
-                                             (ld->added[t] ? " was added without UMI planes" : " got UMI planes but was never added"));
+    if (const int rc = lane_part_tiles(ld, lu->added, "lane umi", "UMI planes"))
+        return rc;
     if (max_e < 0 || max_e > kLuMaxE)
         return fail(ctx, WD_ERR_ARG, "lane umi: max_e is 0.." + std::to_string(kLuMaxE) + ", not " + std::to_string(max_e));
     if (max_family < 2 || max_family > kLuMaxFamily)
@@ -703,7 +618,7 @@ int lu_run(wd_lane_dups *ld, int max_e, int max_family, void *scratch_dev, size_
     int *d_tidx = (int *)(sc + lay.tidx);
     uint32_t *slot = (uint32_t *)(sc + lay.slot), *region = (uint32_t *)(sc + lay.region);
     const uint32_t *label = (const uint32_t *)(ld->ws + ld->lay.label), *members = (const uint32_t *)(ld->ws + ld->lay.members);
-    const uint2 *key = (const uint2 *)(lu->ws + lu->lay.key);
+    const uint2 *key = (const uint2 *)(lu->ws + lu->at.key);
     const size_t wells = (size_t)T * (size_t)N;
     const uint32_t W = (uint32_t)wells;
     const unsigned groups = lu_group_groups(wells);

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Iterable, List, Optional, Sequence
+from typing import Callable, Iterable, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -573,6 +573,35 @@ class Scanner:
                                            int(lane), int(tile)))
 
 
+def _align256(v: int) -> int:
+    return (v + 255) // 256 * 256
+
+
+class _SidePart(NamedTuple):
+    """What LaneDups knows of a side part `name` of its accumulator: it keeps the workspace in d_<name> with
+    <name>_bytes, and what <name>_begin was given in the attribute `arg` (`none` before)."""
+    name: str
+    arg: str
+    none: object
+    conv: Callable          # the begin's argument as it is kept
+    size: Callable          # (accumulator, the begin's argument) -> the workspace's bytes
+    begin: Callable         # (library, handle, the argument, workspace, bytes) -> the return code of the begin entry
+    add: str                # the add entry
+    filters: bool           # the add takes the filter table too
+    cycles: str             # the attribute that holds the cycles a TileBatch given to the add must have
+    phrase: str             # what the shape error calls them
+
+
+_SIDE_PARTS = {p.name: p for p in (
+    _SidePart("index", "I", 0, int, lambda ld, I: ld.sc.lane_index_workspace_bytes(ld.N, ld.max_tiles, I),
+              lambda lib, h, I, ws, n: lib.wd_lane_index_begin(h, I, ws, n), "wd_lane_index_add", False, "I", "index cycles"),
+    _SidePart("qual", "qual_edges", None, lambda e: [int(v) for v in e], lambda ld, e: ld.sc.lane_qual_workspace_bytes(ld.N, ld.max_tiles, ld.L),
+              lambda lib, h, e, ws, n: lib.wd_lane_qual_begin(h, len(e), (ctypes.c_int * max(1, len(e)))(*e), ws, n),
+              "wd_lane_qual_add", True, "L", "cycles"),
+    _SidePart("umi", "U", 0, int, lambda ld, U: ld.sc.lane_umi_workspace_bytes(ld.N, ld.max_tiles, U),
+              lambda lib, h, U, ws, n: lib.wd_lane_umi_begin(h, U, ws, n), "wd_lane_umi_add", False, "U", "UMI cycles"))}
+
+
 class LaneDups:
     """The read classes across all tiles of a lane (include/welldup_lanedups.h): an accumulator the batches of
     a lane are fed to one after the other.  It owns its workspace: a packed copy of every read and the lane's
@@ -584,9 +613,9 @@ class LaneDups:
         self.ws_bytes = scanner.lane_dups_workspace_bytes(self.N, self.max_tiles, self.L)
         self.d_ws = scanner.malloc(self.ws_bytes)
         self.d_labels = self.d_near_labels = 0
-        self.d_index, self.index_bytes, self.I, self.index_listed = 0, 0, 0, 0
-        self.d_qual, self.qual_bytes, self.qual_edges = 0, 0, None
-        self.d_umi, self.umi_bytes, self.U = 0, 0, 0
+        for part in _SIDE_PARTS.values():                # d_index, index_bytes, I; d_qual, qual_bytes, qual_edges; d_umi, umi_bytes, U
+            self._part_set(part, 0, 0, part.none)
+        self.index_listed = 0
         self.d_mol, self.mol_bytes = 0, 0                # the molecule region (umi(molecules=True))
         self.refused = None
         self.added = []                                  # the tile indices given to add, in that order
@@ -608,12 +637,66 @@ class LaneDups:
         self._end()
         self.added = []
         self._begin(self.d_ws, self.ws_bytes)
-        if self.I:
-            self._index_begin()
-        if self.qual_edges is not None:
-            self._qual_begin()
-        if self.U:
-            self._umi_begin()
+        for part in _SIDE_PARTS.values():
+            if getattr(self, part.arg) != part.none:
+                self._part_rebegin(part)
+
+    # ---- the side parts: one body each for begin, begin again after restart(), add and the feeding of an add entry
+    def _part_set(self, part: _SidePart, ptr: int, nbytes: int, arg):
+        setattr(self, "d_" + part.name, ptr)
+        setattr(self, part.name + "_bytes", nbytes)
+        setattr(self, part.arg, arg)
+
+    def _part_begin(self, part: _SidePart, arg):
+        """Allocates the part's workspace and begins it; a begin that fails leaves the accumulator without the part."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        if getattr(self, part.arg) != part.none:
+            raise ValueError("%s_begin is called once" % part.name)
+        arg = part.conv(arg)
+        nbytes = part.size(self, arg)
+        self._part_set(part, self.sc.malloc(max(1, nbytes)), nbytes, arg)
+        try:
+            self._part_rebegin(part)
+        except Exception:
+            self.sc.free(getattr(self, "d_" + part.name))
+            self._part_set(part, 0, 0, part.none)
+            raise
+
+    def _part_rebegin(self, part: _SidePart):
+        self.sc._ck(part.begin(self.sc._lib, self._h, getattr(self, part.arg), ctypes.c_void_p(getattr(self, "d_" + part.name)),
+                               getattr(self, part.name + "_bytes")))
+
+    def _part_add(self, part: _SidePart, tables, tile_indices: Sequence[int], well_stride: int):
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        idx = [int(t) for t in tile_indices]
+        cycles = getattr(self, part.cycles)
+        if isinstance(tables, TileBatch):
+            tb = tables
+            if len(idx) != tb.n_tiles or tb.L != cycles or tb.N != self.N:
+                raise ValueError("the batch has %d tiles of %d wells and %d cycles; %d indices for a lane of %d wells "
+                                 "and %d %s" % (tb.n_tiles, tb.N, tb.L, len(idx), self.N, cycles, part.phrase))
+            tables, well_stride = tb.tables, tb.interleave
+        if not part.filters:
+            tables = tables[:1]
+            if cycles and len(tables[0]) < len(idx) * cycles:
+                raise ValueError("the plane table must hold n_tiles x %s pointers" % part.cycles)
+        self._feed(part.add, idx, tables, well_stride)
+
+    def _feed(self, entry: str, idx: Sequence[int], tables, well_stride: int):
+        """An add entry of the library on the tiles idx, under well_stride - which is 1 again afterwards, whatever happened."""
+        ti = (ctypes.c_int * max(1, len(idx)))(*idx)
+        self.sc.set_option("well_stride", well_stride)
+        try:
+            self.sc._ck(getattr(self.sc._lib, entry)(self._h, len(idx), ti, *tables))
+        finally:
+            self.sc.set_option("well_stride", 1)
+
+    def _key_array(self, d_ws: int, cycles: int, front: int) -> np.ndarray:
+        """The key array of a key part's workspace: behind `front` bytes, the plane pointers and the tile indices."""
+        at = front + _align256(8 * self.max_tiles * cycles) + _align256(4 * self.max_tiles)
+        return self.sc.d2h(d_ws + at, 8 * self.N * self.max_tiles, np.uint64)
 
     def _with_scratch(self, nbytes: int, call):
         """call(scratch pointer, nbytes) -> a return code, checked; the scratch lives for the call."""
@@ -639,45 +722,13 @@ class LaneDups:
     def qual_begin(self, edges: Sequence[int]):
         """Gives the lane a quality part before the first add: edges are the bins' lower edges (1..8 of them,
         ascending from 0, at most 63).  The accumulator owns and frees its workspace."""
-        if self._h is None:
-            raise ValueError("the accumulator is closed")
-        if self.qual_edges is not None:
-            raise ValueError("qual_begin is called once")
-        nbytes = self.sc.lane_qual_workspace_bytes(self.N, self.max_tiles, self.L)
-        self.d_qual, self.qual_bytes = self.sc.malloc(max(1, nbytes)), nbytes
-        try:
-            self.qual_edges = [int(e) for e in edges]
-            self._qual_begin()
-        except Exception:
-            self.sc.free(self.d_qual)
-            self.d_qual, self.qual_bytes, self.qual_edges = 0, 0, None
-            raise
-
-    def _qual_begin(self):
-        e = (ctypes.c_int * max(1, len(self.qual_edges)))(*self.qual_edges)
-        self.sc._ck(self.sc._lib.wd_lane_qual_begin(self._h, len(self.qual_edges), e, ctypes.c_void_p(self.d_qual),
-                                                    self.qual_bytes))
+        self._part_begin(_SIDE_PARTS["qual"], edges)
 
     def qual_add(self, tables, tile_indices: Sequence[int], well_stride: int = 1):
         """Packs the qualities of resident tiles and counts QHist over their PF wells.  tables: the TileBatch `add`
         takes, or the ctypes pointer tables Scanner._tables makes (planes n x L, filters n); tile_indices as `add`
         takes them.  Independent of `add` in order and batching."""
-        if self._h is None:
-            raise ValueError("the accumulator is closed")
-        idx = [int(t) for t in tile_indices]
-        if isinstance(tables, TileBatch):
-            tb = tables
-            if len(idx) != tb.n_tiles or tb.L != self.L or tb.N != self.N:
-                raise ValueError("the batch has %d tiles of %d wells and %d cycles; %d indices for a lane of %d wells "
-                                 "and %d cycles" % (tb.n_tiles, tb.N, tb.L, len(idx), self.N, self.L))
-            tables, well_stride = tb.tables, tb.interleave
-        pt, ft = tables
-        ti = (ctypes.c_int * max(1, len(idx)))(*idx)
-        self.sc.set_option("well_stride", well_stride)
-        try:
-            self.sc._ck(self.sc._lib.wd_lane_qual_add(self._h, len(idx), ti, pt, ft))
-        finally:
-            self.sc.set_option("well_stride", 1)
+        self._part_add(_SIDE_PARTS["qual"], tables, tile_indices, well_stride)
 
     def qualities(self, max_d: int):
         """After finish(), any number of times, before or after index_finish, mismatches and distances
@@ -706,53 +757,19 @@ class LaneDups:
     def index_begin(self, I: int):
         """Gives the lane an index part of I cycles (1..20), before any finish; the accumulator owns and frees its
         workspace."""
-        if self._h is None:
-            raise ValueError("the accumulator is closed")
-        if self.I:
-            raise ValueError("index_begin is called once")
-        nbytes = self.sc.lane_index_workspace_bytes(self.N, self.max_tiles, int(I))
-        self.d_index, self.index_bytes = self.sc.malloc(max(1, nbytes)), nbytes
-        try:
-            self.I = int(I)
-            self._index_begin()
-        except Exception:
-            self.sc.free(self.d_index)
-            self.d_index, self.index_bytes, self.I = 0, 0, 0
-            raise
-
-    def _index_begin(self):
-        self.sc._ck(self.sc._lib.wd_lane_index_begin(self._h, self.I, ctypes.c_void_p(self.d_index), self.index_bytes))
+        self._part_begin(_SIDE_PARTS["index"], I)
 
     def index_add(self, tables, tile_indices: Sequence[int], well_stride: int = 1):
         """Packs the index keys of resident tiles.  tables: a TileBatch of the I index cycles, or the ctypes pointer
         tables Scanner._tables makes (the planes n x I; the filters are not looked at); tile_indices as `add`
         takes them.  Independent of `add` in order and batching."""
-        if self._h is None:
-            raise ValueError("the accumulator is closed")
-        idx = [int(t) for t in tile_indices]
-        if isinstance(tables, TileBatch):
-            tb = tables
-            if len(idx) != tb.n_tiles or tb.L != self.I or tb.N != self.N:
-                raise ValueError("the batch has %d tiles of %d wells and %d cycles; %d indices for a lane of %d wells "
-                                 "and %d index cycles" % (tb.n_tiles, tb.N, tb.L, len(idx), self.N, self.I))
-            tables, well_stride = tb.tables, tb.interleave
-        pt = tables[0]
-        if self.I and len(pt) < len(idx) * self.I:
-            raise ValueError("the plane table must hold n_tiles x I pointers")
-        ti = (ctypes.c_int * max(1, len(idx)))(*idx)
-        self.sc.set_option("well_stride", well_stride)
-        try:
-            self.sc._ck(self.sc._lib.wd_lane_index_add(self._h, len(idx), ti, pt))
-        finally:
-            self.sc.set_option("well_stride", 1)
+        self._part_add(_SIDE_PARTS["index"], tables, tile_indices, well_stride)
 
     def index_keys(self) -> np.ndarray:
         """uint64 [max_tiles * N]: the index key of every well that got index planes (the key array of the index
         workspace; it lies where include/welldup_laneindex.h's arithmetic puts it: behind the counters, the plane
         pointers and the tile indices)."""
-        up = lambda v: (v + 255) // 256 * 256
-        at = 4096 + 4096 + 256 + up(8 * self.max_tiles * self.I) + up(4 * self.max_tiles)
-        return self.sc.d2h(self.d_index + at, 8 * self.N * self.max_tiles, np.uint64)
+        return self._key_array(self.d_index, self.I, 4096 + 4096 + 256)
 
     def index_finish(self, min_pf: int = 1, cap: int = 1 << 16):
         """After finish(), any number of times.  -> (lane index row int64 [5]: [Groups, Listed, GroupSpans,
@@ -781,53 +798,19 @@ class LaneDups:
     def umi_begin(self, U: int):
         """Gives the lane a UMI part of U cycles (1..20), before any finish; the accumulator owns and frees its
         workspace.  A lane may carry an index part and a UMI part at once."""
-        if self._h is None:
-            raise ValueError("the accumulator is closed")
-        if self.U:
-            raise ValueError("umi_begin is called once")
-        nbytes = self.sc.lane_umi_workspace_bytes(self.N, self.max_tiles, int(U))
-        self.d_umi, self.umi_bytes = self.sc.malloc(max(1, nbytes)), nbytes
-        try:
-            self.U = int(U)
-            self._umi_begin()
-        except Exception:
-            self.sc.free(self.d_umi)
-            self.d_umi, self.umi_bytes, self.U = 0, 0, 0
-            raise
-
-    def _umi_begin(self):
-        self.sc._ck(self.sc._lib.wd_lane_umi_begin(self._h, self.U, ctypes.c_void_p(self.d_umi), self.umi_bytes))
+        self._part_begin(_SIDE_PARTS["umi"], U)
 
     def umi_add(self, tables, tile_indices: Sequence[int], well_stride: int = 1):
         """Packs the UMI reads of resident tiles.  tables: a TileBatch of the U UMI cycles, or the ctypes pointer
         tables Scanner._tables makes (the planes n x U; the filters are not looked at); tile_indices as `add`
         takes them.  Independent of `add` in order and batching."""
-        if self._h is None:
-            raise ValueError("the accumulator is closed")
-        idx = [int(t) for t in tile_indices]
-        if isinstance(tables, TileBatch):
-            tb = tables
-            if len(idx) != tb.n_tiles or tb.L != self.U or tb.N != self.N:
-                raise ValueError("the batch has %d tiles of %d wells and %d cycles; %d indices for a lane of %d wells "
-                                 "and %d UMI cycles" % (tb.n_tiles, tb.N, tb.L, len(idx), self.N, self.U))
-            tables, well_stride = tb.tables, tb.interleave
-        pt = tables[0]
-        if self.U and len(pt) < len(idx) * self.U:
-            raise ValueError("the plane table must hold n_tiles x U pointers")
-        ti = (ctypes.c_int * max(1, len(idx)))(*idx)
-        self.sc.set_option("well_stride", well_stride)
-        try:
-            self.sc._ck(self.sc._lib.wd_lane_umi_add(self._h, len(idx), ti, pt))
-        finally:
-            self.sc.set_option("well_stride", 1)
+        self._part_add(_SIDE_PARTS["umi"], tables, tile_indices, well_stride)
 
     def umi_keys(self) -> np.ndarray:
         """uint64 [max_tiles * N]: the UMI read of every well that got UMI planes, packed as index_keys packs an
         index read (the key array of the UMI workspace; it lies where include/welldup_laneumi.h's arithmetic puts it:
         behind the plane pointers and the tile indices)."""
-        up = lambda v: (v + 255) // 256 * 256
-        at = up(8 * self.max_tiles * self.U) + up(4 * self.max_tiles)
-        return self.sc.d2h(self.d_umi + at, 8 * self.N * self.max_tiles, np.uint64)
+        return self._key_array(self.d_umi, self.U, 0)
 
     def umi(self, max_e: int = 0, max_family: int = 256, molecules: bool = False):
         """After finish() of a lane with a UMI part, any number of times, before or after every other pass
@@ -880,7 +863,7 @@ class LaneDups:
         if not self.d_mol:
             raise ValueError("umi_molecules comes after umi(molecules=True)")
         wells = self.max_tiles * self.N
-        at = (4 * wells + 255) // 256 * 256
+        at = _align256(4 * wells)
         shape = (self.max_tiles, self.N)
         if not wells:
             return np.zeros(shape, dtype=np.uint32), np.zeros(shape, dtype=np.uint32)
@@ -901,14 +884,8 @@ class LaneDups:
         """add() from the ctypes pointer tables Scanner._tables makes (planes n x L, filters n)."""
         if self._h is None:
             raise ValueError("the accumulator is closed")
-        pt, ft = tables
-        ti = (ctypes.c_int * max(1, len(tile_indices)))(*tile_indices)
-        self.sc.set_option("well_stride", well_stride)
-        try:
-            self.sc._ck(self.sc._lib.wd_lane_dups_add(self._h, len(tile_indices), ti, pt, ft))
-            self.added.extend(int(t) for t in tile_indices)
-        finally:
-            self.sc.set_option("well_stride", 1)
+        self._feed("wd_lane_dups_add", tile_indices, tables, well_stride)
+        self.added.extend(int(t) for t in tile_indices)
 
     def _label_table(self, attr: str):
         lbl_bytes = 4 * self.N * self.max_tiles
@@ -1183,10 +1160,9 @@ class LaneDups:
     def close(self):
         """Drops the lane, finished or not, and frees the workspace."""
         self._end()
-        for ptr in (self.d_ws, self.d_labels, self.d_near_labels, self.d_index, self.d_qual, self.d_umi, self.d_mol):
-            if ptr:
-                self.sc.free(ptr)
-        self.d_ws = self.d_labels = self.d_near_labels = self.d_index = self.d_qual = self.d_umi = self.d_mol = 0
+        for attr in ["d_ws", "d_labels", "d_near_labels", "d_mol"] + ["d_" + name for name in _SIDE_PARTS]:
+            self.sc.free(getattr(self, attr))
+            setattr(self, attr, 0)
 
 
 class TileBatch:
