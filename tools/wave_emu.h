@@ -1,7 +1,7 @@
 // wave_emu.h - what a kernel's source needs to run on the CPU as it stands (tools/lane_mismatch_emu.cpp,
 // tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp, tools/lane_hops_emu.cpp, tools/lane_gc_emu.cpp, tools/lane_consensus_emu.cpp, tools/lane_umi_emu.cpp, tools/lane_keep_emu.cpp,
 // tools/lane_molecules_emu.cpp, tools/read_classes_emu.cpp, tools/near_emu.cpp, tools/dup_sets_emu.cpp, tools/lane_index_emu.cpp, tools/gen_rings_emu.cpp,
-// tools/scan_queue_emu.cpp, tools/scan_lines_emu.cpp): the 256 lanes of a
+// tools/scan_queue_emu.cpp, tools/scan_lines_emu.cpp, tools/scan_dense_emu.cpp): the 256 lanes of a
 // workgroup are fibers (ucontext) that a round-robin scheduler switches at the collectives - __syncthreads is a
 // rendezvous of the workgroup, __ballot and __shfl of a wave -, LDS is the kernel's static storage, an atomic add or
 // minimum or a compare-and-swap is a plain one (one fiber runs at a time), and the qualifiers are empty.  Include it, then the kernel's
@@ -33,7 +33,9 @@
 // (tools/lane_consensus_emu.cpp; tools/gen_rings_emu.cpp, which clears emu_torn_add for its count pass so that the
 // fill pass's claim of an LDS slot alone is broken).
 // -DWAVE_EMU_TORN_OR breaks atomicOr the same way (tools/scan_lines_emu.cpp: the hit-level masks four targets share a
-// word of).
+// word of; tools/scan_dense_emu.cpp, which builds with both flags and clears emu_torn_or or emu_torn_add at run time).
+// Workgroups have kEmuBlock = 256 lanes unless a unit defines WAVE_EMU_MAX_BLOCK before this header and sets emu_block
+// (a multiple of kWave) before a launch: tools/scan_dense_emu.cpp runs kernels of 64, 256 and 1024 lanes.
 // -DWAVE_EMU_UNIT_DEFS: the emulator includes csrc/read_classes.inc and csrc/tile_classes.inc (the head of the tiledups unit),
 // which define kTdBlock, kSpread, kFpCycles, kLdCmpWords, kInvalid, kMaxCycles, align256 and spread_row themselves:
 // this header then leaves them, and lane_pass.inc, out.  tools/dup_sets_emu.cpp defines it too: csrc/dup_sets.inc
@@ -56,6 +58,13 @@ struct uint2 { uint32_t x, y; };
 static uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{x, y}; }
 struct D3 { unsigned x, y, z; };
 constexpr int kEmuBlock = 256;
+// A unit whose kernels have other workgroup sizes (tools/scan_dense_emu.cpp: 64, 256 and 1024 lanes) defines
+// WAVE_EMU_MAX_BLOCK before this header and sets emu_block before a launch; everyone else gets 256 lanes, as ever.
+#ifndef WAVE_EMU_MAX_BLOCK
+#define WAVE_EMU_MAX_BLOCK 256
+#endif
+constexpr int kEmuMaxBlock = WAVE_EMU_MAX_BLOCK;
+static int emu_block = kEmuBlock;                  // lanes of the workgroups being run: a multiple of kWave, <= kEmuMaxBlock
 #ifndef WD_SHARED_H                                // (an emulator that included csrc/wd_shared.h before this header has the library's kWave)
 constexpr int kWave = 64;
 #endif
@@ -67,7 +76,7 @@ static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 #endif
 // ---- fibers: one per lane of a workgroup, switched at collectives - and at atomics, if the schedule says so
 struct Fiber { ucontext_t ctx; void *sp; bool done; char *stack; const long *wait; long wait_at; };      // wait: the generation of the rendezvous it stands at
-static Fiber emu_fib[kEmuBlock]; static ucontext_t emu_sched; static void *emu_sched_sp; static int emu_lane;
+static Fiber emu_fib[kEmuMaxBlock]; static ucontext_t emu_sched; static void *emu_sched_sp; static int emu_lane;
 // A switch saves the registers a call preserves on the fiber's own stack and changes stacks: swapcontext does the same
 // and a system call for the signal mask on top, which at a switch per atomic was most of an emulator's run time (near_emu: 47 s against 6).
 // Elsewhere than on x86-64, or with -DWAVE_EMU_UCONTEXT, it is swapcontext.
@@ -94,12 +103,12 @@ static void await_(const long &gen, long g) { Fiber &f = emu_fib[emu_lane]; f.wa
 // branch: it is complete when every lane of the wave stands at it, waits at the workgroup's barrier (away) or has ended
 // (gone) - the lanes that went round it - and a lane that is not there sets no bit.
 struct WaveSync { int count = 0, away = 0, gone = 0; long gen = 0; unsigned long long pred[2] = {0, 0}; int val[2][kWave]; };
-static WaveSync emu_ws[kEmuBlock / kWave];
+static WaveSync emu_ws[kEmuMaxBlock / kWave];
 static bool wave_complete_(WaveSync &w) { if (w.count + w.away + w.gone < kWave) return false; w.count = 0; w.gen++; return true; }
 static int bar_count = 0; static long bar_gen = 0;
 static void __syncthreads() {
     long g = bar_gen;
-    if (++bar_count == kEmuBlock) { bar_count = 0; bar_gen++; for (WaveSync &w : emu_ws) w.away = 0; return; }
+    if (++bar_count == emu_block) { bar_count = 0; bar_gen++; for (WaveSync &w : emu_ws) w.away = 0; return; }
     WaveSync &w = emu_ws[emu_lane / kWave]; w.away++; if (w.count) wave_complete_(w);
     await_(bar_gen, g);
 }
@@ -201,7 +210,8 @@ template <class T, class U> static T atomicMin(T *p, U v) { emu_point(); emu_min
 template <class T, class U> static T atomicMin(T *p, U v) { emu_point(); emu_mins++; T o = *p; if ((T)v < o) *p = (T)v; return o; }
 #endif
 #ifdef WAVE_EMU_TORN_OR                            // (the deliberate bug of an or: another fiber may set bits of the word between its load and its store)
-template <class T, class U> static T atomicOr(T *p, U v) { emu_point(); T o = *p; emu_point(); *p = o | (T)v; return o; }
+static bool emu_torn_or = true;                    // (an emulator may switch the bug off: one build for its torn or and its torn add)
+template <class T, class U> static T atomicOr(T *p, U v) { emu_point(); T o = *p; if (emu_torn_or) emu_point(); *p = o | (T)v; return o; }
 #else
 template <class T, class U> static T atomicOr(T *p, U v) { emu_point(); T o = *p; *p |= (T)v; return o; }
 #endif
@@ -244,7 +254,7 @@ static void run_block(unsigned bx, unsigned by, void (*kernel)()) {
     g_block = D3{bx, by, 0};
     g_kernel = kernel;
     for (WaveSync &w : emu_ws) w.away = w.gone = 0;
-    for (int t = 0; t < kEmuBlock; t++) {
+    for (int t = 0; t < emu_block; t++) {
         Fiber &f = emu_fib[t];
         if (!f.stack) f.stack = (char *)malloc(1 << 16);
         f.done = false; f.wait = nullptr;
@@ -258,9 +268,9 @@ static void run_block(unsigned bx, unsigned by, void (*kernel)()) {
         makecontext(&f.ctx, entry_, 0);
 #endif
     }
-    int left = kEmuBlock;
-    while (left) for (int i = 0; i < kEmuBlock; i++) {
-        const int t = emu_reverse ? kEmuBlock - 1 - i : i;
+    int left = emu_block;
+    while (left) for (int i = 0; i < emu_block; i++) {
+        const int t = emu_reverse ? emu_block - 1 - i : i;
         if (!emu_fib[t].done && !(emu_fib[t].wait && *emu_fib[t].wait == emu_fib[t].wait_at)) { emu_lane = t;
 #ifdef WAVE_EMU_FAST
             emu_switch(&emu_sched_sp, emu_fib[t].sp);

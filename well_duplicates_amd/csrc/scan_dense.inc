@@ -36,12 +36,43 @@
 // branch-free survivor test, the register-rotated software pipeline, and nothing but loads and
 // LDS traffic inside its loop.
 // (kDenseChainVersion, kSigCycles, kRowGroups, kDenseMaxK: wd_shared.h - the dispatch needs them too)
-constexpr int kDenseSlots = 64;       // counter slots per tile (power of two): same-line atomics serialise
-constexpr int kMaxSeg = 16;           // window groups: runs of consecutive signatures staged in LDS per wave
-constexpr int kWinMaxK = 128;         // ... for groups whose targets have at most this many different neighbour offsets
-constexpr int kWinGap = 24;           // ... offsets this close share a run
-constexpr int kWinDwords = 1024;      // ... and at most this many signatures per window (4 KB): 16 loads of 64
-constexpr int kMarkBlock = 256;       // mark words per block of the rank scan (8192 wells)
+// (kDenseSlots, kMaxSeg, kWinMaxK, kWinGap, kWinDwords, kMarkBlock, kWinBufs, kWinBufsSym, kRankBlock and the arithmetic
+// of a launch - strides, LDS dwords per wave, window counts, grids: dense_launch.inc, free of HIP, which the CPU
+// emulation of this chain shares)
+#include "dense_launch.inc"
+
+// ---- the seams of this file for the CPU emulation (tools/scan_dense_emu.cpp, which defines WD_EMU) ----
+// What a host compiler cannot take - inline assembly and LDS addresses - stands behind these; on the device each
+// expands to exactly the text that stood in its place, in the style of WD_DYNAMIC_LDS (device_common.inc).
+//   WD_PIN(constraints)     the empty asm that makes values opaque to the optimiser; nothing on the CPU
+//   WD_WAIT_VM0 / _N(n)     s_waitcnt vmcnt(0) / vmcnt(immediate); on the CPU a rendezvous of the wave that lands
+//                           the wave's oldest LDS-DMA pieces until n remain (emu_dma_wait)
+//   WD_LDS_ADDR(p)          the LDS byte address of p; on the CPU its byte offset in the launch's LDS block
+//   WD_DENSE_NOTE(event)    nothing on the device; the CPU emulation counts the regions that overflowed
+//   WD_LOCKSTEP()           nothing on the device, where the lanes of a wave run in lockstep: the places where a lane
+//                           reads LDS words another lane of its wave wrote just before, with no collective between.
+//                           The emulation's fibers are not in lockstep, so this is a rendezvous of the wave there.
+//   WD_DENSE_CONTROL(name, statement)  nothing on the device; the emulation runs the statement when its control
+//                           `name` is on - a bug planted on purpose, to show that the emulation's checks can fail
+// wait_vmcnt and lds_dma_dword (below) have a CPU body each; the address-space casts are empty attributes there
+// (tools/wave_emu.h), so the scalar-cache pointer loads ((address_space(4)) of a.filter) compile as they stand.
+#ifdef WD_EMU
+#define WD_PIN(...) ((void)0)
+#define WD_WAIT_VM0() emu_dma_wait(0)
+#define WD_WAIT_VM_N(n) emu_dma_wait(n)
+#define WD_LDS_ADDR(p) emu_lds_addr(p)
+#define WD_DENSE_NOTE(event) emu_dense_note(kNote_##event)
+#define WD_LOCKSTEP() ((void)__ballot(false))
+#define WD_DENSE_CONTROL(name, statement) do { if (emu_dense_control(kControl_##name)) { statement; } } while (0)
+#else
+#define WD_DENSE_NOTE(event) ((void)0)
+#define WD_LOCKSTEP() ((void)0)
+#define WD_DENSE_CONTROL(name, statement) ((void)0)
+#define WD_PIN(...) asm volatile("" : __VA_ARGS__)
+#define WD_WAIT_VM0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#define WD_WAIT_VM_N(n) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(n) : "memory")
+#define WD_LDS_ADDR(p) ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(p))
+#endif
 using gsig = const __attribute__((address_space(1))) uint32_t *;
 using gidx = const __attribute__((address_space(1))) int32_t *;
 
@@ -326,18 +357,18 @@ __global__ __launch_bounds__(kMarkBlock) void k_dense_rank_words(DenseArgs a)
 }
 
 // per tile: block totals -> marked wells before each block
-__global__ __launch_bounds__(1024) void k_dense_rank_blocks(DenseArgs a)
+__global__ __launch_bounds__(kRankBlock) void k_dense_rank_blocks(DenseArgs a)
 {
-    __shared__ uint32_t s_w[1024 / kWave];
+    __shared__ uint32_t s_w[kRankBlock / kWave];
     if (!dense_packed(a))
         return;
     uint32_t *bp = a.bprefix + (size_t)blockIdx.x * (a.mw_stride / kMarkBlock);
     const long long nb = a.mw_stride / kMarkBlock;
     uint32_t carry = 0;
-    for (long long b0 = 0; b0 < nb; b0 += 1024) {
+    for (long long b0 = 0; b0 < nb; b0 += kRankBlock) {
         const long long b = b0 + threadIdx.x;
         uint32_t total;
-        const uint32_t ex = block_exclusive_scan<1024 / kWave>(b < nb ? bp[b] : 0u, s_w, &total);
+        const uint32_t ex = block_exclusive_scan<kRankBlock / kWave>(b < nb ? bp[b] : 0u, s_w, &total);
         if (b < nb)
             bp[b] = carry + ex;
         carry += total;
@@ -894,12 +925,12 @@ __device__ inline void dense_record_pair(const DenseArgs &a, TALLY_T *tally_t, T
     }
 }
 
-constexpr int kWinBufs = 2;           // LDS windows per wave: the next tile's loads land while this tile is compared
-constexpr int kWinBufsSym = 3;        // ... of the one-ended compare (half the window each): two tiles' windows in flight
-
 // s_waitcnt vmcnt(n) for a wave-uniform n known at run time (the instruction takes an immediate).
 __device__ inline void wait_vmcnt(int n)
 {
+#ifdef WD_EMU
+    emu_dma_wait(n < 48 ? n : 48);
+#else
 #define WD_VM(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
 #define WD_VM8(B) WD_VM(B) WD_VM(B + 1) WD_VM(B + 2) WD_VM(B + 3) WD_VM(B + 4) WD_VM(B + 5) WD_VM(B + 6) WD_VM(B + 7)
     switch (n) {
@@ -914,6 +945,7 @@ __device__ inline void wait_vmcnt(int n)
     }
 #undef WD_VM8
 #undef WD_VM
+#endif
 }
 
 // 64 dwords from global memory straight into LDS (LDS-DMA): lane i's dword at base + voff goes to LDS byte
@@ -923,7 +955,11 @@ __device__ inline void wait_vmcnt(int n)
 // caller's (wait_vmcnt); `base` must be wave-uniform.
 __device__ inline void lds_dma_dword(const void *base, uint32_t voff, uint32_t lds)
 {
+#ifdef WD_EMU
+    emu_dma_issue(base, voff, lds);
+#else
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" : : "s"(lds), "v"(voff), "s"(base) : "memory");
+#endif
 }
 
 // sum over the wave's lanes (wave-uniform result): an inclusive scan inside each row of 16 lanes
@@ -1056,12 +1092,14 @@ template <int MODE, bool SYM, int NPC = 0>
 __global__ __launch_bounds__(kBlock) void k_dense_pairs_win(DenseArgs a)
 {
     static_assert(NPC == 0 || SYM, "fixed piece counts belong to the one-ended compare");
-    extern __shared__ uint32_t s_dyn[];                  // per wave: kWinBufs windows, then the survivor queue
+    WD_DYNAMIC_LDS(s_dyn);                               // per wave: kWinBufs windows, then the survivor queue
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int levels = a.levels;
     const int k = a.k;
     // per wave: kWinBufs windows, one survivor queue per tile of the chunk, their entry counts
+    // (dense_per_wave_dwords, dense_launch.inc, written out: through the function the compiler adds the three terms in
+    // another order.  The CPU emulation's LDS block has the host's bytes exactly, so a difference is a sanitizer report.)
     const int per_wave = a.win_bufs * a.win_dwords + a.tile_chunk * (2 * a.q_per + 1) + (a.tile_chunk & 1);
     uint32_t *s_win = s_dyn + wave * per_wave;
     uint2 *s_q_all = (uint2 *)(s_win + a.win_bufs * a.win_dwords);
@@ -1174,10 +1212,10 @@ __global__ __launch_bounds__(kBlock) void k_dense_pairs_win(DenseArgs a)
         gsig sg = (gsig)((MODE != 0 ? a.sig2 : a.sig) + (size_t)tile * a.sig_stride);    // distances > 0: the screen words
         f_ld = SYM ? 1u : (uint32_t)filt[c];            // (SYM: the filter bytes of both ends are k_dense_verify's business)
         sig_ld = sg[c];
-        const uint32_t dst = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(s_win + buf * a.win_dwords);
+        const uint32_t dst = WD_LDS_ADDR(s_win + buf * a.win_dwords);
         // (opaque: or the compiler evaluates the 16 comparisons once, before the tile loop, and
         // keeps them in spilled registers)
-        asm volatile("" : "+s"(n_pc));
+        WD_PIN("+s"(n_pc));
 #pragma unroll
         for (int j = 0; j < NJ; j++) {
             if (j >= n_pc)
@@ -1190,13 +1228,13 @@ __global__ __launch_bounds__(kBlock) void k_dense_pairs_win(DenseArgs a)
     // loads and nothing else; they go out through inline assembly (lds_dma_dword) with counted waits, the
     // windows of the next `ahead` tiles in flight while this one is compared
     const int n_bufs = NPC > 0 ? kWinBufsSym : a.win_bufs, ahead_max = n_bufs - 1;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)s_win;
+    const uint32_t lds0 = WD_LDS_ADDR(s_win);
     const uint32_t own_off = SYM ? (uint32_t)__builtin_amdgcn_readlane((int)(Ku < kWave ? off_b0 : off_b1), Ku & 63) : 0u;
     auto issue_sym = [&](int tile, int buf) {
         const char *sgb = (const char *)((MODE != 0 ? a.sig2 : a.sig) + (size_t)tile * a.sig_stride);
         const uint32_t dst = lds0 + (uint32_t)(buf * a.win_dwords) * 4u;
         if (NPC == 0)
-            asm volatile("" : "+s"(n_pc));
+            WD_PIN("+s"(n_pc));
 #pragma unroll
         for (int j = 0; j < NJ; j++) {
             if (NPC == 0 && j >= n_pc)
@@ -1211,7 +1249,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_pairs_win(DenseArgs a)
             issue_sym(tile0 + d, d);
     } else {
         issue(tile0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        WD_WAIT_VM0();
         f_cur = f_ld;
         csig = sig_ld;
         if (n_tl > 1)
@@ -1227,14 +1265,16 @@ __global__ __launch_bounds__(kBlock) void k_dense_pairs_win(DenseArgs a)
                 static_assert(A == 1 || A == 2, "one or two tiles behind");
                 const int rem = n_tl - ti - 1;
                 if (rem >= A)
-                    asm volatile("s_waitcnt vmcnt(%0)" : : "n"(A * NPC) : "memory");
+                    WD_WAIT_VM_N(A * NPC);
                 else if (A == 2 && rem == 1)
-                    asm volatile("s_waitcnt vmcnt(%0)" : : "n"(NPC) : "memory");
+                    WD_WAIT_VM_N(NPC);
                 else
-                    asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
+                    WD_WAIT_VM0();
             } else {
                 wait_vmcnt((min(ti + ahead_max, n_tl) - ti - 1) * n_pc);
             }
+            // (the control: tile ti + ahead_max asked for one window early - into the window this tile is about to be compared in)
+            WD_DENSE_CONTROL(early_issue, if (ti + ahead_max < n_tl) issue_sym(tile + ahead_max, buf));
             csig = *(const uint32_t *)((const char *)(s_win + buf * a.win_dwords + lane) + own_off);
         }
         const bool valid = (f_cur & 1u) != 0 && !empty;                    // :236-237
@@ -1248,8 +1288,8 @@ __global__ __launch_bounds__(kBlock) void k_dense_pairs_win(DenseArgs a)
             const char *win_l = (const char *)(s_win + (SYM ? buf : ti % kWinBufs) * a.win_dwords + lane);    // this lane's column
             // (the tables are the same for every tile: opaque, or the compiler reads all lanes out
             // once, before the tile loop, and keeps them in spilled scalar registers)
-            asm volatile("" : "+v"(off_b0), "+v"(off_b1), "+s"(Ku));
-            asm volatile("" : "+v"(dl_0), "+v"(dl_1), "+v"(lev_v), "+v"(mk[0]), "+v"(mk[1]), "+v"(mk[2]), "+v"(mk[3]));
+            WD_PIN("+v"(off_b0), "+v"(off_b1), "+s"(Ku));
+            WD_PIN("+v"(dl_0), "+v"(dl_1), "+v"(lev_v), "+v"(mk[0]), "+v"(mk[1]), "+v"(mk[2]), "+v"(mk[3]));
             // fully unrolled over chunks of 8 elements, so that every lane select below is an
             // immediate: per element one v_readlane, one v_add, one ds_read_b32 and the compare.
             // (Elements past the union's end read the window's first dwords, and membership is only
@@ -1339,12 +1379,12 @@ __global__ __launch_bounds__(kBlock) void k_dense_pairs_win(DenseArgs a)
             if (ti + ahead_max < n_tl)
                 issue_sym(tile + ahead_max, buf + ahead_max >= n_bufs ? buf + ahead_max - n_bufs : buf + ahead_max);
         } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            WD_WAIT_VM0();
             f_nxt = f_ld;
             sig_nxt = sig_ld;
             // (the copies happen HERE: left alone the compiler moves them to the top of the next iteration,
             // behind the loads issued below, and waits for those before the compare)
-            asm volatile("" : "+v"(f_nxt), "+v"(sig_nxt));
+            WD_PIN("+v"(f_nxt), "+v"(sig_nxt));
             if (ti + 2 < n_tl)
                 issue(tile + 2, ti % kWinBufs);
         }
@@ -1357,6 +1397,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_pairs_win(DenseArgs a)
         if (lane == 0)
             s_nq[ti] = n_q <= (uint32_t)a.q_per ? n_q : 0xFFFFFFFFu;
         if (n_q > (uint32_t)a.q_per) {
+            WD_DENSE_NOTE(overflow_win);
             // More survivors than the region holds (low-diversity reads).  Levenshtein: leave the
             // whole group to k_dense_verify, which then needs the packed rows of all its wells;
             // otherwise finish every pair of this group here, one lane per target, cycle by cycle.
@@ -1410,6 +1451,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_pairs_win(DenseArgs a)
     // ---- every tile's survivors -> this group's regions of the global queue.  The Hamming family
     // marks the survivors' wells (they get packed rows) right here; Levenshtein survivors first pass
     // k_dense_mark's exact test ----
+    WD_LOCKSTEP();
     for (int ti = 0; ti < n_tl; ti++) {
         const uint32_t n_q = s_nq[ti];
         if (n_q == 0xFFFFFFFFu)
@@ -1443,7 +1485,7 @@ constexpr int kDenseU = 4;            // neighbours per step of the gather pipel
 template <int MODE, bool IDX16, bool SYM>
 __global__ __launch_bounds__(kBlock) void k_dense_pairs(DenseArgs a)
 {
-    extern __shared__ uint32_t s_dyn[];                  // per wave: kWinBufs windows, then the survivor queue
+    WD_DYNAMIC_LDS(s_dyn);                               // per wave: kWinBufs windows, then the survivor queue
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int levels = a.levels;
@@ -1530,7 +1572,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_pairs(DenseArgs a)
         sig_ld = sg[c];
     };
     issue(tile0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    WD_WAIT_VM0();
     uint32_t f_cur = f_ld, csig = sig_ld;
     if (n_tl > 1)
         issue(tile0 + 1, 1);
@@ -1614,7 +1656,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_pairs(DenseArgs a)
                     i2[u] = ld_idx(2 * U + u);
                 }
                 // everything loaded so far is consumed here, so that no wait for it lands inside the loop
-                asm volatile("" : "+v"(csig));
+                WD_PIN("+v"(csig));
 #pragma unroll
                 for (int u = 0; u < U; u++)
                     s0[u] = sg[i0[u]];
@@ -1634,7 +1676,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_pairs(DenseArgs a)
         }
 
         // ---- the next tile's inputs have landed; start the loads of the one after ----
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        WD_WAIT_VM0();
         const uint32_t f_nxt = f_ld, sig_nxt = sig_ld;
         if (ti + 2 < n_tl)
             issue(tile + 2, ti % kWinBufs);
@@ -1662,6 +1704,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_pairs(DenseArgs a)
                     a.cand[0] = 1u;
             }
         } else if (MODE == 2) {
+            WD_DENSE_NOTE(overflow_gather);
             // More survivors than the region holds (low-diversity reads): leave the whole group to
             // k_dense_verify, which then needs the packed rows of all its wells
             if (lane == 0) {
@@ -1677,6 +1720,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_pairs(DenseArgs a)
         } else {
             // ... or drop the queue and finish every pair of this group here, one lane per target,
             // cycle by cycle
+            WD_DENSE_NOTE(overflow_gather);
             if (lane == 0)
                 a.q_cnt[region] = 0;
             gsig sgx = (gsig)(a.sig + (size_t)tile * a.sig_stride);             // the exact signatures
@@ -1732,6 +1776,7 @@ struct RegionWalk {
         before = inc - cnt;
         total = (uint32_t)__shfl((int)inc, kWave - 1);
         s_pre[lane] = before;
+        WD_LOCKSTEP();
     }
     // region (0..63) and index within it of flattened entry e < total
     __device__ inline void locate(uint32_t e, int &r, uint32_t &j) const

@@ -20,18 +20,7 @@ namespace wd {
 // Group bases of the transposed neighbour table from host-side ring offsets (row = levels+1).
 void set_group_bases(wd_ctx *ctx, const int32_t *lvl_off, int T, int levels)
 {
-    const size_t row = (size_t)levels + 1;
-    const int groups = (T + kWave - 1) / kWave;
-    ctx->h_gbase.assign((size_t)groups + 1, 0);
-    long long pos = 0;
-    for (int g = 0; g < groups; g++) {
-        int kmax = 1;                                  // at least one row so min(q, gk-1) is valid
-        for (int t = g * kWave; t < std::min(T, (g + 1) * kWave); t++)
-            kmax = std::max(kmax, lvl_off[(size_t)t * row + levels] - lvl_off[(size_t)t * row]);
-        ctx->h_gbase[g] = pos;
-        pos += (long long)kmax * kWave;
-    }
-    ctx->h_gbase[groups] = pos;
+    dense_group_bases(lvl_off, T, levels, ctx->h_gbase);      // (dense_launch.inc)
     drop_dense_tables(ctx);
 }
 
@@ -124,8 +113,8 @@ int ensure_dense_tables(wd_ctx *ctx)
             ctx->dense_sym_on = bad == 0;
             ctx->centre0 = c0;
         }
-        const int64_t kpad = std::min<int64_t>(kWinMaxK, (2 * ctx->k_max + 8 + 31) & ~(int64_t)31);
-        if (ctx->k_max >= 1 && ctx->k_max <= kpad) {
+        const int64_t kpad = dense_kpad(ctx->k_max);       // (0: no window tables for these targets)
+        if (kpad > 0) {
             ctx->win_kpad = (int)kpad;
             WD_HIP(ctx, hipMalloc((void **)&ctx->d_ginfo, (size_t)groups * sizeof(int32_t)));
             WD_HIP(ctx, hipMalloc((void **)&ctx->d_uoff, (size_t)groups * kpad * sizeof(uint16_t)));
@@ -141,7 +130,7 @@ int ensure_dense_tables(wd_ctx *ctx)
                                ctx->d_wfull);
             WD_HIP(ctx, hipMemcpyAsync(flags, ctx->d_tblflags, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream));
             WD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            ctx->win_dwords = (int)((flags[1] + kWave - 1) / kWave * kWave);     // whole pieces of 64 dwords
+            ctx->win_dwords = dense_win_dwords_of(flags[1]);                     // whole pieces of 64 dwords
         }
     }
     WD_HIP(ctx, hipGetLastError());
@@ -163,13 +152,7 @@ int ensure_dense_tables(wd_ctx *ctx)
         // well a centre that is ONE block - the last, partial group - and the launch over all 16 834 cost
         // 29 us per 8 tiles to find it)
         std::vector<int32_t> pb;
-        for (int b = 0; b * kWaves < groups; b++) {
-            bool any = false;
-            for (int w = 0; w < kWaves && b * kWaves + w < groups; w++)
-                any = any || ginfo[(size_t)(b * kWaves + w)] == 0;
-            if (any)
-                pb.push_back(b);
-        }
+        dense_pblocks(ginfo.data(), groups, pb);
         (void)hipFree(ctx->d_pblocks);
         ctx->d_pblocks = nullptr;
         ctx->n_pblocks = (int)pb.size();
@@ -205,11 +188,7 @@ bool dense_rows_reserve(wd_ctx *ctx, int n_tiles, int64_t N)
 // one compare-stage wave walks; the whole scan when the overlap is off.
 int dense_part_size(const wd_ctx *ctx, int n_tiles, int tile_chunk)
 {
-    if (!ctx->dense_overlap || n_tiles < 2)
-        return std::max(1, n_tiles);
-    if (ctx->dense_part_tiles > 0)
-        return std::min(ctx->dense_part_tiles, n_tiles);
-    return n_tiles >= 2 * tile_chunk ? tile_chunk : (n_tiles + 1) / 2;
+    return dense_part_tiles_of(ctx->dense_overlap != 0, ctx->dense_part_tiles, n_tiles, tile_chunk);
 }
 
 // The dense path of wd_scan_async (scan_dense.inc): signatures, pairs, verify, reduce.
@@ -277,42 +256,27 @@ int launch_dense(wd_ctx *ctx, const ScanArgs &a, int n_tiles, int64_t N, bool st
     d.strided = strided ? 1 : 0;
     d.check_empty = a.check_empty;
     d.log_hits = a.log_hits;
-    d.sig_stride = (N + 127) & ~(long long)127;
-    d.partial_stride = ((1 + 5 * a.levels) + 15) & ~15;              // whole 128-byte lines per slot
-    d.mask_stride = (((long long)a.T + 3) / 4 + 31) & ~31ll;
-    // survivors per group of 64 targets: on diverse reads almost nobody passes 10 cycles (36 x
-    // P(<= 2 mismatches in 10) = 0.015 per target; ~2 per group for Levenshtein <= 2), so the
-    // region holds mostly duplicate pairs; what does not fit is finished inside k_dense_pairs (or,
-    // for Levenshtein, by k_dense_verify): a speed knob, not a limit
-    const long long n_groups = (a.T + kWave - 1) / kWave;
-    long long q_per = ctx->dense_queue_cap > 0 ? ctx->dense_queue_cap : (lev2 ? 32 : 16);
-    // LDS of a k_dense_pairs wave: its signature windows, then 8 bytes per queue entry
-    q_per = std::max<long long>(1, std::min<long long>(q_per, kWave));      // one queue entry per lane at most
-    d.q_per = (int)q_per;
-    // (the one-ended compare keeps the windows of three tiles in flight while LDS lets five workgroups share a CU)
-    d.win_bufs = kWinBufs;
-    int npc = 0;                                        // pieces of 64 signatures per window, if the kernel is built for that many
-    if (d.sym) {
-        for (d.win_bufs = kWinBufsSym; d.win_bufs > kWinBufs; d.win_bufs--)
-            if ((size_t)kWaves * ((size_t)d.win_bufs * d.win_dwords * 4 + 4 * ((size_t)tile_chunk * (2 * q_per + 1) + 1)) <= 32 * 1024)
-                break;
-        if (d.win_bufs == kWinBufsSym && d.ginfo)
-            for (int cand : {4, 5, 6, 8})
-                if (!npc && d.win_dwords <= cand * kWave &&
-                    (size_t)kWaves * ((size_t)d.win_bufs * cand * kWave * 4 + 4 * ((size_t)tile_chunk * (2 * q_per + 1) + 1)) <= 32 * 1024)
-                    npc = cand;
-        if (npc)
-            d.win_dwords = npc * kWave;
-    }
-    const long long win_bytes = (long long)d.win_bufs * d.win_dwords * sizeof(uint32_t);
-    d.mw_stride = (((N + 31) / 32) + kMarkBlock - 1) / kMarkBlock * kMarkBlock;
+    // strides, the survivor queue's size, the LDS windows per wave and the kernel's piece count: dense_launch.inc,
+    // which the CPU emulation of the chain (tools/scan_dense_emu.cpp) launches by too
+    const DenseShape shp = dense_shape(N, a.T, a.levels, tile_chunk, ctx->dense_queue_cap, lev2, d.sym != 0, d.ginfo != nullptr,
+                                       ctx->win_dwords);
+    d.sig_stride = shp.sig_stride;
+    d.partial_stride = shp.partial_stride;
+    d.mask_stride = shp.mask_stride;
+    const long long n_groups = shp.n_groups;
+    const long long q_per = shp.q_per;
+    d.q_per = shp.q_per;
+    d.win_bufs = shp.win_bufs;
+    const int npc = shp.npc;                            // pieces of 64 signatures per window, if the kernel is built for that many
+    d.win_dwords = shp.win_dwords;
+    d.mw_stride = shp.mw_stride;
     // scratch of ONE part (the largest); set s of a buffer starts s parts in
     const size_t sig_words = (size_t)d.sig_stride * part * ((lev2 || a.k > 0) ? 2 : 1);
     const size_t mark_words = (size_t)part * d.mw_stride;
     const size_t part_need = (size_t)part * kDenseSlots * d.partial_stride;
     const size_t mask_need = (size_t)part * d.mask_stride;
     const size_t regions = (size_t)part * (size_t)n_groups;
-    const size_t cand_words = (kDenseSlots + 1 + 31) & ~(size_t)31;
+    const size_t cand_words = shp.cand_words;
     if ((rc = dense_reserve(ctx, ctx->d_sig, ctx->sig_cap, sig_words * n_sets, "signature planes")) ||
         (rc = dense_reserve(ctx, ctx->d_partial, ctx->partial_cap, part_need * n_sets, "counter slots")) ||
         (rc = dense_reserve(ctx, ctx->d_mask, ctx->mask_cap, mask_need * n_sets, "hit masks")) ||
@@ -341,8 +305,7 @@ int launch_dense(wd_ctx *ctx, const ScanArgs &a, int n_tiles, int64_t N, bool st
     for (size_t i = 0; i < n_plane_ptrs && aligned4; i++)
         aligned4 = ((uintptr_t)ctx->h_tbl[i] & 3u) == 0;
     const int pmode = lev2 ? 2 : (a.k == 0 ? 0 : 1);
-    const unsigned mark_blocks = (unsigned)((n_groups + kWave * kWaves - 1) / (kWave * kWaves));
-    const long long dense_bpt = (a.T + kBlock - 1) / kBlock;
+    const unsigned mark_blocks = shp.mark_blocks;
     // st: the compare stage's stream, sp: the pack stage's
     hipStream_t st = n_parts > 1 ? ctx->dense_hi : ctx->stream, sp = n_parts > 1 ? ctx->dense_lo : ctx->stream;
     if (n_parts > 1) {
@@ -354,7 +317,10 @@ int launch_dense(wd_ctx *ctx, const ScanArgs &a, int n_tiles, int64_t N, bool st
         const int t0 = c * part, nt = std::min(part, n_tiles - t0), set = c & 1;
         if (c >= 2)                                 // the scratch set is free when part c - 2 has been verified
             WD_HIP(ctx, hipStreamWaitEvent(st, ctx->dense_ev_pack[set], 0));
-        const int tc = std::max(1, std::min(tile_chunk, nt));
+        d.pblocks = d.ginfo ? ctx->d_pblocks : nullptr;
+        d.n_pblocks = d.ginfo ? ctx->n_pblocks : 0;
+        const DensePart prt = dense_part(shp, N, a.T, nt, tile_chunk, d.n_pblocks);
+        const int tc = prt.tc;
         d.planes = a.planes + (strided ? (size_t)t0 : (size_t)t0 * a.L);
         d.filter = a.filter + t0;
         d.out_per_target = a.out_per_target ? a.out_per_target + (size_t)t0 * a.T * a.levels : nullptr;
@@ -374,13 +340,11 @@ int launch_dense(wd_ctx *ctx, const ScanArgs &a, int n_tiles, int64_t N, bool st
         d.cand = ctx->d_cand + cand_words * set;
         d.rows = want_rows ? ctx->d_rows + (size_t)part * (size_t)N * kRowGroups * set : nullptr;
         // (k_dense_sig clears the part's scratch: dense_clear_scratch)
-        const dim3 grid((unsigned)((long long)kXcds * ((dense_bpt + kXcds - 1) / kXcds) * ((nt + tc - 1) / tc)));
-        const dim3 grid4((unsigned)((N + 4ll * kBlock - 1) / (4ll * kBlock)), (unsigned)nt);
-        const dim3 grid1((unsigned)((N + kBlock - 1) / kBlock), (unsigned)nt);
+        const dim3 grid(prt.pairs);
+        const dim3 grid4(prt.wells4, (unsigned)nt);
+        const dim3 grid1(prt.wells1, (unsigned)nt);
         // the gather kernel: over the listed target blocks only, when the window kernel takes the rest
-        d.pblocks = d.ginfo ? ctx->d_pblocks : nullptr;
-        d.n_pblocks = d.ginfo ? ctx->n_pblocks : 0;
-        const dim3 pgrid = d.n_pblocks > 0 ? dim3((unsigned)((long long)d.n_pblocks * ((nt + tc - 1) / tc))) : grid;
+        const dim3 pgrid(prt.pairs_listed);
         if (aligned4 && strided)
             hipLaunchKernelGGL((k_dense_sig<true, true>), grid4, dim3(kBlock), 0, st, d);
         else if (aligned4)
@@ -390,9 +354,8 @@ int launch_dense(wd_ctx *ctx, const ScanArgs &a, int n_tiles, int64_t N, bool st
         else
             hipLaunchKernelGGL((k_dense_sig<false, false>), grid1, dim3(kBlock), 0, st, d);
         // LDS of a compare-stage wave: its windows, one queue per tile of the chunk, their counts
-        const size_t q_lds = (size_t)kWaves * ((size_t)win_bytes + 4 * ((size_t)tc * (2 * d.q_per + 1) + (tc & 1)));
-        hipLaunchKernelGGL(k_dense_counts, dim3((unsigned)((a.T + 4 * kBlock - 1) / (4 * kBlock)), (unsigned)((nt + tc - 1) / tc)),
-                           dim3(kBlock), 0, st, d);
+        const size_t q_lds = prt.q_lds;
+        hipLaunchKernelGGL(k_dense_counts, dim3(prt.counts_x, prt.chunks), dim3(kBlock), 0, st, d);
 #define WD_LAUNCH_PAIRS(MODE, SYM)                                                                              \
     do {                                                                                                        \
         if (d.ginfo)                                                                                            \
@@ -446,16 +409,13 @@ int launch_dense(wd_ctx *ctx, const ScanArgs &a, int n_tiles, int64_t N, bool st
             WD_HIP(ctx, hipStreamWaitEvent(sp, ctx->dense_ev_cmp[set], 0));
         }
         if (d.rows) {
-            hipLaunchKernelGGL(k_dense_rank_words, dim3((unsigned)(d.mw_stride / kMarkBlock), (unsigned)nt), dim3(kMarkBlock), 0, sp, d);
-            hipLaunchKernelGGL(k_dense_rank_blocks, dim3((unsigned)nt), dim3(1024), 0, sp, d);
+            hipLaunchKernelGGL(k_dense_rank_words, dim3(prt.rank_words, (unsigned)nt), dim3(kMarkBlock), 0, sp, d);
+            hipLaunchKernelGGL(k_dense_rank_blocks, dim3((unsigned)nt), dim3(kRankBlock), 0, sp, d);
             // with a compare stage beside it the pack kernel gets a bounded footprint: dense_pack_blocks
             // workgroups in all (they walk their tiles with a stride), not one per kBlock * VEC wells
             dim3 pg4 = grid4, pg1 = grid1;
-            if (n_parts > 1 && ctx->dense_pack_blocks > 0) {
-                const unsigned per_tile = (unsigned)std::max(1, ctx->dense_pack_blocks / nt);
-                pg4.x = std::min(pg4.x, per_tile);
-                pg1.x = std::min(pg1.x, per_tile);
-            }
+            pg4.x = dense_pack_grid_x(pg4.x, n_parts > 1, ctx->dense_pack_blocks, nt);
+            pg1.x = dense_pack_grid_x(pg1.x, n_parts > 1, ctx->dense_pack_blocks, nt);
             if (aligned4 && strided && ctx->dense_nt)
                 hipLaunchKernelGGL((k_dense_pack<4, true, true>), pg4, dim3(kBlock), 0, sp, d);
             else if (aligned4 && strided)
@@ -467,7 +427,7 @@ int launch_dense(wd_ctx *ctx, const ScanArgs &a, int n_tiles, int64_t N, bool st
             else
                 hipLaunchKernelGGL((k_dense_pack<1, false>), pg1, dim3(kBlock), 0, sp, d);
         }
-        const dim3 vgrid(kXcds * ((mark_blocks + kXcds - 1) / kXcds), (unsigned)nt);
+        const dim3 vgrid(prt.verify_x, (unsigned)nt);
         if (strided)
             hipLaunchKernelGGL((k_dense_verify<true>), vgrid, dim3(kBlock), 0, sp, d);
         else

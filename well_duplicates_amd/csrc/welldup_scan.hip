@@ -26,6 +26,7 @@ namespace {
 #include "scan_sequential.inc"
 #include "scan_lev_generic.inc"
 #include "gen_rings.inc"
+#include "dense_launch.inc"                // (dense_tile_chunk_of: the dense path's launch arithmetic, free of HIP)
 
 // Batch shapes (cycles read unconditionally, then per conditional batch).  The Hamming family
 // is instantiated for a few shapes so they can be tuned; the banded edit-distance family
@@ -373,7 +374,7 @@ try {
                           levels <= 8 && kk <= 2 && kk >= 0 &&    // levels: 8-bit hit masks
                           n_tiles <= 65535;                        // tiles ride in gridDim.y
     bool use_dense = dense_ok && (ctx->dense_kernel == 1 || (ctx->dense_kernel < 0 && ctx->T >= 65536));
-    const int tile_chunk = std::max(1, std::min({ctx->dense_tile_chunk, n_tiles, 16}));    // (LDS: one survivor queue per tile)
+    const int tile_chunk = dense_tile_chunk_of(ctx->dense_tile_chunk, n_tiles);            // (LDS: one survivor queue per tile)
     if (use_dense && lev2 && L > kSigCycles) {
         // rows for the parts in flight (two scratch sets), not for the whole scan
         const int part = dense_part_size(ctx, n_tiles, tile_chunk);
