@@ -21,6 +21,7 @@ K_PASS, K_MAX_PASSES, K_QCAP = sr.K_PASS, sr.K_MAX_PASSES, sr.K_QCAP
 K_FINISH_IN_PLACE, K_FINISH_ALL_MAX = sr.K_FINISH_IN_PLACE, sr.K_FINISH_ALL_MAX
 INVALID = 0xFFFFFFFF                          # WD_INVALID_TARGET
 FAMILIES, LAYOUTS = ("ham", "lev2"), ("ptr", "plane", "il")
+ALL_FAMILIES = FAMILIES + ("lev",)            # "lev": Levenshtein <= k by the banded DP - tests/levk_cases.py's, not a family of cases()
 # slots per target at the pass boundaries (127 a pass, lane 63 of the second slot shadows the centre)
 K_EDGES = (1, 63, 64, 65, 126, 127, 128, 253, 254, 255, 381, 382, 507, 508)
 
@@ -45,7 +46,7 @@ class Case:
                  hit_cap=1 << 20, check_empty=False, tags=()):
         """lists: per target (centre, [neighbour wells], level cuts [levels + 1] into them); tiles: [(planes, filt)]"""
         self.name, self.fam, self.layout, self.k, self.L, self.tpb, self.levels, self.n = name, fam, layout, k, L, tpb, levels, n
-        self.mode = 2 if fam == "lev2" else (0 if k == 0 else 1)
+        self.mode = 2 if fam in ("lev2", "lev") else (0 if k == 0 else 1)
         self.queue_first, self.sort, self.per_target, self.hit_cap, self.check_empty = queue_first, sort, per_target, hit_cap, check_empty
         self.tags = set(tags)
         self.kk = min(k, L)                   # what the kernel is given: wd_scan_async caps the threshold at the read's length
@@ -86,7 +87,7 @@ def truth(case):
     empty = (np.diff(case.lvl_off, axis=1) <= 0).any(axis=1)
     slots = np.arange(case.nbr.shape[0])
     tgt = np.searchsorted(case.lvl_off[:, 0], slots, side="right") - 1
-    out_tile, out_pt, hits, status = [], [], [], 0
+    out_tile, out_pt, hits, dists, status = [], [], [], [], 0
     for i, (planes, filt) in enumerate(case.tiles):
         f = filt
         if case.check_empty and empty.any():
@@ -104,8 +105,9 @@ def truth(case):
         out_pt.append(np.where(valid[:, None] == 1, dups, -1).astype(np.int64) & 0xFFFFFFFF)
         ok = (valid[tgt] == 1) & (dist <= (0 if case.mode == 0 else case.k))
         hits.append(np.stack([np.full(ok.sum(), i), tgt[ok], slots[ok], dist[ok]], axis=1))
+        dists.append(dist)                    # (every pair's, per tile; -1 where the centre is invalid)
     case._truth = dict(out_tile=np.array(out_tile, dtype=np.int64), out_pt=np.array(out_pt).astype(np.uint32),
-                       hits=np.concatenate(hits).astype(np.int32), status=status)
+                       hits=np.concatenate(hits).astype(np.int32), status=status, dist=dists)
     return case._truth
 
 
@@ -115,7 +117,7 @@ def write_case(path, case, line_pairs=0, extra=()):
     t = truth(case)
     centre, lvl_off, perm = case.view()
     extra = np.asarray(extra, dtype="<i4")
-    head = np.array([0x31435153, FAMILIES.index(case.fam), LAYOUTS.index(case.layout), case.B1, case.n, len(case.tiles), case.T,
+    head = np.array([0x31435153, ALL_FAMILIES.index(case.fam), LAYOUTS.index(case.layout), case.B1, case.n, len(case.tiles), case.T,
                      case.levels, case.L, case.kk, case.tpb, perm is not None, case.per_target, case.check_empty, case.hit_cap,
                      t["hits"].shape[0], case.nbr.shape[0], t["status"], line_pairs, extra.shape[0]], dtype="<i4")
     with open(path, "wb") as fh:

@@ -24,8 +24,8 @@
 //
 // Instantiated: what the launchers can launch for the two default families - k_scan_q<false|true, 1..8, 0, 1>,
 // <true, 4, 0, 4> (equality / Hamming), <false|true, 4|5|6, kLev2Closed, 1> and <true, 8, kLev2Closed, 4> (Levenshtein
-// <= 2 by the closed form).  The banded DP (LEVH 1..3) is out of scope: its queue entries are 16 bytes and its state
-// a different one; nothing here says anything about it.
+// <= 2 by the closed form).  The banded DP (LEVH 1..3, 16-byte queue entries) runs in tools/scan_lev_emu.cpp, with the two
+// other kernels of Levenshtein <= k.
 //
 // The cases are not made here: tests/test_scanq_emu.py writes each case of tests/scanq_cases.py into a file, and this
 // program takes the files as its arguments (tools/scan_emu_common.h says what a file holds; the sibling,

@@ -13,7 +13,7 @@ __host__ __device__ inline size_t lev_generic_lds_bytes(int L, int H)
 template <bool STRIDED>
 __global__ __launch_bounds__(kWave) void k_scan_lev_generic(ScanArgs a, int H)
 {
-    extern __shared__ uint32_t smem[];
+    WD_DYNAMIC_LDS(smem);               // (device_common.inc: lev_generic_lds_bytes(L, H) bytes, the launch's figure)
     const int lane = threadIdx.x;
     const int levels = a.levels;
     const int L = a.L;

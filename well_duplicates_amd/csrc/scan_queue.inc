@@ -305,6 +305,9 @@ __host__ __device__ inline int scan_q_lds_dwords(int levels, int tpb, int entry_
 // Entry = {well index, target << 24 | slot, state lo, state hi}.  State of LevState<H>, H <= 3
 // (k <= 7, values <= 8): W = 2H+1 band cells of 4 bits, the last W well codes (3 bits each)
 // and the last H+1 centre codes - 28 + 21 + 12 = 61 bits.
+#ifndef WD_LEV_CELL_MASK
+#define WD_LEV_CELL_MASK 15         // (a control build of tools/scan_lev_emu.cpp keeps three bits, to show that its test notices)
+#endif
 template <int H>
 __device__ inline uint64_t lev_pack(const LevState<H> &s, uint64_t ch)
 {
@@ -312,7 +315,7 @@ __device__ inline uint64_t lev_pack(const LevState<H> &s, uint64_t ch)
     uint64_t pk = 0;
 #pragma unroll
     for (int d = 0; d < W; d++)
-        pk |= (uint64_t)(s.r[d] & 15) << (4 * d);
+        pk |= (uint64_t)(s.r[d] & WD_LEV_CELL_MASK) << (4 * d);
     pk |= (s.wh & ((1ull << (3 * W)) - 1)) << 28;
     pk |= (ch & ((1ull << (3 * (H + 1))) - 1)) << 49;
     return pk;
@@ -335,6 +338,7 @@ template <bool STRIDED, int H, int WS = 1>
 __device__ inline void q_drain_lev(const QEnv &v, uint4 *q_a, uint4 *q_b, int &qn, int j0, int lane)
 {
     q_wave_sync();
+    WD_Q_CHECK(drain, qn, qn >= 0 && qn <= kQCap);
     const int L = v.L, k = v.k, cap = v.k + 1;
     constexpr int NB = 8;
     int nb = WS == 4 ? 4 : 1;                          // cycles of the first drain round (then 2, 4, 8, 8 ...): most survivors of
@@ -393,6 +397,7 @@ __device__ inline void q_drain_lev(const QEnv &v, uint4 *q_a, uint4 *q_b, int &q
                     qb[pos] = make_uint4(idx, ent.y, (uint32_t)pk, (uint32_t)(pk >> 32));
                 }
                 n2 += __popcll(m);
+                WD_Q_CHECK(compact, n2, n2 <= n);
             }
         }
         q_wave_sync();
@@ -916,8 +921,11 @@ __global__ __launch_bounds__(kBlock, LEVH > 0 ? 4 : (WS == 4 ? WD_Q_OCC_IL : 6))
                         const uint64_t m0 = __ballot(al0), m1 = __ballot(al1);
                         if (m0 | m1) {
                             const int n0 = __popcll(m0), n1 = __popcll(m1);
-                            if (qn + n0 + n1 > kQCap)
+                            if (qn + n0 + n1 > kQCap) {
+                                WD_Q_CHECK(drain_mid, qn, qn <= kQCap);
                                 q_drain_lev<STRIDED, (LEVH > 0 ? LEVH : 1), WS>(env, (uint4 *)q_a, (uint4 *)q_b, qn, B1, lane);
+                            }
+                            WD_Q_CHECK(push, qn + n0 + n1, qn + n0 + n1 <= kQCap);
                             if (al0) {
                                 const int pos = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32),
                                                          __builtin_amdgcn_mbcnt_lo((uint32_t)m0, 0u));
