@@ -55,6 +55,11 @@ rank takes every add of k_lt_spread) and the lane whose odd wells repeat their l
 the tie worst case; with `--capacity N` the selection there has to refine the root ids to the end, the longest it can
 be.  The histogram passes taken are printed, and the bytes a pass streams (8 per well) over the time of a pass against
 the pure read.
+`--adapter [NAME]` times LaneDups.adapter (the lane's duplication by insert length, include/welldup_laneadapter.h; E 1, O
+8) five times beside LaneDups.gc(0), the equality finish and a pure read of as many bytes as the pass reads - medians
+and spreads of five -, on three inputs: the planted lane, the `--equal` lane, and a lane of three tiles whose every
+read carries the adapter from a random cycle on (every search finds something).  Run it on the shipped library and,
+with WELLDUP_LIB, on a `tools/build_variant.py ladnaive tiledups -DWD_LAD_NAIVE=1` build: the code-by-code search.
 `--gc` times LaneDups.gc(0) (the lane's duplication against its reads' GC content, include/welldup_lanegc.h) per tile
 of the lane beside the equality finish, LaneDups.mismatches(0) and LaneDups.top(100) on the same batches and labels,
 and beside Scanner.stream_read_gbs over as many bytes as the pass reads - every packed row of the lane, label and
@@ -90,7 +95,7 @@ For per-kernel times run it under
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/lanedups_probe.py
 
 (the k_ld_* rows of the stats are this stage, k_li_* the index part, k_lm_* the mismatch pass, k_lg_* the distance pass,
-k_lq_* the quality part, k_ls_* the saturation pass, k_lt_* the top pass, k_lh_* the hops pass, k_lgc_* the GC pass,
+k_lq_* the quality part, k_ls_* the saturation pass, k_lt_* the top pass, k_lh_* the hops pass, k_lgc_* the GC pass, k_lad_* the adapter pass,
 k_lc_* the consensus pass and the gather of the UMI pass, k_lu_* the UMI pass, k_lk_* the keep pass, k_td_* the per-tile classes, k_dense_* the scan)."""
 import argparse
 import os
@@ -134,6 +139,9 @@ ap.add_argument("--capacity", type=int, default=0, metavar="C", help="the candid
 ap.add_argument("--gc", action="store_true",
                 help="also time LaneDups.gc(0) beside the equality finish, mismatches(0), top(100) and a pure read of as "
                      "many bytes (three inputs with --equal)")
+ap.add_argument("--adapter", nargs="?", const="truseq", default=None, metavar="NAME",
+                help="also time LaneDups.adapter (truseq, nextera, smallrna or 8..32 letters of ACGT; E 1, O 8) five times "
+                     "beside gc(0), the equality finish and a pure read of as many bytes (three inputs with --equal)")
 ap.add_argument("--consensus", action="store_true",
                 help="also time LaneDups.consensus(K, M) beside mismatches(K), the equality finish and a pure read of "
                      "label and members (needs --hamming; three inputs with --equal)")
@@ -349,6 +357,36 @@ def time_gc(acc, tiles_n, t_finish, what):
              t_g / t_read, t_m / tiles_n, t_t / tiles_n, t_finish / tiles_n))
 
 
+def time_adapter(acc, tiles_n, t_finish, what):
+    """LaneDups.adapter(codes, 1, 8) five times and LaneDups.gc(0) five times on the same labels, each after a first
+    call that pays for loading the kernels - the medians and the spread (max - min) of the five -, and a pure read of as
+    many bytes as the pass reads, from the accumulator's own workspace"""
+    from well_duplicates_amd.lane_passes import parse_adapter
+    name, codes = parse_adapter(a.adapter)
+    acc.adapter(codes, 1, 8)
+    runs = [clock(lambda: acc.adapter(codes, 1, 8)) for _ in range(5)]
+    acc.gc(0)
+    t_gs = sorted(clock(lambda: acc.gc(0))[1] for _ in range(5))
+    t_as = sorted(t for _, t in runs)
+    t_a, t_g = t_as[2], t_gs[2]
+    row, tiles, hist = runs[0][0]
+    nbytes = tiles_n * n * (4 * ((a.cycles + 9) // 10) + 8)
+    gbs = sc.stream_read_gbs(acc.d_ws, min(nbytes, acc.ws_bytes))
+    t_read = nbytes / gbs / 1e6
+    assert all((r[0] == row).all() and (r[1] == tiles).all() and (r[2] == hist).all() for r, _ in runs), "the runs differ"
+    assert row[0] == row[1:4].sum() == tiles[:, 0].sum() and (hist[:, :3].sum(axis=0) == row[1:4]).all() and \
+        (hist[:-1, :3].sum(axis=0) == row[4:7]).all() and hist[:, 3].sum() == row[2] + row[3] and \
+        tiles[:, 4].sum() == (np.arange(a.cycles) * hist[:-1, :3].sum(axis=1)).sum(), "the adapter rows do not add up"
+    print("%s: adapter %s, E 1, O 8: %d PF wells, %d single, %d roots, %d copies; with adapter %d, inexact %d, partial %d; "
+          "%d values of a taken" % (what, name, row[0], row[1], row[2], row[3], row[4:7].sum(), row[8], row[9],
+                                    int((hist[:-1, :3].sum(axis=1) > 0).sum())))
+    print("  %-22s %9.3f ms  (median of five, spread %.3f; %.4f ms per tile; %.1f MB per tile at %.0f GB/s; a pure read of as "
+          "many bytes: %.4f ms per tile at %.0f GB/s; adapter / read = %.2f; gc(0): %.4f ms per tile, median of five, spread "
+          "%.3f ms; adapter / gc = %.2f; the equality finish: %.4f)"
+          % ("lane adapter", t_a, t_as[-1] - t_as[0], t_a / tiles_n, nbytes / tiles_n / 1e6, nbytes / t_a / 1e6,
+             t_read / tiles_n, gbs, t_a / t_read, t_g / tiles_n, t_gs[-1] - t_gs[0], t_a / t_g, t_finish / tiles_n))
+
+
 def time_consensus(acc, tiles_n, t_finish, what):
     """LaneDups.consensus(K, M) and, on the same labels, LaneDups.mismatches(K), each after a first call that pays for
     loading the kernels; and a pure read of 8 bytes per well, from the accumulator's own workspace"""
@@ -402,6 +440,8 @@ if a.top:
     time_top(ld, max(1, a.tiles), t_fin, "the planted lane")
 if a.gc:
     time_gc(ld, max(1, a.tiles), t_fin, "the planted lane")
+if a.adapter:
+    time_adapter(ld, max(1, a.tiles), t_fin, "the planted lane")
 ld.close()
 if a.hamming:
     near, t_near = clock(lambda: ldn.finish(hamming=a.hamming))
@@ -556,6 +596,8 @@ if a.equal:
         time_top(eq, 3, e_fin, "every read equal, three tiles")
     if a.gc:
         time_gc(eq, 3, e_fin, "every read equal, three tiles")
+    if a.adapter:
+        time_adapter(eq, 3, e_fin, "every read equal, three tiles")
     if a.consensus:
         time_consensus(eq, 3, e_fin, "every read equal, three tiles")
     if a.quality:
@@ -648,6 +690,33 @@ if a.distance or a.saturation or a.top or a.gc:
     if a.gc:
         time_gc(nb, 3, n_fin, "every odd well a copy of its left neighbour, three tiles")
     nb.close()
+    three.free()
+if a.adapter:
+    # three tiles without planted copies whose every read carries the adapter from a random cycle on (as much as fits)
+    from well_duplicates_amd.lane_passes import parse_adapter
+    bare = synth.SynthSpec(seed=5, n_clusters=n, row=a.cols, plant_per_64k=0)
+    codes = np.array(parse_adapter(a.adapter)[1], dtype=np.uint8)
+    rng = np.random.default_rng(29)
+    three = TileBatch(sc, 3, a.cycles, n)
+    for s in range(3):
+        sc.h2d(three.filter_ptr(s), np.ones(n, dtype=np.uint8))
+        at = rng.integers(0, a.cycles - 8 + 1, n)
+        for c in range(a.cycles):
+            sc.synth_plane(three.plane_ptr(s, c), bare, 1, 1101 + s, c)
+            sc.synchronize()
+            plane = sc.d2h(three.plane_ptr(s, c), n, np.uint8).copy()
+            j = c - at
+            inside = (j >= 0) & (j < codes.size)
+            plane[inside] = codes[j[inside]] | 0x80
+            sc.h2d(three.plane_ptr(s, c), plane)
+    sc.synchronize()
+    ad = LaneDups(sc, n, 3, a.cycles)
+    ad.add(three, [0, 1, 2])
+    _, ad_fin = clock(lambda: ad.finish())
+    time_adapter(ad, 3, ad_fin, "every read with the adapter at a random cycle, three tiles")
+    got = ad.adapter(codes, 1, 8)[0]
+    assert got[4:7].sum() == got[0] == 3 * n, "a read is without its adapter"
+    ad.close()
     three.free()
 
 

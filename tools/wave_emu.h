@@ -1,5 +1,5 @@
 // wave_emu.h - what a kernel's source needs to run on the CPU as it stands (tools/lane_mismatch_emu.cpp,
-// tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp, tools/lane_hops_emu.cpp, tools/lane_gc_emu.cpp, tools/lane_consensus_emu.cpp, tools/lane_umi_emu.cpp, tools/lane_keep_emu.cpp,
+// tools/lane_distance_emu.cpp, tools/lane_quality_emu.cpp, tools/lane_saturation_emu.cpp, tools/lane_top_emu.cpp, tools/lane_hops_emu.cpp, tools/lane_gc_emu.cpp, tools/lane_adapter_emu.cpp, tools/lane_consensus_emu.cpp, tools/lane_umi_emu.cpp, tools/lane_keep_emu.cpp,
 // tools/lane_molecules_emu.cpp, tools/read_classes_emu.cpp, tools/near_emu.cpp, tools/dup_sets_emu.cpp, tools/lane_index_emu.cpp, tools/gen_rings_emu.cpp,
 // tools/scan_queue_emu.cpp, tools/scan_lines_emu.cpp, tools/scan_dense_emu.cpp, tools/scan_lev_emu.cpp): the 256 lanes of a
 // workgroup are fibers (ucontext) that a round-robin scheduler switches at the collectives - __syncthreads is a

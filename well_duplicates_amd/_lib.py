@@ -226,6 +226,19 @@ LANEGC_HIST_COLS = 4
 LANEGC_LANE_COLS = 8
 LANEGC_TILE_COLS = 5
 
+# name -> (restype, argtypes); every symbol include/welldup_laneadapter.h declares beyond those above
+LANEADAPTER_PROTOTYPES = {
+    "wd_lane_adapter_scratch": (_i, [_i, _i, ctypes.POINTER(_sz)]),
+    "wd_lane_adapter": (_i, [_vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+}
+LANEADAPTER_MIN_LEN = 8
+LANEADAPTER_MAX_LEN = 32
+LANEADAPTER_MAX_E = 3
+LANEADAPTER_MIN_OVERLAP = 3
+LANEADAPTER_HIST_COLS = 4
+LANEADAPTER_LANE_COLS = 10
+LANEADAPTER_TILE_COLS = 5
+
 # name -> (restype, argtypes); every symbol include/welldup_laneconsensus.h declares beyond those above
 LANECONSENSUS_PROTOTYPES = {
     "wd_lane_consensus_scratch": (_i, [_i, _i64, _i, ctypes.POINTER(_sz)]),
@@ -359,7 +372,7 @@ def unit_of_kernel(kernel: str) -> str:
         return "ingest"
     if kernel.startswith("k_sets"):
         return "sets"
-    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_", "k_ls_", "k_lt_", "k_lh_", "k_lgc_", "k_lc_", "k_lu_", "k_lk_")):
+    if kernel.startswith(("k_td_", "k_tn_", "k_ld_", "k_ln_", "k_li_", "k_lm_", "k_lg_", "k_lq_", "k_ls_", "k_lt_", "k_lh_", "k_lgc_", "k_lad_", "k_lc_", "k_lu_", "k_lk_")):
         return "tiledups"
     return "scan"
 
@@ -423,7 +436,8 @@ def load():
             list(LANEINDEX_PROTOTYPES.items()) + list(LANEMISMATCH_PROTOTYPES.items()) + \
             list(LANEDISTANCE_PROTOTYPES.items()) + list(LANEQUALITY_PROTOTYPES.items()) + \
             list(LANESATURATION_PROTOTYPES.items()) + list(LANETOP_PROTOTYPES.items()) + \
-            list(LANEHOPS_PROTOTYPES.items()) + list(LANEGC_PROTOTYPES.items()) + list(LANECONSENSUS_PROTOTYPES.items()) + \
+            list(LANEHOPS_PROTOTYPES.items()) + list(LANEGC_PROTOTYPES.items()) + list(LANEADAPTER_PROTOTYPES.items()) + \
+            list(LANECONSENSUS_PROTOTYPES.items()) + \
             list(LANEUMI_PROTOTYPES.items()) + list(LANEKEEP_PROTOTYPES.items()) + list(LANEMOLECULES_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res

@@ -26,6 +26,8 @@ Differences from the reference, all deliberate:
     --lane-dups-hamming, --lane-dups-index, --lane-dups-mismatches, --lane-dups-distance, --lane-dups-quality,
     --lane-dups-saturation, --lane-dups-top, --lane-dups-top-out, --lane-dups-hops, --lane-dups-hops-mismatches,
     --lane-dups-hops-out, --lane-dups-gc, --lane-dups-gc-bins, --lane-dups-gc-max-n, --lane-dups-gc-out,
+    --lane-dups-adapter, --lane-dups-adapter-mismatches, --lane-dups-adapter-min-overlap, --lane-dups-adapter-bins,
+    --lane-dups-adapter-dimer, --lane-dups-adapter-out,
     --lane-dups-consensus, --lane-dups-consensus-max-d, --lane-dups-consensus-max-family, --lane-dups-consensus-out,
     --lane-dups-umi, --lane-dups-umi-mismatches, --lane-dups-umi-max-family, --lane-dups-umi-out,
     --lane-dups-keep, --lane-dups-keep-min-q, --lane-dups-keep-out, --lane-dups-keep-umi;
@@ -60,6 +62,10 @@ Differences from the reference, all deliberate:
     --lane-dups-gc holds the duplication against the molecule: every PF read by its GC content and by what it is in
     its class or cluster - the distinct molecules, the duplication, the mean family size and the library size per GC
     bin, over every PF read and without an alignment (report.write_lane_gc);
+    --lane-dups-adapter NAME|SEQ holds the duplication against the insert length: every PF read by the position at
+    which it runs into the adapter, with mismatches and with partial overlaps at its end - the share of adapter dimers,
+    of reads that read through into the adapter, and the duplication of the short inserts against the rest
+    (report.write_lane_adapter);
     --lane-dups-consensus lets every family of three or more wells vote: the base most of its members call at a cycle
     is the molecule's, a member that disagrees made the error - the lane's error profile by cycle and by direction,
     G>T apart from T>G, which the comparison with a first well cannot give (report.write_lane_consensus);
@@ -87,7 +93,7 @@ import numpy as np
 
 from . import bcl as bcl_direct_reader
 from . import _lib, report, workload
-from .lane_passes import (DEFAULT_QUALITY_BINS, LANE_PASSES, check_cycle_ranges, check_options, dest,  # noqa: F401
+from .lane_passes import (ALL_PASSES, DEFAULT_QUALITY_BINS, LANE_PASSES, check_cycle_ranges, check_options, dest,  # noqa: F401
                           parse_quality_bins, resolve_passes, write_keep_filter, write_lane_keep_filters)
 from .report import LENGTH, TALLY, output_writer  # noqa: F401  (reference module surface)
 from .scanner import INVALID_TARGET, LaneDups, Scanner, TileBatch, compare_mode
@@ -353,6 +359,33 @@ def parse_args(argv=None):
     p.add_argument("--lane-dups-gc-out", default=None, metavar="FILE",
                    help="with --lane-dups-gc: also write a line per g to FILE, tab-separated: lane, gc, single, roots, "
                         "copies, family_wells")
+    p.add_argument("--lane-dups-adapter", default=None, metavar="NAME|SEQ",
+                   help="with --lane-dups: search every PF read of a lane for the adapter - truseq (AGATCGGAAGAGC), "
+                        "nextera (CTGTCTCTTATACACATCT), smallrna (TGGAATTCTCGG), or 8..32 letters of ACGT - at every "
+                        "position, and count the read by the first position that matches (its insert length when "
+                        "--cycles starts at the read's first cycle) and by what it is in its class (its cluster with "
+                        "--lane-dups-hamming); print, after the GC block, per bin of insert length and for the reads "
+                        "without adapter the distinct molecules, the reads, the duplication in the bin and against the "
+                        "lane's, the mean family size and the library size; then the share of reads with adapter and "
+                        "of adapter dimers and the duplication of dimers, of the other reads with adapter and of the "
+                        "reads without.  The scanned cycles must be one run of consecutive cycles")
+    p.add_argument("--lane-dups-adapter-mismatches", type=int, default=None, metavar="E",
+                   help="with --lane-dups-adapter: the mismatches allowed where the whole adapter fits, 0..3 (default "
+                        "1); where only o of its m bases fit before the read's end, floor(E * o / m)")
+    p.add_argument("--lane-dups-adapter-min-overlap", type=int, default=None, metavar="O",
+                   help="with --lane-dups-adapter: the fewest bases of the adapter that count as a match at the read's "
+                        "end, 3..the adapter's length (default 8, or the adapter's length if that is less)")
+    p.add_argument("--lane-dups-adapter-bins", type=int, default=None, metavar="B",
+                   help="with --lane-dups-adapter: the bins of insert length printed, %d..%d (default 10), of equal "
+                        "width over the scanned cycles: the bin of position a among L is min(B - 1, a * B // L)"
+                        % (report.LANE_ADAPTER_MIN_BINS, report.LANE_ADAPTER_MAX_BINS))
+    p.add_argument("--lane-dups-adapter-dimer", type=int, default=None, metavar="D",
+                   help="with --lane-dups-adapter: a read whose adapter begins at position D or before it is an adapter "
+                        "dimer (default 10)")
+    p.add_argument("--lane-dups-adapter-out", default=None, metavar="FILE",
+                   help="with --lane-dups-adapter: also write a line per position to FILE, tab-separated: lane, insert, "
+                        "single, roots, copies, family_wells, cumulative (the share of PF reads whose adapter begins at "
+                        "or before the position: the adapter content curve, exact)")
     p.add_argument("--lane-dups-consensus", action="store_true",
                    help="with --lane-dups: gather the wells of every class (every cluster with --lane-dups-hamming K) of "
                         "three or more wells, take the base that more than half of them call at a cycle for the "
@@ -420,7 +453,7 @@ def parse_args(argv=None):
                         "file>, the tile's filter file with the PF bit cleared on every dropped well.  Put in place of "
                         "the run directory's own files they make bcl2fastq or BCL Convert emit the deduplicated lane")
     args = p.parse_args(argv)
-    check_options(args, p.error)                # the passes after a lane's finish: lane_passes.LANE_PASSES
+    check_options(args, p.error)                # the passes after a lane's finish: lane_passes.ALL_PASSES
     if not args.coord_file and not args.all_wells:
         p.error("the following arguments are required: -f/--coord_file (or --all-wells)")
     if args.layout == "interleaved" and (args.all_wells or (args.edit_distance > 3 and not args.hamming)):
@@ -575,7 +608,7 @@ def lane_cluster_members(class_labels: np.ndarray, cluster_labels: np.ndarray):
 # check_lane_dups_fits' keywords and the flag each is reported under, in the order of the message's clauses: the
 # label stage's two, then every pass's own (keywords of one flag make one clause)
 _FIT_CLAUSES = (("scratch", "--lane-dups-hamming"), ("index", "--lane-dups-index")) + \
-    tuple(clause for p in LANE_PASSES for clause in p.fit)
+    tuple(clause for p in ALL_PASSES for clause in p.fit)
 
 
 def check_lane_dups_fits(need: int, free: int, tiles: int, wells: int, cycles: int, **parts):
@@ -1148,7 +1181,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                 # scan_lanes fills these, lane_done reads them
                 results = {"counts": {}, "logs": {}, "sets": {}, "members": {}, "tdups": {}, "tmembers": {},
                            "tnear": {}, "tnmembers": {}, "ldups": {}, "lmembers": {}, "lnear": {}, "lindex": {},
-                           "lmindex": {}, **{p.key: {} for p in LANE_PASSES}}
+                           "lmindex": {}, **{p.key: {} for p in ALL_PASSES}}
                 def lane_done(lane):
                     for t in dict(lane_tiles)[lane]:
                         c = results["counts"][(lane, t)]
@@ -1196,7 +1229,7 @@ def _main(args, log, wdist, rank, world, device, opener, early):
                         write_cluster_members(args.tile_dups_out, results["tnmembers"])
                     elif args.tile_dups_out:
                         write_set_members(args.tile_dups_out, results["tmembers"], column="class")
-                    for p in LANE_PASSES:
+                    for p in ALL_PASSES:
                         path = getattr(args, dest(p.out[0])) if p.out else None
                         if path:
                             with open(path, "w") as fh:

@@ -14,7 +14,7 @@
 // label only, and so do k_ls_min and k_ls_tally (lane_saturation.inc).  k_lt_hist, k_lt_collect, k_lt_spread and k_lt_rows
 // (lane_top.inc) read label, members and the rows.  k_lh_tally (lane_hops.inc) reads label and the index workspace's
 // key, which k_li_pack alone writes (lane_index.inc, wd_lane_index_add, which refuses after a finish).  k_lgc_tally
-// (lane_gc.inc) reads label, members and every row of the lane.  k_lc_reserve and k_lc_scatter (lane_consensus.inc) read
+// (lane_gc.inc) reads label, members and every row of the lane, and so does k_lad_tally (lane_adapter.inc).  k_lc_reserve and k_lc_scatter (lane_consensus.inc) read
 // label and members, k_lc_vote members and the rows of the voted families.  k_lk_score and k_lk_mark (lane_keep.inc)
 // read label, members and the quality rows - or, launched by wd_lane_keep_molecules, the caller's mol and molmem in
 // their places, which k_lu_pairs_mol and k_lu_group_mol (lane_umi.inc) wrote from label, members and the UMI keys.

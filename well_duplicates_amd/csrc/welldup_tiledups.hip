@@ -25,7 +25,9 @@
 // end, reads the labels alone: the lane's distinct reads against its depth of welldup_lanesaturation.h.
 // lane_top.inc, which lane_saturation.inc includes at its end, reads the labels, the members and the rows: the lane's
 // most frequent reads and their spread of welldup_lanetop.h.  lane_gc.inc (after lane_distance.inc) reads the labels, the members
-// and every row of the lane: its duplication against its reads' GC content of welldup_lanegc.h.  lane_consensus.inc (after
+// and every row of the lane: its duplication against its reads' GC content of welldup_lanegc.h.  lane_adapter.inc (after
+// it, with its piece loads) searches every row for the adapter: the duplication by insert length of
+// welldup_laneadapter.h.  lane_consensus.inc (after
 // it) gathers the members of every family and counts their calls against the family's vote: welldup_laneconsensus.h.
 // lane_umi.inc (after it) groups the wells of every family by their UMI read, packed by lane_index.inc's kernel and
 // gathered by lane_consensus.inc's: welldup_laneumi.h.  lane_keep.inc, which lane_top.inc includes at its end and
@@ -240,6 +242,7 @@ try {
 #include "lane_hops.inc"      // which libraries a lane's duplicate copies join (include/welldup_lanehops.h)
 #include "lane_distance.inc"  // how far apart a lane's duplicate copies lie (include/welldup_lanedistance.h)
 #include "lane_gc.inc"        // a lane's duplication against its reads' GC content (include/welldup_lanegc.h)
+#include "lane_adapter.inc"   // a lane's duplication by insert length (include/welldup_laneadapter.h)
 #include "lane_consensus.inc" // a lane's errors against its families' vote (include/welldup_laneconsensus.h)
 #include "lane_umi.inc"       // a lane's duplicates split by molecular identifier (include/welldup_laneumi.h)
 #include "lane_quality.inc"   // reported base quality against a lane's duplicate copies (include/welldup_lanequality.h)

@@ -1,8 +1,9 @@
 """The passes that run after a lane's finish, as one table: the Python counterpart of csrc/lane_pass.inc (DESIGN 5.20,
 5.20.1).
 
-Every --lane-dups-<pass> of count_well_duplicates is one LanePass entry of LANE_PASSES, in the order the passes run
-and print.  The CLI's option checks, its defaults, the device memory check, the calls after a lane's finish, the lane's
+Every --lane-dups-<pass> of count_well_duplicates is one LanePass entry of ALL_PASSES, in the order the passes run
+and print: LANE_PASSES, the ten passes up to --lane-dups-keep-umi in the order they were added, and the adapter pass,
+which runs and prints after the GC pass.  The CLI's option checks, its defaults, the device memory check, the calls after a lane's finish, the lane's
 blocks and the --...-out files all loop over this table; a pass is written down nowhere else in the driver.  The label
 stage - finish, the near finish, the members and the index finish - is not a pass: it stays code in scan_lanes.
 """
@@ -89,7 +90,7 @@ def check_cycle_ranges(error, flag, text, example, most):
 
 def check_options(args, error):
     """Every `needs`, then every range, then what is neither; error = ArgumentParser.error."""
-    options = [o for p in LANE_PASSES for o in p.options]
+    options = [o for p in ALL_PASSES for o in p.options]
     for o in options:
         for need in o.needs if given(args, o.flag) else ():
             any_of = (need,) if isinstance(need, str) else need
@@ -99,14 +100,14 @@ def check_options(args, error):
         value = getattr(args, dest(o.flag))
         if o.lo is not None and given(args, o.flag) and not (o.lo <= value and (o.hi is None or value <= o.hi)):
             error("%s takes %s, not %d" % (o.flag, o.takes or "%d..%d" % (o.lo, o.hi), value))
-    for p in LANE_PASSES:
+    for p in ALL_PASSES:
         if p.check is not None:
             p.check(args, error)
 
 
 def resolve_passes(args, run):
     """The passes a command line asks for, with their parameters: [(LanePass, params)] in the table's order."""
-    resolved = [(p, p.resolve(args, run)) for p in LANE_PASSES]
+    resolved = [(p, p.resolve(args, run)) for p in ALL_PASSES]
     return [(p, params) for p, params in resolved if params is not None]
 
 
@@ -229,6 +230,55 @@ def _resolve_gc(args, run):
 def _run_gc(ld, lc, p):
     """(max_n, bins): LaneDups.gc(max_n) -> LaneGCCounts."""
     return report.LaneGCCounts.from_rows(*ld.gc(p["max_n"]), lc.names, p["max_n"], p["bins"], lc.lane_near)
+
+
+ADAPTER_NAMES = {"truseq": "AGATCGGAAGAGC", "nextera": "CTGTCTCTTATACACATCT", "smallrna": "TGGAATTCTCGG"}
+
+
+def parse_adapter(text):
+    """--lane-dups-adapter NAME|SEQ -> (what the block calls it, its codes 0..3); ValueError lists the names."""
+    seq = ADAPTER_NAMES.get(text.lower(), text.upper())
+    if not (_lib.LANEADAPTER_MIN_LEN <= len(seq) <= _lib.LANEADAPTER_MAX_LEN and set(seq) <= set("ACGT")):
+        raise ValueError("%s, or %d..%d letters of ACGT, not %r" % (
+            ", ".join("%s (%s)" % item for item in ADAPTER_NAMES.items()), _lib.LANEADAPTER_MIN_LEN,
+            _lib.LANEADAPTER_MAX_LEN, text))
+    return (text.lower() if text.lower() in ADAPTER_NAMES else seq), ["ACGT".index(ch) for ch in seq]
+
+
+def _check_adapter(args, error):
+    if args.lane_dups_adapter is None:
+        return
+    try:
+        m = len(parse_adapter(args.lane_dups_adapter)[1])
+    except ValueError as e:
+        error("--lane-dups-adapter takes %s" % e)
+    if args.lane_dups_adapter_min_overlap is not None and args.lane_dups_adapter_min_overlap > m:
+        error("--lane-dups-adapter-min-overlap takes %d..%d, the adapter's length, not %d" % (
+            _lib.LANEADAPTER_MIN_OVERLAP, m, args.lane_dups_adapter_min_overlap))
+
+
+def _resolve_adapter(args, run):
+    if args.lane_dups_adapter is None:
+        return None
+    name, codes = parse_adapter(args.lane_dups_adapter)
+    cycles = list(run.cycle_list)
+    if any(b != a + 1 for a, b in zip(cycles, cycles[1:])):
+        raise ValueError("--lane-dups-adapter takes scanned cycles that are one ascending run of consecutive cycles (a "
+                         "position in a read that skips cycles is not an insert length), not --cycles %s" % args.cycles)
+    overlap = _first(args.lane_dups_adapter_min_overlap, min(8, len(codes)))
+    if overlap > len(cycles):
+        raise ValueError("--lane-dups-adapter-min-overlap takes %d..%d, the scanned cycles, not %d" % (
+            _lib.LANEADAPTER_MIN_OVERLAP, len(cycles), overlap))
+    return {"name": name, "codes": codes, "e": _first(args.lane_dups_adapter_mismatches, 1), "overlap": overlap,
+            "bins": args.lane_dups_adapter_bins or 10, "dimer": _first(args.lane_dups_adapter_dimer, 10)}
+
+
+def _run_adapter(ld, lc, p):
+    """(name, codes, E, O, bins, dimer): LaneDups.adapter(codes, E, O) -> LaneAdapterCounts, its positions numbered
+    from the first scanned cycle."""
+    return report.LaneAdapterCounts.from_rows(*ld.adapter(p["codes"], p["e"], p["overlap"]), lc.names, p["name"],
+                                              len(p["codes"]), p["e"], p["overlap"], p["bins"], p["dimer"], lc.lane_near,
+                                              lc.cycle_list[0] if lc.cycle_list else 0)
 
 
 def _resolve_consensus(args, run):
@@ -398,3 +448,20 @@ LANE_PASSES = (
              _resolve_keep, (("keep", "--lane-dups-keep"), ("molecules", "--lane-dups-keep-umi")), _keep_bytes,
              _run_keep, report.write_lane_keep, parts=lambda p: {"quality": p["edges"]}),
 )
+
+# the eleventh pass: it runs and prints after the GC pass, whose loading of the rows and whose block it follows
+ADAPTER_PASS = LanePass(
+    "ladapter", "--lane-dups-adapter",
+    (Option("--lane-dups-adapter", ("--lane-dups",)),
+     Option("--lane-dups-adapter-mismatches", ("--lane-dups-adapter",), 0, _lib.LANEADAPTER_MAX_E),
+     Option("--lane-dups-adapter-min-overlap", ("--lane-dups-adapter",), _lib.LANEADAPTER_MIN_OVERLAP, None,
+            "%d..the adapter's length" % _lib.LANEADAPTER_MIN_OVERLAP),
+     Option("--lane-dups-adapter-bins", ("--lane-dups-adapter",), report.LANE_ADAPTER_MIN_BINS, report.LANE_ADAPTER_MAX_BINS),
+     Option("--lane-dups-adapter-dimer", ("--lane-dups-adapter",), 0, None, "an insert length of 0 or more"),
+     Option("--lane-dups-adapter-out", ("--lane-dups-adapter",))),
+    _resolve_adapter, (("adapter", "--lane-dups-adapter"),),
+    lambda sc, run, p: {"adapter": sc.lane_adapter_scratch_bytes(run.n_tiles, len(run.cycle_list))},
+    _run_adapter, report.write_lane_adapter, ("--lane-dups-adapter-out", report.write_lane_adapter_tsv),
+    check=_check_adapter)
+_AFTER = [p.key for p in LANE_PASSES].index("lgc") + 1
+ALL_PASSES = LANE_PASSES[:_AFTER] + (ADAPTER_PASS,) + LANE_PASSES[_AFTER:]

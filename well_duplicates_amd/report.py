@@ -1438,6 +1438,37 @@ def gc_quartiles(distinct: Sequence[int]):
     return q1, q3
 
 
+def hist_over(hist, keys) -> List[int]:
+    """hist[key] = [Single, Roots, Copies, FamilyWells] (the GC pass's by g, the adapter pass's by a) -> [distinct
+    molecules, reads by the molecule's key, redundant wells, Roots, FamilyWells, Copies by their own read] summed over
+    the keys."""
+    rows = [hist[key] for key in keys]
+    s, r, c, f = (sum(row[i] for row in rows) for i in range(4))
+    return [s + r, s + f, f - r, r, f, c]
+
+
+def _share(v, of):
+    return v / of if of else 0.0
+
+
+def _num(v, fmt="%.5f"):
+    return "n/a" if v is None else fmt % v
+
+
+def hist_bin_columns(part, every) -> str:
+    """The columns a line of the GC block and of the adapter block share, from hist_over of the line's keys and of
+    every key: the distinct molecules and their share, the reads by the molecule's key, the redundant wells among
+    them, the duplication in the bin and against the lane's, the mean family size, the copies by their own read and
+    library_size of the bin."""
+    distinct, reads, redundant, roots, family, copies = part
+    dup, lane_dup = _share(redundant, reads), _share(every[2], every[1])
+    return ("Distinct: %i (%.5f)\tReads: %i\tRedundant: %i\tDuplication: %.5f\tRelative: %s\tMeanFamily: %s\t"
+            "Copies: %i\tLibrarySize: %s" % (
+                distinct, _share(distinct, every[0]), reads, redundant, dup,
+                _num(dup / lane_dup if lane_dup else None, "%.3f"), _num(family / roots if roots else None, "%.3f"),
+                copies, _num(library_size(reads, distinct), "%.0f")))
+
+
 @dataclass
 class LaneGCCounts:
     """A lane's duplication against its reads' GC content (include/welldup_lanegc.h, LaneDups.gc): the lane row's
@@ -1492,9 +1523,7 @@ class LaneGCCounts:
     def over(self, gs) -> List[int]:
         """[distinct molecules, reads by the molecule's GC, redundant wells, Roots, FamilyWells, Copies by their own
         read] summed over the g of gs."""
-        rows = [self.hist[g] for g in gs]
-        s, r, c, f = (sum(row[i] for row in rows) for i in range(LANE_GC_HIST_COLS))
-        return [s + r, s + f, f - r, r, f, c]
+        return hist_over(self.hist, gs)
 
     def mean_gc(self, col) -> Optional[float]:
         """The mean of g / L over the wells of col(row) per g; None without a well."""
@@ -1534,12 +1563,8 @@ def write_lane_gc(lane, counts: LaneGCCounts, verbose: bool = False, out=None) -
         dup = share(redundant, reads)
         if distinct and 100 * distinct >= every[0] and (best is None or dup > best[1]):
             best = (b, dup, gs)
-        size = library_size(reads, distinct)
-        print("LaneGC: %s%s\tBin: %i\tGC: %s\tDistinct: %i (%.5f)\tReads: %i\tRedundant: %i\tDuplication: %.5f\t"
-              "Relative: %s\tMeanFamily: %s\tCopies: %i\tLibrarySize: %s" % (
-                  lane, ham, b, "%i-%i" % (gs[0], gs[-1]) if gs else "-", distinct, share(distinct, every[0]), reads,
-                  redundant, dup, num(dup / lane_dup if lane_dup else None, "%.3f"),
-                  num(family / roots if roots else None, "%.3f"), copies, num(size, "%.0f")), file=out)
+        print("LaneGC: %s%s\tBin: %i\tGC: %s\t%s" % (
+            lane, ham, b, "%i-%i" % (gs[0], gs[-1]) if gs else "-", hist_bin_columns(c.over(gs), every)), file=out)
     lane_mean = share(sum(t[2] for t in c.tiles.values()), sum(t[1] for t in c.tiles.values()) * L)
     if verbose:
         means = c.tile_means()
@@ -1572,6 +1597,139 @@ def write_lane_gc_tsv(lane, counts: LaneGCCounts, out, header: bool = True) -> N
         print("lane\tgc\tsingle\troots\tcopies\tfamily_wells", file=out)
     for g, row in enumerate(counts.hist):
         print("%s\t%i\t%i\t%i\t%i\t%i" % (lane, g, row[0], row[1], row[2], row[3]), file=out)
+
+
+# ---- --lane-dups-adapter: a lane's duplication by insert length (include/welldup_laneadapter.h) ----
+LANE_ADAPTER_HIST_COLS = 4
+LANE_ADAPTER_LANE_COLS = 10
+LANE_ADAPTER_TILE_COLS = 5
+LANE_ADAPTER_MIN_BINS, LANE_ADAPTER_MAX_BINS = 2, 100
+
+
+@dataclass
+class LaneAdapterCounts:
+    """A lane's duplication by insert length (include/welldup_laneadapter.h, LaneDups.adapter): the lane row's
+    columns, per tile (by the tile's name) [PF, Adapter, Copies, CopiesAdapter, SumA], and hist[a] = [Single, Roots,
+    Copies, FamilyWells] for a = 0 .. L, row L the reads without adapter."""
+    k: int = 0
+    name: str = ""
+    m: int = 0
+    max_e: int = 1
+    min_overlap: int = 8
+    bins: int = 10
+    dimer: int = 10
+    first_cycle: int = 0
+    pf: int = 0
+    single: int = 0
+    roots: int = 0
+    copies: int = 0
+    ad_single: int = 0
+    ad_roots: int = 0
+    ad_copies: int = 0
+    ad_family_wells: int = 0
+    inexact: int = 0
+    partial: int = 0
+    tiles: Dict[str, List[int]] = field(default_factory=dict)
+    hist: List[List[int]] = field(default_factory=lambda: [[0] * LANE_ADAPTER_HIST_COLS])
+
+    @classmethod
+    def from_rows(cls, lane_row: Sequence[int], tile_rows: Sequence[Sequence[int]], hist, tile_names: Sequence,
+                  name: str, m: int, max_e: int, min_overlap: int, bins: int = 10, dimer: int = 10, k: int = 0,
+                  first_cycle: int = 0) -> "LaneAdapterCounts":
+        """The three results of LaneDups.adapter(codes, max_e, min_overlap); tile_names as LaneDupCounts.from_rows
+        takes them; name: what --lane-dups-adapter was given; m: the adapter's length; bins: the lines
+        write_lane_adapter prints; dimer: the largest a of an adapter dimer; k: the K of --lane-dups-hamming;
+        first_cycle: the number of the first scanned cycle, as --cycles counts them."""
+        b = [int(v) for v in lane_row]
+        h = [[int(v) for v in row] for row in hist]
+        assert len(b) == LANE_ADAPTER_LANE_COLS and len(h) >= 1 and all(len(row) == LANE_ADAPTER_HIST_COLS for row in h)
+        assert LANE_ADAPTER_MIN_BINS <= bins <= LANE_ADAPTER_MAX_BINS and dimer >= 0
+        tiles = {}
+        for tname, row in zip(tile_names, tile_rows):
+            assert len(row) == LANE_ADAPTER_TILE_COLS
+            if tname is not None:
+                tiles[tname] = [int(v) for v in row]
+        return cls(int(k), str(name), int(m), int(max_e), int(min_overlap), int(bins), int(dimer), int(first_cycle), *b,
+                   tiles, h)
+
+    @property
+    def cycles(self) -> int:
+        return len(self.hist) - 1
+
+    @property
+    def with_adapter(self) -> int:
+        return self.ad_single + self.ad_roots + self.ad_copies
+
+    def bin_of(self, a: int) -> int:
+        """of a < L: min(B - 1, a * B // L): bins of equal width over 0 .. L - 1"""
+        return min(self.bins - 1, a * self.bins // self.cycles)
+
+    def over(self, positions) -> List[int]:
+        """hist_over of these rows: the columns the GC block counts per bin, here by the molecule's a."""
+        return hist_over(self.hist, positions)
+
+    def mean_a(self, col) -> Optional[float]:
+        """The mean of a over the wells with adapter of col(row) per a; None without a well."""
+        n = sum(col(row) for row in self.hist[:-1])
+        return sum(a * col(row) for a, row in enumerate(self.hist[:-1])) / n if n else None
+
+
+def write_lane_adapter(lane, counts: LaneAdapterCounts, verbose: bool = False, out=None) -> None:
+    """The block that follows the GC block of a lane under --lane-dups-adapter: a line per bin of a - the range of
+    positions it takes, numbered from the first scanned cycle, and the columns of a GC bin (hist_bin_columns), by the
+    molecule's a - and a line "none" for the reads without adapter; with verbose a line per tile; then the summary:
+    the share of PF reads with adapter, the share that are dimers (a <= the dimer length), the duplication of the
+    dimers, of the other reads with adapter and of the reads without, the first matches that are inexact and partial
+    as shares of the matches, and the mean a of the distinct molecules and of the redundant wells (the copies, each by
+    its own read).  Offset: the first scanned cycle where that is not 0 - the inserts are longer by it."""
+    out = out or sys.stdout
+    c = counts
+    ham = "\tHamming: %i" % c.k if c.k else ""
+    L = c.cycles
+    every = c.over(range(L + 1))
+    print(file=out)
+    for b in range(c.bins):
+        ps = [a for a in range(L) if c.bin_of(a) == b]
+        print("LaneAdapter: %s%s\tBin: %i\tInsert: %s\t%s" % (
+            lane, ham, b, "%i-%i" % (c.first_cycle + ps[0], c.first_cycle + ps[-1]) if ps else "-",
+            hist_bin_columns(c.over(ps), every)), file=out)
+    print("LaneAdapter: %s%s\tBin: none\tInsert: -\t%s" % (lane, ham, hist_bin_columns(c.over([L]), every)), file=out)
+    if verbose:
+        for tile in sorted(c.tiles):
+            t = c.tiles[tile]
+            print("LaneAdapterTile: %s\tTile: %s\tPF: %i\tAdapter: %i (%.5f)\tMeanInsert: %s\tCopies: %i\t"
+                  "CopiesAdapter: %i (%.5f)" % (lane, tile, t[0], t[1], _share(t[1], t[0]),
+                                                _num(c.first_cycle + t[4] / t[1] if t[1] else None, "%.2f"), t[2], t[3],
+                                                _share(t[3], t[2])), file=out)
+    cut = min(c.dimer + 1, L)
+    parts = [c.over(range(cut)), c.over(range(cut, L)), c.over([L])]
+    dimers = sum(sum(row[:3]) for row in c.hist[:cut])
+    m_distinct, m_copies = c.mean_a(lambda row: row[0] + row[1]), c.mean_a(lambda row: row[2])
+    mean = lambda v: _num(None if v is None else c.first_cycle + v, "%.2f")
+    print("LaneAdapterSummary: %s%s\tAdapter: %s\tLength: %i\tMismatches: %i\tMinOverlap: %i\tCycles: %i\t%sBins: %i\t"
+          "PF: %i\tWithAdapter: %i (%.5f)\tDimers (a <= %i): %i (%.5f)\tDuplication: %.5f\tDuplication of dimers: %.5f\t"
+          "of other reads with adapter: %.5f\tof reads without: %.5f\tInexact: %i (%.5f)\tPartial: %i (%.5f)\t"
+          "MeanInsert distinct: %s\tMeanInsert redundant: %s" % (
+              lane, ham, c.name, c.m, c.max_e, c.min_overlap, L,
+              "Offset: %i\t" % c.first_cycle if c.first_cycle else "", c.bins, c.pf, c.with_adapter,
+              _share(c.with_adapter, c.pf), c.dimer, dimers, _share(dimers, c.pf), _share(every[2], every[1]),
+              _share(parts[0][2], parts[0][1]), _share(parts[1][2], parts[1][1]), _share(parts[2][2], parts[2][1]),
+              c.inexact, _share(c.inexact, c.with_adapter), c.partial, _share(c.partial, c.with_adapter),
+              mean(m_distinct), mean(m_copies)), file=out)
+
+
+def write_lane_adapter_tsv(lane, counts: LaneAdapterCounts, out, header: bool = True) -> None:
+    """--lane-dups-adapter-out: a line per a = 0 .. L - 1 and a line "none" - lane, insert (a numbered from the first
+    scanned cycle), single, roots, copies, family_wells, cumulative: the share of PF reads with a at or before the
+    line's - the adapter content curve, exact; "-" on the last line."""
+    if header:
+        print("lane\tinsert\tsingle\troots\tcopies\tfamily_wells\tcumulative", file=out)
+    seen = 0
+    for a, row in enumerate(counts.hist):
+        seen += sum(row[:3])
+        last = a == counts.cycles
+        print("%s\t%s\t%i\t%i\t%i\t%i\t%s" % (lane, "none" if last else "%i" % (counts.first_cycle + a), row[0], row[1],
+                                              row[2], row[3], "-" if last else "%.5f" % _share(seen, counts.pf)), file=out)
 
 
 # ---- --lane-dups-consensus: a lane's errors against its families' vote (include/welldup_laneconsensus.h) ----

@@ -330,6 +330,11 @@ class Scanner:
         tile and the histogram per g; it does not depend on the wells of a tile)."""
         return self._workspace_bytes(self._lib.wd_lane_gc_scratch, max_tiles, L)
 
+
+    def lane_adapter_scratch_bytes(self, max_tiles: int, L: int) -> int:
+        """Device bytes LaneDups.adapter needs beside the accumulator's workspace (wd_lane_adapter_scratch: the
+        counters per tile, the histogram per a, the tile indices and the search's table)."""
+        return self._workspace_bytes(self._lib.wd_lane_adapter_scratch, max_tiles, L)
     def lane_consensus_scratch_bytes(self, max_tiles: int, n_clusters: int, L: int) -> int:
         """Device bytes LaneDups.consensus needs beside the accumulator's workspace (wd_lane_consensus_scratch: 8 bytes
         per well of the lane - where a family's members begin, and the member list with the family table - and the
@@ -970,6 +975,33 @@ class LaneDups:
         self._with_scratch(self.sc.lane_gc_scratch_bytes(self.max_tiles, self.L),
                            lambda d_scratch, sbytes: self.sc._lib.wd_lane_gc(
                                self._h, int(max_n), d_scratch, sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
+                               tile_rows.ctypes.data_as(ctypes.c_void_p), hist.ctypes.data_as(ctypes.c_void_p)))
+        return lane_row, tile_rows, hist
+
+    def adapter(self, codes, max_e: int = 1, min_overlap: int = 8):
+        """After finish(), any number of times, before or after every other pass (wd_lane_adapter,
+        include/welldup_laneadapter.h): every PF well by a, the first position at which its own read matches the
+        adapter - codes, 8..32 values 0..3 (A C G T) - with at most max_e mismatches at full overlap, fewer in
+        proportion where only min_overlap or more of the adapter's bases fit before the read's end, and by what it is
+        under the labels the finish left: a lone read, the first well of a group, or a copy.  a = L: no adapter.
+        -> (lane row int64 [10]: [PF, Single, Roots, Copies, AdSingle, AdRoots, AdCopies, AdFamilyWells, Inexact,
+        Partial], tile rows int64 [max_tiles, 5]: [PF, Adapter, Copies, CopiesAdapter, SumA] by the well's own tile,
+        hist int64 [L + 1, 4]: [a][Single, Roots, Copies, FamilyWells], FamilyWells the groups' wells by the root's
+        a).  The scratch is allocated for the call and released.  An adapter, max_e or min_overlap out of range
+        (min_overlap is 3..min(m, L)) or a call before a successful finish raises ValueError."""
+        if self._h is None:
+            raise ValueError("the accumulator is closed")
+        codes = np.asarray(codes).reshape(-1)
+        if codes.size and not (0 <= int(codes.min()) and int(codes.max()) <= 3):
+            raise ValueError("an adapter's codes are 0..3 (A C G T)")
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        lane_row = np.zeros(_lib.LANEADAPTER_LANE_COLS, dtype=np.int64)
+        tile_rows = np.zeros((self.max_tiles, _lib.LANEADAPTER_TILE_COLS), dtype=np.int64)
+        hist = np.zeros((self.L + 1, _lib.LANEADAPTER_HIST_COLS), dtype=np.int64)
+        self._with_scratch(self.sc.lane_adapter_scratch_bytes(self.max_tiles, self.L),
+                           lambda d_scratch, sbytes: self.sc._lib.wd_lane_adapter(
+                               self._h, codes.ctypes.data_as(ctypes.c_void_p), int(codes.size), int(max_e),
+                               int(min_overlap), d_scratch, sbytes, lane_row.ctypes.data_as(ctypes.c_void_p),
                                tile_rows.ctypes.data_as(ctypes.c_void_p), hist.ctypes.data_as(ctypes.c_void_p)))
         return lane_row, tile_rows, hist
 
